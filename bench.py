@@ -12,6 +12,12 @@ src/CORA_problem.cpp:822-867) with every operand resident in HBM:
 Prints ONE JSON line on rank 0.  Launch for N > 1:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline (metric, value, unit, ms_per_step, ...).
+--full adds everything else the line used to carry: the kernel alone and its rooflines (cache-resident, HBM-rotated,
+PMC traffic and rocprofv3 kernel times from child runs), per-chunk statistics, the STPCG loop and the staircase at this
+size, the CPU baselines and the parity checks against the CPU oracle, and for N > 1 the per-phase figures.
+--dump-outputs DIR writes what the last timed step computed (the product, N x columns, float64) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -25,6 +31,20 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_LIMIT = 60 * 10 ** 6  # bytes that --dump-outputs may write in all (headers aside)
+
+
+def dump_outputs(path, name, a):
+    """Writes a (rows x columns) as path/<name>.npy in float64.  Above DUMP_LIMIT only a fixed sample of rows (seed 0,
+    ascending) is written, with the row numbers beside it as path/<name>_rows.npy (float64, exact below 2^53)."""
+    os.makedirs(path, exist_ok=True)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.nbytes > DUMP_LIMIT:
+        keep = DUMP_LIMIT // (8 * (a.shape[1] + 1))
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+        np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(path, name + ".npy"), a)
 
 
 def algorithmic_bytes(d, n, r, N, nnz, p):
@@ -324,6 +344,13 @@ def main():
                     help="the all-core column with a sweep over several thread counts (~10 s of host time); by default only "
                          "two thread counts are tried (the container's CPU quota and half of it, ~1 s each)")
     ap.add_argument("--no-cpu-all-cores", action="store_true", help="skip the all-core column altogether")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything beside it: rooflines (with --pmc-traffic), "
+                         "per-chunk statistics, the STPCG loop and the staircase, CPU baselines (--cpu-*), parity against "
+                         "the CPU oracle, N > 1 phases.  Off: the run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the output of the last timed step as DIR/<name>.npy (float64; a fixed, seeded sample of "
+                         "its rows when it is larger than %d MB)" % (DUMP_LIMIT // 10 ** 6))
     ap.add_argument("--kernel-only", action="store_true", help=argparse.SUPPRESS)  # the child run of --pmc-traffic
     args = ap.parse_args()
 
@@ -540,6 +567,61 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.op == "cert":
+        b_spmm, _ = algorithmic_bytes(dm["d"], dm["n"], dm["r"], dm["N"], dm["nnz"], k_op)
+        b_hvp = b_spmm + (dm["n"] * dm["d"] ** 2 + dm["r"]) * 8   # + the Lambda blocks
+    if args.dump_outputs:   # the product of the last timed step (download is collective: every rank takes part)
+        res_ = ctx.download(out.data_ptr(), p) if args.op == "hvp" else ctx.download(ok.data_ptr(), k_op)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, "hvp" if args.op == "hvp" else "certificate_product", res_)
+
+    def headline():
+        """The headline line: what a plain run prints, and the head of the --full one."""
+        return {
+            "metric": "riemannian_hessian_vector_products_per_sec" if args.op == "hvp" else
+                      "certificate_operator_products_per_sec",
+            "value": args.steps / elapsed,
+            "unit": "Hvp/s" if args.op == "hvp" else "products/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": "synthetic SE(3) odometry chain, %d poses + %d landmarks + %d range edges (seed 42); "
+                            "%s at relaxation rank p=%d; N=%d, nnz(Q)=%d"
+                            % (dm["n"], dm["l"], dm["r"],
+                               "Hvp = Proj_Y((Q - Lambda) Ydot)" if args.op == "hvp" else
+                               "certificate operator (Q - Lambda) X, %d columns" % k_op, p, dm["N"], dm["nnz"]),
+                "parallelism": "1 GPU" if world == 1 else
+                               "rows of Q over %d GPUs (pose-aligned, nnz-balanced) + one RCCL all-gather (issued by the library "
+                               "itself on the handle's stream) of the %d rows of the operand (of %d) that other ranks read, "
+                               "packed and scattered by the library's own kernels" % (world, comm.exchanged_rows, rows),
+                "algorithmic_bytes_per_hvp": b_hvp,
+                "algorithmic_bytes_per_spmm": b_spmm,
+            },
+            "value_is": "steps / wall time of the timed region (K back-to-back products between two barriers + "
+                        "synchronisations, host clock); with --full, per-chunk statistics of the same launches: value_stats",
+        }
+
+    if not args.full:
+        if rank == 0:
+            result = headline()
+            if world > 1:
+                result["multi_gpu"] = {"transport": type(comm).__name__, "transports_timed": transport_runs,
+                                       "value_is_quoted_on": "the faster of the transports whose product is consistent "
+                                                             "(transports_timed[*].ok)"}
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(result) + "\n").encode())
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # ---- roofline: the kernel alone, HIP events on the stream it runs on ------
     # (N > 1: the exchange is part of the step, so the kernel alone is timed on a handle-local product: the operand's
     # remote rows are current after the timed region above)
@@ -563,9 +645,6 @@ def main():
             comm.local_products(False)
         else:
             comm.exchange = ex_fn
-    if args.op == "cert":
-        b_spmm, _ = algorithmic_bytes(dm["d"], dm["n"], dm["r"], dm["N"], dm["nnz"], k_op)
-        b_hvp = b_spmm + (dm["n"] * dm["d"] ** 2 + dm["r"]) * 8   # + the Lambda blocks
     stats = ctx.format_stats()
     # what the FORMAT makes a product move at least: its own bytes of Q (not the CSR's 12 nnz + 4 (N + 1)), the operand
     # read once, the result written once, and for the epilogues the point's rows and the Lambda blocks
@@ -704,36 +783,7 @@ def main():
         if traffic:
             b2b["frac_traffic"] = traffic / kernel_us / 1e3 / HBM_PEAK_GBS
         b2b["frac_compulsory"] = (comp_read + comp_write) / kernel_us / 1e3 / HBM_PEAK_GBS
-        result = {
-            "metric": "riemannian_hessian_vector_products_per_sec" if args.op == "hvp" else
-                      "certificate_operator_products_per_sec",
-            "value": args.steps / elapsed,
-            "unit": "Hvp/s" if args.op == "hvp" else "products/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": "synthetic SE(3) odometry chain, %d poses + %d landmarks + %d range edges (seed 42); "
-                            "%s at relaxation rank p=%d; N=%d, nnz(Q)=%d"
-                            % (dm["n"], dm["l"], dm["r"],
-                               "Hvp = Proj_Y((Q - Lambda) Ydot)" if args.op == "hvp" else
-                               "certificate operator (Q - Lambda) X, %d columns" % k_op, p, dm["N"], dm["nnz"]),
-                "parallelism": "1 GPU" if world == 1 else
-                               "rows of Q over %d GPUs (pose-aligned, nnz-balanced) + one RCCL all-gather (issued by the library "
-                               "itself on the handle's stream) of the %d rows of the operand (of %d) that other ranks read, "
-                               "packed and scattered by the library's own kernels" % (world, comm.exchanged_rows, rows),
-                "algorithmic_bytes_per_hvp": b_hvp,
-                "algorithmic_bytes_per_spmm": b_spmm,
-            },
-            "value_is": "steps / wall time of the timed region (K back-to-back products between two barriers + "
-                        "synchronisations, host clock); per-chunk statistics of the same launches: value_stats",
-        }
+        result = headline()
         if extras is not None and extras.get("hvp_in_stpcg_us"):
             # the line's roofline: the product as the solver runs it -- inside the STPCG loop, the preconditioner's two
             # sweeps over the factor between two products -- HIP events around it in every iteration

@@ -8,9 +8,9 @@ import subprocess
 import pytest
 
 from cora_amd import build as _build
+from oracle import build_ref_tests
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_MAIN = "/root/reference/examples/main.cpp"   # only in the build container; never copied
 
 
 def _compile(src, out, extra=()):
@@ -40,7 +40,11 @@ def test_symbol_and_eigen_style_surface(tmp_path):
     assert r.returncode == 0, r.stdout[-2000:]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_MAIN), reason="the reference tree is only mounted in the build container")
-def test_reference_examples_main_compiles_unmodified(tmp_path):
-    """The reference's own examples/main.cpp, from where it lies, unmodified."""
-    _compile(REF_MAIN, str(tmp_path / "ref_main"))
+def test_reference_examples_main_compiles_unmodified():
+    """The reference's own examples/main.cpp, from where it lies, unmodified: compiled and linked by build() into
+    oracle/_ref/ (oracle/build_ref_tests.py) where the reference tree is present; the test reads only what build() left."""
+    out = build_ref_tests.MAIN_OUT
+    if os.path.exists(build_ref_tests.failure_log(out)):
+        pytest.fail(open(build_ref_tests.failure_log(out)).read()[-3000:])
+    if not os.path.exists(out):
+        pytest.skip("oracle/_ref/ref_examples_main was not built: build() ran without the reference tree")

@@ -434,7 +434,7 @@ def test_bench_two_ranks_runs_end_to_end_over_gloo(tmp_path):
     env = dict(os.environ, CORA_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29631", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3",
-           "--poses", "20000", "--pmc-traffic", "off"]
+           "--poses", "20000", "--pmc-traffic", "off", "--full"]
     r = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1]

@@ -4,8 +4,8 @@ tests/test_construct_problem.cpp, tests/test.cpp -- compiled unmodified, from wh
 libcora_hip.so (oracle/build_ref_tests.py; Catch2 and the Eigen-based test helper replaced by the stand-ins under
 tests/drop_in/shim/), and RUN against the committed golden fixtures (byte-identical copies of the reference's tests/data).
 
-The binaries are built in the build container, where /root/reference is mounted (__graft_entry__.build()), into
-oracle/_ref/ (git-ignored) and travel to the GPU box with the snapshot; the reference's sources never do."""
+The binaries are built by __graft_entry__.build() where the reference tree is present, into oracle/_ref/ (git-ignored);
+the tests read nothing but what build() left there, never the reference's sources."""
 import os
 import subprocess
 import sys
@@ -20,11 +20,11 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 def _binary(unit):
-    if build_ref_tests.available():
-        build_ref_tests.build()
     path = os.path.join(build_ref_tests.OUT, "ref_" + unit)
+    if os.path.exists(build_ref_tests.failure_log(path)):
+        pytest.fail(open(build_ref_tests.failure_log(path)).read()[-3000:])
     if not os.path.exists(path):
-        pytest.skip("oracle/_ref/ref_%s was not built: the reference tree is only mounted in the build container" % unit)
+        pytest.skip("oracle/_ref/ref_%s was not built: build() ran without the reference tree" % unit)
     return path
 
 

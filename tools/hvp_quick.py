@@ -1,7 +1,8 @@
 """Quick Hvp timing at 10^5 poses: back to back, rotated (HBM-resident) and inside STPCG, for variant builds.
 python tools/hvp_quick.py [label]"""
 import json, subprocess, sys
-out = subprocess.run([sys.executable, "bench.py", "--steps", "1000", "--warmup", "100", "--cpu-seconds", "0.2", "--pmc-traffic", "off"],
+out = subprocess.run([sys.executable, "bench.py", "--steps", "1000", "--warmup", "100", "--cpu-seconds", "0.2", "--pmc-traffic", "off",
+                      "--full"],
                      capture_output=True, text=True).stdout.strip().splitlines()[-1]
 d = json.loads(out); e = d["extras"]
 print("%-50s hvp %.2f us | hbm-resident %.2f us | spmm %.2f (hbm %.2f) | in-stpcg %.2f | iteration %.1f | parity %.1e" % (
