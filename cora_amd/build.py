@@ -25,7 +25,7 @@ KERNEL_PARTS = [("spmm_g0", 1, 1), ("spmm_g1", 1, 2), ("spmm_g2", 1, 4), ("spmm_
 
 
 def sources():
-    srcs = [os.path.join(CSRC, f) for f in ("format_build.cpp", "trisolve_build.cpp", "kernels.hip", "capi.hip", "p2p.hip")]
+    srcs = [os.path.join(CSRC, f) for f in ("config.cpp", "format_build.cpp", "trisolve_build.cpp", "kernels.hip", "capi.hip", "p2p.hip")]
     srcs += sorted(glob.glob(os.path.join(CSRC, "host", "*.cpp")))
     return srcs
 
@@ -93,10 +93,11 @@ def build(force=False, verbose=False):
         if not forced and os.path.exists(o) and os.path.getmtime(o) > newest:
             continue
         jobs.append((s, [HIPCC] + FLAGS + extra + (["-x", "hip"] if s.endswith(".hip") else []) + ["-c", s, "-o", o]))
-    # the kernel units are the long poles: start them first; at most MAXJOBS compilers at a time.  Every compiler's
-    # output is drained by subprocess.run (a child blocked on a full pipe would never exit).
+    # the kernel units are the long poles: start them first; at most maxjobs compilers at a time (CORA_BUILD_JOBS, else
+    # MAX_JOBS, else up to 16).  Every compiler's output is drained by subprocess.run (a child blocked on a full pipe
+    # would never exit).
     jobs.sort(key=lambda j: 0 if j[0].endswith("kernels.hip") else 1)
-    maxjobs = int(os.environ.get("CORA_BUILD_JOBS", str(max(2, (os.cpu_count() or 4)))))
+    maxjobs = int(os.environ.get("CORA_BUILD_JOBS") or os.environ.get("MAX_JOBS") or min(16, os.cpu_count() or 4))
 
     def run(job):
         s, cmd = job

@@ -46,6 +46,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include <vector>
 
 #include "../../include/cora_hip.h"
+#include "config.h"
 #include "cora_internal.h"
 #include "kernels.h"
 #include "p2p.h"

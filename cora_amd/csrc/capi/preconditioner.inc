@@ -23,12 +23,7 @@ static int install_factor(cora_ctx *c, cora_ctx::DevFactor &f, int m, const int3
                           const double *Lx, const std::vector<int32_t> &row_of, int32_t zero_row,
                           const std::vector<int32_t> *group = nullptr) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const bool timing = std::getenv("CORA_TRI_TIMING") != nullptr;
-  auto tick = [t_prev = std::chrono::steady_clock::now(), timing](const char *what) mutable {
-    const auto now = std::chrono::steady_clock::now();
-    if (timing) std::fprintf(stderr, "  [install] %-26s %.3f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-    t_prev = now;
-  };
+  cora::PhaseTimer tick(cora::env_flag(cora::Env::TriTiming), "  [install]", 26, 3);
   f.chunk_at = 0;
   f.chunk_used = 0;
   f.stages.clear();
@@ -152,25 +147,11 @@ static int install_factor(cora_ctx *c, cora_ctx::DevFactor &f, int m, const int3
       H.b_hdr.resize(H.b_hdr.size() + 8, 0);
       HIP_TRY(c, up(&Q.fwd.hdr, H.f_hdr));
       HIP_TRY(c, up(&Q.fwd.idx, H.f_idx));
-      // LAB BUILDS ONLY (-DCORA_SUB_F32=1 on capi.hip AND the kernels_tri units: the sweeps then read fp32 coefficients).  A
-      // compile-time constant since round 6: as an environment switch of the product library it uploaded floats into a buffer
-      // the default kernels read as doubles.  Measured at 10^5 poses, p = 5 (profiles/r06_kernel_evolution.md): forward sweep
-      // 35.8 -> 33.3 us, backward 35.2 -> 34.6, iteration 110.5 -> 107.2 us (3 %): the sweeps are not bound by the factor's bytes.
-#if defined(CORA_SUB_F32) && CORA_SUB_F32
-      constexpr bool f32 = true;
-#else
-      constexpr bool f32 = false;
-#endif
-      if (f32) {
-        std::vector<float> ff(H.f_val.begin(), H.f_val.end()), fb(H.b_val.begin(), H.b_val.end());
-        HIP_TRY(c, up(reinterpret_cast<float **>(const_cast<double **>(&Q.fwd.val)), ff));
-        HIP_TRY(c, up(reinterpret_cast<float **>(const_cast<double **>(&Q.bwd.val)), fb));
-      } else
       HIP_TRY(c, up(&Q.fwd.val, H.f_val));
       HIP_TRY(c, up(&Q.bwd.rows, H.b_rows));
       HIP_TRY(c, up(&Q.bwd.hdr, H.b_hdr));
       HIP_TRY(c, up(&Q.bwd.idx, H.b_idx));
-      if (!f32) HIP_TRY(c, up(&Q.bwd.val, H.b_val));
+      HIP_TRY(c, up(&Q.bwd.val, H.b_val));
       HIP_TRY(c, up(&Q.tgt_row, H.tgt_row));
       HIP_TRY(c, up(&Q.tgt_slot, H.tgt_slot));
       HIP_TRY(c, up(&Q.c_ptr, H.c_ptr));
@@ -197,26 +178,13 @@ static int install_factor(cora_ctx *c, cora_ctx::DevFactor &f, int m, const int3
           };
           cora::parallel_parts(nth, part);
           io.back() = make_int2(0, 0);
-          if (std::getenv("CORA_IO_STATS")) {  // lab: runs of consecutive rows per block
-            size_t tot = 0, mx = 0;
-            std::vector<size_t> hist(12, 0);
-            for (size_t b = 0; b < nblk; ++b) {
-              const int32_t r0 = desc[b].row_begin, nb = desc[b].nrows;
-              size_t runs = nb > 0;
-              for (int k = 1; k < nb; ++k) runs += io[static_cast<size_t>(r0) + k].x != io[static_cast<size_t>(r0) + k - 1].x + 1;
-              tot += runs; mx = std::max(mx, runs); hist[std::min<size_t>(runs, 11)]++;
-            }
-            std::fprintf(stderr, "io runs per block: mean %.2f max %zu, histogram", double(tot) / std::max<size_t>(nblk, 1), mx);
-            for (size_t h : hist) std::fprintf(stderr, " %zu", h);
-            std::fprintf(stderr, "\n");
-          }
           return io;
         };
         // (the rows of a block in memory order are the same set for both sweeps: the runs are found once, from the
         // forward list; only the tile positions differ)
         {
           const std::vector<int2> iof = io_of(H.rows), iob = io_of(H.b_rows);
-          bool runs_ok = std::getenv("CORA_SUB_IO_LISTS") == nullptr;  // (lab switch: the 8-byte index lists)
+          bool runs_ok = !cora::env_flag(cora::Env::SubIoLists);  // (lab switch: the 8-byte index lists)
           std::vector<uint16_t> tpf(iof.size() + 8, 0), tpb(iob.size() + 8, 0);
           for (size_t b = 0; b < desc.size(); ++b) {
             SubDesc &d = desc[b];
@@ -280,7 +248,7 @@ static int install_factor(cora_ctx *c, cora_ctx::DevFactor &f, int m, const int3
             }
         }
         f.fuse_ok = ok;
-        if (std::getenv("CORA_TRI_TIMING")) std::fprintf(stderr, "  [tri plan] sweep fusion possible: %d\n", int(ok));
+        if (tick.on()) std::fprintf(stderr, "  [tri plan] sweep fusion possible: %d\n", int(ok));
       }
       HIP_TRY(c, up(&Q.desc, desc));
       tick("  sub: units");

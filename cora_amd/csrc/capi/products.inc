@@ -17,7 +17,7 @@ static int implicit_lift(cora_ctx *c, const double *dX, int ld, double *w0, doub
   const bool mine = last >= L.base && last < L.base + L.shard_rows;
   if (mine) HIP_TRY(c, launch_zero_row(w1, static_cast<size_t>(last), ld, c->stream));
   if (sharded) {  // every rank: all translation rows of B^T X (the solve is replicated)
-    if (c->native_comm && c->comm_user == c->native_comm && !std::getenv("CORA_IMPLICIT_WHOLE_GATHER")) {
+    if (c->native_comm && c->comm_user == c->native_comm && !cora::env_flag(cora::Env::ImplicitWholeGather)) {
       // the library's own communication gathers the translation rows alone, packed: 2 / 9 of a shard's rows at d = 3
       if (native_allgather_rows(c->native_comm, w1, ld, L.trn_base - L.base, L.nl_trans))
         return fail(c, CORA_ERR_HIP, "all-gather step failed: " + native_error(c->native_comm));
@@ -61,12 +61,12 @@ static int apply_product(cora_ctx *c, const double *dX, int ld, int epi, double 
 
 // true when products of this handle run as two launches around the exchange (exchange_and_product)
 static bool product_overlaps_exchange(const cora_ctx *c) {
-  static const bool off = std::getenv("CORA_NO_EXCHANGE_OVERLAP") != nullptr;
+  const bool off = cora::env_flag(cora::Env::NoExchangeOverlap);
   // The split costs a second launch and two cross-stream dependencies (a few microseconds); it pays when the interior
   // slices run longer than that.  Measured with the in-process transport, 8 partitions of the 10^5-pose graph on one
   // GPU (500 slices per rank, a 3 us product): 290-350 us per step serial, 460 us split -- so the default takes the
   // split from kOverlapMinSlices interior slices on (about 10 us of product; 10^6 poses on 8 GPUs: 5 000 per rank).
-  static const int min_slices = [] { const char *e = std::getenv("CORA_EXCHANGE_OVERLAP_MIN_SLICES"); return e ? std::atoi(e) : 2048; }();
+  const int64_t min_slices = cora::env_int(cora::Env::ExchangeOverlapMinSlices);
   const bool wanted = c->overlap_exchange == 2 || (c->overlap_exchange == 1 && c->n_slices_int >= min_slices);
   return c->F.L.world > 1 && wanted && !off && c->native_comm && c->comm_user == c->native_comm &&
          c->comm_exchange != nullptr && c->n_slices_int > 0 && c->n_slices_bnd > 0 &&

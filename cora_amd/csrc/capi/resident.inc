@@ -128,7 +128,7 @@ int cora_tnt_accept_dev(cora_ctx *c, const double *dX, double *dPg, double out[4
   NEED_RANK(c);
   if (!dX || !dPg || !out || dX == dPg) return fail(c, CORA_ERR_ARG, "bad arguments");
   int rc;
-  const bool fast = c->F.L.world == 1 && c->trial_x == dX && c->d_G_trial && !std::getenv("CORA_NO_TNT_FUSE");
+  const bool fast = c->F.L.world == 1 && c->trial_x == dX && c->d_G_trial && !cora::env_flag(cora::Env::NoTntFuse);
   if (fast) {
     c->trial_x = nullptr;
     if (dX != c->d_Y) HIP_TRY(c, hipMemcpyAsync(c->d_Y, dX, vec_bytes(c, c->ld), hipMemcpyDeviceToDevice, c->stream));

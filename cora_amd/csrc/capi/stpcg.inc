@@ -90,7 +90,7 @@ static int stpcg_run(cora_ctx *c, const double *dGrad, const double *dPg, double
   // `batch` iterations between two looks, everything waited for (every rank must enqueue the same collective calls, so
   // the decision may only depend on a state that no iteration in flight can have advanced).
   // (the three switches of the host loop are read per solve: tests/test_gpu_solver.py runs one problem under each form)
-  const int batch_env = [] { const char *e = std::getenv("CORA_STPCG_BATCH"); return e ? std::atoi(e) : 0; }();
+  const int batch_env = static_cast<int>(cora::env_int(cora::Env::StpcgBatch));
   const int batch = batch_env > 0 ? batch_env : (n > 1000000 ? 1 : 4);
   int enqueued = 0;
   // Fused iteration (explicit formulation, one shard, row strides up to 12): six passes instead of nine --
@@ -100,7 +100,7 @@ static int stpcg_run(cora_ctx *c, const double *dGrad, const double *dPg, double
   const bool chol = c->precond == CORA_PRECOND_BLOCK_CHOLESKY || c->precond == CORA_PRECOND_REGULARIZED_CHOLESKY;
   const size_t off = static_cast<size_t>(c->F.L.base) * c->ld;
   const bool fused = sharded || (!c->implicit && c->ld <= 12 && n % 2 == 0 && (off * sizeof(double)) % 16 == 0 &&
-                                 !std::getenv("CORA_NO_FUSE"));
+                                 !cora::env_flag(cora::Env::NoFuse));
   // Sweep-fused iteration (the above, with a two-stage Cholesky solve plan): five passes and a scalar step --
   //   Hp = H p with the partials of kappa | kappa | forward sweep on r += alpha Hp with <r, r> | last stage (2 products) |
   //   backward sweep with v = Proj_Y(x) and <r, v> | s += alpha p, p = -v + beta p
@@ -115,7 +115,7 @@ static int stpcg_run(cora_ctx *c, const double *dGrad, const double *dPg, double
     size_t need = std::max<size_t>(4 * 512, static_cast<size_t>((units + 255) / 256) + 8);
     const cora_ctx::DevFactor &f = c->precond_f;
     sweep_fused = !c->implicit && chol && f.ready && f.fuse_ok && !f.stages.empty() && f.stages[0].is_sub && c->ld * c->F.L.d <= 24 && c->ld <= 11 &&
-                  !std::getenv("CORA_NO_SWEEP_FUSE");  // (row stride x d > 24: the fused backward sweep spills)
+                  !cora::env_flag(cora::Env::NoSweepFuse);  // (row stride x d > 24: the fused backward sweep spills)
     // slots of the sweep-fused reductions: <r, r> per block of the forward sweep's launch, |y|^2 per solve block,
     // |row|^2 per row of the last stage's forward product
     size_t rr_slots = 0, yy_slots = 0, sq_slots = 0;
@@ -127,8 +127,8 @@ static int stpcg_run(cora_ctx *c, const double *dGrad, const double *dPg, double
     }
     // one explicit inverse W = L^-1 and nothing else (two products per solve), no pinned-row stage in between
     inverse_fused = !sharded && !sweep_fused && chol && f.ready && f.stages.size() == 1 && !f.stages[0].dense && !f.stages[0].is_sub &&
-                    !f.stages[0].has_fwd_a && !f.stages[0].has_bwd_a && !std::getenv("CORA_NO_INVERSE_FUSE");
-    static const bool residual_slots = !std::getenv("CORA_NO_RESIDUAL_SLOTS");
+                    !f.stages[0].has_fwd_a && !f.stages[0].has_bwd_a && !cora::env_flag(cora::Env::NoInverseFuse);
+    const bool residual_slots = !cora::env_flag(cora::Env::NoResidualSlots);
     if (inverse_fused) {
       const RowOpDev &fb = f.stages[0].fwd_b;
       sq_slots = static_cast<size_t>(rowop_rowsq_slots(fb)) + 8;
@@ -196,8 +196,7 @@ static int stpcg_run(cora_ctx *c, const double *dGrad, const double *dPg, double
       // (round 5: a solve block adds the partials BEHIND the loads of its right-hand sides -- kernels.hip, late_kappa --, which
       // moved the break-even up: at 10^5 poses the iteration goes from 111.8 to 110.6 us without the launch; 10^6 poses, 24 k
       // partials, keep it)
-      static const int fold_max = [] { const char *e = std::getenv("CORA_KAPPA_FOLD_MAX"); return e ? std::atoi(e) : 4096; }();
-      if (!sharded && kappa_blocks <= fold_max && !std::getenv("CORA_NO_KAPPA_FOLD")) {
+      if (!sharded && kappa_blocks <= cora::env_int(cora::Env::KappaFoldMax) && !cora::env_flag(cora::Env::NoKappaFold)) {
         FF.kappa_partial = tail.kappa_partial = kappa_partial;
         FF.n_kappa = tail.n_kappa = kappa_blocks;
       }
@@ -210,7 +209,7 @@ static int stpcg_run(cora_ctx *c, const double *dGrad, const double *dPg, double
   // between them is the dependency itself -- and a six-launch graph per iteration costs the host more than six launches:
   // iteration at 10^5 poses 116 -> 122 us, the reference's data sets unchanged.  tools/launch_lab.hip shows the gain only
   // for kernels shorter than the launch rate, 3.5 -> 2.1 us each.  Kept: same bits, tested, one switch.
-  const bool graphs_on = [] { const char *e = std::getenv("CORA_STPCG_GRAPH"); return e && e[0] == '1'; }();  // (read per solve: tests flip it)
+  const bool graphs_on = cora::env_flag(cora::Env::StpcgGraph);  // (read per solve: tests flip it)
   const bool use_graph = graphs_on && fused && !sharded && !c->prof_stpcg && max_iters >= batch;
   std::vector<uintptr_t> key;
   if (use_graph) {
@@ -234,7 +233,7 @@ static int stpcg_run(cora_ctx *c, const double *dGrad, const double *dPg, double
     tail.seq_counter = c->d_seq_counter;
     FF.dot.seq_counter = FB.dot.seq_counter = c->d_seq_counter;
   }
-  const int depth_env = [] { const char *e = std::getenv("CORA_STPCG_DEPTH"); return e ? std::atoi(e) : -1; }();
+  const int depth_env = static_cast<int>(cora::env_int(cora::Env::StpcgDepth));
   const bool pipelined = !sharded && !use_graph && batch_env <= 0;
   const int depth = depth_env >= 0 ? depth_env : (batch == 1 ? 0 : 1);
   // Small problems, the default: the host runs ahead by the next iteration's PRODUCT only.  The reductions' block of
@@ -242,7 +241,7 @@ static int stpcg_run(cora_ctx *c, const double *dGrad, const double *dPg, double
   // last launch of k and the product of k + 1, which is what the host needs to see the state and enqueue the rest of
   // k + 1 -- the GPU does not wait for the host, and past the stopping point there is one product (its results are never
   // read), not one whole neutral iteration.  CORA_STPCG_DEPTH=1 is the whole-iteration form.
-  const int ahead_env = [] { const char *e = std::getenv("CORA_STPCG_AHEAD"); return e ? std::atoi(e) : -1; }();  // (lab)
+  const int ahead_env = static_cast<int>(cora::env_int(cora::Env::StpcgAhead));  // (lab)
   const bool product_ahead = pipelined && !c->prof_stpcg && (ahead_env >= 0 ? ahead_env != 0 : (depth == 1 && depth_env < 0));
   bool have_product = false;
   std::deque<unsigned long long> in_flight;

@@ -8,7 +8,6 @@
 // src/CORA_problem.cpp:625-712) with the variable layout of
 // include/CORA/CORA_problem.h:151-157.
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +15,7 @@
 #include <stdexcept>
 #include <thread>
 
+#include "config.h"
 #include "cora_internal.h"
 #include "parallel.h"
 
@@ -26,7 +26,7 @@ int g_pad_even = 0;
 int g_long_chunk = kLongChunk;
 int g_interleave = 0;  // measured: no gain on MI355X (kept for the lab)
 // pose slices in the chain layout (CORA_CHAIN_SLICES=0: the plain layout with every column explicit, measurement switch)
-int g_chain_slices = [] { const char *e = std::getenv("CORA_CHAIN_SLICES"); return (e && e[0] == '0') ? 0 : 1; }();
+int g_chain_slices = env_flag(Env::ChainSlices) ? 1 : 0;
 
 namespace {
 
@@ -83,12 +83,7 @@ void build_format(int d, int n, int r, int nt, const int32_t *rowptr,
                   const int32_t *col, const double *val, int rank, int world,
                   HostFormat &F, bool distribute_long_rows) {
   const bool dist_long = distribute_long_rows && world > 1;
-  const bool timing = std::getenv("CORA_FORMAT_TIMING") != nullptr;
-  auto tick = [t_prev = std::chrono::steady_clock::now(), timing](const char *what) mutable {
-    const auto now = std::chrono::steady_clock::now();
-    if (timing) std::fprintf(stderr, "  [format] %-28s %.4f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-    t_prev = now;
-  };
+  PhaseTimer tick(env_flag(Env::FormatTiming), "  [format]", 28, 4);
   if (d != 2 && d != 3) throw std::runtime_error("cora: dimension d must be 2 or 3");
   if (n < 0 || r < 0 || nt < n) throw std::runtime_error("cora: invalid problem sizes");
   if (world < 1 || rank < 0 || rank >= world) throw std::runtime_error("cora: invalid rank/world");
@@ -501,7 +496,7 @@ void build_format(int d, int n, int r, int nt, const int32_t *rowptr,
     };
     {
       unsigned nth = n_pose_slices < 64 ? 1u : std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
-      if (const char *e = std::getenv("CORA_FORMAT_THREADS")) nth = static_cast<unsigned>(std::max(1, std::atoi(e)));
+      if (env_set(Env::FormatThreads)) nth = static_cast<unsigned>(env_int(Env::FormatThreads));
       parallel_parts(nth, [&](unsigned t) {
         Scratch W;
         W.pc.resize(static_cast<size_t>(lanes));
@@ -536,15 +531,7 @@ void build_format(int d, int n, int r, int nt, const int32_t *rowptr,
     std::vector<RowRef> rows;
     rows.reserve(L.nl_ranges);
     for (int64_t i = 0; i < L.nl_ranges; ++i) rows.push_back(local_row(L.rng_base + i));
-    // LAB BUILDS ONLY (-DCORA_LAB_BUILD): a launch without the range slices -- WRONG range rows -- measured what folding them
-    // into the pose slices could gain at best (round 5: nothing).  Not in the product library: a user who set the variable got
-    // silent garbage.
-#ifdef CORA_LAB_BUILD
-    const bool lab_skip = std::getenv("CORA_LAB_SKIP_RANGE_SLICES") != nullptr;
-#else
-    constexpr bool lab_skip = false;
-#endif
-    for (int64_t k0 = 0; k0 < L.nl_ranges && !lab_skip; k0 += kWave) {
+    for (int64_t k0 = 0; k0 < L.nl_ranges; k0 += kWave) {
       const int64_t cnt = std::min<int64_t>(kWave, L.nl_ranges - k0);
       emit_slice(F, rows, k0, k0 + cnt, kSliceOblique,
                  static_cast<int32_t>(L.rng_base + k0), static_cast<int32_t>(k0),
@@ -680,8 +667,7 @@ void build_format(int d, int n, int r, int nt, const int32_t *rowptr,
     // 2-4 % faster up to a row stride of 6, 3-9 % SLOWER from 10 on, hence kPoseFirstMaxLD.  CORA_SLICE_LJF=0
     // switches it off (measurement switch).
     F.slices_pose_first.clear();
-    const char *ljf = std::getenv("CORA_SLICE_LJF");
-    if (!(ljf && ljf[0] == '0')) {
+    if (env_flag(Env::SliceLjf)) {
       F.slices_pose_first = F.slices;
       const size_t per = (F.slices.size() + 7) / 8;
       for (size_t x = 0; x < 8; ++x) {

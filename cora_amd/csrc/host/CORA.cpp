@@ -16,6 +16,7 @@
 
 #include "../../../include/cora_hip.h"
 #include "dense.h"
+#include "../config.h"
 #include "../parallel.h"
 
 namespace CORA {
@@ -34,8 +35,7 @@ uint64_t bitsOf(const Matrix &m) {
   return h;
 }
 void traceBits(const char *stage, const Matrix &m, double a = 0, double b = 0, long n = 0) {
-  static const bool on = std::getenv("CORA_TRACE_BITS") != nullptr;
-  if (on) std::printf("[bits] %-14s %016llx  %a  %a  %ld\n", stage, static_cast<unsigned long long>(bitsOf(m)), a, b, n);
+  if (cora::env_flag(cora::Env::TraceBits)) std::printf("[bits] %-14s %016llx  %a  %a  %ld\n", stage, static_cast<unsigned long long>(bitsOf(m)), a, b, n);
 }
 }  // namespace
 
@@ -93,7 +93,7 @@ CoraResult solveCORA(Problem &problem, const Matrix &x0, int max_relaxation_rank
   // certificate matrix, storage of its factor, random start columns) is prepared on a thread of its own while the first
   // TNT solve keeps the device busy.  (The future's destructor joins: an exception below cannot leave the thread behind.)
   std::future<void> cert_prepared;
-  if (!std::getenv("CORA_NO_CERT_PREPARE"))
+  if (!cora::env_flag(cora::Env::NoCertPrepare))
     cert_prepared = std::async(std::launch::async, [&problem, LOBPCG_BLOCK_SIZE] {
       problem.prepareCertification(std::max<Index>(LOBPCG_BLOCK_SIZE, static_cast<Index>(problem.getRelaxationRank()) + 2));
     });

@@ -15,6 +15,7 @@
 #include "../../../include/cora_hip.h"
 #include "dense.h"
 #include "sparse_cholesky.h"
+#include "../config.h"
 #include "../parallel.h"
 
 namespace CORA {
@@ -244,12 +245,7 @@ void Problem::fillDataMatrix() {
 }
 
 void Problem::updateProblemData() {  // src/CORA_problem.cpp:500-510
-  const bool timing = std::getenv("CORA_TRI_TIMING") != nullptr;
-  auto tick = [t_prev = std::chrono::steady_clock::now(), timing](const char *what) mutable {
-    const auto now = std::chrono::steady_clock::now();
-    if (timing) std::fprintf(stderr, "  [update] %-26s %.3f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-    t_prev = now;
-  };
+  cora::PhaseTimer tick(cora::env_flag(cora::Env::TriTiming), "  [update]", 26, 3);
   fillRangeSubmatrices();
   tick("range submatrices");
   fillRelPoseSubmatrices();
@@ -354,8 +350,7 @@ void Problem::fillImplicitFormulationMatrices() const {
   SparseMatrix M(m, m);
   M.setFromTriplets(std::move(t));
   // same nested-dissection order as the preconditioner, restricted to the translations
-  int leaf = 8;
-  if (const char *env = std::getenv("CORA_ND_LEAF")) leaf = std::max(1, std::atoi(env));
+  const int leaf = cora::env_set(cora::Env::NdLeaf) ? static_cast<int>(cora::env_int(cora::Env::NdLeaf)) : 8;
   SparseMatrix none(nt, nt);
   const auto perm = coraOrdering(0, numPoses(), 0, static_cast<int>(nt), none, static_cast<int>(m), leaf);
   const CholeskyFactor F = choleskyFactor(M, static_cast<int>(m), 0.0, perm, symbolic_cache_.get());
@@ -415,14 +410,8 @@ void Problem::ensurePreconditioner() const {  // src/CORA_problem.cpp:512-623
     const int m = static_cast<int>(pin_last_translation_ ? N - 1 : N);
     // poses per nested-dissection leaf: 8 / 4 / 2 / 1 give an STPCG iteration of 158 / 157 / 152 / 152 us at 10^5 poses
     // (fewer substitution levels per block; nnz(L) 4.99 / 4.82 / 4.82 / 4.8 M)
-    int leaf = 2;
-    if (const char *env = std::getenv("CORA_ND_LEAF")) leaf = std::max(1, std::atoi(env));
-    const bool timing = std::getenv("CORA_TRI_TIMING") != nullptr;
-    auto tick = [t_prev = std::chrono::steady_clock::now(), timing](const char *what) mutable {
-      const auto now = std::chrono::steady_clock::now();
-      if (timing) std::fprintf(stderr, "  [precond] %-26s %.3f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-      t_prev = now;
-    };
+    const int leaf = cora::env_set(cora::Env::NdLeaf) ? static_cast<int>(cora::env_int(cora::Env::NdLeaf)) : 2;
+    cora::PhaseTimer tick(cora::env_flag(cora::Env::TriTiming), "  [precond]", 26, 3);
     // Partitioned handle: the exact solve is a sequential recurrence over the whole chain and does not shard, so the
     // preconditioner becomes BLOCK JACOBI OVER THE RANKS -- every rank factorises the diagonal block of its own rows of
     // (Q + lambda I) and applies it to its own rows with the same device solve plan.  The rows a rank owns,
@@ -484,12 +473,12 @@ void Problem::ensurePreconditioner() const {  // src/CORA_problem.cpp:512-623
             ~JoinReserve() { if (t.joinable()) t.join(); }
           } join_reserve{reserve};
           perm = coraOrdering(dim_, numPoses(), numRangeMeasurements(), numTranslationalStates(), data_matrix_, m, leaf);
-          if (timing) std::fprintf(stderr, "  [precond] elimination order (thread) %.4f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_ord).count());
+          if (tick.on()) std::fprintf(stderr, "  [precond] elimination order (thread) %.4f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_ord).count());
           // ... and so is everything of the factorisation that the regularisation does not decide: the symbolic analysis
           // (Q + lambda I has Q's pattern) and the first touch of the factor's storage (18 + 10 ms at 10^5 poses, behind
           // the 20-28 ms of the norm estimate)
           if (kind == CORA_PRECOND_REGULARIZED_CHOLESKY) choleskyAnalyze(data_matrix_, m, perm, symbolic_cache_.get());
-          if (timing) std::fprintf(stderr, "  [precond] order + analysis + storage (thread) %.4f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_ord).count());
+          if (tick.on()) std::fprintf(stderr, "  [precond] order + analysis + storage (thread) %.4f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_ord).count());
         } catch (...) {
           ordering_error = std::current_exception();
         }
@@ -520,11 +509,9 @@ void Problem::ensurePreconditioner() const {  // src/CORA_problem.cpp:512-623
       cora_set_formulation(ctx_.get(), 0);
       const Scalar Dnorm = spectralNormEstimate(ctx_.get(), N);
       cora_set_formulation(ctx_.get(), formulation_ == Formulation::Implicit ? 1 : 0);
-      Scalar max_cond = 1e6;
-      if (const char *env = std::getenv("CORA_REG_CHOLESKY_MAX_COND")) {
-        max_cond = std::stod(env);
+      const Scalar max_cond = cora::env_real(cora::Env::RegCholeskyMaxCond);
+      if (cora::env_set(cora::Env::RegCholeskyMaxCond))
         std::cout << "Loaded CORA_REG_CHOLESKY_MAX_COND from environment variable: " << max_cond << std::endl;
-      }
       precond_lambda_ = Dnorm / (max_cond - 1);
       tick("spectral norm (device)");
       F = factorise(data_matrix_, precond_lambda_);
@@ -1007,12 +994,7 @@ CertResults Problem::certifyImpl(const Matrix &Y, Scalar eta, size_t nx, const M
   std::lock_guard<std::recursive_mutex> lock(*cert_mutex_);
   checkMatrixShape("Problem::certify_solution::Y", getExpectedVariableSize(), relaxation_rank_, Y.rows(), Y.cols());
   const Index N = getDataMatrixSize(), p = Y.cols();
-  const bool timing = std::getenv("CORA_TRI_TIMING") != nullptr;
-  auto tick = [t_prev = std::chrono::steady_clock::now(), timing](const char *what) mutable {
-    const auto now = std::chrono::steady_clock::now();
-    if (timing) std::fprintf(stderr, "  [certify] %-26s %.3f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-    t_prev = now;
-  };
+  cora::PhaseTimer tick(cora::env_flag(cora::Env::TriTiming), "  [certify]", 26, 3);
   // ratio of the extreme singular values of Y from the p x p Gram matrix (:1039-1049)
   {
     Vector ev;

@@ -1,7 +1,6 @@
 #include "CORA_utils.h"
 
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +12,7 @@
 #include "../../../include/cora_hip.h"
 #include "dense.h"
 #include "sparse_cholesky.h"
+#include "../config.h"
 #include "../parallel.h"
 
 namespace CORA {
@@ -71,12 +71,7 @@ CertResults fast_verification(const SparseMatrix &S, Scalar eta, const std::vect
     std::iota(natural.begin(), natural.end(), 0);
   }
   const std::vector<int32_t> &perm = perm_in.empty() ? natural : perm_in;
-  const bool timing = std::getenv("CORA_TRI_TIMING") != nullptr;
-  auto tick = [t_prev = std::chrono::steady_clock::now(), timing](const char *what) mutable {
-    const auto now = std::chrono::steady_clock::now();
-    if (timing) std::fprintf(stderr, "    [verify] %-24s %.3f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-    t_prev = now;
-  };
+  cora::PhaseTimer tick(cora::env_flag(cora::Env::TriTiming), "    [verify]", 24, 3);
   // The PSD test runs on the host and leaves the device idle; step 2 below -- the unpreconditioned eigensolver for 1 % of
   // the budget -- needs nothing from it.  With the problem's own operator at hand (no handle to build) on one GPU it is
   // started NOW on a thread of its own and joined after the factorisation: a failed certification no longer pays for it
@@ -99,7 +94,7 @@ CertResults fast_verification(const SparseMatrix &S, Scalar eta, const std::vect
       if (th.joinable()) th.join();
     }
   } spec;
-  if (S_op && ctx && n > 100 && cora_world(ctx) == 1 && std::getenv("CORA_NO_CERT_SPECULATION") == nullptr) {
+  if (S_op && ctx && n > 100 && cora_world(ctx) == 1 && !cora::env_flag(cora::Env::NoCertSpeculation)) {
     spec.ran = true;
     spec.th = std::thread([&, c = ctx] {
       try {
@@ -189,7 +184,7 @@ CertResults fast_verification(const SparseMatrix &S, Scalar eta, const std::vect
     // switched off: Problem::setVerificationLab / FastVerificationLab per call, CORA_NO_PIVOT_SEED=1 for a whole process;
     // without it the search is the reference's own: bootstrap block, then the ILDL-preconditioned run, :112-167)
     const bool seeded = !F.negative_direction.empty() && (!lab || lab->seed_negative_direction) &&
-                        std::getenv("CORA_NO_PIVOT_SEED") == nullptr;
+                        !cora::env_flag(cora::Env::NoPivotSeed);
     std::vector<HostColumns> X0s = X0;
     if (seeded) {
       if (x0_cols >= 24) {  // no room for one more column: the seed takes the place of the last one

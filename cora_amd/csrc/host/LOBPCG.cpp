@@ -1,6 +1,5 @@
 #include "LOBPCG.h"
 
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -9,6 +8,7 @@
 
 #include "../../../include/cora_hip.h"
 #include "dense.h"
+#include "../config.h"
 
 namespace CORA {
 
@@ -97,12 +97,7 @@ LOBPCGResult LOBPCGSolver::run(const DeviceOperator &A, const std::optional<Devi
   if (m < 1 || m > 24) throw std::invalid_argument("LOBPCG: block size must be in [1, 24]");
   if (static_cast<size_t>(m) < nev) throw std::invalid_argument("LOBPCG: block smaller than nev");
   if (start.size() > 4) throw std::invalid_argument("LOBPCG: at most four pieces in the start block");
-  const bool timing = std::getenv("CORA_TRI_TIMING") != nullptr;
-  auto tick = [t_prev = std::chrono::steady_clock::now(), timing](const char *what) mutable {
-    const auto now = std::chrono::steady_clock::now();
-    if (timing) std::fprintf(stderr, "      [lobpcg] %-22s %.4f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-    t_prev = now;
-  };
+  cora::PhaseTimer tick(cora::env_flag(cora::Env::TriTiming), "      [lobpcg]", 22, 4);
   for (double *p : owned_) cora_dev_free(c_, p);
   owned_.clear();
   m_ = m;

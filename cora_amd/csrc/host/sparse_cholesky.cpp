@@ -1,7 +1,6 @@
 #include "sparse_cholesky.h"
 
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,6 +13,7 @@
 #include <functional>
 #include <numeric>
 #include <stdexcept>
+#include "../config.h"
 #include "../parallel.h"
 
 namespace CORA {
@@ -251,7 +251,7 @@ std::shared_ptr<const Symbolic> symbolicFor(const SparseMatrix &A, int n, const 
         key2 ^= key2 >> 31;
       }
   }
-  const bool use_cache = cache != nullptr && std::getenv("CORA_CHOL_NO_SYMBOLIC_CACHE") == nullptr;
+  const bool use_cache = cache != nullptr && !cora::env_flag(cora::Env::CholNoSymbolicCache);
   if (use_cache) {
     std::lock_guard<std::mutex> lock(cache->impl->m);
     auto &slot = cache->impl->slot;
@@ -262,12 +262,7 @@ std::shared_ptr<const Symbolic> symbolicFor(const SparseMatrix &A, int n, const 
         return slot[0];
       }
   }
-  const bool timing_ = std::getenv("CORA_TRI_TIMING") != nullptr;
-  auto tick_ = [t_prev = std::chrono::steady_clock::now(), timing_](const char *what) mutable {
-    const auto now = std::chrono::steady_clock::now();
-    if (timing_) std::fprintf(stderr, "      [symbolic] %-20s %.4f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-    t_prev = now;
-  };
+  cora::PhaseTimer tick_(cora::env_flag(cora::Env::TriTiming), "      [symbolic]", 20, 4);
   auto S = std::make_shared<Symbolic>();
   S->key = key;
   S->key2 = key2;
@@ -277,7 +272,7 @@ std::shared_ptr<const Symbolic> symbolicFor(const SparseMatrix &A, int n, const 
   std::vector<int32_t> &Cp = S->Cp, &Ci = S->Ci, &Cmap = S->Cmap;
   Cp.assign(static_cast<size_t>(n) + 1, 0);
   unsigned np_ = n < 20000 ? 1u : std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
-  if (const char *e = std::getenv("CORA_SYMBOLIC_THREADS")) np_ = static_cast<unsigned>(std::max(1, std::atoi(e)));
+  if (cora::env_set(cora::Env::SymbolicThreads)) np_ = static_cast<unsigned>(cora::env_int(cora::Env::SymbolicThreads));
   parallelRun(np_, [&](unsigned t) {  // entries per column (columns are independent)
     for (int k = static_cast<int>(static_cast<int64_t>(n) * t / np_); k < static_cast<int>(static_cast<int64_t>(n) * (t + 1) / np_); ++k) {
       const int old = perm[k];
@@ -545,12 +540,7 @@ CholeskyFactor choleskyFactor(const SparseMatrix &A, int m, double shift, const 
   const int n = m;
   F.n = n;
   if (static_cast<int>(perm.size()) != n) throw std::invalid_argument("choleskyFactor: bad permutation size");
-  const bool timing = std::getenv("CORA_TRI_TIMING") != nullptr;
-  auto tick = [t_prev = std::chrono::steady_clock::now(), timing](const char *what) mutable {
-    const auto now = std::chrono::steady_clock::now();
-    if (timing) std::fprintf(stderr, "    [cholesky] %-24s %.3f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-    t_prev = now;
-  };
+  cora::PhaseTimer tick(cora::env_flag(cora::Env::TriTiming), "    [cholesky]", 24, 3);
   F.perm = perm;
   F.iperm.assign(static_cast<size_t>(A.rows()), -1);
   for (int i = 0; i < n; ++i) F.iperm[perm[i]] = i;
@@ -620,7 +610,7 @@ CholeskyFactor choleskyFactor(const SparseMatrix &A, int m, double shift, const 
   };
   int first_failure = n;  // sequential semantics: the smallest k whose pivot is not positive
   unsigned nth = std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
-  if (const char *e = std::getenv("CORA_CHOL_THREADS")) nth = static_cast<unsigned>(std::max(1, std::atoi(e)));
+  if (cora::env_set(cora::Env::CholThreads)) nth = static_cast<unsigned>(cora::env_int(cora::Env::CholThreads));
   std::vector<int32_t> task;  // row -> subtree task (-1: a separator above the tasks)
   int ntask = 0;
   std::vector<int32_t> tptr, trows;
@@ -693,7 +683,7 @@ CholeskyFactor choleskyFactor(const SparseMatrix &A, int m, double shift, const 
     // factor is the same bit for bit.  That relies on the row's elimination order visiting every column below k0
     // before the first trailing one; a row for which this does not hold sends the whole group down the plain path.
     int k0 = n;
-    if (std::getenv("CORA_CHOL_NO_TRAILING_GROUP") == nullptr)
+    if (!cora::env_flag(cora::Env::CholNoTrailingGroup))
       while (k0 > 0 && n - k0 < 32 && task[k0 - 1] < 0 && Cp[k0] - Cp[k0 - 1] >= 64) --k0;
     if (n - k0 < 2) k0 = n;
     {

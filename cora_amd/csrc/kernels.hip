@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "config.h"
 #include "cora_internal.h"
 #include "kernels.h"
 

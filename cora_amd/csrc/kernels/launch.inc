@@ -31,16 +31,14 @@ static hipError_t launch_spmm_ld(const SpmmArgs &A_in, int epi, hipStream_t st) 
   const int grid = A.n_chunks + 8 * ((A.n_slices + 7) / 8);
   A.kappa_long_base = grid;  // = launch_spmm_blocks(A_in): the long rows' own slots follow the per-block ones
   if (A.n_real_chunks + A.n_slices == 0) return hipSuccess;
-  // lab switch: extra (unused) LDS per block limits the wavefronts resident per CU
-  static const unsigned xlds = [] { const char *e = std::getenv("CORA_SPMM_EXTRA_LDS"); return e ? static_cast<unsigned>(std::atoi(e)) : 0u; }();
   switch (epi) {
-    case EPI_NONE: hipLaunchKernelGGL((k_spmm<LD, D, EPI_NONE>), dim3(grid), dim3(64), xlds, st, A); break;
-    case EPI_S: hipLaunchKernelGGL((k_spmm<LD, D, EPI_S>), dim3(grid), dim3(64), xlds, st, A); break;
+    case EPI_NONE: hipLaunchKernelGGL((k_spmm<LD, D, EPI_NONE>), dim3(grid), dim3(64), 0, st, A); break;
+    case EPI_S: hipLaunchKernelGGL((k_spmm<LD, D, EPI_S>), dim3(grid), dim3(64), 0, st, A); break;
     case EPI_HVP_K:
       if (!A.kappa_partial) return hipErrorInvalidValue;
-      hipLaunchKernelGGL((k_spmm<LD, D, EPI_HVP_K>), dim3(grid), dim3(64), xlds, st, A);
+      hipLaunchKernelGGL((k_spmm<LD, D, EPI_HVP_K>), dim3(grid), dim3(64), 0, st, A);
       break;
-    default: hipLaunchKernelGGL((k_spmm<LD, D, EPI_HVP>), dim3(grid), dim3(64), xlds, st, A); break;
+    default: hipLaunchKernelGGL((k_spmm<LD, D, EPI_HVP>), dim3(grid), dim3(64), 0, st, A); break;
   }
   return hipGetLastError();
 }
@@ -63,7 +61,7 @@ hipError_t launch_spmm_g5(const SpmmArgs &A, int ld, int d, int epi, hipStream_t
 #if CORA_LDG & 1
 // slices from which the pose slices read X through their LDS windows (kWinMinSlices; CORA_SPMM_WINDOW_MIN_SLICES or
 // cora_debug_spmm_window_min_slices: the tests run the window form of every row stride on small problems)
-int g_win_min_slices = [] { const char *e = std::getenv("CORA_SPMM_WINDOW_MIN_SLICES"); return e ? std::atoi(e) : kWinMinSlices; }();
+int g_win_min_slices = static_cast<int>(env_int(Env::SpmmWindowMinSlices));
 SPMM_GROUP(0)
 hipError_t launch_spmm(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st) {
   if (ld <= 5) return launch_spmm_g0(A, ld, d, epi, st);

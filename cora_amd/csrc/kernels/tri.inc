@@ -416,16 +416,8 @@ __device__ __forceinline__ void group_sum_all(double (&x)[N], int gs) {
   }
 }
 
-#ifndef CORA_SUB_F32
-#define CORA_SUB_F32 0  // lab: the substitution blocks' coefficients stored as fp32 (capi.hip uploads them so with CORA_SUB_F32=1)
-#endif
-#if CORA_SUB_F32
-typedef float SubCoef;
-#else
-typedef double SubCoef;
-#endif
 struct SubRegs {  // a lane's entries of one level: coefficients and (two per dword) local row indices
-  SubCoef v[kSubNpl];
+  double v[kSubNpl];
   uint32_t i[kSubNpl / 2];
   int32_t row;  // forward sweeps that store a level's rows as they are solved (kDirect): the internal row of the lane's row
 };
@@ -596,7 +588,7 @@ __global__ __launch_bounds__(kSubThreads, CORA_SUB_MIN_BLOCKS) void k_subblock(S
   const SubDesc bd = S.desc[b];
   const int nb = bd.nrows, rb = bd.row_begin;
   const int nlev = BWD ? bd.b_nlev : bd.f_nlev;
-  const SubCoef *__restrict__ gv = reinterpret_cast<const SubCoef *>(Q.val) + (BWD ? bd.b_ent_begin : bd.f_ent_begin);
+  const double *__restrict__ gv = Q.val + (BWD ? bd.b_ent_begin : bd.f_ent_begin);
   const uint16_t *__restrict__ gi = Q.idx;
   const int4 *__restrict__ gh = reinterpret_cast<const int4 *>(Q.hdr) + (BWD ? bd.b_lev_begin : bd.f_lev_begin);
   const int wave_base = __builtin_amdgcn_readfirstlane(tid);
@@ -642,7 +634,7 @@ __global__ __launch_bounds__(kSubThreads, CORA_SUB_MIN_BLOCKS) void k_subblock(S
       const u32x2 q = factor_load(reinterpret_cast<const u32x2 *>(gi + h.w + lane * 4));
       R.i[0] = q.x, R.i[1] = q.y;
     }
-    const SubCoef *__restrict__ pv = gv + h.z + lane;
+    const double *__restrict__ pv = gv + h.z + lane;
 #pragma unroll
     for (int u = 0; u < kSubNpl; ++u)
       if (u < npl) R.v[u] = factor_load(pv + u * nlane);

@@ -6,7 +6,10 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <vector>
+
+#include "config.h"
 
 namespace cora {
 
@@ -210,14 +213,18 @@ static int hip_err(std::string *err, hipError_t e, const char *what) {
 int p2p_create(int device, int rank, int world, P2PState **out, void *blob_out, std::string *err) {
   if (!out || !blob_out || world < 1 || world > kP2PMaxWorld || rank < 0 || rank >= world)
     return set_err(err, "p2p: bad arguments (at most " + std::to_string(kP2PMaxWorld) + " ranks)");
+  double secs;
+  try {
+    secs = env_real(Env::P2pTimeoutS);
+  } catch (const std::exception &) {
+    return set_err(err, "p2p: CORA_P2P_TIMEOUT_S is not a number");
+  }
   if (hip_err(err, hipSetDevice(device), "hipSetDevice")) return 1;
   auto *s = new P2PState;
   s->device = device;
   s->rank = rank;
   s->world = world;
   s->bytes = kAgDataOff + 2ull * world * kP2PSlotBytes;
-  const char *te = std::getenv("CORA_P2P_TIMEOUT_S");
-  const double secs = te ? std::max(0.001, std::atof(te)) : 60.0;
   s->timeout_ticks = static_cast<unsigned long long>(secs * 1e8);  // wall_clock64: 100 MHz
   // Memory the peers write and this rank polls: uncached first (what RCCL's own flags and buffers live in on this part),
   // then fine-grained, then ordinary device memory (coherent at system scope through the atomics' cache policy only).

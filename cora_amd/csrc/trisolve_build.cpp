@@ -2,7 +2,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -13,38 +12,35 @@
 #include <future>
 #include <thread>
 #include <utility>
+#include "config.h"
 #include "parallel.h"
 
 namespace cora {
 
 namespace {
-// Tunables below marked "env" are read ONCE, when the library is loaded (lab sweeps set them per process: tools/plan_sweep.sh).
-// They were process-wide variables that every build_tri_plan call rewrote from the environment -- a data race between the
-// rank threads that build their plans at the same time (round-4 advice).
-int64_t env_i64(const char *name, int64_t dflt, int64_t lo, int64_t hi) {
-  const char *e = std::getenv(name);
-  return e ? std::min(hi, std::max(lo, static_cast<int64_t>(std::atoll(e)))) : dflt;
-}
+// Tunables read from the environment here are read ONCE, when the library is loaded (lab sweeps set them per process:
+// tools/plan_sweep.sh).  They were process-wide variables that every build_tri_plan call rewrote from the environment -- a
+// data race between the rank threads that build their plans at the same time (round-4 advice).
 constexpr int kBorderRowNnz = 4096;  // rows of L longer than this (landmarks) always belong to the last stage
 constexpr int kFirstCap = 64;        // rows of a stage-0 subtree: what one wavefront holds (a pair of
                                      // nested-dissection leaves, their separator and range rows); 32 / 40 / 48 /
                                      // 64 measured 154 / 155 / 162 / 151 us per apply at 10^5 poses
 constexpr int kCapGrowth = 16;       // stage k subtrees hold up to kFirstCap * kCapGrowth^k rows
 constexpr int kTopCap = 1536;        // stop cutting once this few rows are left: they form the last stage
-const int64_t kTopInverseNnz = env_i64("CORA_TRI_TOP_INV", 2500000, 0, INT64_MAX);  // ... or once the inverse of what is left has this few entries:
+const int64_t kTopInverseNnz = env_int(Env::TriTopInv);  // ... or once the inverse of what is left has this few entries:
                                              // a launch floor (~5 us) is worth ~25 MB of traffic, so small
                                              // factors are applied as ONE explicit inverse (2 products)
-const int kShortRow = static_cast<int>(env_i64("CORA_TRI_SHORT_ROW", 64, 8, 1 << 30));  // entries: <= this -> 8 lanes per row
-const int kWaveRow = static_cast<int>(env_i64("CORA_TRI_WAVE_ROW", 1024, 64, 1 << 30));  // entries: <= this -> one wavefront per row, else chunked
-const int kChunk = static_cast<int>(env_i64("CORA_TRI_CHUNK", 512, 64, 1 << 30));
+const int kShortRow = static_cast<int>(env_int(Env::TriShortRow));  // entries: <= this -> 8 lanes per row
+const int kWaveRow = static_cast<int>(env_int(Env::TriWaveRow));  // entries: <= this -> one wavefront per row, else chunked
+const int kChunk = static_cast<int>(env_int(Env::TriChunk));
 constexpr int kDenseBlock = 64;      // stage-0 blocks up to this many rows use the dense wavefront kernel
-const int kSubRows = static_cast<int>(env_i64("CORA_TRI_SUB_ROWS", 512, 32, 2048));  // workgroup blocks (SubBlockOpHost): rows of a block (its tile of right-hand sides sits in LDS:
-const int kSubEnt = static_cast<int>(env_i64("CORA_TRI_SUB_ENT", 5000, 100, 1 << 30));  // 512 rows x 24 columns = 96 KB) and entries of L per block (streamed since round 2: a cap on a block's work, not on LDS)
+const int kSubRows = static_cast<int>(env_int(Env::TriSubRows));  // workgroup blocks (SubBlockOpHost): rows of a block (its tile of right-hand sides sits in LDS:
+const int kSubEnt = static_cast<int>(env_int(Env::TriSubEnt));  // 512 rows x 24 columns = 96 KB) and entries of L per block (streamed since round 2: a cap on a block's work, not on LDS)
 constexpr int kSnCapChain = 4;  // rows of a supernode of the substitution blocks (a 3-D pose: 3 rotation rows + translation)
-const int kLaneEntries = static_cast<int>(env_i64("CORA_TRI_LANE_ENTRIES", 8, 1, 8));  // entries one lane of a row walks through (<= kSubNpl of the kernel: they sit in registers)
-const int kLevelLanes = static_cast<int>(env_i64("CORA_TRI_LEVEL_LANES", 256, 64, 256));  // rows x lanes per row of one level (<= 256 = kSubThreads of the kernel)
+const int kLaneEntries = static_cast<int>(env_int(Env::TriLaneEntries));  // entries one lane of a row walks through (<= kSubNpl of the kernel: they sit in registers)
+const int kLevelLanes = static_cast<int>(env_int(Env::TriLevelLanes));  // rows x lanes per row of one level (<= 256 = kSubThreads of the kernel)
 constexpr int kSubWaves = 4, kWaveLanes = 64;  // wavefronts of a substitution block's workgroup (kSubThreads of the kernel / 64)
-const int kSplitMinRows = static_cast<int>(env_i64("CORA_TRI_SPLIT_MIN_ROWS", 1 << 20, 1, 1 << 30));  // a chunk of a level is closed early when the next rows are half as long, from this many rows on.
+const int kSplitMinRows = static_cast<int>(env_int(Env::TriSplitMinRows));  // a chunk of a level is closed early when the next rows are half as long, from this many rows on.
                               // Never, since round 4: closing early saves padding (tile reads 15.4 M instead of 16.3 M at 10^5
                               // poses) and costs barrier levels (25.0 k instead of 20.0 k); measured: 10^5 poses 117.6 / 118.4 us
                               // per iteration (16 / never), 10^4 poses 62.9 / 58.4, tiers 83.1 / 78.6 us per product, mrclam3b 85.7 / 77.0
@@ -101,15 +97,10 @@ void finalize(const RowList &R, RowOpHost &op) {
 void build_tri_plan(int m, const int32_t *Lp, const int32_t *Li, const double *Lx,
                     const std::vector<int32_t> &row_of, int32_t zero_row, TriPlan &P,
                     const std::vector<int32_t> *group, int32_t aux_base) {
-  int kSnCap = kSnCapChain;  // (local: plans are built from several rank threads at once)
-  if (const char *e = std::getenv("CORA_TRI_SN_CAP")) kSnCap = std::min(32, std::max(1, std::atoi(e)));
-  const bool timing = std::getenv("CORA_TRI_TIMING") != nullptr;
-  auto tick = [t_prev = std::chrono::steady_clock::now(), timing](const char *what) mutable {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "  [tri plan] %-28s %.3f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-    t_prev = now;
-  };
+  const bool sn_cap_set = env_set(Env::TriSnCap);
+  int kSnCap = sn_cap_set ? static_cast<int>(env_int(Env::TriSnCap)) : kSnCapChain;  // (local: plans are built from several rank threads at once)
+  const bool timing = env_flag(Env::TriTiming);
+  PhaseTimer tick(timing, "  [tri plan]", 28, 3);
   P = TriPlan();
   P.m = m;
   P.zero_row = zero_row;
@@ -210,7 +201,7 @@ void build_tri_plan(int m, const int32_t *Lp, const int32_t *Li, const double *L
     });
     for (unsigned t = 0; t < nt0; ++t) closed = closed && !open_[t];
   }
-  const bool check_tree = closed && std::getenv("CORA_TRI_CHECK_ETREE") != nullptr;  // test hook: both ways, must agree
+  const bool check_tree = closed && env_flag(Env::TriCheckEtree);  // test hook: both ways, must agree
   const std::vector<int32_t> parent_closed = check_tree ? parent : std::vector<int32_t>();
   if (!closed || check_tree) {
     std::fill(parent.begin(), parent.end(), -1);
@@ -232,7 +223,7 @@ void build_tri_plan(int m, const int32_t *Lp, const int32_t *Li, const double *L
   // ten times as high for its size (MR.CLAM 3b: 560 levels at 20 k rows, a chain of 450 k rows: 77) -- and there 8 rows
   // per supernode take 10-15 % off an iteration (mrclam6 115 -> 103, tiers 98 -> 84 us per product end to end), while
   // on the chains they cost 8 % (rows get longer).  16 exceeds what a level of the kernel holds.
-  if (!std::getenv("CORA_TRI_SN_CAP")) {
+  if (!sn_cap_set) {
     std::vector<int32_t> depth(static_cast<size_t>(m), 1);
     int height = 0;
     for (int i = 0; i < m; ++i) {
@@ -261,8 +252,7 @@ void build_tri_plan(int m, const int32_t *Lp, const int32_t *Li, const double *L
   // ---- two-stage form: workgroup blocks solved by substitution + ONE explicit inverse of what is left
   bool sub0 = false;
   {
-    const char *e = std::getenv("CORA_TRI_SUB");
-    const bool want = aux_base >= 0 && !(e && std::atoi(e) == 0);
+    const bool want = aux_base >= 0 && env_int(Env::TriSub) != 0;
     if (want && remaining + (m - first_border) > kTopCap && inverse_nnz_of_rest() > kTopInverseNnz) {
       std::vector<int64_t> esz(m, 0);
       for (int v = 0; v < first_border; ++v) { sz[v] = 1; esz[v] = Lp[v + 1] - Lp[v] - 1; }
@@ -270,55 +260,20 @@ void build_tri_plan(int m, const int32_t *Lp, const int32_t *Li, const double *L
         const int p = parent[v];
         if (p >= 0 && p < first_border) { sz[p] += sz[v]; esz[p] += esz[v]; }
       }
-      // Height of every subtree in rows (a block's barrier levels grow with it: a supernode of <= kSnCap rows per level).
-      // A launch of the sweep lasts as long as its DEEPEST block -- on the reference's mid-size data sets a block is alone
-      // on its CU (mrclam6: 17 levels where the mean is 7.8, profiles/r05_kernel_evolution.md step 13) -- so subtrees much
-      // taller than the typical block are not taken whole: their top rows go to the last stage and what hangs below them
-      // becomes blocks of its own.  Two passes: the blocks the size caps alone would give, the median of their heights,
-      // then the same selection with heights capped at CORA_TRI_LEVEL_CAP times that median.  OFF by default (0): measured
-      // in round 6 (profiles/r06_kernel_evolution.md) at 1.25 / 1.5 / 2.0 -- mrclam6 85.7-87.6 -> 88.8-91.6 / 88.0-89.1 /
-      // 85.8-87.5 us per product end to end, tiers 68.1-68.5 -> 70.6 / 68.8-69.2 / 67.8-68.4, mrclam3b 65.8-66.3 -> 65.3-67.2 /
-      // 70.7-74.7 / 66.9-67.1, 10^5 poses unchanged: what the deepest blocks lose the last stage's products gain (the rows cut
-      // off the tall subtrees join the explicit inverse).  Kept as a switch.
-      std::vector<int32_t> hgt(static_cast<size_t>(first_border), 1);
-      for (int v = 0; v < first_border; ++v) {
-        const int p = parent[v];
-        if (p >= 0 && p < first_border) hgt[p] = std::max(hgt[p], hgt[v] + 1);
-      }
       int64_t taken = 0;
       int nblocks = 0;
-      auto select = [&](int32_t max_height, std::vector<int32_t> *heights) {
-        taken = 0;
-        nblocks = 0;
-        for (int v = first_border - 1; v >= 0; --v) {
-          const int p = parent[v];
-          if (p >= 0 && p < first_border && stage[p] == 0) {
-            stage[v] = 0;
-            blk[v] = blk[p];
-            ++taken;
-          } else if (sz[v] <= kSubRows && esz[v] <= kSubEnt && hgt[v] <= max_height &&
-                     (sz[v] >= kMinBlock || p < 0 || p >= first_border) &&
-                     !(group && p >= 0 && (*group)[v] >= 0 && (*group)[v] == (*group)[p])) {
-            stage[v] = 0;
-            blk[v] = v;
-            ++nblocks;
-            ++taken;
-            if (heights) heights->push_back(hgt[v]);
-          }
-        }
-      };
-      const double level_cap = [] { const char *e = std::getenv("CORA_TRI_LEVEL_CAP"); return e ? std::atof(e) : 0.0; }();
-      std::vector<int32_t> heights;
-      select(INT32_MAX, &heights);
-      if (level_cap > 0.0 && heights.size() >= 8) {
-        std::nth_element(heights.begin(), heights.begin() + heights.size() / 2, heights.end());
-        const int32_t median = heights[heights.size() / 2];
-        const int32_t max_height = static_cast<int32_t>(std::ceil(level_cap * median));
-        if (*std::max_element(heights.begin(), heights.end()) > max_height) {
-          if (timing) std::fprintf(stderr, "  [tri plan] block heights: median %d rows, cap %d\n", median, max_height);
-          std::fill(stage.begin(), stage.end(), -1);
-          std::fill(blk.begin(), blk.end(), -1);
-          select(max_height, nullptr);
+      for (int v = first_border - 1; v >= 0; --v) {
+        const int p = parent[v];
+        if (p >= 0 && p < first_border && stage[p] == 0) {
+          stage[v] = 0;
+          blk[v] = blk[p];
+          ++taken;
+        } else if (sz[v] <= kSubRows && esz[v] <= kSubEnt && (sz[v] >= kMinBlock || p < 0 || p >= first_border) &&
+                   !(group && p >= 0 && (*group)[v] >= 0 && (*group)[v] == (*group)[p])) {
+          stage[v] = 0;
+          blk[v] = v;
+          ++nblocks;
+          ++taken;
         }
       }
       // what is left above the blocks is applied as one explicit inverse: worth it while its entries stay a fraction of
@@ -872,7 +827,7 @@ void build_tri_plan(int m, const int32_t *Lp, const int32_t *Li, const double *L
     {
       const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
       size_t nth = std::min<size_t>(std::min<size_t>(hw, 48), std::max<size_t>(members.size() / 8, 1));
-      if (const char *e = std::getenv("CORA_TRI_THREADS")) nth = std::max(1, std::atoi(e));
+      if (env_set(Env::TriThreads)) nth = static_cast<size_t>(env_int(Env::TriThreads));
       cora::parallel_parts(static_cast<unsigned>(nth), [&](unsigned t) {
         for (size_t b = t; b < members.size(); b += nth) build_block(b);
       });
@@ -1049,8 +1004,9 @@ void build_tri_plan(int m, const int32_t *Lp, const int32_t *Li, const double *L
     if (sub0) {
       int64_t extra = 0;
       for (size_t t = 0; t < nz; ++t) extra += static_cast<int64_t>(aux_of[wt_col[k][t]].size());
-      int64_t unfold_min = 2000000;  // extra entries that outweigh a launch AND the sum's own chain of latencies (measured: folded wins at 10^4 and 10^5 poses -- 7.7 vs 10.8 us, 13.6 vs 19.7 us --, loses at 10^6: 203 vs 99 us)
-      if (const char *e = std::getenv("CORA_TRI_UNFOLD_MIN")) unfold_min = std::atoll(e);
+      // extra entries that outweigh a launch AND the sum's own chain of latencies (default 2 000 000; measured: folded wins
+      // at 10^4 and 10^5 poses -- 7.7 vs 10.8 us, 13.6 vs 19.7 us --, loses at 10^6: 203 vs 99 us)
+      const int64_t unfold_min = env_int(Env::TriUnfoldMin);
       fold = extra < unfold_min;
       if (timing) std::fprintf(stderr, "  [tri plan] top stage: %lld entries, %lld more with the aux sums folded in: %s\n",
                                static_cast<long long>(nz), static_cast<long long>(extra), fold ? "folded" : "separate sum");
@@ -1061,21 +1017,6 @@ void build_tri_plan(int m, const int32_t *Lp, const int32_t *Li, const double *L
       F.begin_row(row_of[i]);
       for (int32_t q = cnt[i]; q < cnt[i + 1]; ++q) {
         F.add(row_of[cc[q]], vv[q]);
-#ifdef CORA_LAB_BUILD
-        // LAB (wrong results): upper bounds of two forms of the folded product that were priced before building --
-        //   CORA_LAB_DROP_PAIR_AUX : columns with at most two aux rows (the separators) gather none of them: what a grouped gather
-        //                            of [b | aux | aux] could gain at best (round 6, step 8: 13.0 -> 9.7 us);
-        //   CORA_LAB_AUX_CAP=n     : columns with more than n aux rows (the landmarks: one per solve block) gather n of them: what a
-        //                            hierarchical reduction of the landmark slots inside the forward sweep (the round-5 review's
-        //                            item 1a: "the last stage sees 8 partials per row") could gain at best.
-        static const bool lab_drop = std::getenv("CORA_LAB_DROP_PAIR_AUX") != nullptr;
-        static const int lab_cap = std::getenv("CORA_LAB_AUX_CAP") ? std::atoi(std::getenv("CORA_LAB_AUX_CAP")) : 0;
-        if (lab_drop && aux_of[cc[q]].size() <= 2) continue;
-        if (lab_cap > 0 && sub0 && fold && static_cast<int>(aux_of[cc[q]].size()) > lab_cap) {
-          for (int a = 0; a < lab_cap; ++a) F.add(aux_base + aux_of[cc[q]][a], vv[q]);
-          continue;
-        }
-#endif
         if (sub0 && fold)
           for (int32_t a : aux_of[cc[q]]) F.add(aux_base + a, vv[q]);
       }

@@ -493,17 +493,19 @@ int cora_debug_stpcg_path(const cora_ctx *ctx);
  * device-resident STPCG iterations captured once as a hipGraph and replayed (one GPU, fused forms).
  * out[0] = graphs captured so far, out[1] = batches replayed (both 0 unless the switch is on). */
 int cora_debug_stpcg_graph(const cora_ctx *ctx, long out[2]);
-/* EVERY environment variable the library reads (round 6: one table; `grep -rn 'getenv("CORA_' cora_amd/csrc` finds the same
- * names and no others).  NONE changes what is computed beyond the rounding of a different (equally valid) order of operations;
- * the two lab switches that produced wrong results (CORA_LAB_SKIP_RANGE_SLICES, the CORA_SUB_F32 upload) are no longer in the
- * product library: they exist only in builds with -DCORA_LAB_BUILD / -DCORA_SUB_F32=1.
+/* EVERY environment variable the library reads: the table of cora_amd/csrc/config.h, the only place that reads them
+ * (tests/test_config_cpu.py checks that this list names the same variables).  NONE changes what is computed beyond the
+ * rounding of a different (equally valid) order of operations.  A switch ("=1") is on when the variable is set to a
+ * non-empty value that does not start with 0; numbers are clamped to their range.  [once]: read at first use and kept for
+ * the life of the process; every other variable is read each time a call needs it.
  *
- * Forms of the STPCG iteration (all tested against each other, tests/test_gpu_solver.py; read per solve):
+ * Forms of the STPCG iteration (all tested against each other, tests/test_gpu_solver.py):
  *   CORA_NO_FUSE=1            one pass per operation instead of the fused vector passes
  *   CORA_NO_SWEEP_FUSE=1      vector passes are not folded into the sweeps of the two-stage Cholesky solve
  *   CORA_NO_INVERSE_FUSE=1    ... nor into the two products of a one-explicit-inverse plan
- *   CORA_NO_RESIDUAL_SLOTS=1  the one-explicit-inverse iteration finishes <r, r> with a ticket in its residual pass
- *   CORA_NO_KAPPA_FOLD=1, CORA_KAPPA_FOLD_MAX=n (4096)   kappa = <p, Hp> gets a launch of its own (always | above n partials)
+ *   CORA_NO_RESIDUAL_SLOTS=1  [once] the one-explicit-inverse iteration finishes <r, r> with a ticket in its residual pass
+ *   CORA_NO_KAPPA_FOLD=1, CORA_KAPPA_FOLD_MAX=n (4096) [once]   kappa = <p, Hp> gets a launch of its own (always | above n
+ *                             partials)
  *   CORA_NO_TNT_FUSE=1        cora_tnt_accept_dev forms Q X again instead of taking the trial's
  * Host loop of cora_stpcg_dev (same numbers, tests run one problem under each):
  *   CORA_STPCG_DEPTH=0|1      the host waits for every iteration | runs one whole iteration ahead (default: the next
@@ -512,26 +514,34 @@ int cora_debug_stpcg_graph(const cora_ctx *ctx, long out[2]);
  *   CORA_STPCG_BATCH=n        n iterations enqueued, all waited for (the form partitioned handles always use)
  *   CORA_STPCG_GRAPH=1        opt-in hipGraph replay of batches (measured slower on this part)
  * Partitioned handles:
- *   CORA_NO_EXCHANGE_OVERLAP=1, CORA_EXCHANGE_OVERLAP_MIN_SLICES=n (2048)   interior slices beside the exchange: never | from n
- *                             interior slices per rank
+ *   CORA_NO_EXCHANGE_OVERLAP=1, CORA_EXCHANGE_OVERLAP_MIN_SLICES=n (2048) [once]   interior slices beside the exchange:
+ *                             never | from n interior slices per rank
  *   CORA_IMPLICIT_WHOLE_GATHER=1   the implicit formulation gathers whole shards instead of the packed translation rows
+ *   CORA_P2P_TIMEOUT_S=x      seconds a collective of the device-side transport waits for its peers (60, at least 0.001)
  * Format of Q and the product's launch (same products to rounding; bit-identical where the order of sums is unchanged):
- *   CORA_CHAIN_SLICES=0       pose slices in the plain layout (all columns explicit)
- *   CORA_SLICE_LJF=...        order of the slices inside an XCD's range (longest first)
- *   CORA_SPMM_EXTRA_LDS=bytes, CORA_SPMM_WINDOW_MIN_SLICES=n   occupancy / LDS-window experiments of k_spmm
+ *   CORA_CHAIN_SLICES=0       [once] pose slices in the plain layout (all columns explicit)
+ *   CORA_SLICE_LJF=0          no longest-first order of the slices inside an XCD's range
+ *   CORA_SPMM_WINDOW_MIN_SLICES=n (2048) [once]   k_spmm's LDS-window form from n slices on
+ *                             (cora_debug_spmm_window_min_slices overrides it)
  *   CORA_FORMAT_THREADS=n, CORA_FORMAT_TIMING=1   host threads of the format builder; its phase times on stderr
  * Solve plan of a Cholesky factor (trisolve_build.cpp; every plan solves the same system, tests/test_trisolve_cpu.py):
- *   CORA_TRI_SUB=0|1          force the explicit-stage form | the substitution-block form
- *   CORA_TRI_SN_CAP=n         rows per supernode whose diagonal block is inverted (default: a pose)
- *   CORA_TRI_UNFOLD_MIN=n     aux sums folded into the last stage's first product below n extra entries
- *   CORA_TRI_LEVEL_CAP=x      (round 6; default 0 = off: measured, no gain) subtrees taller than x times the median block are
- *                             not taken whole as solve blocks
+ *   CORA_TRI_SUB=0            the explicit-stage form instead of the substitution blocks
+ *   CORA_TRI_SN_CAP=n         rows per supernode whose diagonal block is inverted, 1-32 (default: 4 or 8 by tree height)
+ *   CORA_TRI_UNFOLD_MIN=n     aux sums folded into the last stage's first product below n extra entries (2000000)
  *   CORA_TRI_THREADS=n, CORA_TRI_CHECK_ETREE=1, CORA_TRI_TIMING=1   builder threads; elimination tree computed both ways
  *                             and compared; phase times of set-up on stderr
- *   CORA_SUB_IO_LISTS=1, CORA_IO_STATS=1   row I/O of the sweeps from index lists instead of run tables; run statistics
+ *   CORA_SUB_IO_LISTS=1       row I/O of the sweeps from index lists instead of run tables
+ *   [once] lab tunables of the plan, with their defaults and ranges (tools/plan_sweep.sh):
+ *   CORA_TRI_TOP_INV=n (2500000, >= 0)   entries of an inverse of what is left that make it the last stage
+ *   CORA_TRI_SHORT_ROW=n (64, 8..2^30), CORA_TRI_WAVE_ROW=n (1024, 64..2^30), CORA_TRI_CHUNK=n (512, 64..2^30)
+ *                             row classes of a product: 8 lanes | a wavefront per row | chunks of n entries
+ *   CORA_TRI_SUB_ROWS=n (512, 32..2048), CORA_TRI_SUB_ENT=n (5000, 100..2^30)   rows and entries of a substitution block
+ *   CORA_TRI_LANE_ENTRIES=n (8, 1..8), CORA_TRI_LEVEL_LANES=n (256, 64..256)   entries per lane, lanes per level
+ *   CORA_TRI_SPLIT_MIN_ROWS=n (2^20, 1..2^30)   level chunks closed early from n rows on
  * Host factorisation and ordering (sparse_cholesky.cpp, CORA_problem.cpp; bit-identical factors in every setting):
  *   CORA_CHOL_THREADS=n, CORA_SYMBOLIC_THREADS=n, CORA_CHOL_NO_SYMBOLIC_CACHE=1, CORA_CHOL_NO_TRAILING_GROUP=1
- *   CORA_ND_LEAF=n            poses per leaf of the nested dissection (2)
+ *   CORA_ND_LEAF=n            poses per leaf of the nested dissection, >= 1 (2 for the preconditioner, 8 for the
+ *                             translation factor of the implicit formulation)
  *   CORA_REG_CHOLESKY_MAX_COND=x   kappa_max of the regularised preconditioner (1e6, src/CORA_problem.cpp:551)
  * solveCORA (host/CORA.cpp, CORA_utils.cpp):
  *   CORA_NO_CERT_PREPARE=1    the first certification's pattern work is not prepared beside the first TNT solve
@@ -539,7 +549,11 @@ int cora_debug_stpcg_graph(const cora_ctx *ctx, long out[2]);
  *   CORA_NO_PIVOT_SEED=1      (round 6) fast_verification keeps the reference's plain order after a failed factorisation --
  *                             LOBPCG from the bootstrap block, then the ILDL branch (src/CORA_utils.cpp:112-167) -- instead of
  *                             seeding the block with the failed pivot's direction of non-positive curvature
- *   CORA_TRACE_BITS=1         the bits of every stage of the staircase on stderr (determinism bisection) */
+ *   CORA_TRACE_BITS=1         [once] the bits of every stage of the staircase on stdout (determinism bisection) */
+/* The effective value of every variable above, one "NAME=value" line each, " (default)" appended where the variable is
+ * unset (switches print 1 | 0).  Reading a [once] variable here fixes it as its first use would.  Writes at most len bytes
+ * including the terminating NUL; returns the length of the whole text (a larger buffer is needed when >= len). */
+int cora_debug_config(char *buf, int len);
 
 int cora_debug_format_spmm_host(const cora_ctx *ctx, const double *X, int ldx,
                                 int k, double *out, int ldo);
