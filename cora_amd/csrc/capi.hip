@@ -106,6 +106,9 @@ struct cora_ctx {
   int32_t *d_api2int = nullptr;
   double *d_diag_inv = nullptr;  // 1/diag(Q), local rows
   double *d_lam_st = nullptr, *d_lam_ob = nullptr;
+  // [pose slice][kSymEl(d)][64] (HostFormat::own_sym): sym(Q_PP) as uploaded, and S_P = sym(Q_PP) - Lambda_P of the
+  // current point, which the pose slices' epilogues read instead of their own block and Lambda (k_point_finish writes it)
+  double *d_own_sym = nullptr, *d_S = nullptr;
   // partitioned handles: distributed long rows (HostFormat::long_rows): partial-sum slots, rows, owners
   double *d_long_out = nullptr;
   int32_t *d_long_rows = nullptr, *d_long_owner = nullptr;
@@ -333,6 +336,7 @@ SpmmArgs spmm_args(const cora_ctx *c, const double *X, double *out) {
   A.Y = c->d_Y;
   A.lam_st = c->d_lam_st;
   A.lam_ob = c->d_lam_ob;
+  A.S = c->d_S;
   const Layout &L = c->F.L;
   A.win_rot_lo = static_cast<int32_t>(L.rot_base);
   A.win_rot_hi = static_cast<int32_t>(L.rot_base + static_cast<int64_t>(L.nl_poses) * L.d);
@@ -442,7 +446,7 @@ int point_finish(cora_ctx *c, bool wait = true) {
   int rc = ensure_red(c, static_cast<size_t>(std::max(nb, 1)) * 4);
   if (rc) return rc;
   int nblocks = 0;
-  HIP_TRY(c, launch_point_finish(R, c->ld, c->d_Y, c->d_G, c->d_rgrad, c->d_lam_st, c->d_lam_ob, c->d_red,
+  HIP_TRY(c, launch_point_finish(R, c->ld, c->d_Y, c->d_G, c->d_rgrad, c->d_lam_st, c->d_lam_ob, c->d_own_sym, c->d_S, c->d_red,
                                  &nblocks, c->stream));
   if (!wait) {
     c->h_scalars[4] = 0.0;

@@ -134,6 +134,9 @@ int cora_ctx_create_part_opts(int device, int d, int n_poses, int n_ranges, int 
   CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_lam_st),
                        (static_cast<size_t>(F.L.nl_poses) * d * d + 2) * sizeof(double)));
   CREATE_TRY(hipMemset(c->d_lam_st, 0, (static_cast<size_t>(F.L.nl_poses) * d * d + 2) * sizeof(double)));
+  // S starts as sym(Q_PP) (Lambda = 0, what d_lam_st holds until the first point): a product before it means what it did
+  CREATE_TRY(to_device(&c->d_own_sym, F.own_sym));
+  CREATE_TRY(to_device(&c->d_S, F.own_sym));
   CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_lam_ob),
                        std::max<size_t>(F.L.nl_ranges, 1) * sizeof(double)));
   CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_scalars), 8 * sizeof(double)));
@@ -173,7 +176,7 @@ void cora_ctx_destroy(cora_ctx *c) {
     if (c->ev_operand) (void)hipEventDestroy(c->ev_operand);
     if (c->ev_exchanged) (void)hipEventDestroy(c->ev_exchanged);
     void *ptrs[] = {c->d_slices_int, c->d_slices_bnd, c->d_slices, c->d_slices_pf, c->d_head_val, c->d_long_out, c->d_long_rows, c->d_long_owner, c->d_sval, c->d_scol, c->d_perm, c->d_chunks, c->d_chunk_order, c->d_lval, c->d_lcol,
-                    c->d_partials, c->d_tickets, c->d_api2int, c->d_diag_inv, c->d_lam_st, c->d_lam_ob,
+                    c->d_partials, c->d_tickets, c->d_api2int, c->d_diag_inv, c->d_lam_st, c->d_lam_ob, c->d_own_sym, c->d_S,
                     c->d_stage, c->d_red, c->d_scalars, c->d_flag, c->d_ticket, c->d_stpcg, c->d_seq_counter};
     if (c->stpcg_graph) (void)hipGraphExecDestroy(c->stpcg_graph);
     for (void *p : ptrs)

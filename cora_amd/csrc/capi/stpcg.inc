@@ -221,7 +221,7 @@ static int stpcg_run(cora_ctx *c, const double *dGrad, const double *dPg, double
     }
     auto U = [](const void *q) { return reinterpret_cast<uintptr_t>(q); };
     key = {static_cast<uintptr_t>(c->stpcg_path), static_cast<uintptr_t>(c->ld), static_cast<uintptr_t>(batch), static_cast<uintptr_t>(n),
-           U(dS), U(dR), U(dV), U(dP), U(dHp), U(c->d_red), static_cast<uintptr_t>(kappa_blocks), U(c->d_Y), U(c->d_lam_st), U(t), U(t2),
+           U(dS), U(dR), U(dV), U(dP), U(dHp), U(c->d_red), static_cast<uintptr_t>(kappa_blocks), U(c->d_Y), U(c->d_lam_st), U(c->d_S), U(t), U(t2),
            static_cast<uintptr_t>(c->precond), static_cast<uintptr_t>(c->precond_f.generation), U(c->stream),
            static_cast<uintptr_t>(c->F.slices.size())};
     for (int i = 0; i < kScratchSlots; ++i) key.push_back(U(c->scratch[i]));  // (whatever a solve in the batch borrows)

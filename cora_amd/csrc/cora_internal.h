@@ -43,7 +43,8 @@ constexpr int32_t kSliceTypeMask = 0xff;
 //     s0[a], a <= d : column t_P      -- Q(rot(P)_a, t_P) for a < d,  Q(t_P, t_P) for a = d
 //     s1[a], a <= d : column t_{P+1}  -- Q(rot(P)_a, t_{P+1}),        Q(t_P, t_{P+1})       (zeros without a next local pose)
 //     nxt[c][a]     : column rot(P+1)_c, rows rot(P)_a               (zeros without a next local pose)
-//     own[c][a]     : column rot(P)_c,   rows rot(P)_a
+//     own[c][a]     : column rot(P)_c,   rows rot(P)_a   -- read by EPI_NONE only: the epilogues that subtract Lambda
+//                     (EPI_S, EPI_HVP, EPI_HVP_K) take the block S_P = sym(own) - Lambda_P instead (HostFormat::own_sym)
 //   taken from elsewhere (checked bit for bit when the format is built; a slice that fails keeps the plain layout and
 //   its translation rows go to row slices):
 //     Q(t_P, rot(P)_c)      = s0[c] of the same lane
@@ -69,6 +70,12 @@ constexpr int kSliceTailMaxShift = 9;   // SliceDesc::type bits 9..15: the longe
 constexpr int32_t kSliceTailMaxMask = 0x7f;
 constexpr int kChainFixed(int d) { return 2 * (d + 1) + 2 * d * d; }   // doubles per lane in the fixed slots
 constexpr int kChainHead(int d) { return d * d + d + 1; }              // doubles per slice in head_val
+// A symmetric d x d block stored as its upper triangle: d(d+1)/2 doubles, entry (a, c) with a <= c in slot kSymSlot
+// (d = 3: 00 01 02 11 12 22).  Per pose slice [slot][64], indexed by the local pose P as (P / 64, slot, P % 64).
+constexpr int kSymEl(int d) { return d * (d + 1) / 2; }
+constexpr int kSymSlot(int a, int c, int d) {
+  return a <= c ? a * d - a * (a - 1) / 2 + c - a : c * d - c * (c - 1) / 2 + a - c;
+}
 
 // One wavefront's work, stored slot-major ([k][lane]) so that every load is a
 // fully coalesced 512 B (values) / 256 B (columns).
@@ -123,6 +130,10 @@ struct HostFormat {
   // [pose slice][kChainHead(d)]: what lane 0 of a chain slice takes from the pose before it --
   // [a * d + c] = Q(rot(P)_a, rot(P-1)_c), [d * d + c] = Q(t_P, rot(P-1)_c), [d * d + d] = Q(t_P, t_{P-1})
   std::vector<double> head_val;
+  // [pose slice][kSymEl(d)][64]: sym(Q_PP) = (own + own^T) / 2 of every lane of a chain slice (kSymSlot order; zeros in
+  // plain slices and past the slice's poses).  The handle's S array starts as a copy and k_point_finish writes
+  // S_P = sym(Q_PP) - Lambda_P from it at every point (own is not bit-symmetric: the two halves differ by up to an ulp).
+  std::vector<double> own_sym;
   std::vector<double> sval;
   std::vector<int32_t> scol;
   std::vector<int32_t> perm;      // internal rows for kSliceEuclidPerm slices

@@ -227,7 +227,7 @@ void build_format(int d, int n, int r, int nt, const int32_t *rowptr,
   tick("owners + numbering");
   // ---- 3. local rows -> slices ---------------------------------------------
   std::vector<double> slice_key;  // position of each slice along the pose chain (work ordering)
-  F.slices.clear(); F.sval.clear(); F.scol.clear(); F.perm.clear(); F.head_val.clear();
+  F.slices.clear(); F.sval.clear(); F.scol.clear(); F.perm.clear(); F.head_val.clear(); F.own_sym.clear();
   F.chunks.clear(); F.lval.clear(); F.lcol.clear();
   F.padded_nnz = F.long_nnz = F.nnz_local = 0; F.max_width = 0; F.n_long_rows = 0;
   F.diag.assign(static_cast<size_t>(std::max<int64_t>(L.local_rows, 1)), 0.0);
@@ -291,6 +291,8 @@ void build_format(int d, int n, int r, int nt, const int32_t *rowptr,
     const int n_pose_slices = (L.nl_poses + kWave - 1) / kWave;
     std::vector<SliceOut> outs(static_cast<size_t>(n_pose_slices));
     F.head_val.assign(static_cast<size_t>(n_pose_slices) * HV, 0.0);
+    const int SE = kSymEl(d);
+    F.own_sym.assign(static_cast<size_t>(n_pose_slices) * SE * kWave, 0.0);
     auto build_slice = [&](int p0, SliceOut &O, Scratch &W) {
       std::vector<PoseCols> &pc = W.pc;
       std::vector<RowEnt> &tr = W.tr;
@@ -450,6 +452,11 @@ void build_format(int d, int n, int r, int nt, const int32_t *rowptr,
           auto put = [&](int slot, double v) { O.v[static_cast<size_t>(slot) * kWave + lane] = active ? v : 0.0; };
           for (int a = 0; a <= d; ++a) { put(a, C.s0[a]); put(d + 1 + a, C.s1[a]); }
           for (int k = 0; k < d * d; ++k) { put(2 * (d + 1) + k, C.nxt[k]); put(2 * (d + 1) + d * d + k, C.own[k]); }
+          if (active) {  // sym(Q_PP) for the epilogues that fold Lambda into the own block (HostFormat::own_sym)
+            double *os = &F.own_sym[static_cast<size_t>(p0 / kWave) * SE * kWave + lane];
+            for (int a = 0; a < d; ++a)
+              for (int c = a; c < d; ++c) os[static_cast<size_t>(kSymSlot(a, c, d)) * kWave] = 0.5 * (C.own[c * d + a] + C.own[a * d + c]);
+          }
           // general slots; padded slots repeat a column of the lane (or the lane's own first row) with zero values
           int32_t fill = static_cast<int32_t>(L.rot_base + static_cast<int64_t>(std::min(p0 + lane, L.nl_poses - 1)) * d);
           for (int k = 0; k < gw; ++k) {

@@ -36,6 +36,9 @@ struct SpmmArgs {
   const double *Y;     // current point (epilogues)
   const double *lam_st;  // [local pose][d*d]
   const double *lam_ob;  // [local range]
+  // [pose slice][kSymEl(d)][64]: S_P = sym(Q_PP) - Lambda_P (cora_internal.h, HostFormat::own_sym) -- what the chain
+  // slices of EPI_S / EPI_HVP / EPI_HVP_K read for the pose's own block; plain slices keep own slots + lam_st
+  const double *S = nullptr;
   // EPI_HVP_K: [launch_spmm_kappa_slots()] one partial sum of <X, out> per block, then one per long row (written by
   // whichever chunk finishes the row -- a fixed slot whatever the arrival order)
   double *kappa_partial = nullptr;
@@ -249,8 +252,8 @@ hipError_t launch_zero_row(double *x, size_t row, int ld, hipStream_t st);
 
 hipError_t launch_spmm(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st);
 hipError_t launch_point_finish(const RowArgs &R, int ld, const double *Y, const double *G,
-                               double *rgrad, double *lam_st, double *lam_ob, double *partial,
-                               int *nblocks, hipStream_t st);
+                               double *rgrad, double *lam_st, double *lam_ob, const double *own_sym, double *S,
+                               double *partial, int *nblocks, hipStream_t st);
 hipError_t launch_tangent_project(const RowArgs &R, int ld, const double *Y, const double *V,
                                   const double *scale, double *out, hipStream_t st);
 hipError_t launch_project_manifold(const RowArgs &R, int ld, const double *A, const double *V,

@@ -94,8 +94,8 @@ SPMM_GROUP(5)
 #if CORA_TU & 2
 
 hipError_t launch_point_finish(const RowArgs &R, int ld, const double *Y, const double *G,
-                               double *rgrad, double *lam_st, double *lam_ob, double *partial,
-                               int *nblocks, hipStream_t st) {
+                               double *rgrad, double *lam_st, double *lam_ob, const double *own_sym, double *S,
+                               double *partial, int *nblocks, hipStream_t st) {
   const int64_t units = static_cast<int64_t>(R.nl_poses) + R.nl_ranges + R.nl_trans;
   const int grid = static_cast<int>((units + 255) / 256);
   *nblocks = grid;
@@ -103,9 +103,9 @@ hipError_t launch_point_finish(const RowArgs &R, int ld, const double *Y, const 
 #define CASE(L)                                                                               \
   if (ld == L) {                                                                              \
     if (R.d == 2) hipLaunchKernelGGL((k_point_finish<L, 2>), dim3(grid), dim3(256), 0, st, R, \
-                                     Y, G, rgrad, lam_st, lam_ob, partial);                   \
+                                     Y, G, rgrad, lam_st, lam_ob, own_sym, S, partial);       \
     else hipLaunchKernelGGL((k_point_finish<L, 3>), dim3(grid), dim3(256), 0, st, R, Y, G,    \
-                            rgrad, lam_st, lam_ob, partial);                                  \
+                            rgrad, lam_st, lam_ob, own_sym, S, partial);                      \
     return hipGetLastError();                                                                 \
   }
   CORA_LD_CASES(CASE)

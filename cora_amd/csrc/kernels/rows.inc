@@ -27,6 +27,8 @@ __global__ __launch_bounds__(256) void k_point_finish(const RowArgs R, const dou
                                                       double *__restrict__ rgrad,
                                                       double *__restrict__ lam_st,
                                                       double *__restrict__ lam_ob,
+                                                      const double *__restrict__ own_sym,
+                                                      double *__restrict__ S,
                                                       double *__restrict__ partial) {
   __shared__ double sm[4];
   const int64_t u = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
@@ -56,6 +58,16 @@ __global__ __launch_bounds__(256) void k_point_finish(const RowArgs R, const dou
         for (int c = 0; c < LD; ++c) g[a][c] = fma(-s, y[b][c], g[a][c]);
       }
     // note: g[a] is updated with y only, so the in-place update above is exact
+    // S_P = sym(Q_PP) - Lambda_P, the block the pose slices' epilogues read for the pose's own columns (coalesced:
+    // consecutive poses are consecutive doubles of a slot)
+    const size_t so = static_cast<size_t>(un.idx / kWave) * kSymEl(D) * kWave + static_cast<size_t>(un.idx % kWave);
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+      for (int b = a; b < D; ++b) {
+        const size_t k = so + static_cast<size_t>(kSymSlot(a, b, D)) * kWave;
+        S[k] = own_sym[k] - 0.5 * (m[a][b] + m[b][a]);
+      }
 #pragma unroll
     for (int a = 0; a < D; ++a) store_row<LD>(rgrad + (un.row + a) * LD, g[a]);
   } else if (un.kind == 1) {

@@ -4,6 +4,9 @@
 //   EPI_NONE : out = Q X                       (Problem::dataMatrixProduct, :742-746)
 //   EPI_S    : out = Q X - Lambda X            (certificate operator, :1162-1166)
 //   EPI_HVP  : out = Proj_Y(Q X - Lambda X)    (Riemannian Hvp, :822-867)
+// A chain slice's epilogues take the pose's own block and Lambda_P as ONE symmetric block, S_P = sym(Q_PP) - Lambda_P
+// (SpmmArgs::S, written by k_point_finish): 6 doubles per pose at d = 3 instead of 9 own slots + 9 of Lambda, and no
+// Lambda term after the slots.  EPI_NONE reads the own slots, so Q X keeps its bits.
 // One wavefront per slice, lane = row, LD accumulators per lane in registers.
 // Blocks [0, n_chunks) handle chunks of the long (landmark) rows instead.
 // ---------------------------------------------------------------------------
@@ -240,23 +243,23 @@ __device__ __forceinline__ double pose_slice(const SpmmArgs &A, const SliceDesc 
   // or gather", the consumers sank below the last of them and twelve rows stayed live at once)
   constexpr bool kWin = kWinLD && WIN;
   constexpr int kRotRows = (kWave + 2) * D, kTrnRows = LD <= kWinTrnMaxLD ? kWave + 2 : 0;
-  // cooperative Hvp epilogue (CORA_POSE_COOP_EPI): the slice's rows of Y, its Lambda blocks and its rows of the result
-  // are contiguous too -- requested with coalesced loads BEFORE the slot loop, handed to the lanes through the window's
-  // LDS after it, and the result rows leave through LDS as 512-byte runs instead of 16-byte pieces of 64 lines
+  // cooperative Hvp epilogue (CORA_POSE_COOP_EPI): the slice's rows of Y and its rows of the result are contiguous too --
+  // requested with coalesced loads BEFORE the slot loop, handed to the lanes through the window's LDS after it, and the
+  // result rows leave through LDS as 512-byte runs instead of 16-byte pieces of 64 lines
   constexpr bool kCoopT = kWinLD && CORA_POSE_COOP_EPI && EPI >= EPI_HVP && D * LD <= CORA_POSE_COOP_MAX_DLD;
   constexpr bool kCoop = kCoopT && WIN;
-  constexpr int kYEl = kWave * D * LD, kLEl = kWave * D * D;
+  constexpr int kYEl = kWave * D * LD;
   constexpr int kWinEl = (kRotRows + kTrnRows) * LD;
-  // (the cooperative epilogue hands Y rows + Lambda blocks in, result rows + the slice's translation rows out)
-  constexpr int kCoopEl = kYEl + (kLEl > kWave * LD ? kLEl : kWave * LD);
+  // (the cooperative epilogue hands Y rows in, result rows + the slice's translation rows out)
+  constexpr int kCoopEl = kYEl + kWave * LD;
   // staged stores (window form, row strides up to CORA_POSE_COOP_MAX_LD, every epilogue): result rows + translation rows
   constexpr bool kStaged = kWin && LD <= CORA_POSE_COOP_MAX_LD;
   constexpr int kStagedEl = kStaged ? kYEl + kWave * LD : 0;
   constexpr int kNeedEl = (kCoopT && kCoopEl > kStagedEl) ? kCoopEl : kStagedEl;
   constexpr int kSmemEl = !kWinLD ? 1 : (kNeedEl > kWinEl ? kNeedEl : kWinEl);
   __shared__ __attribute__((aligned(16))) double win[kSmemEl];
-  constexpr int kYIt = (D * LD + 1) / 2, kLIt = (D * D + 1) / 2;  // (pairs of doubles per lane and access)
-  double ystage[kCoopT ? 2 * kYIt : 1], lstage[kCoopT ? 2 * kLIt : 1];
+  constexpr int kYIt = (D * LD + 1) / 2;  // (pairs of doubles per lane and access)
+  double ystage[kCoopT ? 2 * kYIt : 1];
   // Chain layout (kSliceChainFlag, cora_internal.h): the lane owns the pose's translation row as well, the chain's columns
   // are implied, and what Q's symmetry gives comes from the lane before (lane 0: the slice's head block).
   const bool chain = (sd.type & kSliceChainFlag) != 0;  // wave-uniform
@@ -265,6 +268,11 @@ __device__ __forceinline__ double pose_slice(const SpmmArgs &A, const SliceDesc 
   // loaded (L1 / L2 hits)
   constexpr bool kNxtRegs = LD <= 5 || (LD <= 8 && EPI < 2);
   constexpr int kFV = kChainFixed(D);
+  // the epilogues that subtract Lambda read S_P (SpmmArgs::S) for the own block: the own slots -- the last d x d fixed
+  // slots, whole 512-byte lines of the stream -- are not read at all
+  constexpr bool kFold = EPI != EPI_NONE;
+  constexpr int kFVRead = kFold ? 2 * (D + 1) + D * D : kFV;
+  constexpr int kSE = kSymEl(D);
   // Everything that does not depend on the windows is requested HERE, ahead of the windows' own loads: all wavefronts of
   // a launch are resident at once, so a launch lasts as long as a wavefront's chain of dependent memory latencies -- the
   // fixed slots' values, the tail's first 64 entries and (below) the epilogue's operands arrive with the window rows.
@@ -282,8 +290,11 @@ __device__ __forceinline__ double pose_slice(const SpmmArgs &A, const SliceDesc 
   // Wide rows cannot hold d + 1 accumulator rows: there the translation row goes first, on its own -- its slots' values,
   // nine rows of X from the windows, the tail -- and is stored before the rotation rows start.
   constexpr bool kFuseT = (D + 1) * LD <= CORA_POSE_FUSE_T_MAX;
-  double fx[kEarly ? kFV : 1];
+  double fx[kEarly ? kFVRead : 1], sx[kEarly && kFold ? kSE : 1];
   auto fixed = [&](int i) { if constexpr (kEarly) return fx[i]; else return stream_load(vp + static_cast<size_t>(i) * kWave); };
+  // entry k of S_P (chain slices start at a multiple of 64 poses; the address is formed where it is used)
+  auto s_load = [&](int k) { return stream_load(A.S + static_cast<size_t>(sd.aux0) * kSE + static_cast<size_t>(k) * kWave + lane); };
+  auto sym = [&](int k) { if constexpr (kEarly && kFold) return sx[k]; else return s_load(k); };
   double headv = 0.0;  // lane h < kChainHead(D): entry h of the slice's head block
   if (chain) {
     if (lane < kChainHead(D)) headv = A.head_val[static_cast<size_t>(sd.aux0 / kWave) * kChainHead(D) + lane];
@@ -296,20 +307,23 @@ __device__ __forceinline__ double pose_slice(const SpmmArgs &A, const SliceDesc 
     }
     if constexpr (kEarly) {
 #pragma unroll
-      for (int i = 0; i < kFV; ++i) fx[i] = stream_load(vp + static_cast<size_t>(i) * kWave);
+      for (int i = 0; i < kFVRead; ++i) fx[i] = stream_load(vp + static_cast<size_t>(i) * kWave);
+      if constexpr (kFold) {
+#pragma unroll
+        for (int k = 0; k < kSE; ++k) sx[k] = s_load(k);
+      }
     }
   }
-  // the cooperative epilogue's operands: the slice's rows of Y and its Lambda blocks, requested with coalesced loads --
-  // plain slices with the window's rows; chain slices right AFTER the windows have landed: a third of the wavefront's
-  // bytes, needed last, travels while the fixed slots and the tail are computed instead of holding up their operands
+  // the cooperative epilogue's operand: the slice's rows of Y, requested with coalesced loads -- plain slices with the
+  // window's rows; chain slices right AFTER the windows have landed: bytes needed last travel while the fixed slots and
+  // the tail are computed instead of holding up their operands
   // (all wavefronts of a launch start together and share the memory system: what is requested first lands first)
   auto coop_prefetch = [&] {
     if constexpr (kCoopT) {
       const double *__restrict__ Yp = A.Y + static_cast<size_t>(sd.row0) * LD;
-      const double *__restrict__ Lq = A.lam_st + static_cast<size_t>(sd.aux0) * (D * D);
 #pragma unroll
       // ONE predicate per access (an odd count reads one double past the slice's rows: Y has the range rows behind
-      // its rotation rows, the Lambda array is allocated with the slack).  The two-way form -- a pair, else a single
+      // its rotation rows).  The two-way form -- a pair, else a single
       // double into the same registers -- made the compiler wait for EVERY outstanding load before each pair (a
       // write-after-write hazard on the staging registers): thirteen loads, one after the other.
       for (int i = 0; i < kYIt; ++i) {
@@ -318,14 +332,6 @@ __device__ __forceinline__ double pose_slice(const SpmmArgs &A, const SliceDesc 
         if (e < n) v = *reinterpret_cast<const Pair8 *>(Yp + e);
         ystage[2 * i] = v.x;
         ystage[2 * i + 1] = v.y;
-      }
-#pragma unroll
-      for (int i = 0; i < kLIt; ++i) {
-        const int e = 2 * (i * kWave + lane), n = sd.nrows * D * D;
-        Pair8 v{0.0, 0.0};
-        if (e < n) v = *reinterpret_cast<const Pair8 *>(Lq + e);
-        lstage[2 * i] = v.x;
-        lstage[2 * i + 1] = v.y;
       }
     }
   };
@@ -606,13 +612,17 @@ __device__ __forceinline__ double pose_slice(const SpmmArgs &A, const SliceDesc 
         for (int j = 0; j < LD; ++j) acct[j] = fma(ps1[c], x[j], acct[j]);
       }
     }
-    // (e) the pose's own block; the translation row's share of these columns is Q(t_P, rot(P)_c) = s0[c]
+    // (e) the pose's own block -- S_P = sym(Q_PP) - Lambda_P when an epilogue subtracts Lambda; the translation row's
+    // share of these columns is Q(t_P, rot(P)_c) = s0[c]
     phase_fence();
 #pragma unroll
     for (int c = 0; c < D; ++c) {
       double v[D], x[LD];
 #pragma unroll
-      for (int a = 0; a < D; ++a) v[a] = fixed(2 * (D + 1) + D * D + c * D + a);
+      for (int a = 0; a < D; ++a) {
+        if constexpr (kFold) v[a] = sym(kSymSlot(a, c, D));
+        else v[a] = fixed(2 * (D + 1) + D * D + c * D + a);
+      }
       x_rot(own_row + c, x);
 #pragma unroll
       for (int j = 0; j < LD; ++j) {
@@ -684,12 +694,37 @@ __device__ __forceinline__ double pose_slice(const SpmmArgs &A, const SliceDesc 
     }
   };
   if constexpr (kCoopT) if (kCoop) {
-    double xo[D][LD];  // the pose's own rows of X (inside the rotation window; lanes past nrows read rows they ignore)
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
+    // the pose's own rows of X (inside the rotation window; lanes past nrows read rows they ignore): <X, out> needs them,
+    // and so does a plain slice, which subtracts Lambda_P X_P here (a chain slice has it in S_P)
+    auto x_own = [&](int b, double (&x)[LD]) {
       const int l = sd.row0 + lane * D + b - w0;
 #pragma unroll
-      for (int j = 0; j < LD; ++j) xo[b][j] = win[l * LD + j];
+      for (int j = 0; j < LD; ++j) x[j] = win[l * LD + j];
+    };
+    constexpr bool kKap = EPI == EPI_HVP_K;
+    double xo[kKap ? D : 1][LD];
+    if constexpr (kKap) {
+#pragma unroll
+      for (int b = 0; b < D; ++b) x_own(b, xo[b]);
+    }
+    if (!chain) {
+      const double *__restrict__ Lp = A.lam_st + static_cast<size_t>(sd.aux0 + min(lane, sd.nrows - 1)) * (D * D);
+#pragma unroll
+      for (int b = 0; b < D; ++b) {
+        double x[LD];
+        if constexpr (kKap) {
+#pragma unroll
+          for (int j = 0; j < LD; ++j) x[j] = xo[kKap ? b : 0][j];
+        } else {
+          x_own(b, x);
+        }
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+          const double lam = Lp[a * D + b];
+#pragma unroll
+          for (int j = 0; j < LD; ++j) acc[a][j] = fma(-lam, x[j], acc[a][j]);
+        }
+      }
     }
     __syncthreads();
 #pragma unroll
@@ -698,30 +733,17 @@ __device__ __forceinline__ double pose_slice(const SpmmArgs &A, const SliceDesc 
       if (e < kYEl) win[e] = ystage[2 * i];
       if (e + 1 < kYEl) win[e + 1] = ystage[2 * i + 1];
     }
-#pragma unroll
-    for (int i = 0; i < kLIt; ++i) {
-      const int e = 2 * (i * kWave + lane);
-      if (e < kLEl) win[kYEl + e] = lstage[2 * i];
-      if (e + 1 < kLEl) win[kYEl + e + 1] = lstage[2 * i + 1];
-    }
     __syncthreads();
     double y[D][LD];
 #pragma unroll
-    for (int b = 0; b < D; ++b) {
+    for (int b = 0; b < D; ++b)
 #pragma unroll
       for (int j = 0; j < LD; ++j) y[b][j] = win[(lane * D + b) * LD + j];
-#pragma unroll
-      for (int a = 0; a < D; ++a) {
-        const double lam = win[kYEl + lane * (D * D) + a * D + b];
-#pragma unroll
-        for (int j = 0; j < LD; ++j) acc[a][j] = fma(-lam, xo[b][j], acc[a][j]);
-      }
-    }
     stiefel_project_thread<LD, D>(y, acc);
     double kap = 0.0;
-    if (EPI == EPI_HVP_K && lane < sd.nrows) {
+    if (kKap && lane < sd.nrows) {
 #pragma unroll
-      for (int a = 0; a < D; ++a) kap += dot_row<LD>(xo[a], acc[a]);
+      for (int a = 0; a < D; ++a) kap += dot_row<LD>(xo[kKap ? a : 0], acc[a]);
     }
     staged_store();
     return kap + kap_t;
@@ -733,10 +755,7 @@ __device__ __forceinline__ double pose_slice(const SpmmArgs &A, const SliceDesc 
   constexpr bool kKeepX = EPI == EPI_HVP_K && D * LD <= 18;  // the pose's own rows of X stay in registers for <X, out>
   double xs[kKeepX ? D : 1][LD];
   if (EPI != EPI_NONE && active) {
-    const double *Lp = A.lam_st + static_cast<size_t>(sd.aux0 + lane) * (D * D);
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      double x[LD];
+    auto x_own = [&](int b, double (&x)[LD]) {
       if (kWinLD && kWin) {  // the pose's own rows are inside the rotation window
         const int l = sd.row0 + lane * D + b - w0;
 #pragma unroll
@@ -744,16 +763,27 @@ __device__ __forceinline__ double pose_slice(const SpmmArgs &A, const SliceDesc 
       } else {
         load_row<LD>(X + (prow + b) * LD, x);
       }
+    };
+    if (!chain) {  // plain slices: - Lambda_P X_P (a chain slice has it in S_P)
+      const double *Lp = A.lam_st + static_cast<size_t>(sd.aux0 + lane) * (D * D);
 #pragma unroll
-      for (int a = 0; a < D; ++a) {
-        const double lam = Lp[a * D + b];
+      for (int b = 0; b < D; ++b) {
+        double x[LD];
+        x_own(b, x);
 #pragma unroll
-        for (int j = 0; j < LD; ++j) acc[a][j] = fma(-lam, x[j], acc[a][j]);
+        for (int a = 0; a < D; ++a) {
+          const double lam = Lp[a * D + b];
+#pragma unroll
+          for (int j = 0; j < LD; ++j) acc[a][j] = fma(-lam, x[j], acc[a][j]);
+        }
+        if (kKeepX) {
+#pragma unroll
+          for (int j = 0; j < LD; ++j) xs[kKeepX ? b : 0][j] = x[j];
+        }
       }
-      if (kKeepX) {
+    } else if (kKeepX) {
 #pragma unroll
-        for (int j = 0; j < LD; ++j) xs[kKeepX ? b : 0][j] = x[j];
-      }
+      for (int b = 0; b < D; ++b) x_own(b, xs[kKeepX ? b : 0]);
     }
     if (EPI >= EPI_HVP) {
       double y[D][LD];
