@@ -500,6 +500,48 @@ class Context:
     def sync(self):
         self._chk(self.L.cora_sync(self.h))
 
+    # ---- per-measurement residuals (include/cora_hip.h, cora_set_measurements)
+    def set_measurements(self, edge_rows, edge_data, range_rows, range_data):
+        """edge_rows [m][4] / range_rows [r][3] int32 API rows, edge_data [m][d*d + d + 2] = R row-major, t, kappa, tau,
+        range_data [r][2] = r, omega.  Replaces the handle's table."""
+        er = np.ascontiguousarray(np.asarray(edge_rows, dtype=np.int32).reshape(-1, 4))
+        ed = np.ascontiguousarray(np.asarray(edge_data, dtype=np.float64).reshape(-1, self.d * self.d + self.d + 2))
+        rr = np.ascontiguousarray(np.asarray(range_rows, dtype=np.int32).reshape(-1, 3))
+        rd = np.ascontiguousarray(np.asarray(range_data, dtype=np.float64).reshape(-1, 2))
+        if len(er) != len(ed) or len(rr) != len(rd):
+            raise CoraError(1, "rows and data of a measurement table must have the same length")
+        self._chk(self.L.cora_set_measurements(self.h, C.c_int64(len(er)), er.ctypes.data_as(_ip), _d(ed),
+                                               C.c_int64(len(rr)), rr.ctypes.data_as(_ip), _d(rd)))
+
+    def measurement_counts(self):
+        """(edges, ranges) of the handle's measurement table."""
+        out = (C.c_int64 * 2)()
+        self._chk(self.L.cora_measurement_counts(self.h, out))
+        return int(out[0]), int(out[1])
+
+    def _residuals(self, call):
+        ne, nr = self.measurement_counts()
+        rot, trn, rng = np.zeros(max(ne, 1)), np.zeros(max(ne, 1)), np.zeros(max(nr, 1))
+        sums = np.zeros(3)
+        self._chk(call(_d(rot), _d(trn), _d(rng), _d(sums)))
+        return dict(edge_rot=rot[:ne], edge_trans=trn[:ne], range=rng[:nr], sums=sums)
+
+    def measurement_residuals(self, X):
+        """Residuals of every measurement of the table at the host matrix X (N x k): dict edge_rot, edge_trans, range,
+        sums = [sum rot, sum trans, sum range]; 1/2 sum(sums) = evaluateObjective(X)."""
+        X = _f(X)
+        return self._residuals(lambda *o: self.L.cora_measurement_residuals(self.h, _d(X), X.shape[0], X.shape[1], *o))
+
+    def measurement_residuals_dev(self, x, k):
+        """The same at a resident vector x of k columns."""
+        return self._residuals(lambda *o: self.L.cora_measurement_residuals_dev(self.h, C.c_void_p(x), int(k), *o))
+
+    def debug_measurement_residuals_host(self, X):
+        """Test hook: the translated table executed on the host (no GPU needed)."""
+        X = _f(X)
+        return self._residuals(lambda *o: self.L.cora_debug_measurement_residuals_host(self.h, _d(X), X.shape[0],
+                                                                                      X.shape[1], *o))
+
     # ---- test hook
     def debug_format_spmm_host(self, X):
         X = _f(X)

@@ -2,7 +2,7 @@
 // device memory and stream; every compute entry point ends in a HIP kernel of
 // kernels.hip -- there is no CPU fallback.
 //
-// ONE translation unit in ten pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
+// ONE translation unit in eleven pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
 // error / device macros and the helpers every part uses; the entry points live in capi/*.inc, included at the end in this order:
 //   handle.inc          creation of (partitioned) handles, destruction, rank state, row maps, statistics
 //   resident.inc        device vectors, the current point, the trust-region trial / accept pair, products, projections
@@ -12,6 +12,7 @@
 //   stpcg.inc           the device-resident Steihaug-Toint PCG (every form of the iteration), injected communication
 //   blocks.inc          row moves, STPCG measurement hooks, LOBPCG's block algebra, timers
 //   host_pointer.inc    the host-pointer operator API (one entry per reference method), host-side debug hooks
+//   measurements.inc    the measurement table of a handle and the per-measurement residuals
 //   comm.inc            native communication: RCCL, in-process and device-side (p2p.h) transports
 #include <hip/hip_runtime.h>
 // RCCL's types and the few enumerators used, declared here (NCCL's public ABI: they have not changed since 2.0): the
@@ -73,8 +74,20 @@ static int native_product_gather(cora_native_comm *nc, double *dX, int ld, hipSt
                                  hipEvent_t after_collective = nullptr);
 static const std::string &native_error(const cora_native_comm *nc);
 static int native_allgather_rows(cora_native_comm *nc, double *dX, int ld, int64_t row0, int64_t nrows);  // one piece of every shard, packed
+// The measurement table of cora_set_measurements (capi/measurements.inc), rows already translated to the internal order,
+// structure-of-arrays [field][measurement] on the host and on the device (ResidualArgs, kernels.h)
+struct MeasurementTable {
+  bool set = false;
+  int64_t n_edges = 0, n_ranges = 0;
+  std::vector<int32_t> edge_rows, range_rows;  // [4][n_edges], [3][n_ranges]
+  std::vector<double> edge_data, range_data;   // [d*d + d + 2][n_edges], [2][n_ranges]
+  int32_t *d_edge_rows = nullptr, *d_range_rows = nullptr;
+  double *d_edge_data = nullptr, *d_range_data = nullptr;
+  double *d_out = nullptr;  // [n_edges] rotation | [n_edges] translation | [n_ranges] range | 3 sums
+};
 struct cora_ctx {
   HostFormat F;
+  MeasurementTable meas;
   cora_native_comm *native_comm = nullptr;  // owned: the library's own communication (cora_comm_create_*)
   cora::P2PState *p2p_pending = nullptr;    // a mailbox exported by cora_comm_p2p_handle, not yet connected
   int device = -1;
@@ -486,6 +499,14 @@ int set_point_dev_impl(cora_ctx *c, const double *dY) {
   return point_finish(c);
 }
 
+void free_measurements(cora_ctx *c) {  // (the device must be current)
+  MeasurementTable &M = c->meas;
+  for (void *p : {static_cast<void *>(M.d_edge_rows), static_cast<void *>(M.d_range_rows), static_cast<void *>(M.d_edge_data),
+                  static_cast<void *>(M.d_range_data), static_cast<void *>(M.d_out)})
+    if (p) (void)hipFree(p);
+  M = MeasurementTable();
+}
+
 void free_rank_state(cora_ctx *c) {
   for (double **p : {&c->d_Y, &c->d_G, &c->d_rgrad, &c->d_G_trial}) {
     if (*p) (void)hipFree(*p);
@@ -506,6 +527,7 @@ extern "C" {
 #include "capi/stpcg.inc"
 #include "capi/blocks.inc"
 #include "capi/host_pointer.inc"
+#include "capi/measurements.inc"
 
 }  // extern "C"
 

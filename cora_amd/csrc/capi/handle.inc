@@ -172,6 +172,7 @@ void cora_ctx_destroy(cora_ctx *c) {
     if (c->p2p_pending) cora::p2p_destroy(c->p2p_pending);
     c->p2p_pending = nullptr;
     free_rank_state(c);
+    free_measurements(c);
     if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
     if (c->ev_operand) (void)hipEventDestroy(c->ev_operand);
     if (c->ev_exchanged) (void)hipEventDestroy(c->ev_exchanged);

@@ -254,6 +254,7 @@ void Problem::updateProblemData() {  // src/CORA_problem.cpp:500-510
   tick("data matrix");
   cert_block_.reset();  // (its device memory belongs to the handle)
   ctx_.reset();  // the device copy of Q is rebuilt lazily
+  measurements_ready_ = false;
   precond_ready_ = false;
   std::lock_guard<std::recursive_mutex> lock(*cert_mutex_);
   cert_perm_.clear();
@@ -317,6 +318,7 @@ void Problem::ensureContext() const {
       cora_require_comm(c, 1);  // no callbacks (they are installed on the handle afterwards): fail loudly until then
     }
     implicit_ready_ = false;
+    measurements_ready_ = false;
   }
   if (formulation_ == Formulation::Implicit && !implicit_ready_) fillImplicitFormulationMatrices();
   {
@@ -686,6 +688,83 @@ Matrix Problem::retract(const Matrix &Y, const Matrix &V) const {
                          out.data(), static_cast<int>(out.rows())),
             "Problem::retract");
   return lowered(std::move(out));
+}
+
+// ---- per-measurement residuals (extension; include/cora_hip.h, cora_set_measurements) ----------------
+// The handle's table in the row order of fillRelPoseSubmatrices (pose-pose, pose priors, pose-landmark, landmark priors)
+// and of range_measurements_, rows in the API order; built on the first call after the handle was (re)created.
+void Problem::ensureMeasurementTable() const {
+  ensureContext();
+  if (measurements_ready_) return;
+  const int d = dim_, nf = d * d + d + 2;
+  const size_t m = rel_pose_pose_measurements_.size() + pose_priors_.size() + rel_pose_landmark_measurements_.size() +
+                   landmark_priors_.size();
+  const size_t nr = range_measurements_.size();
+  std::vector<int32_t> edge_rows(4 * m), range_rows(3 * nr);
+  std::vector<double> edge_data(static_cast<size_t>(nf) * m, 0.0), range_data(2 * nr);
+  size_t row = 0;
+  auto add = [&](const Symbol &a, const Symbol &b, const Matrix *R, const Vector &t, Scalar kappa, Scalar tau) {
+    int32_t *er = edge_rows.data() + 4 * row;
+    double *ed = edge_data.data() + static_cast<size_t>(nf) * row;
+    er[0] = static_cast<int32_t>(getRotationIdx(a) * d);
+    er[1] = R ? static_cast<int32_t>(getRotationIdx(b) * d) : -1;
+    er[2] = static_cast<int32_t>(getTranslationIdx(a));
+    er[3] = static_cast<int32_t>(getTranslationIdx(b));
+    if (R)
+      for (int r = 0; r < d; ++r)
+        for (int c = 0; c < d; ++c) ed[r * d + c] = (*R)(r, c);
+    for (int c = 0; c < d; ++c) ed[d * d + c] = t(c);
+    ed[d * d + d] = kappa;
+    ed[d * d + d + 1] = tau;
+    ++row;
+  };
+  for (const auto &rpm : rel_pose_pose_measurements_)
+    add(rpm.first_id, rpm.second_id, &rpm.R, rpm.t, rpm.getRotPrecision(), rpm.getTransPrecision());
+  for (const auto &pp : pose_priors_) add(origin_symbol_, pp.id, &pp.R, pp.t, pp.getRotPrecision(), pp.getTransPrecision());
+  for (const auto &pl : rel_pose_landmark_measurements_)
+    add(pl.first_id, pl.second_id, nullptr, pl.t, 0.0, pl.getTransPrecision());
+  for (const auto &lp : landmark_priors_) add(origin_symbol_, lp.id, nullptr, lp.p, 0.0, lp.getTransPrecision());
+  for (size_t k = 0; k < nr; ++k) {
+    const RangeMeasurement &rm = range_measurements_[k];
+    range_rows[3 * k] = static_cast<int32_t>(numPosesDim() + static_cast<Index>(k));
+    range_rows[3 * k + 1] = static_cast<int32_t>(getTranslationIdx(rm.first_id));
+    range_rows[3 * k + 2] = static_cast<int32_t>(getTranslationIdx(rm.second_id));
+    range_data[2 * k] = rm.r;
+    range_data[2 * k + 1] = rm.getPrecision();
+  }
+  CORA_CALL(cora_set_measurements(ctx_.get(), static_cast<int64_t>(m), edge_rows.data(), edge_data.data(),
+                                  static_cast<int64_t>(nr), range_rows.data(), range_data.data()),
+            "Problem::measurementResiduals");
+  measurements_ready_ = true;
+}
+
+MeasurementResiduals Problem::measurementResiduals(const Matrix &Y) const {
+  checkUpToDate();
+  checkMatrixShape("Problem::measurementResiduals::Y", getExpectedVariableSize(), Y.cols(), Y.rows(), Y.cols());
+  ensureMeasurementTable();
+  Matrix full_tmp;
+  if (formulation_ == Formulation::Implicit) full_tmp = getTranslationExplicitSolution(Y);
+  const Matrix &X = formulation_ == Formulation::Implicit ? full_tmp : Y;
+  const size_t npp = rel_pose_pose_measurements_.size(), nprior = pose_priors_.size();
+  const size_t npl = rel_pose_landmark_measurements_.size(), nlp = landmark_priors_.size();
+  const size_t m = npp + nprior + npl + nlp;
+  std::vector<double> rot(std::max<size_t>(m, 1)), trans(std::max<size_t>(m, 1));
+  MeasurementResiduals out;
+  out.range.resize(range_measurements_.size());
+  double sums[3] = {0, 0, 0};
+  CORA_CALL(cora_measurement_residuals(ctx_.get(), X.data(), static_cast<int>(X.rows()), static_cast<int>(X.cols()), rot.data(),
+                                       trans.data(), out.range.data(), sums),
+            "Problem::measurementResiduals");
+  out.rel_pose_rot.assign(rot.begin(), rot.begin() + npp);
+  out.rel_pose_trans.assign(trans.begin(), trans.begin() + npp);
+  out.pose_prior_rot.assign(rot.begin() + npp, rot.begin() + npp + nprior);
+  out.pose_prior_trans.assign(trans.begin() + npp, trans.begin() + npp + nprior);
+  out.pose_landmark.assign(trans.begin() + npp + nprior, trans.begin() + npp + nprior + npl);
+  out.landmark_prior.assign(trans.begin() + npp + nprior + npl, trans.begin() + m);
+  out.rot_sum = sums[0];
+  out.trans_sum = sums[1];
+  out.range_sum = sums[2];
+  return out;
 }
 
 // src/CORA_problem.cpp:1168-1197: [Y; -chol(Q33red) \ (B^T Y); 0], computed on the device

@@ -41,6 +41,21 @@ struct CoraDataSubmatrices {
   SparseMatrix rel_pose_rotation_precision_matrix;
 };
 
+/** EXTENSION beyond the reference's Problem (which can report only f = 1/2 <X, Q X>): the residual of every measurement at
+ * a point, per kind and in the order the measurements were added.  With X_a the d x k rotation block of pose a, x_t(s) the
+ * translation row of symbol s and x_rho the unit row of a range (include/cora_hip.h, "per-measurement residuals"):
+ *   rotation part     kappa |X_b - R^T X_a|_F^2                           (relative poses, pose priors with a = the origin)
+ *   translation part  tau |x_t(b) - x_t(a) - sum_c t_c X_a[c, :]|^2       (every kind but ranges; priors with a = the origin)
+ *   range             omega |x_t(b) - x_t(a) + r x_rho|^2
+ * No 1/2 in the values:  1/2 (rot_sum + trans_sum + range_sum) = evaluateObjective(X) for any X. */
+struct MeasurementResiduals {
+  std::vector<Scalar> rel_pose_rot, rel_pose_trans;      // getRPMs() order
+  std::vector<Scalar> pose_prior_rot, pose_prior_trans;
+  std::vector<Scalar> pose_landmark, landmark_prior;     // translation part (these kinds have no rotation part)
+  std::vector<Scalar> range;                             // getRangeMeasurements() order
+  Scalar rot_sum = 0, trans_sum = 0, range_sum = 0;      // over all kinds
+};
+
 class Problem {
  private:
   int dim_;
@@ -79,6 +94,7 @@ class Problem {
                           bool resident) const;
   mutable bool precond_ready_ = false;
   mutable bool implicit_ready_ = false;  // chol(Q33[0:nt-1]) installed on the handle
+  mutable bool measurements_ready_ = false;  // measurement table installed on the handle (measurementResiduals)
   mutable Scalar precond_lambda_ = 0;   // regularisation actually used
   mutable long precond_nnz_ = 0;         // nnz(L)
   mutable int precond_levels_ = 0;       // height of the elimination tree
@@ -112,6 +128,7 @@ class Problem {
   Matrix dataMatrixProduct(const Matrix &Y) const;
   void ensureContext() const;
   void ensurePreconditioner() const;
+  void ensureMeasurementTable() const;
   void fillImplicitFormulationMatrices() const;
   [[noreturn]] void throwLast(int status, const char *where) const;
 
@@ -149,6 +166,10 @@ class Problem {
   std::map<Symbol, int> getLandmarkSymbolMap() const { return landmark_symbol_idxs_; }
   const std::vector<RangeMeasurement> &getRangeMeasurements() const { return range_measurements_; }
   const std::vector<RelativePoseMeasurement> &getRPMs() const { return rel_pose_pose_measurements_; }
+  // (extensions: the other measurement kinds, for callers that label measurementResiduals' values)
+  const std::vector<RelativePoseLandmarkMeasurement> &getRPLMs() const { return rel_pose_landmark_measurements_; }
+  const std::vector<PosePrior> &getPosePriors() const { return pose_priors_; }
+  const std::vector<LandmarkPrior> &getLandmarkPriors() const { return landmark_priors_; }
 
   SparseMatrix data_matrix_;
 
@@ -208,6 +229,7 @@ class Problem {
     comm_user_ = user;
     cert_block_.reset();
     ctx_.reset();
+    measurements_ready_ = false;
     precond_ready_ = false;
   }
   int partitionWorld() const { return part_world_; }
@@ -221,6 +243,12 @@ class Problem {
   Matrix precondition(const Matrix &V) const;
   Matrix projectToManifold(const Matrix &A) const;
   Matrix retract(const Matrix &Y, const Matrix &V) const;
+
+  /** EXTENSION beyond the reference: per-measurement residuals at Y (struct MeasurementResiduals above), evaluated on the
+   * device from a measurement table that is built from the measurement vectors on the first call and kept on the handle.
+   * Y: getExpectedVariableSize() rows and any 1..24 columns (the relaxed and the rounded solution are both served); in the
+   * implicit formulation it is completed with getTranslationExplicitSolution(Y) first.  Single-GPU handles only. */
+  MeasurementResiduals measurementResiduals(const Matrix &Y) const;
 
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;

@@ -266,6 +266,41 @@ int cora_problem_lambda_blocks(cora_problem *p, const double *Y, double *stiefel
   });
 }
 
+int cora_problem_measurement_counts(const cora_problem *p, int64_t counts[5]) {
+  return guarded([&] {
+    const Problem &q = p->problem;
+    counts[0] = q.numPosePoseMeasurements();
+    counts[1] = q.numPosePriors();
+    counts[2] = q.numPoseLandmarkMeasurements();
+    counts[3] = q.numLandmarkPriors();
+    counts[4] = q.numRangeMeasurements();
+  });
+}
+
+int cora_problem_measurement_residuals(cora_problem *p, const double *Y, int cols, double *rel_pose_rot,
+                                       double *rel_pose_trans, double *pose_prior_rot, double *pose_prior_trans,
+                                       double *pose_landmark, double *landmark_prior, double *range, double sums[3]) {
+  return guarded([&] {
+    Problem &q = p->problem;
+    const MeasurementResiduals r = q.measurementResiduals(wrap(Y, q.getExpectedVariableSize(), cols));
+    auto put = [](double *dst, const std::vector<Scalar> &v) {
+      if (dst && !v.empty()) std::memcpy(dst, v.data(), sizeof(double) * v.size());
+    };
+    put(rel_pose_rot, r.rel_pose_rot);
+    put(rel_pose_trans, r.rel_pose_trans);
+    put(pose_prior_rot, r.pose_prior_rot);
+    put(pose_prior_trans, r.pose_prior_trans);
+    put(pose_landmark, r.pose_landmark);
+    put(landmark_prior, r.landmark_prior);
+    put(range, r.range);
+    if (sums) {
+      sums[0] = r.rot_sum;
+      sums[1] = r.trans_sum;
+      sums[2] = r.range_sum;
+    }
+  });
+}
+
 int cora_problem_tnt(cora_problem *p, const double *x0, const double *opts, double *x_out, double stats[7]) {
   return guarded([&] {
     Problem &q = p->problem;

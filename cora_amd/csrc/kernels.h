@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "cora_internal.h"
@@ -314,5 +315,29 @@ hipError_t launch_upload(int64_t N, int k, int ld, const double *src, const int3
                          double *dst, hipStream_t st);
 hipError_t launch_download(int64_t N, int k, int ld, const double *src, const int32_t *api2int,
                            double *dst, hipStream_t st);
+
+// Per-measurement residuals (kernels/residuals.inc; include/cora_hip.h, cora_set_measurements).  The table is
+// structure-of-arrays, [field][measurement], rows are INTERNAL rows of X:
+//   edges : rows [4][n] = first rotation row of a, of b (-1: no rotation part), translation row of a, of b
+//           data [d*d + d + 2][n] = R row-major, t, kappa, tau;  out0 = rotation, out1 = translation residual
+//   ranges: rows [3][n] = range row, translation row of a, of b;  data [2][n] = r, omega;  out0 = residual
+// partial: [2][blocks] (edges) / [1][blocks] (ranges) block sums of the outputs, a fixed slot per block
+// (launch_reduce_partials adds them up).  k = columns of X read (ld >= k; the padding column of k = 1 is not trusted).
+struct ResidualArgs {
+  int64_t n = 0;
+  int d = 0, ld = 0, k = 0;
+  const int32_t *rows = nullptr;
+  const double *data = nullptr;
+  const double *X = nullptr;
+  double *out0 = nullptr, *out1 = nullptr;
+  double *partial = nullptr;
+};
+constexpr int kResidualLanes = 8;  // lanes that share one measurement (they stride over the columns of X)
+inline int residual_blocks(int64_t n) {  // blocks of a launch over n measurements (= partial sums per output)
+  const int64_t per_block = 256 / kResidualLanes;
+  return static_cast<int>(std::min<int64_t>((n + per_block - 1) / per_block, 2048));
+}
+hipError_t launch_edge_residuals(const ResidualArgs &A, hipStream_t st);   // n == 0: no launch
+hipError_t launch_range_residuals(const ResidualArgs &A, hipStream_t st);  // n == 0: no launch
 
 }  // namespace cora

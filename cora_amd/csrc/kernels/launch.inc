@@ -357,6 +357,31 @@ hipError_t launch_download(int64_t N, int k, int ld, const double *src, const in
   return hipGetLastError();
 }
 
+// per-measurement residuals (kernels/residuals.inc): 16-byte pieces of a row where the stride is even, 8-byte otherwise
+hipError_t launch_edge_residuals(const ResidualArgs &A, hipStream_t st) {
+  if (A.n <= 0) return hipSuccess;
+  if ((A.d != 2 && A.d != 3) || A.k < 1 || A.k > A.ld) return hipErrorInvalidValue;
+  const dim3 grid(residual_blocks(A.n)), block(256);
+  const bool wide = A.ld % 2 == 0;
+  if (A.d == 2) {
+    if (wide) hipLaunchKernelGGL((k_edge_residuals<2, 2>), grid, block, 0, st, A);
+    else hipLaunchKernelGGL((k_edge_residuals<2, 1>), grid, block, 0, st, A);
+  } else {
+    if (wide) hipLaunchKernelGGL((k_edge_residuals<3, 2>), grid, block, 0, st, A);
+    else hipLaunchKernelGGL((k_edge_residuals<3, 1>), grid, block, 0, st, A);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_range_residuals(const ResidualArgs &A, hipStream_t st) {
+  if (A.n <= 0) return hipSuccess;
+  if (A.k < 1 || A.k > A.ld) return hipErrorInvalidValue;
+  const dim3 grid(residual_blocks(A.n)), block(256);
+  if (A.ld % 2 == 0) hipLaunchKernelGGL((k_range_residuals<2>), grid, block, 0, st, A);
+  else hipLaunchKernelGGL((k_range_residuals<1>), grid, block, 0, st, A);
+  return hipGetLastError();
+}
+
 #endif  // CORA_TU & 2
 #if CORA_TU & 4
 

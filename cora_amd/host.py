@@ -216,6 +216,28 @@ class Problem:
                                                     ob.ctypes.data_as(_dp)))
         return st[:, :dm["d"] * dm["n"]], ob[:dm["r"]]
 
+    def measurement_residuals(self, Y):
+        """Problem::measurementResiduals: dict of numpy arrays rel_pose_rot, rel_pose_trans, pose_prior_rot,
+        pose_prior_trans, pose_landmark, landmark_prior, range (each in the order the measurements were added) and the
+        scalars rot_sum, trans_sum, range_sum; 1/2 of the three sums is evaluateObjective(Y).  Y: variable_size() rows,
+        1..24 columns."""
+        Y = np.asfortranarray(np.asarray(Y, dtype=np.float64))
+        if Y.ndim != 2 or Y.shape[0] != self.variable_size():
+            raise HostError("expected %d rows, got shape %s" % (self.variable_size(), Y.shape))
+        cnt = (C.c_int64 * 5)()
+        self._chk(self.L.cora_problem_measurement_counts(self.h, cnt))
+        names = ["rel_pose_rot", "rel_pose_trans", "pose_prior_rot", "pose_prior_trans", "pose_landmark",
+                 "landmark_prior", "range"]
+        sizes = [cnt[0], cnt[0], cnt[1], cnt[1], cnt[2], cnt[3], cnt[4]]
+        out = {k: np.zeros(max(int(n), 1)) for k, n in zip(names, sizes)}
+        sums = np.zeros(3)
+        self._chk(self.L.cora_problem_measurement_residuals(self.h, Y.ctypes.data_as(_dp), int(Y.shape[1]),
+                                                            *[out[k].ctypes.data_as(_dp) for k in names],
+                                                            sums.ctypes.data_as(_dp)))
+        res = {k: out[k][:int(n)] for k, n in zip(names, sizes)}
+        res.update(rot_sum=float(sums[0]), trans_sum=float(sums[1]), range_sum=float(sums[2]))
+        return res
+
     def tnt(self, x0, max_iterations=0, max_inner=0, grad_tol=0, pgrad_tol=0, max_seconds=0, verbose=False,
             host_stpcg=False):
         dm = self.dims()

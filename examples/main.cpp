@@ -7,6 +7,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -17,11 +18,11 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r]" << std::endl;
+    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv]" << std::endl;
     return 1;
   }
   int max_rank = 10;
-  std::string tum, save_dir;
+  std::string tum, save_dir, residuals;
   bool jacobi = false, implicit = false, odom = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
@@ -31,6 +32,8 @@ int main(int argc, char **argv) {
     else if (a == "--tum" && i + 1 < argc) tum = argv[++i];
     else if (a == "--save-dir" && i + 1 < argc) save_dir = argv[++i];  // cora_<robot>.tum / .g2o per robot, like saveSolutions
     else if (a == "--max-rank" && i + 1 < argc) max_rank = std::atoi(argv[++i]);
+    // per-measurement residuals of the solution, one line each: kind,first,second,rotation,translation_or_range
+    else if (a == "--residuals" && i + 1 < argc) residuals = argv[++i];
   }
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
@@ -61,6 +64,34 @@ int main(int argc, char **argv) {
                 "(TNT %.3f, certification %.3f, saddle escape %.3f)\n",
                 secs(t_start, t_parsed), secs(t_parsed, t_assembled), secs(t_assembled, t_device),
                 secs(t_device, t_solved), info.tnt_seconds, info.certify_seconds, info.escape_seconds);
+    if (!residuals.empty()) {  // (an extension beyond the reference: Problem::measurementResiduals)
+      const CORA::MeasurementResiduals res = problem.measurementResiduals(soln.first.x);
+      std::ofstream csv(residuals);
+      if (!csv) throw std::runtime_error("cannot write " + residuals);
+      csv.precision(17);
+      const std::string origin = problem.getOriginSymbol().string();
+      size_t lines = 0;
+      auto line = [&](const char *kind, const std::string &first, const std::string &second, double rot, double other) {
+        csv << kind << ',' << first << ',' << second << ',' << rot << ',' << other << '\n';
+        ++lines;
+      };
+      for (size_t i = 0; i < problem.getRPMs().size(); ++i)
+        line("rel_pose", problem.getRPMs()[i].first_id.string(), problem.getRPMs()[i].second_id.string(),
+             res.rel_pose_rot[i], res.rel_pose_trans[i]);
+      for (size_t i = 0; i < problem.getPosePriors().size(); ++i)
+        line("pose_prior", origin, problem.getPosePriors()[i].id.string(), res.pose_prior_rot[i], res.pose_prior_trans[i]);
+      for (size_t i = 0; i < problem.getRPLMs().size(); ++i)
+        line("pose_landmark", problem.getRPLMs()[i].first_id.string(), problem.getRPLMs()[i].second_id.string(), 0.0,
+             res.pose_landmark[i]);
+      for (size_t i = 0; i < problem.getLandmarkPriors().size(); ++i)
+        line("landmark_prior", origin, problem.getLandmarkPriors()[i].id.string(), 0.0, res.landmark_prior[i]);
+      for (size_t i = 0; i < problem.getRangeMeasurements().size(); ++i)
+        line("range", problem.getRangeMeasurements()[i].first_id.string(), problem.getRangeMeasurements()[i].second_id.string(),
+             0.0, res.range[i]);
+      std::printf("residuals: rotation %.9g  translation %.9g  range %.9g  half of their total %.9g  (final cost %.9g)\n",
+                  res.rot_sum, res.trans_sum, res.range_sum, 0.5 * (res.rot_sum + res.trans_sum + res.range_sum), soln.first.f);
+      std::cout << "wrote " << residuals << " (" << lines << " measurements)" << std::endl;
+    }
     if (!tum.empty()) {
       CORA::saveSolnToTum(problem, aligned, tum);
       std::cout << "wrote " << tum << std::endl;

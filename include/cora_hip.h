@@ -339,6 +339,54 @@ int cora_gram_batch_dev(cora_ctx *ctx, int n, const double *const *dA, const int
 int cora_combine_dev(cora_ctx *ctx, int n, const double *const *dX, const int *k, const double *const *C,
                      int kout, double *dOut);
 
+/* ------------------------------------------------ per-measurement residuals
+ *
+ * An EXTENSION beyond the reference, whose Problem keeps the measurements only until fillDataMatrix() has summed them
+ * into Q (src/CORA_problem.cpp:625-712) and can therefore report one number, f = 1/2 <X, Q X>.  The handle keeps a table
+ * of the measurements themselves and evaluates every one of them at a resident X in one gather pass.  With X_a the
+ * d x k block of pose a's rotation rows, x_t(s) the translation row of symbol s and x_rho(m) the unit row of range m:
+ *   edge  (a, b, R, t, kappa, tau) -- relative poses, pose priors (a = the origin pose), pose-landmark measurements and
+ *         landmark priors (a = the origin pose, t = the prior position), in the row order of fillRelPoseSubmatrices
+ *         (src/CORA_problem.cpp:149-295):
+ *             rot   = kappa |X_b - R^T X_a|_F^2          (0, and R not read, when b has no rotation: second row -1)
+ *             trans = tau |x_t(b) - x_t(a) - sum_c t_c X_a[c, :]|^2
+ *   range (a, b, r, omega):  res = omega |x_t(b) - x_t(a) + r x_rho(m)|^2
+ * NO factor 1/2 goes into the per-measurement values.  With Q as fillDataMatrix() builds it,
+ *   1/2 (sum rot + sum trans + sum res) = f(X)  for ANY X (on the manifold or not; R is orthogonal),
+ * and at a good solution the residual form keeps the digits the quadratic form cancels.
+ *
+ * cora_set_measurements: the table, in API rows (variable layout above).
+ *   edge_rows  [n_edges][4] int32: first rotation row of a, first rotation row of b or -1, translation row of a, of b
+ *   edge_data  [n_edges][d*d + d + 2]: R row-major, t, kappa, tau
+ *   range_rows [n_ranges][3]: range row, translation row of a, translation row of b
+ *   range_data [n_ranges][2]: r, omega
+ * CORA_ERR_ARG with a message: a rotation row that is not a multiple of d below d*n, a range row outside [d*n, d*n + r),
+ * a translation row outside [d*n + r, N), non-finite data, a partitioned handle (world > 1: not supported yet).  Every
+ * row is translated to the internal order once (cora_row_map); a pose's rotation block is kept by its first internal
+ * row, and a layout in which its d rows are not consecutive is an error, not a wrong number.  The device copy is
+ * structure-of-arrays ([field][measurement]) in the order given -- keep Problem order: odometry edges then touch
+ * neighbouring internal rows.  A second call replaces the table.  Works on a plan-only handle (device < 0): everything
+ * except the upload.
+ * cora_measurement_counts: out = { edges, ranges } of the current table (0, 0 without one).
+ * cora_measurement_residuals_dev: dX is a resident vector of k columns, 1 <= k <= 24 (ld = cora_ld_for(k)), k independent
+ *   of the handle's rank as in cora_spmm_dev (the relaxed and the rounded solution are both served).  edge_rot,
+ *   edge_trans [n_edges] and range_res [n_ranges] are HOST pointers, each may be NULL; sums[3] = { sum rot, sum trans,
+ *   sum res } (may be NULL).  Synchronises.  CORA_ERR_NOT_READY before a table is set.  A measurement's value has the
+ *   same bits wherever it stands in the table, and two calls give the same bits (fixed summation orders, no atomics).
+ * cora_measurement_residuals: the host-pointer form (X: N x k column-major, uploaded first). */
+int cora_set_measurements(cora_ctx *ctx, int64_t n_edges, const int32_t *edge_rows, const double *edge_data,
+                          int64_t n_ranges, const int32_t *range_rows, const double *range_data);
+int cora_measurement_counts(const cora_ctx *ctx, int64_t out[2]);
+int cora_measurement_residuals_dev(cora_ctx *ctx, const double *dX, int k, double *edge_rot, double *edge_trans,
+                                   double *range_res, double sums[3]);
+int cora_measurement_residuals(cora_ctx *ctx, const double *X, int ldx, int k, double *edge_rot, double *edge_trans,
+                               double *range_res, double sums[3]);
+/* Test hook: the TRANSLATED table executed on the host on X permuted into the internal order (the analogue of
+ * cora_debug_format_spmm_host): table building and row translation can be tested where no GPU exists.  Never used by
+ * any compute entry point. */
+int cora_debug_measurement_residuals_host(cora_ctx *ctx, const double *X, int ldx, int k, double *edge_rot,
+                                          double *edge_trans, double *range_res, double sums[3]);
+
 /* Timing helpers: HIP events on the handle's stream. */
 int cora_timer_start(cora_ctx *ctx);
 int cora_timer_stop_ms(cora_ctx *ctx, float *ms); /* synchronises */

@@ -99,6 +99,14 @@ int cora_problem_op(cora_problem *p, const char *op, int cols, const double *A, 
                     const double *C, double *out);
 /* compute_Lambda_blocks(Y): stiefel d x dn (ld d), oblique r */
 int cora_problem_lambda_blocks(cora_problem *p, const double *Y, double *stiefel, double *oblique);
+/* Problem::measurementResiduals (an extension beyond the reference; formulas in include/cora_hip.h, "per-measurement
+ * residuals").  counts: [0] relative poses, [1] pose priors, [2] pose-landmark measurements, [3] landmark priors,
+ * [4] ranges.  Y: getExpectedVariableSize() x cols, 1 <= cols <= 24.  Each output has the length of its kind's count, in
+ * the order the measurements were added, and may be NULL; sums = { rotation, translation, range } (may be NULL). */
+int cora_problem_measurement_counts(const cora_problem *p, int64_t counts[5]);
+int cora_problem_measurement_residuals(cora_problem *p, const double *Y, int cols, double *rel_pose_rot,
+                                       double *rel_pose_trans, double *pose_prior_rot, double *pose_prior_trans,
+                                       double *pose_landmark, double *landmark_prior, double *range, double sums[3]);
 
 /* Riemannian TNT (the call of src/CORA.cpp:139-140 with the parameters of :95-109) from x0
  * (N x rank).  opts (may be NULL): [0] max_iterations, [1] max_TPCG_iterations, [2] gradient
