@@ -542,6 +542,38 @@ class Context:
         return self._residuals(lambda *o: self.L.cora_debug_measurement_residuals_host(self.h, _d(X), X.shape[0],
                                                                                       X.shape[1], *o))
 
+    # ---- new values of Q on the same pattern (include/cora_hip.h, cora_update_values)
+    @staticmethod
+    def _csr(rowptr, colidx):
+        return (np.ascontiguousarray(rowptr, dtype=np.int32), np.ascontiguousarray(colidx, dtype=np.int32))
+
+    def values_map_build(self, rowptr, colidx):
+        rowptr, colidx = self._csr(rowptr, colidx)
+        if len(rowptr) != self.N + 1:
+            raise CoraError(5, "rowptr must have N+1 entries")
+        self._chk(self.L.cora_values_map_build(self.h, rowptr.ctypes.data_as(_ip), colidx.ctypes.data_as(_ip)))
+
+    def update_values(self, rowptr, colidx, vals):
+        """Replaces the values of Q in place (host values, CSR order, the pattern of creation).  Afterwards the handle
+        is in the state of a fresh one: set the point and the preconditioner again."""
+        rowptr, colidx = self._csr(rowptr, colidx)
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        if len(rowptr) != self.N + 1:
+            raise CoraError(5, "rowptr must have N+1 entries")
+        if len(colidx) != rowptr[-1] or len(vals) != rowptr[-1]:
+            raise CoraError(5, "colidx and vals must have rowptr[N] entries")
+        self._chk(self.L.cora_update_values(self.h, rowptr.ctypes.data_as(_ip), colidx.ctypes.data_as(_ip), _d(vals)))
+
+    def update_values_dev(self, d_vals):
+        """The same from nnz doubles in CSR order on the device (a raw pointer as an int); needs the map."""
+        self._chk(self.L.cora_update_values_dev(self.h, C.c_void_p(d_vals)))
+
+    def update_values_times(self):
+        """Milliseconds of the last update: map build, host check, upload, device passes, host refresh."""
+        out = (C.c_double * 5)()
+        self._chk(self.L.cora_update_values_times(self.h, out))
+        return [out[i] for i in range(5)]
+
     # ---- test hook
     def debug_format_spmm_host(self, X):
         X = _f(X)

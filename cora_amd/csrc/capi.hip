@@ -2,7 +2,7 @@
 // device memory and stream; every compute entry point ends in a HIP kernel of
 // kernels.hip -- there is no CPU fallback.
 //
-// ONE translation unit in eleven pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
+// ONE translation unit in twelve pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
 // error / device macros and the helpers every part uses; the entry points live in capi/*.inc, included at the end in this order:
 //   handle.inc          creation of (partitioned) handles, destruction, rank state, row maps, statistics
 //   resident.inc        device vectors, the current point, the trust-region trial / accept pair, products, projections
@@ -13,6 +13,7 @@
 //   blocks.inc          row moves, STPCG measurement hooks, LOBPCG's block algebra, timers
 //   host_pointer.inc    the host-pointer operator API (one entry per reference method), host-side debug hooks
 //   measurements.inc    the measurement table of a handle and the per-measurement residuals
+//   values.inc          in-place update of Q's values: source map, host-pointer and device-pointer update
 //   comm.inc            native communication: RCCL, in-process and device-side (p2p.h) transports
 #include <hip/hip_runtime.h>
 // RCCL's types and the few enumerators used, declared here (NCCL's public ABI: they have not changed since 2.0): the
@@ -211,6 +212,15 @@ struct cora_ctx {
   std::vector<uintptr_t> stpcg_graph_key;
   unsigned long long *d_seq_counter = nullptr;  // the device's copy of dot_seq (kernels.h, DotArgs::seq_counter)
   long stpcg_graph_replays = 0, stpcg_graph_captures = 0;
+  // in-place update of Q's values (capi/values.inc): the source map, built at the first update, its device copy
+  // (sources of the five arrays at vmap_off, mirror pairs, a staging buffer for host values) and what it needs to know
+  ValueMap vmap;
+  int32_t *d_vmap_src = nullptr, *d_vmap_mirror = nullptr;
+  double *d_vmap_vals = nullptr;
+  size_t vmap_off[5] = {0, 0, 0, 0, 0};
+  bool dist_long = true;            // the handle was created with distributed long rows (no CORA_PART_WHOLE_LONG_ROWS)
+  bool host_values_stale = false;   // cora_update_values_dev moved the device's values only: F's value arrays are old
+  double values_ms[5] = {0, 0, 0, 0, 0};  // cora_update_values_times
   std::vector<std::pair<double *, size_t>> user_allocs;  // live vectors of cora_dev_alloc (pointer, bytes)
   std::vector<std::pair<double *, size_t>> pool;         // released ones, kept for the next request of the same size
   std::string err;
@@ -528,6 +538,7 @@ extern "C" {
 #include "capi/blocks.inc"
 #include "capi/host_pointer.inc"
 #include "capi/measurements.inc"
+#include "capi/values.inc"
 
 }  // extern "C"
 

@@ -38,6 +38,7 @@ int cora_ctx_create_part_opts(int device, int d, int n_poses, int n_ranges, int 
     return fail(nullptr, CORA_ERR_SHAPE, msg);
   }
   c->device = device;
+  c->dist_long = (flags & CORA_PART_WHOLE_LONG_ROWS) == 0;
   if (device < 0) {  // plan-only handle: format inspection / host tests
     *out = c;
     return CORA_OK;
@@ -178,7 +179,8 @@ void cora_ctx_destroy(cora_ctx *c) {
     if (c->ev_exchanged) (void)hipEventDestroy(c->ev_exchanged);
     void *ptrs[] = {c->d_slices_int, c->d_slices_bnd, c->d_slices, c->d_slices_pf, c->d_head_val, c->d_long_out, c->d_long_rows, c->d_long_owner, c->d_sval, c->d_scol, c->d_perm, c->d_chunks, c->d_chunk_order, c->d_lval, c->d_lcol,
                     c->d_partials, c->d_tickets, c->d_api2int, c->d_diag_inv, c->d_lam_st, c->d_lam_ob, c->d_own_sym, c->d_S,
-                    c->d_stage, c->d_red, c->d_scalars, c->d_flag, c->d_ticket, c->d_stpcg, c->d_seq_counter};
+                    c->d_stage, c->d_red, c->d_scalars, c->d_flag, c->d_ticket, c->d_stpcg, c->d_seq_counter,
+                    c->d_vmap_src, c->d_vmap_mirror, c->d_vmap_vals};
     if (c->stpcg_graph) (void)hipGraphExecDestroy(c->stpcg_graph);
     for (void *p : ptrs)
       if (p) (void)hipFree(p);

@@ -204,6 +204,9 @@ int cora_inner_product(cora_ctx *c, const double *A, int lda, const double *B, i
 
 int cora_debug_format_spmm_host(const cora_ctx *c, const double *X, int ldx, int k, double *out, int ldo) {
   if (!c || !X || !out || k <= 0 || k > kMaxLD) return CORA_ERR_ARG;
+  if (c->host_values_stale)
+    return fail(const_cast<cora_ctx *>(c), CORA_ERR_NOT_READY,
+                "the host copy of the format holds the values from before cora_update_values_dev: update with host values first");
   const HostFormat &F = c->F;
   const int ld = ld_for(k);
   const int64_t N = F.L.N;

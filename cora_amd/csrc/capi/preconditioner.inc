@@ -2,9 +2,17 @@
 int cora_precond_setup(cora_ctx *c, int kind) {
   if (!c) return CORA_ERR_ARG;
   if (kind == CORA_PRECOND_NONE || kind == CORA_PRECOND_JACOBI) {
-    if (kind == CORA_PRECOND_JACOBI)
+    if (kind == CORA_PRECOND_JACOBI && c->host_values_stale) {
+      // (cora_update_values_dev: the diagonal the device holds is newer than F.diag -- a zero shows as an infinite reciprocal)
+      HIP_TRY(c, hipSetDevice(c->device));
+      std::vector<double> dinv(c->F.diag.size());
+      HIP_TRY(c, hipMemcpy(dinv.data(), c->d_diag_inv, dinv.size() * sizeof(double), hipMemcpyDeviceToHost));
+      for (double v : dinv)
+        if (!std::isfinite(v)) return fail(c, CORA_ERR_NAN, "zero on the diagonal of Q: Jacobi preconditioner undefined");
+    } else if (kind == CORA_PRECOND_JACOBI) {
       for (double v : c->F.diag)
         if (!(v != 0.0)) return fail(c, CORA_ERR_NAN, "zero on the diagonal of Q: Jacobi preconditioner undefined");
+    }
     c->precond = kind;
     return CORA_OK;
   }

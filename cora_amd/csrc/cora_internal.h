@@ -151,11 +151,46 @@ struct HostFormat {
   int max_width = 0;
 };
 
+// Provenance mode of build_format (build_value_map): `val` holds 1 + the CSR position of every entry, so every slot of
+// the format names its source; the equalities a chain slice is checked for are recorded in `mirror` instead of tested,
+// and pose slice j takes the chain layout only where chain[j] says the handle's own slice did.
+struct ProvenanceBuild {
+  std::vector<char> chain;
+  std::vector<int32_t> mirror;
+};
+
 // Builds the partition + sliced format.  Throws std::runtime_error on invalid input.
 // distribute_long_rows (world > 1 only): see HostFormat::long_rows.
 void build_format(int d, int n, int r, int nt, const int32_t *rowptr,
                   const int32_t *col, const double *val, int rank, int world,
-                  HostFormat &out, bool distribute_long_rows = true);
+                  HostFormat &out, bool distribute_long_rows = true, ProvenanceBuild *prov = nullptr);
+
+// Where every stored value of a HostFormat comes from in the CSR the format was built from (cora_update_values: the
+// sparsity pattern of Q stays, only numbers move).  A source is a CSR position, or kNoSource for a slot that holds no
+// entry (padding; a column one of a pose's rows does not have).  kSourceAdd0 marks the slots build_format fills by
+// ADDING the entry to +0.0 (the rotation rows' union pattern, the diagonal): the update adds too, so that a -0.0 in the
+// CSR ends as the same +0.0.  Rows with a repeated column index have no map (their slots are sums of several entries):
+// build_value_map refuses them, creation keeps accepting them.
+constexpr int32_t kNoSource = -1;
+constexpr int32_t kSourceAdd0 = INT32_MIN;  // flag bit; position = src & INT32_MAX
+struct ValueMap {
+  bool built = false;
+  uint64_t pattern_hash = 0;   // of (rowptr, colidx): checked on every later update
+  int64_t nnz = 0;
+  std::vector<int32_t> sval, lval, head_val, diag;  // one source per slot of the array of the same name
+  std::vector<int32_t> own_sym;  // two sources per slot ([2 * slot], [2 * slot + 1]): the slot is half their sum
+  // The equalities the chain layout relies on (format_build.cpp: trot/s0, prev/nxt, hq/s1, ht/s1[d]) as pairs of
+  // sources: the values at [2 * j] and [2 * j + 1] must compare equal (kNoSource: zero) or the update is refused.
+  std::vector<int32_t> mirror;
+};
+uint64_t pattern_hash(int64_t N, const int32_t *rowptr, const int32_t *col);
+// Recomputes the format's structure from (rowptr, col), compares it with F's own (slices, columns, chunks, row maps) and
+// records the sources.  Throws std::runtime_error (pattern differs, repeated column in a row, invalid CSR).
+void build_value_map(const HostFormat &F, const int32_t *rowptr, const int32_t *col, bool distribute_long_rows, ValueMap &M);
+// Why `val` cannot replace the values (non-finite entry, broken mirror equality), or nullptr.
+const char *value_map_check_host(const ValueMap &M, const double *val);
+// F's five value arrays from `val` through the map: the bits build_format would have produced.
+void value_map_apply_host(const ValueMap &M, const double *val, HostFormat &F);
 
 // Every column index a slice stores (general slots and tail of a chain slice; all slots of the others); the implied
 // columns of a chain slice are rows of the local shard.

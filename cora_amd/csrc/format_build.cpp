@@ -8,6 +8,7 @@
 // src/CORA_problem.cpp:625-712) with the variable layout of
 // include/CORA/CORA_problem.h:151-157.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -81,7 +82,7 @@ void emit_slice(HostFormat &F, const std::vector<RowRef> &rows, size_t begin,
 
 void build_format(int d, int n, int r, int nt, const int32_t *rowptr,
                   const int32_t *col, const double *val, int rank, int world,
-                  HostFormat &F, bool distribute_long_rows) {
+                  HostFormat &F, bool distribute_long_rows, ProvenanceBuild *prov) {
   const bool dist_long = distribute_long_rows && world > 1;
   PhaseTimer tick(env_flag(Env::FormatTiming), "  [format]", 28, 4);
   if (d != 2 && d != 3) throw std::runtime_error("cora: dimension d must be 2 or 3");
@@ -285,8 +286,19 @@ void build_format(int d, int n, int r, int nt, const int32_t *rowptr,
       SliceDesc sd{};
       std::vector<double> v;
       std::vector<int32_t> c;
+      std::vector<int32_t> mirror;  // provenance mode: the pairs of sources the checks below would have compared
       int64_t padded = 0, nnz = 0;
       int maxw = 0;
+    };
+    // The identities of the chain layout.  Provenance mode (ProvenanceBuild, cora_internal.h): the values are 1 + their
+    // CSR position, a pair that differs is recorded (0: no entry there) and the slice follows the handle's own layout.
+    auto differ = [prov](double x, double y, SliceOut &O) {
+      if (!prov) return x != y;
+      if (x != y) {
+        O.mirror.push_back(static_cast<int32_t>(x) - 1);
+        O.mirror.push_back(static_cast<int32_t>(y) - 1);
+      }
+      return false;
     };
     const int n_pose_slices = (L.nl_poses + kWave - 1) / kWave;
     std::vector<SliceOut> outs(static_cast<size_t>(n_pose_slices));
@@ -384,16 +396,16 @@ void build_format(int d, int n, int r, int nt, const int32_t *rowptr,
             else { C.tc.push_back(static_cast<int32_t>(c)); C.tv.push_back(v); }
           }
           for (int c = 0; c < d; ++c)
-            if (trot[c] != C.s0[c]) chain = false;  // Q31 = Q13^T on the pose's own block
+            if (differ(trot[c], C.s0[c], O)) chain = false;  // Q31 = Q13^T on the pose's own block
         }
         for (int q = 1; q < cnt && chain; ++q) {  // what lane q takes from lane q - 1
           const ChainLane &C = cl[q], &B = cl[q - 1];
           for (int a = 0; a < d; ++a)
             for (int c = 0; c < d; ++c)
-              if (C.prev[c * d + a] != B.nxt[a * d + c]) chain = false;  // Q(rot(P)_a, rot(P-1)_c) = Q(rot(P-1)_c, rot(P)_a)
+              if (differ(C.prev[c * d + a], B.nxt[a * d + c], O)) chain = false;  // Q(rot(P)_a, rot(P-1)_c) = Q(rot(P-1)_c, rot(P)_a)
           for (int c = 0; c < d; ++c)
-            if (C.hq[c] != B.s1[c]) chain = false;                        // Q(t_P, rot(P-1)_c) = Q(rot(P-1)_c, t_P)
-          if (C.ht != B.s1[d]) chain = false;                             // Q(t_P, t_{P-1}) = Q(t_{P-1}, t_P)
+            if (differ(C.hq[c], B.s1[c], O)) chain = false;                      // Q(t_P, rot(P-1)_c) = Q(rot(P-1)_c, t_P)
+          if (differ(C.ht, B.s1[d], O)) chain = false;                           // Q(t_P, t_{P-1}) = Q(t_{P-1}, t_P)
         }
         size_t T = 0;  // the tail is stored as PAIRS of entries (cora_internal.h): an odd count is padded with a zero
         for (int q = 0; q < cnt && chain; ++q) {
@@ -417,7 +429,9 @@ void build_format(int d, int n, int r, int nt, const int32_t *rowptr,
           T += C.tc.size() / 2;
         }
         if (T > 0xffffu) chain = false;
+        if (prov && !prov->chain[static_cast<size_t>(p0 / kWave)]) chain = false;
       }
+      if (!chain) O.mirror.clear();
       SliceDesc sd{};
       sd.row0 = static_cast<int32_t>(L.rot_base + static_cast<int64_t>(p0) * d);
       sd.nrows = cnt;
@@ -528,6 +542,7 @@ void build_format(int d, int n, int r, int nt, const int32_t *rowptr,
       F.max_width = std::max(F.max_width, O.maxw);
       slice_key.push_back(O.sd.aux0);
       F.slices.push_back(O.sd);
+      if (prov) prov->mirror.insert(prov->mirror.end(), O.mirror.begin(), O.mirror.end());
       std::vector<double>().swap(O.v);
       std::vector<int32_t>().swap(O.c);
     }
@@ -791,6 +806,130 @@ void format_spmm_host(const HostFormat &F, const double *X, int ld, double *out)
     for (int j = 0; j < ld; ++j) out[static_cast<size_t>(c0.row) * ld + j] = acc[j];
     ci += c0.nchunks;
   }
+}
+
+// ---- in-place update of the values (cora_update_values): where every stored value comes from -------------------------
+
+uint64_t pattern_hash(int64_t N, const int32_t *rowptr, const int32_t *col) {
+  // FNV-1a over 64-bit words: the dimensions, the row pointers, the column indices
+  uint64_t h = 1469598103934665603ull;
+  auto mix = [&h](uint64_t v) { h = (h ^ v) * 1099511628211ull; };
+  mix(static_cast<uint64_t>(N));
+  for (int64_t i = 0; i <= N; ++i) mix(static_cast<uint32_t>(rowptr[i]));
+  const int64_t nnz = rowptr[N];
+  for (int64_t q = 0; q < nnz; ++q) mix(static_cast<uint32_t>(col[q]));
+  return h;
+}
+
+void build_value_map(const HostFormat &F, const int32_t *rowptr, const int32_t *col, bool distribute_long_rows, ValueMap &M) {
+  const Layout &L = F.L;
+  const int d = L.d;
+  const int64_t N = L.N;
+  M = ValueMap();
+  if (rowptr[0] != 0) throw std::runtime_error("cora: rowptr[0] must be 0");
+  for (int64_t i = 0; i < N; ++i)
+    if (rowptr[i + 1] < rowptr[i]) throw std::runtime_error("cora: rowptr not monotone");
+  if (rowptr[N] != F.nnz_global) throw std::runtime_error("cora: the number of nonzeros differs from the handle's matrix");
+  const int64_t nnz = rowptr[N];
+  {  // a slot that is the sum of several entries has no single source
+    std::vector<int32_t> rc;
+    for (int64_t i = 0; i < N; ++i) {
+      rc.assign(col + rowptr[i], col + rowptr[i + 1]);
+      std::sort(rc.begin(), rc.end());
+      if (std::adjacent_find(rc.begin(), rc.end()) != rc.end())
+        throw std::runtime_error("cora: a row repeats a column index: such a matrix cannot be updated in place (merge the "
+                                 "duplicates, or create a new handle)");
+    }
+  }
+  ProvenanceBuild prov;
+  prov.chain.assign(static_cast<size_t>((L.nl_poses + kWave - 1) / kWave), 0);
+  for (const SliceDesc &sd : F.slices)
+    if ((sd.type & kSliceTypeMask) == kSliceStiefel && (sd.type & kSliceChainFlag)) prov.chain[static_cast<size_t>(sd.aux0 / kWave)] = 1;
+  std::vector<double> pos(static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+  for (int64_t q = 0; q < nnz; ++q) pos[static_cast<size_t>(q)] = static_cast<double>(q + 1);
+  HostFormat G;
+  build_format(d, L.n, L.r, L.nt, rowptr, col, pos.data(), L.rank, L.world, G, distribute_long_rows, &prov);
+  auto same_pod = [](const auto &a, const auto &b) {
+    return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0);
+  };
+  if (G.L.rows != L.rows || G.L.base != L.base || G.L.local_rows != L.local_rows || !same_pod(G.api2int, F.api2int) ||
+      !same_pod(G.slices, F.slices) || !same_pod(G.slices_pose_first, F.slices_pose_first) || !same_pod(G.scol, F.scol) ||
+      !same_pod(G.perm, F.perm) || !same_pod(G.chunks, F.chunks) || !same_pod(G.chunk_order, F.chunk_order) ||
+      !same_pod(G.lcol, F.lcol) || !same_pod(G.long_rows, F.long_rows) || G.sval.size() != F.sval.size() ||
+      G.lval.size() != F.lval.size() || G.head_val.size() != F.head_val.size() || G.own_sym.size() != F.own_sym.size() ||
+      G.diag.size() != F.diag.size())
+    throw std::runtime_error("cora: the sparsity pattern differs from the one the handle was created with");
+  auto source = [](double v) { return v == 0.0 ? kNoSource : static_cast<int32_t>(v) - 1; };
+  auto add0 = [](int32_t s) { return s == kNoSource ? s : (s | kSourceAdd0); };
+  M.sval.resize(G.sval.size());
+  for (size_t i = 0; i < G.sval.size(); ++i) M.sval[i] = source(G.sval[i]);
+  M.lval.resize(G.lval.size());
+  for (size_t i = 0; i < G.lval.size(); ++i) M.lval[i] = source(G.lval[i]);
+  M.diag.resize(G.diag.size());
+  for (size_t i = 0; i < G.diag.size(); ++i) M.diag[i] = add0(source(G.diag[i]));
+  const int HV = kChainHead(d), FV = kChainFixed(d), SE = kSymEl(d);
+  M.head_val.resize(G.head_val.size());
+  for (size_t i = 0; i < G.head_val.size(); ++i) {
+    const int32_t s = source(G.head_val[i]);
+    M.head_val[i] = static_cast<int>(i % HV) < d * d ? add0(s) : s;  // the rotation rows' entries are sums from +0.0
+  }
+  M.own_sym.assign(2 * G.own_sym.size(), kNoSource);
+  // which slots of the pose slices hold entries of the rotation rows (added to +0.0 by build_slice); sym(Q_PP) of a
+  // chain slice's lane from the sources of its own block
+  for (const SliceDesc &sd : G.slices) {
+    if ((sd.type & kSliceTypeMask) != kSliceStiefel) continue;
+    int32_t *sv = M.sval.data() + sd.off;
+    if (!(sd.type & kSliceChainFlag)) {
+      for (size_t i = 0; i < static_cast<size_t>(sd.width) * d * kWave; ++i) sv[i] = add0(sv[i]);
+      continue;
+    }
+    for (int slot = 0; slot < FV + sd.width * d; ++slot) {
+      if (slot == d || slot == 2 * d + 1) continue;  // s0[d], s1[d]: entries of the translation row, copied as they are
+      for (int lane = 0; lane < kWave; ++lane) sv[static_cast<size_t>(slot) * kWave + lane] = add0(sv[static_cast<size_t>(slot) * kWave + lane]);
+    }
+    int32_t *os = M.own_sym.data() + 2 * static_cast<size_t>(sd.aux0 / kWave) * SE * kWave;
+    const int own0 = 2 * (d + 1) + d * d;
+    for (int lane = 0; lane < sd.nrows; ++lane)
+      for (int a = 0; a < d; ++a)
+        for (int c = a; c < d; ++c) {
+          const size_t o = static_cast<size_t>(kSymSlot(a, c, d)) * kWave + lane;
+          os[2 * o] = sv[static_cast<size_t>(own0 + c * d + a) * kWave + lane];
+          os[2 * o + 1] = sv[static_cast<size_t>(own0 + a * d + c) * kWave + lane];
+        }
+  }
+  M.mirror.swap(prov.mirror);
+  M.nnz = nnz;
+  M.pattern_hash = pattern_hash(N, rowptr, col);
+  M.built = true;
+}
+
+namespace {
+inline double mapped(const double *val, int32_t s) {
+  if (s == kNoSource) return 0.0;
+  const double v = val[s & INT32_MAX];
+  return s < 0 ? 0.0 + v : v;
+}
+}  // namespace
+
+const char *value_map_check_host(const ValueMap &M, const double *val) {
+  for (int64_t q = 0; q < M.nnz; ++q)
+    if (!std::isfinite(val[q])) return "a value is not finite";
+  for (size_t j = 0; j + 1 < M.mirror.size(); j += 2) {
+    const double a = M.mirror[j] == kNoSource ? 0.0 : val[M.mirror[j]];
+    const double b = M.mirror[j + 1] == kNoSource ? 0.0 : val[M.mirror[j + 1]];
+    if (a != b)
+      return "the values break the symmetry the chain layout of the handle relies on (Q(i, j) and Q(j, i) of a pose's "
+             "couplings to itself and to its neighbour must be equal)";
+  }
+  return nullptr;
+}
+
+void value_map_apply_host(const ValueMap &M, const double *val, HostFormat &F) {
+  for (size_t i = 0; i < M.sval.size(); ++i) F.sval[i] = mapped(val, M.sval[i]);
+  for (size_t i = 0; i < M.lval.size(); ++i) F.lval[i] = mapped(val, M.lval[i]);
+  for (size_t i = 0; i < M.head_val.size(); ++i) F.head_val[i] = mapped(val, M.head_val[i]);
+  for (size_t i = 0; i < M.diag.size(); ++i) F.diag[i] = mapped(val, M.diag[i]);
+  for (size_t i = 0; i < F.own_sym.size(); ++i) F.own_sym[i] = 0.5 * (mapped(val, M.own_sym[2 * i]) + mapped(val, M.own_sym[2 * i + 1]));
 }
 
 }  // namespace cora

@@ -135,6 +135,21 @@ static SparseMatrix diagonal(const std::vector<Scalar> &d) {
   return m;
 }
 
+// What symbolic_cache_ points to: the symbolic analyses and, behind them, the measurement weights (CORA_problem.h)
+namespace {
+struct SharedState : SymbolicCache {
+  MeasurementWeights weights;
+};
+}  // namespace
+std::shared_ptr<SymbolicCache> Problem::newSharedState() { return std::make_shared<SharedState>(); }
+MeasurementWeights &Problem::weights() const { return static_cast<SharedState *>(symbolic_cache_.get())->weights; }
+const MeasurementWeights &Problem::getMeasurementWeights() const { return weights(); }
+
+// weight i of a kind (MeasurementWeights: an empty vector is all ones, and leaves the precision's bits alone)
+static inline Scalar weighted(Scalar precision, const std::vector<Scalar> &w, size_t i) {
+  return w.empty() ? precision : precision * w[i];
+}
+
 void Problem::fillRangeSubmatrices() {
   const Index off = rotAndRangeMatrixSize();
   const Index r = numRangeMeasurements(), nt = numTranslationalStates();
@@ -143,7 +158,7 @@ void Problem::fillRangeSubmatrices() {
   for (Index k = 0; k < r; ++k) {
     const RangeMeasurement &m = range_measurements_[k];
     dist[k] = m.r;
-    prec[k] = m.getPrecision();
+    prec[k] = weighted(m.getPrecision(), weights().range, static_cast<size_t>(k));
     inc.push_back({k, getTranslationIdx(m.first_id) - off, -1.0});
     inc.push_back({k, getTranslationIdx(m.second_id) - off, 1.0});
   }
@@ -171,16 +186,21 @@ void Problem::fillRelPoseSubmatrices() {
     ++row;
   };
   // row order: pose-pose, pose priors, pose-landmark, landmark priors (:190-294)
+  size_t i = 0;
   for (const auto &rpm : rel_pose_pose_measurements_) {
-    rprec[row] = rpm.getRotPrecision();
-    add(rpm.first_id, rpm.second_id, rpm.t, rpm.getTransPrecision());
+    rprec[row] = weighted(rpm.getRotPrecision(), weights().rel_pose_rot, i);
+    add(rpm.first_id, rpm.second_id, rpm.t, weighted(rpm.getTransPrecision(), weights().rel_pose_trans, i++));
   }
+  i = 0;
   for (const auto &pp : pose_priors_) {
-    rprec[row] = pp.getRotPrecision();
-    add(origin_symbol_, pp.id, pp.t, pp.getTransPrecision());
+    rprec[row] = weighted(pp.getRotPrecision(), weights().pose_prior_rot, i);
+    add(origin_symbol_, pp.id, pp.t, weighted(pp.getTransPrecision(), weights().pose_prior_trans, i++));
   }
-  for (const auto &pl : rel_pose_landmark_measurements_) add(pl.first_id, pl.second_id, pl.t, pl.getTransPrecision());
-  for (const auto &lp : landmark_priors_) add(origin_symbol_, lp.id, lp.p, lp.getTransPrecision());
+  i = 0;
+  for (const auto &pl : rel_pose_landmark_measurements_)
+    add(pl.first_id, pl.second_id, pl.t, weighted(pl.getTransPrecision(), weights().pose_landmark, i++));
+  i = 0;
+  for (const auto &lp : landmark_priors_) add(origin_symbol_, lp.id, lp.p, weighted(lp.getTransPrecision(), weights().landmark_prior, i++));
 
   data_submatrices_.rel_pose_incidence_matrix = SparseMatrix(m, nt);
   data_submatrices_.rel_pose_incidence_matrix.setFromTriplets(std::move(inc));
@@ -202,10 +222,12 @@ void Problem::fillRotConnLaplacian() {
     for (Index r = 0; r < d; ++r)
       for (Index c = 0; c < d; ++c) t.push_back({j * d + r, i * d + c, -kappa * R(c, r)});
   };
+  size_t i = 0;
   for (const auto &m : rel_pose_pose_measurements_)
-    add(getRotationIdx(m.first_id), getRotationIdx(m.second_id), m.getRotPrecision(), m.R);
+    add(getRotationIdx(m.first_id), getRotationIdx(m.second_id), weighted(m.getRotPrecision(), weights().rel_pose_rot, i++), m.R);
+  i = 0;
   for (const auto &p : pose_priors_)
-    add(getRotationIdx(origin_symbol_), getRotationIdx(p.id), p.getRotPrecision(), p.R);
+    add(getRotationIdx(origin_symbol_), getRotationIdx(p.id), weighted(p.getRotPrecision(), weights().pose_prior_rot, i++), p.R);
   data_submatrices_.rotation_conn_laplacian = SparseMatrix(numPosesDim(), numPosesDim());
   data_submatrices_.rotation_conn_laplacian.setFromTriplets(std::move(t));
 }
@@ -246,6 +268,7 @@ void Problem::fillDataMatrix() {
 
 void Problem::updateProblemData() {  // src/CORA_problem.cpp:500-510
   cora::PhaseTimer tick(cora::env_flag(cora::Env::TriTiming), "  [update]", 26, 3);
+  validateWeights(weights());  // (measurements added after setMeasurementWeights: the weights must be set again)
   fillRangeSubmatrices();
   tick("range submatrices");
   fillRelPoseSubmatrices();
@@ -262,6 +285,61 @@ void Problem::updateProblemData() {  // src/CORA_problem.cpp:500-510
   cert_lambda_pos_.clear();
   cert_lambda_q_.clear();
   problem_data_up_to_date_ = true;
+}
+
+void Problem::validateWeights(const MeasurementWeights &w) const {
+  auto check = [](const std::vector<Scalar> &v, size_t n, const char *kind) {
+    if (v.empty()) return;
+    if (v.size() != n)
+      throw std::invalid_argument(std::string("Problem: measurement weights: ") + kind + " has " + std::to_string(v.size()) +
+                                  " weights for " + std::to_string(n) + " measurements");
+    for (Scalar x : v)
+      if (!std::isfinite(x) || x < 0.0)
+        throw std::invalid_argument(std::string("Problem: measurement weights: a weight of ") + kind + " is negative or not finite");
+  };
+  check(w.rel_pose_rot, rel_pose_pose_measurements_.size(), "rel_pose_rot");
+  check(w.rel_pose_trans, rel_pose_pose_measurements_.size(), "rel_pose_trans");
+  check(w.pose_prior_rot, pose_priors_.size(), "pose_prior_rot");
+  check(w.pose_prior_trans, pose_priors_.size(), "pose_prior_trans");
+  check(w.pose_landmark, rel_pose_landmark_measurements_.size(), "pose_landmark");
+  check(w.landmark_prior, landmark_priors_.size(), "landmark_prior");
+  check(w.range, range_measurements_.size(), "range");
+}
+
+void Problem::setMeasurementWeights(const MeasurementWeights &w) {
+  validateWeights(w);
+  weights() = w;
+  if (!ctx_ || !problem_data_up_to_date_ || data_matrix_.nonZeros() == 0) {  // no handle to keep: the plain assembly
+    updateProblemData();
+    return;
+  }
+  // The products of the host sparse algebra keep structural zeros (SparseMatrix::times, setFromTriplets), so a zero
+  // weight leaves the pattern alone and Q(w) has the pattern of Q; the comparison below is the guard of that.
+  const std::vector<int32_t> outer = data_matrix_.outer, inner = data_matrix_.inner;
+  fillRangeSubmatrices();
+  fillRelPoseSubmatrices();
+  fillDataMatrix();
+  if (data_matrix_.outer != outer || data_matrix_.inner != inner) {  // another pattern: a rebuilt handle after all
+    updateProblemData();
+    return;
+  }
+  const bool had_table = measurements_ready_;
+  {
+    const int rc = cora_update_values(ctx_.get(), data_matrix_.outerIndexPtr(), data_matrix_.innerIndexPtr(), data_matrix_.valuePtr());
+    if (rc != CORA_OK) throwLast(rc, "Problem::setMeasurementWeights");
+  }
+  // the handle is back in the state of a fresh one at the same rank (include/cora_hip.h): what hangs on the values is redone
+  precond_ready_ = false;
+  implicit_ready_ = false;
+  measurements_ready_ = false;
+  cert_block_.reset();  // (Ritz vectors of the old operator)
+  {
+    std::lock_guard<std::recursive_mutex> lock(*cert_mutex_);  // the value caches go, cert_perm_ and symbolic_cache_ stay
+    cert_S_ = SparseMatrix();
+    cert_lambda_pos_.clear();
+    cert_lambda_q_.clear();
+  }
+  if (had_table) ensureMeasurementTable();  // kappa, tau, omega of the table follow the weights
 }
 
 const SparseMatrix &Problem::getDataMatrix() {
@@ -718,19 +796,32 @@ void Problem::ensureMeasurementTable() const {
     ed[d * d + d + 1] = tau;
     ++row;
   };
-  for (const auto &rpm : rel_pose_pose_measurements_)
-    add(rpm.first_id, rpm.second_id, &rpm.R, rpm.t, rpm.getRotPrecision(), rpm.getTransPrecision());
-  for (const auto &pp : pose_priors_) add(origin_symbol_, pp.id, &pp.R, pp.t, pp.getRotPrecision(), pp.getTransPrecision());
+  // (kappa, tau and omega carry the weights of setMeasurementWeights: 1/2 of the residuals' sum stays f)
+  const MeasurementWeights &W = weights();
+  size_t i = 0;
+  for (const auto &rpm : rel_pose_pose_measurements_) {
+    add(rpm.first_id, rpm.second_id, &rpm.R, rpm.t, weighted(rpm.getRotPrecision(), W.rel_pose_rot, i),
+        weighted(rpm.getTransPrecision(), W.rel_pose_trans, i));
+    ++i;
+  }
+  i = 0;
+  for (const auto &pp : pose_priors_) {
+    add(origin_symbol_, pp.id, &pp.R, pp.t, weighted(pp.getRotPrecision(), W.pose_prior_rot, i),
+        weighted(pp.getTransPrecision(), W.pose_prior_trans, i));
+    ++i;
+  }
+  i = 0;
   for (const auto &pl : rel_pose_landmark_measurements_)
-    add(pl.first_id, pl.second_id, nullptr, pl.t, 0.0, pl.getTransPrecision());
-  for (const auto &lp : landmark_priors_) add(origin_symbol_, lp.id, nullptr, lp.p, 0.0, lp.getTransPrecision());
+    add(pl.first_id, pl.second_id, nullptr, pl.t, 0.0, weighted(pl.getTransPrecision(), W.pose_landmark, i++));
+  i = 0;
+  for (const auto &lp : landmark_priors_) add(origin_symbol_, lp.id, nullptr, lp.p, 0.0, weighted(lp.getTransPrecision(), W.landmark_prior, i++));
   for (size_t k = 0; k < nr; ++k) {
     const RangeMeasurement &rm = range_measurements_[k];
     range_rows[3 * k] = static_cast<int32_t>(numPosesDim() + static_cast<Index>(k));
     range_rows[3 * k + 1] = static_cast<int32_t>(getTranslationIdx(rm.first_id));
     range_rows[3 * k + 2] = static_cast<int32_t>(getTranslationIdx(rm.second_id));
     range_data[2 * k] = rm.r;
-    range_data[2 * k + 1] = rm.getPrecision();
+    range_data[2 * k + 1] = weighted(rm.getPrecision(), W.range, k);
   }
   CORA_CALL(cora_set_measurements(ctx_.get(), static_cast<int64_t>(m), edge_rows.data(), edge_data.data(),
                                   static_cast<int64_t>(nr), range_rows.data(), range_data.data()),

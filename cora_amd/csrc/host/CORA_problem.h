@@ -56,6 +56,19 @@ struct MeasurementResiduals {
   Scalar rot_sum = 0, trans_sum = 0, range_sum = 0;      // over all kinds
 };
 
+/** EXTENSION beyond the reference: a weight per measurement, multiplied into the precision the data matrix is assembled
+ * with (kappa and tau of a relative pose or pose prior, tau of a pose-landmark measurement or landmark prior, omega of a
+ * range).  The same seven vectors as MeasurementResiduals, in the same order -- a robust-cost loop reads residuals and
+ * writes weights kind by kind.  An EMPTY vector means all ones; otherwise its length must be the number of measurements of
+ * the kind and every weight finite and >= 0.  A zero weight switches a measurement off without changing the sparsity
+ * pattern of Q (its entries stay, as zeros). */
+struct MeasurementWeights {
+  std::vector<Scalar> rel_pose_rot, rel_pose_trans;
+  std::vector<Scalar> pose_prior_rot, pose_prior_trans;
+  std::vector<Scalar> pose_landmark, landmark_prior;
+  std::vector<Scalar> range;
+};
+
 class Problem {
  private:
   int dim_;
@@ -88,6 +101,7 @@ class Problem {
   cora_allgather_fn comm_allgather_ = nullptr;
   void *comm_user_ = nullptr;
   mutable std::shared_ptr<cora_ctx> ctx_;
+  void validateWeights(const MeasurementWeights &w) const;  // lengths and values, std::invalid_argument
   // the Ritz block of the last certify_solution_resident, on the device (declared after ctx_: released before the handle)
   mutable std::shared_ptr<class LOBPCGSolver> cert_block_;
   CertResults certifyImpl(const Matrix &Y, Scalar eta, size_t nx, const Matrix &eigvec_bootstrap, size_t max_LOBPCG_iters,
@@ -100,7 +114,12 @@ class Problem {
   mutable int precond_levels_ = 0;       // height of the elimination tree
   // symbolic analyses of this problem's factorisations (preconditioner block, certificate matrix): kept with the
   // Problem and gone with it (shared between copies of one Problem: they factorise the same patterns)
-  mutable std::shared_ptr<SymbolicCache> symbolic_cache_ = std::make_shared<SymbolicCache>();
+  // The measurement weights (setMeasurementWeights) live in the same heap block, behind this pointer, and not in a member
+  // of their own: the size of a Problem and the offsets of its members are part of the library's ABI -- a program built
+  // against the header of one version runs with the library of the next -- so they are shared between copies too.
+  mutable std::shared_ptr<SymbolicCache> symbolic_cache_ = newSharedState();
+  static std::shared_ptr<SymbolicCache> newSharedState();
+  MeasurementWeights &weights() const;
   // cert_* below is written by prepareCertification(), which solveCORA runs on a thread of its own beside the first TNT
   // solve, and read by certify_solution / get_certificate_matrix: every one of them holds this lock for its whole body
   // (round-4 advice; shared between copies like the cache above so that Problem stays copyable)
@@ -249,6 +268,24 @@ class Problem {
    * Y: getExpectedVariableSize() rows and any 1..24 columns (the relaxed and the rounded solution are both served); in the
    * implicit formulation it is completed with getTranslationExplicitSolution(Y) first.  Single-GPU handles only. */
   MeasurementResiduals measurementResiduals(const Matrix &Y) const;
+
+  /** EXTENSION beyond the reference: re-weights the measurements (struct MeasurementWeights above) and assembles Q(w)
+   * again on the host.  The stored measurements are not touched; the weights stay until they are set again (also across
+   * updateProblemData()).  Unit weights give the data matrix of an unweighted problem bit for bit.
+   *
+   * A device handle that already exists is UPDATED IN PLACE (cora_update_values, include/cora_hip.h): the pattern of Q(w)
+   * is the pattern of Q, so the format, the partition, the resident vectors and an installed communicator stay and only
+   * the values move -- context() returns the same handle as before.  What depended on the values is redone on next use:
+   * the preconditioner, the factor of the implicit formulation, the value caches of certification (their orderings and
+   * symbolic analyses are kept).  Only if the pattern did change is the handle dropped and rebuilt, as
+   * updateProblemData() does.
+   * The measurement table follows the weights: measurementResiduals() then returns WEIGHTED residuals (w kappa, w tau,
+   * w omega in the formulas above), so that 1/2 of their sum stays evaluateObjective().
+   * Copies of one Problem share their weights (as they share the symbolic analyses): set them on one, and the others
+   * assemble with them at their next updateProblemData().
+   * Throws std::invalid_argument for a wrong length, a negative or a non-finite weight (nothing is changed then). */
+  void setMeasurementWeights(const MeasurementWeights &w);
+  const MeasurementWeights &getMeasurementWeights() const;
 
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;

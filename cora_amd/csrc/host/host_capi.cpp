@@ -301,6 +301,34 @@ int cora_problem_measurement_residuals(cora_problem *p, const double *Y, int col
   });
 }
 
+int cora_problem_set_measurement_weights(cora_problem *p, const double *const weights[7], const int64_t lengths[7]) {
+  return guarded([&] {
+    MeasurementWeights w;
+    std::vector<Scalar> *dst[7] = {&w.rel_pose_rot, &w.rel_pose_trans, &w.pose_prior_rot, &w.pose_prior_trans,
+                                   &w.pose_landmark, &w.landmark_prior, &w.range};
+    for (int k = 0; k < 7; ++k)
+      if (weights && weights[k] && lengths && lengths[k] > 0) dst[k]->assign(weights[k], weights[k] + lengths[k]);
+    p->problem.setMeasurementWeights(w);
+  });
+}
+
+int cora_problem_get_measurement_weights(const cora_problem *p, double *const weights[7]) {
+  return guarded([&] {
+    const Problem &q = p->problem;
+    const MeasurementWeights &w = q.getMeasurementWeights();
+    const std::vector<Scalar> *src[7] = {&w.rel_pose_rot, &w.rel_pose_trans, &w.pose_prior_rot, &w.pose_prior_trans,
+                                         &w.pose_landmark, &w.landmark_prior, &w.range};
+    const size_t n[7] = {static_cast<size_t>(q.numPosePoseMeasurements()), static_cast<size_t>(q.numPosePoseMeasurements()),
+                         static_cast<size_t>(q.numPosePriors()), static_cast<size_t>(q.numPosePriors()),
+                         static_cast<size_t>(q.numPoseLandmarkMeasurements()), static_cast<size_t>(q.numLandmarkPriors()),
+                         static_cast<size_t>(q.numRangeMeasurements())};
+    for (int k = 0; k < 7; ++k) {
+      if (!weights[k]) continue;
+      for (size_t i = 0; i < n[k]; ++i) weights[k][i] = src[k]->empty() ? 1.0 : (*src[k])[i];
+    }
+  });
+}
+
 int cora_problem_tnt(cora_problem *p, const double *x0, const double *opts, double *x_out, double stats[7]) {
   return guarded([&] {
     Problem &q = p->problem;

@@ -340,4 +340,16 @@ inline int residual_blocks(int64_t n) {  // blocks of a launch over n measuremen
 hipError_t launch_edge_residuals(const ResidualArgs &A, hipStream_t st);   // n == 0: no launch
 hipError_t launch_range_residuals(const ResidualArgs &A, hipStream_t st);  // n == 0: no launch
 
+// In-place update of Q's values (kernels/update_values.inc).  src: the sources of ValueMap (cora_internal.h), vals: the
+// new CSR values on the device.
+// check: flag |= 1 where a value is not finite, |= 2 where a mirror pair (mirror[2j], mirror[2j + 1]) differs.
+hipError_t launch_values_check(int64_t nnz, const double *vals, int64_t n_pairs, const int32_t *mirror, int *flag,
+                               hipStream_t st);
+// dst[i] = vals[src[i]] (0 without a source);  reciprocal: dst[i] = 1 / that
+hipError_t launch_values_gather(int64_t n, const int32_t *src, const double *vals, double *dst, bool reciprocal,
+                                hipStream_t st);
+// dst0[i] = dst1[i] = 0.5 * (vals[src[2i]] + vals[src[2i + 1]])
+hipError_t launch_values_gather_sym(int64_t n, const int32_t *src, const double *vals, double *dst0, double *dst1,
+                                    hipStream_t st);
+
 }  // namespace cora

@@ -382,6 +382,30 @@ hipError_t launch_range_residuals(const ResidualArgs &A, hipStream_t st) {
   return hipGetLastError();
 }
 
+// in-place update of Q's values (kernels/update_values.inc): two slots per thread
+hipError_t launch_values_check(int64_t nnz, const double *vals, int64_t n_pairs, const int32_t *mirror, int *flag,
+                               hipStream_t st) {
+  if (nnz <= 0 && n_pairs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_values_check, dim3(grid_for(std::max(nnz, n_pairs))), dim3(256), 0, st, nnz, vals, n_pairs, mirror, flag);
+  return hipGetLastError();
+}
+
+hipError_t launch_values_gather(int64_t n, const int32_t *src, const double *vals, double *dst, bool reciprocal,
+                                hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const dim3 grid(grid_for((n + 1) / 2)), block(256);
+  if (reciprocal) hipLaunchKernelGGL((k_values_gather<true>), grid, block, 0, st, n, src, vals, dst);
+  else hipLaunchKernelGGL((k_values_gather<false>), grid, block, 0, st, n, src, vals, dst);
+  return hipGetLastError();
+}
+
+hipError_t launch_values_gather_sym(int64_t n, const int32_t *src, const double *vals, double *dst0, double *dst1,
+                                    hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_values_gather_sym, dim3(grid_for((n + 1) / 2)), dim3(256), 0, st, n, src, vals, dst0, dst1);
+  return hipGetLastError();
+}
+
 #endif  // CORA_TU & 2
 #if CORA_TU & 4
 

@@ -238,6 +238,30 @@ class Problem:
         res.update(rot_sum=float(sums[0]), trans_sum=float(sums[1]), range_sum=float(sums[2]))
         return res
 
+    WEIGHT_KINDS = ("rel_pose_rot", "rel_pose_trans", "pose_prior_rot", "pose_prior_trans", "pose_landmark",
+                    "landmark_prior", "range")
+
+    def set_measurement_weights(self, weights):
+        """Problem::setMeasurementWeights: dict kind -> array of weights (kinds as in measurement_residuals; a missing or
+        empty kind means all ones).  Re-assembles Q; an existing device handle is updated in place (context_ptr() does
+        not change).  measurement_residuals() then returns weighted residuals."""
+        unknown = set(weights) - set(self.WEIGHT_KINDS)
+        if unknown:
+            raise HostError("unknown measurement kinds: %s" % sorted(unknown))
+        arrs = [np.ascontiguousarray(weights.get(k, ()), dtype=np.float64).reshape(-1) for k in self.WEIGHT_KINDS]
+        ptrs = (_dp * 7)(*[a.ctypes.data_as(_dp) if a.size else None for a in arrs])
+        lens = (C.c_int64 * 7)(*[a.size for a in arrs])
+        self._chk(self.L.cora_problem_set_measurement_weights(self.h, ptrs, lens))
+
+    def get_measurement_weights(self):
+        cnt = (C.c_int64 * 5)()
+        self._chk(self.L.cora_problem_measurement_counts(self.h, cnt))
+        sizes = [cnt[0], cnt[0], cnt[1], cnt[1], cnt[2], cnt[3], cnt[4]]
+        arrs = [np.zeros(max(int(n), 1)) for n in sizes]
+        ptrs = (_dp * 7)(*[a.ctypes.data_as(_dp) for a in arrs])
+        self._chk(self.L.cora_problem_get_measurement_weights(self.h, ptrs))
+        return {k: a[:int(n)] for k, a, n in zip(self.WEIGHT_KINDS, arrs, sizes)}
+
     def tnt(self, x0, max_iterations=0, max_inner=0, grad_tol=0, pgrad_tol=0, max_seconds=0, verbose=False,
             host_stpcg=False):
         dm = self.dims()

@@ -10,6 +10,7 @@
 #include <fstream>
 #include <iostream>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "CORA.h"
@@ -18,11 +19,11 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv]" << std::endl;
+    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv]" << std::endl;
     return 1;
   }
   int max_rank = 10;
-  std::string tum, save_dir, residuals;
+  std::string tum, save_dir, residuals, weights;
   bool jacobi = false, implicit = false, odom = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
@@ -34,6 +35,9 @@ int main(int argc, char **argv) {
     else if (a == "--max-rank" && i + 1 < argc) max_rank = std::atoi(argv[++i]);
     // per-measurement residuals of the solution, one line each: kind,first,second,rotation,translation_or_range
     else if (a == "--residuals" && i + 1 < argc) residuals = argv[++i];
+    // measurement weights, one line each: kind,index,weight -- kind one of rel_pose_rot, rel_pose_trans, pose_prior_rot,
+    // pose_prior_trans, pose_landmark, landmark_prior, range; index in the order of the file's measurements of that kind
+    else if (a == "--weights" && i + 1 < argc) weights = argv[++i];
   }
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
@@ -44,6 +48,40 @@ int main(int argc, char **argv) {
     if (jacobi) problem.setPreconditioner(CORA::Preconditioner::Jacobi);
     if (implicit) problem.setFormulation(CORA::Formulation::Implicit);
     problem.updateProblemData();
+    if (!weights.empty()) {  // (an extension beyond the reference: Problem::setMeasurementWeights)
+      std::ifstream csv(weights);
+      if (!csv) throw std::runtime_error("cannot read " + weights);
+      CORA::MeasurementWeights w;
+      const size_t npp = problem.getRPMs().size(), npr = problem.getPosePriors().size();
+      const std::pair<const char *, std::pair<std::vector<CORA::Scalar> *, size_t>> kinds[] = {
+          {"rel_pose_rot", {&w.rel_pose_rot, npp}},     {"rel_pose_trans", {&w.rel_pose_trans, npp}},
+          {"pose_prior_rot", {&w.pose_prior_rot, npr}}, {"pose_prior_trans", {&w.pose_prior_trans, npr}},
+          {"pose_landmark", {&w.pose_landmark, problem.getRPLMs().size()}},
+          {"landmark_prior", {&w.landmark_prior, problem.getLandmarkPriors().size()}},
+          {"range", {&w.range, problem.getRangeMeasurements().size()}}};
+      std::string text;
+      size_t lines = 0;
+      while (std::getline(csv, text)) {
+        if (text.empty() || text[0] == '#') continue;
+        const size_t c1 = text.find(','), c2 = text.find(',', c1 == std::string::npos ? c1 : c1 + 1);
+        if (c2 == std::string::npos) throw std::runtime_error(weights + ": expected kind,index,weight, got '" + text + "'");
+        const std::string kind = text.substr(0, c1);
+        const size_t index = std::stoul(text.substr(c1 + 1, c2 - c1 - 1));
+        const double value = std::stod(text.substr(c2 + 1));
+        bool known = false;
+        for (const auto &k : kinds) {
+          if (kind != k.first) continue;
+          known = true;
+          if (index >= k.second.second) throw std::runtime_error(weights + ": no " + kind + " measurement " + std::to_string(index));
+          if (k.second.first->empty()) k.second.first->assign(k.second.second, 1.0);
+          (*k.second.first)[index] = value;
+        }
+        if (!known) throw std::runtime_error(weights + ": unknown kind '" + kind + "'");
+        ++lines;
+      }
+      problem.setMeasurementWeights(w);
+      std::cout << "read " << weights << " (" << lines << " weights)" << std::endl;
+    }
     const auto t_assembled = clk::now();
     problem.ensurePreconditionerReady();  // device copy of Q, Cholesky factor, solve plan
     const auto t_device = clk::now();

@@ -387,6 +387,52 @@ int cora_measurement_residuals(cora_ctx *ctx, const double *X, int ldx, int k, d
 int cora_debug_measurement_residuals_host(cora_ctx *ctx, const double *X, int ldx, int k, double *edge_rot,
                                           double *edge_trans, double *range_res, double sums[3]);
 
+/* ---- New VALUES of Q on a live handle (same sparsity pattern) ----------------------------------------------------------
+ * Re-weighting measurements changes numbers of Q, never its pattern, and everything a handle derives from the pattern --
+ * the row order, the slices, the column indices, the partition, the exchange lists -- stays.  These calls move the
+ * values only: a gather pass per value array through a SOURCE MAP (for every stored value, the CSR position it comes
+ * from).  The stored bits are exactly the ones a handle created from the same CSR holds.
+ *
+ * cora_values_map_build   builds the map from (rowptr, colidx), which must be the pattern the handle was created with:
+ *                         the structure is recomputed and compared with the handle's own (CORA_ERR_ARG when it
+ *                         differs), and a 64-bit hash of the pattern is kept and checked by every later update.  Lazy:
+ *                         a handle that is never updated pays nothing; cora_update_values builds the map on its first
+ *                         call.  Costs about one format build and 4 bytes per stored value (host and device), plus a
+ *                         device staging buffer of nnz doubles.
+ * cora_update_values      vals: the new values on the HOST, CSR order, with the pattern passed again.  Also works on a
+ *                         plan-only handle (device < 0): the host format is refreshed through the same map.
+ * cora_update_values_dev  d_vals: nnz doubles in CSR order ON THE DEVICE (assembled there by the caller).  Needs the map
+ *                         (CORA_ERR_NOT_READY before).  The host copy of the format is NOT refreshed:
+ *                         cora_debug_format_spmm_host answers CORA_ERR_NOT_READY until the next cora_update_values.
+ * Partitioned handles: every rank passes the WHOLE matrix, as to cora_ctx_create_part; the map is per rank and the call
+ * is not collective (but the ranks' products only agree again once every rank has been updated).
+ *
+ * SYMMETRY.  A pose slice in the chain layout stores Q(rot(P), t_P), the couplings of neighbouring poses and
+ * Q(t_P, t_{P+1}) ONCE and reads the transposed entries from there; creation checks that the two copies are equal and
+ * falls back to a plain slice otherwise.  An update cannot change the layout, so it REQUIRES the same equalities of the
+ * new values (compared as numbers, entry against entry) and refuses values that break one.  A symmetric Q -- what
+ * CORA::Problem assembles -- always passes.
+ * DUPLICATES.  A row that repeats a column index is accepted by creation (the entries are summed) but has no source map:
+ * both map-building calls refuse it with CORA_ERR_ARG.  Merge duplicates before creating a handle that is to be updated.
+ *
+ * STATE after a successful update -- that of a handle freshly created from the new values, at the same rank:
+ *   gone     the current point and a kept trial product (CORA_ERR_NOT_READY until the next cora_set_point*), the
+ *            preconditioner (cora_precond_setup again; Jacobi then uses the new diagonal; an installed Cholesky factor
+ *            belongs to the old values and must be installed again), the implicit factor; the formulation is explicit.
+ *   survives the rank, the stream, every vector of cora_dev_alloc with its contents, scratch memory, the communicator,
+ *            the aux factor (cora_aux_set_cholesky: the caller's own matrix) and the measurement table -- whose kappa,
+ *            tau and omega describe the OLD weights until the caller sets a new table (cora_set_measurements).
+ * ERRORS.  CORA_ERR_ARG: another pattern or number of nonzeros, a broken equality, a value that is not finite, a null
+ * pointer, duplicates.  Values are checked (on the device by a kernel of their own) BEFORE anything is written: a
+ * refused update leaves the handle exactly as it was.  cora_last_error says which.
+ *
+ * cora_update_values_times: wall-clock milliseconds of the last update's phases -- [0] map build (first call only),
+ * [1] host check, [2] upload of the values, [3] device check + gather passes, [4] refresh of the host format. */
+int cora_values_map_build(cora_ctx *ctx, const int32_t *rowptr, const int32_t *colidx);
+int cora_update_values(cora_ctx *ctx, const int32_t *rowptr, const int32_t *colidx, const double *vals);
+int cora_update_values_dev(cora_ctx *ctx, const double *d_vals);
+int cora_update_values_times(const cora_ctx *ctx, double ms[5]);
+
 /* Timing helpers: HIP events on the handle's stream. */
 int cora_timer_start(cora_ctx *ctx);
 int cora_timer_stop_ms(cora_ctx *ctx, float *ms); /* synchronises */

@@ -108,6 +108,16 @@ int cora_problem_measurement_residuals(cora_problem *p, const double *Y, int col
                                        double *rel_pose_trans, double *pose_prior_rot, double *pose_prior_trans,
                                        double *pose_landmark, double *landmark_prior, double *range, double sums[3]);
 
+/* Problem::setMeasurementWeights / getMeasurementWeights (an extension beyond the reference; CORA/CORA_problem.h,
+ * struct MeasurementWeights).  Seven arrays in the order of cora_problem_measurement_residuals' outputs: rel_pose_rot,
+ * rel_pose_trans, pose_prior_rot, pose_prior_trans, pose_landmark, landmark_prior, range.  set: a NULL array or a length
+ * of 0 means all ones, otherwise lengths[k] must be the count of the kind and every weight finite and >= 0
+ * (CORA_HOST_ERR_ARG otherwise, nothing changed).  Q is assembled again; a device handle that exists is updated in place
+ * (cora_update_values) and stays the same handle.  Afterwards cora_problem_measurement_residuals returns WEIGHTED
+ * residuals.  get: every non-NULL array receives the count of its kind (ones where none were set). */
+int cora_problem_set_measurement_weights(cora_problem *p, const double *const weights[7], const int64_t lengths[7]);
+int cora_problem_get_measurement_weights(const cora_problem *p, double *const weights[7]);
+
 /* Riemannian TNT (the call of src/CORA.cpp:139-140 with the parameters of :95-109) from x0
  * (N x rank).  opts (may be NULL): [0] max_iterations, [1] max_TPCG_iterations, [2] gradient
  * tolerance, [3] preconditioned gradient tolerance, [4] max seconds, [5] verbose, [6] non-zero: drive
