@@ -415,7 +415,8 @@ class Context:
         self._chk(self.L.cora_debug_profile_stpcg(self.h, int(on)))
 
     def stpcg_path(self):
-        """Iteration form of the last stpcg_dev call: 0 unfused, 1 fused vector passes, 2 sweep-fused."""
+        """Iteration form of the last stpcg_dev call: 0 unfused, 1 fused vector passes, 2 sweep-fused (the passes ride on
+        the two sweeps of a two-stage Cholesky plan), 3 inverse-fused (on the two products of a one-inverse plan)."""
         return int(self.L.cora_debug_stpcg_path(self.h))
 
     def stpcg_graph_stats(self):

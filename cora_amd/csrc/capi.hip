@@ -202,7 +202,7 @@ struct cora_ctx {
   int prof_hvp_count = 0;
   double prof_phase_us[7] = {0, 0, 0, 0, 0, 0, 0};  // mean time between marks k and k + 1 (-1: not recorded); [6]: two marks in a row
   bool prof_kappa_folded = false;  // the profiled iterations had no kappa launch (SubFuse::n_kappa)
-  int stpcg_path = 0;  // iteration form of the last cora_stpcg_dev: 0 unfused, 1 fused vector passes, 2 sweep-fused
+  int stpcg_path = 0;  // iteration form of the last cora_stpcg_dev: 0 unfused, 1 fused vector passes, 2 sweep-fused (two-stage plan), 3 inverse-fused (one-inverse plan)
   // A batch of device-resident STPCG iterations as a hipGraph: the launches of an iteration have the same arguments
   // every time (the scalars live in device memory, the sequence number the host waits for is a device counter), so a
   // batch is captured once and replayed -- replayed launches follow each other 1.3 us closer than launches enqueued
