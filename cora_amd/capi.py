@@ -25,6 +25,32 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int)
 
 
+# fields of cora_debug_factor_shape / cora_debug_factor_plan_host (include/cora_hip.h), in order
+SHAPE_KEYS = ("stages", "form", "blocks", "block_rows", "max_rows", "max_lev", "max_level_lanes", "max_npl", "io_runs",
+              "fuse_ok", "aux_rows", "aux_sum", "top_rows", "zero_row", "n8", "n64", "long_rows", "chunks", "max_chunks",
+              "lds24", "nnzL", "nnzW", "mixed_products", "generation")
+FORM_PLAIN, FORM_DENSE, FORM_SUB = 0, 1, 2
+FACTOR_PRECOND, FACTOR_IMPLICIT, FACTOR_AUX = 0, 1, 2
+
+
+def _csc_factor(Lp, Li, Lx):
+    return (np.ascontiguousarray(Lp, dtype=np.int32), np.ascontiguousarray(Li, dtype=np.int32),
+            np.ascontiguousarray(Lx, dtype=np.float64))
+
+
+def factor_plan_host(Lp, Li, Lx, aux_ok=True):
+    """Shape of the solve plan of a factor (CSC, diagonal first) that is installed nowhere: dict over SHAPE_KEYS
+    (cora_debug_factor_plan_host; no GPU needed)."""
+    L = load()
+    Lp, Li, Lx = _csc_factor(Lp, Li, Lx)
+    out = (C.c_int64 * len(SHAPE_KEYS))()
+    rc = L.cora_debug_factor_plan_host(len(Lp) - 1, Lp.ctypes.data_as(_ip), Li.ctypes.data_as(_ip), _d(Lx),
+                                       int(bool(aux_ok)), out)
+    if rc:
+        raise CoraError(rc, L.cora_last_error(None).decode())
+    return dict(zip(SHAPE_KEYS, [int(v) for v in out]))
+
+
 class CoraError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("%s: %s" % (STATUS.get(code, str(code)), msg))
@@ -201,6 +227,37 @@ class Context:
         self._chk(self.L.cora_precond_entries(self.h, s))
         keys = ["top_forward", "top_backward", "sub_forward_slots", "sub_backward_slots", "sub_blocks", "aux_rows"]
         return dict(zip(keys, [int(x) for x in s]))
+
+    def precond_stats(self):
+        """Solve plan of the installed preconditioner (cora_precond_stats)."""
+        s = (C.c_int64 * 4)()
+        self._chk(self.L.cora_precond_stats(self.h, s))
+        return dict(zip(["stages", "nnzW", "nnzL", "top_rows"], [int(x) for x in s]))
+
+    def factor_shape(self, which):
+        """Shape of the solve plan of an installed factor (FACTOR_PRECOND | FACTOR_IMPLICIT | FACTOR_AUX): dict over
+        SHAPE_KEYS (cora_debug_factor_shape); CORA_ERR_NOT_READY where none is installed."""
+        out = (C.c_int64 * len(SHAPE_KEYS))()
+        self._chk(self.L.cora_debug_factor_shape(self.h, int(which), out))
+        return dict(zip(SHAPE_KEYS, [int(v) for v in out]))
+
+    def _set_cholesky(self, call, Lp, Li, Lx, perm, m=None):
+        Lp, Li, Lx = _csc_factor(Lp, Li, Lx)
+        perm = np.ascontiguousarray(perm, dtype=np.int32)
+        self._chk(call(self.h, int(len(Lp) - 1 if m is None else m), Lp.ctypes.data_as(_ip), Li.ctypes.data_as(_ip), _d(Lx),
+                       perm.ctypes.data_as(_ip)))
+
+    def precond_set_cholesky(self, Lp, Li, Lx, perm, m=None):
+        """Installs L (CSC, diagonal first) of P (Q + lambda I)[0:m] P^T, m = N or N - 1, perm new -> old in API rows."""
+        self._set_cholesky(self.L.cora_precond_set_cholesky, Lp, Li, Lx, perm, m)
+
+    def aux_set_cholesky(self, Lp, Li, Lx, perm, m=None):
+        """Installs a factor of the caller's own matrix, N rows (cora_aux_set_cholesky)."""
+        self._set_cholesky(self.L.cora_aux_set_cholesky, Lp, Li, Lx, perm, m)
+
+    def aux_solve_dev(self, b, k, x):
+        """x = (P^T L L^T P)^-1 b on k-column resident vectors, b != x (cora_aux_solve_dev)."""
+        self._chk(self.L.cora_aux_solve_dev(self.h, C.c_void_p(b), int(k), C.c_void_p(x)))
 
     def set_stream(self, stream_ptr):
         self._chk(self.L.cora_set_stream(self.h, C.c_void_p(stream_ptr)))

@@ -149,6 +149,7 @@ struct cora_ctx {
                            // the STPCG passes can be fused into the sweeps (SubFuse, kernels.h)
     bool ready = false;
     int64_t entries[6] = {0, 0, 0, 0, 0, 0};  // cora_precond_entries (counted at install, before the host copy is dropped)
+    int64_t shape[kShapeFields] = {0};        // cora_debug_factor_shape (the same)
     unsigned long long generation = 0;  // counts installs: a captured STPCG graph carries the plan's arrays and sizes
   };
   DevFactor precond_f, implicit_f, aux_f;  // aux_f: the caller's own factor (cora_aux_set_cholesky)

@@ -250,3 +250,17 @@ int cora_debug_factor_solve_host(int m, const int32_t *Lp, const int32_t *Li, co
   }
   return CORA_OK;
 }
+
+int cora_debug_factor_plan_host(int m, const int32_t *Lp, const int32_t *Li, const double *Lx, int aux_ok, int64_t out[24]) {
+  if (m <= 0 || !Lp || !Li || !Lx || !out) return CORA_ERR_ARG;
+  try {
+    std::vector<int32_t> row_of(static_cast<size_t>(m));
+    for (int i = 0; i < m; ++i) row_of[i] = i;
+    TriPlan P;
+    build_tri_plan(m, Lp, Li, Lx, row_of, -1, P, nullptr, aux_ok ? m : -1);
+    tri_plan_shape(P, out);
+  } catch (const std::exception &e) {
+    return fail(nullptr, CORA_ERR_ARG, e.what());
+  }
+  return CORA_OK;
+}

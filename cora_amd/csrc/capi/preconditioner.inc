@@ -44,6 +44,7 @@ static int install_factor(cora_ctx *c, cora_ctx::DevFactor &f, int m, const int3
     return fail(c, CORA_ERR_ARG, e.what());
   }
   tick("plan (host)");
+  tri_plan_shape(f.plan, f.shape);
   auto up = [&](auto **dst, const auto &vec) -> hipError_t {
     using T = typename std::remove_reference<decltype(vec)>::type::value_type;
     const size_t bytes = (std::max<size_t>(vec.size(), 1) * sizeof(T) + 255) & ~static_cast<size_t>(255);
@@ -213,6 +214,7 @@ static int install_factor(cora_ctx *c, cora_ctx::DevFactor &f, int m, const int3
             if (nr > kSubMaxRuns) runs_ok = false;
           }
           Q.io_runs = runs_ok ? 1 : 0;
+          f.shape[kShapeIoRuns] = Q.io_runs;
           HIP_TRY(c, up(&Q.fwd.io, iof));
           HIP_TRY(c, up(&Q.bwd.io, iob));
           HIP_TRY(c, up(&Q.fwd.tpos, tpf));
@@ -326,6 +328,17 @@ static int install_factor(cora_ctx *c, cora_ctx::DevFactor &f, int m, const int3
   tick("upload");
   f.ready = true;
   ++f.generation;
+  f.shape[kShapeFuseOk] = f.fuse_ok ? 1 : 0;
+  f.shape[kShapeGeneration] = static_cast<int64_t>(f.generation);
+  return CORA_OK;
+}
+
+int cora_debug_factor_shape(const cora_ctx *c, int which, int64_t out[24]) {
+  if (!c || !out || which < 0 || which > 2) return CORA_ERR_ARG;
+  const cora_ctx::DevFactor &f = which == 0 ? c->precond_f : (which == 1 ? c->implicit_f : c->aux_f);
+  if (!f.ready) return fail(const_cast<cora_ctx *>(c), CORA_ERR_NOT_READY, "no factor installed");
+  static_assert(kShapeFields == 24, "include/cora_hip.h documents 24 fields");
+  std::copy(f.shape, f.shape + kShapeFields, out);
   return CORA_OK;
 }
 

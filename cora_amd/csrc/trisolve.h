@@ -142,4 +142,19 @@ void build_tri_plan(int m, const int32_t *Lp, const int32_t *Li, const double *L
 // right-hand side, indexed by internal row).  Never used by a compute entry point.
 void tri_plan_solve_host(const TriPlan &plan, int64_t rows, const double *rhs, double *out);
 
+// Test hook: the shape of a plan in numbers (cora_debug_factor_shape / cora_debug_factor_plan_host, include/cora_hip.h
+// lists the fields).  Taken while the host arrays still exist: install_factor drops them after the upload.  The fields
+// only a device install knows (kShapeIoRuns, kShapeFuseOk, kShapeGeneration) are left at -1.
+constexpr int kShapeFields = 24;
+enum TriShapeField : int {
+  kShapeStages = 0, kShapeForm, kShapeBlocks, kShapeBlockRows, kShapeMaxRows, kShapeMaxLev, kShapeMaxLevelLanes, kShapeMaxNpl,
+  kShapeIoRuns, kShapeFuseOk, kShapeAuxRows, kShapeAuxSum, kShapeTopRows, kShapeZeroRow, kShapeN8, kShapeN64, kShapeLongRows,
+  kShapeChunks, kShapeMaxChunks, kShapeLds24, kShapeNnzL, kShapeNnzW, kShapeMixedProducts, kShapeGeneration
+};
+// dynamic LDS of a substitution launch: the tile (max_rows rows of tile_stride doubles, 16-byte rounded) + the level headers
+inline int64_t sub_lds_bytes(int64_t max_rows, int64_t max_lev, int tile_stride) {
+  return ((max_rows * tile_stride * 8 + 15) & ~static_cast<int64_t>(15)) + (max_lev + 2) * 16;
+}
+void tri_plan_shape(const TriPlan &plan, int64_t out[kShapeFields]);
+
 }  // namespace cora

@@ -1206,4 +1206,44 @@ void tri_plan_solve_host(const TriPlan &P, int64_t rows, const double *rhs, doub
   }
 }
 
+void tri_plan_shape(const TriPlan &P, int64_t out[kShapeFields]) {
+  for (int k = 0; k < kShapeFields; ++k) out[k] = 0;
+  out[kShapeIoRuns] = out[kShapeFuseOk] = out[kShapeGeneration] = -1;
+  out[kShapeStages] = static_cast<int64_t>(P.stages.size());
+  out[kShapeZeroRow] = P.zero_row;
+  out[kShapeNnzL] = P.nnzL;
+  out[kShapeNnzW] = P.nnzW;
+  if (P.stages.empty()) return;
+  const TriStage &S0 = P.stages[0];
+  out[kShapeTopRows] = P.stages.back().rows;
+  if (S0.dense) {
+    out[kShapeForm] = 1;
+    out[kShapeBlocks] = static_cast<int64_t>(S0.blocks_op.nrows.size());
+    for (int32_t nb : S0.blocks_op.nrows) out[kShapeBlockRows] = std::max<int64_t>(out[kShapeBlockRows], nb);
+  } else if (S0.sub) {
+    const SubBlockOpHost &H = S0.sub_op;
+    out[kShapeForm] = 2;
+    out[kShapeBlocks] = static_cast<int64_t>(H.nrows.size());
+    for (int32_t nb : H.nrows) out[kShapeBlockRows] = std::max<int64_t>(out[kShapeBlockRows], nb);
+    out[kShapeMaxRows] = H.max_rows;
+    out[kShapeMaxLev] = H.max_lev;
+    out[kShapeMaxLevelLanes] = H.max_level_lanes;
+    out[kShapeMaxNpl] = H.max_npl;
+    out[kShapeAuxRows] = H.n_aux;
+    out[kShapeAuxSum] = P.stages.size() > 1 && !P.stages[1].fwd_a.empty() ? 1 : 0;
+    out[kShapeLds24] = sub_lds_bytes(H.max_rows, H.max_lev, 24);
+  }
+  for (const TriStage &S : P.stages)
+    for (const RowOpHost *op : {&S.fwd_a, &S.fwd_b, &S.bwd_a, &S.bwd_b}) {
+      const int64_t nlong = static_cast<int64_t>(op->long_out.size());
+      out[kShapeN8] += op->n8;
+      out[kShapeN64] += op->n64;
+      out[kShapeLongRows] += nlong;
+      out[kShapeChunks] += static_cast<int64_t>(op->chunk_begin.size());
+      for (int64_t r = 0; r < nlong; ++r)
+        out[kShapeMaxChunks] = std::max<int64_t>(out[kShapeMaxChunks], op->long_chunk_ptr[r + 1] - op->long_chunk_ptr[r]);
+      if (op->n8 > 0 && op->n64 > 0 && nlong > 0) ++out[kShapeMixedProducts];
+    }
+}
+
 }  // namespace cora

@@ -659,6 +659,25 @@ int cora_debug_format_spmm_host(const cora_ctx *ctx, const double *X, int ldx,
 int cora_debug_factor_solve_host(int m, const int32_t *Lp, const int32_t *Li, const double *Lx, int k,
                                  const double *B, double *X, int64_t stats[4]);
 
+/* Test hook: the shape of the solve plan of an INSTALLED factor -- which: 0 the preconditioner's, 1 the implicit
+ * formulation's, 2 the aux factor's (CORA_ERR_NOT_READY where none is installed).  Recorded at the install, before the
+ * host plan is dropped; no kernel and no dispatch depends on it.
+ *   [0] stages | [1] form of stage 0: 0 a plain stage of row products (one stage: one explicit inverse), 1 dense
+ *   wavefront blocks, 2 substitution blocks | [2] blocks of stage 0 | [3] rows of its largest block |
+ *   substitution blocks: [4] rows of the largest tile (block rows + coupled rows), [5] level headers of the longest
+ *   block, [6] lanes of the widest level, [7] most entries per lane | [8] 1: row I/O from run tables, 0: from index
+ *   lists | [9] 1: the STPCG passes can be fused into the sweeps | [10] aux rows | [11] 1: the aux sums are a product of
+ *   their own | [12] rows of the last stage | [13] the internal row every solve zeroes (-1: none) |
+ *   over all row products of the plan: [14] 8-lane rows, [15] wavefront rows, [16] long rows, [17] their chunks,
+ *   [18] most chunks of one row | [19] dynamic LDS bytes of a substitution launch at a row stride of 24 |
+ *   [20] nnz(L) | [21] entries of the explicit inverses | [22] row products with all three row classes |
+ *   [23] installs on this factor so far.
+ * cora_debug_factor_plan_host: the same for a factor that is not installed anywhere -- the plan alone is built (rows in
+ * their own order; aux_ok != 0 allows the substitution form, as every install does); [8], [9] and [23] are -1. */
+int cora_debug_factor_shape(const cora_ctx *ctx, int which, int64_t out[24]);
+int cora_debug_factor_plan_host(int m, const int32_t *Lp, const int32_t *Li, const double *Lx, int aux_ok,
+                                int64_t out[24]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,13 +58,31 @@ def make_graph(d=3, n=200, n_landmarks=3, n_ranges=100, n_loops=0, seed=42):
         used.add((i, k))
         dist = np.linalg.norm(T[i] - L[k]) + rng.normal(0, 0.1)
         g.ranges.append(("A%d" % i, "L%d" % k, abs(dist), 0.01))
+    g.truth = (R, T, L)   # what the measurements were drawn from (ground_truth below)
     return g
+
+
+def ground_truth(g):
+    """N x d: the poses, bearings and landmarks a graph of make_graph was drawn from, in the rows of Q (rotation rows
+    R_i^T, one unit bearing per range measurement pointing from the landmark to the pose, translations, landmarks)."""
+    R, T, L = g.truth
+    d, n, r = g.dim, len(R), len(g.ranges)
+    X = np.zeros(((d + 1) * n + r + len(L), d))
+    for i in range(n):
+        X[d * i:d * i + d] = R[i].T
+    for k, (a, b, _, _) in enumerate(g.ranges):
+        v = T[int(a[1:])] - L[int(b[1:])]
+        X[d * n + k] = v / np.linalg.norm(v)
+    X[d * n + r:d * n + r + n] = T
+    X[d * n + r + n:] = L
+    return X
 
 
 def make_problem(**kw):
     from oracle import oracle as orc
     g = make_graph(**kw)
     A = asm.assemble(g)
+    A["truth"] = ground_truth(g)
     Q = orc.CSR.from_scipy(A["Q"])
     dm = orc.Dims(A["d"], A["n"], A["r"], A["N"])
     return A, Q, dm

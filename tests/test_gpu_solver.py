@@ -189,7 +189,9 @@ def test_tnt_regularized_cholesky(d, n, p, loops):
 def test_cholesky_preconditioner_every_row_stride(d, n, p):
     """The solve kernels are instantiated per row stride (odd strides use scalar loads, even ones 16-byte
     loads): every class of stride, on graphs small enough for the one-stage plan (a single explicit inverse)
-    and large enough for dense leaf blocks plus a top stage."""
+    and, from 12 000 poses, large enough for the two-stage plan: substitution blocks around one explicit inverse.
+    (Dense wavefront blocks and three explicit stages -- what these sizes took in round 1 -- are no longer reached by
+    pose chains; tests/test_gpu_tri_forms.py runs them, and asserts which form a plan took.)"""
     import ctypes as C
     import scipy.sparse as sp
     P = host.Problem.synthetic(dim=d, n_poses=n, n_landmarks=6, n_ranges=n // 2, n_loops=5, seed=100 + p,

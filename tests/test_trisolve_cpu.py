@@ -9,17 +9,10 @@ import pytest
 import scipy.sparse as sp
 
 from cora_amd import capi
+from tri_forms import factor_csc as _factor_csc, spd as _spd
 
 _ip = C.POINTER(C.c_int32)
 _dp = C.POINTER(C.c_double)
-
-
-def _factor_csc(A):
-    """dense Cholesky -> CSC of L with the diagonal first (structural zeros stay exact zeros)."""
-    L = np.linalg.cholesky(A.toarray())
-    Ls = sp.csc_matrix(np.where(np.abs(L) > 0, L, 0.0))
-    Ls.sort_indices()
-    return Ls
 
 
 def _solve(Ls, B):
@@ -34,24 +27,9 @@ def _solve(Ls, B):
     rc = lib.cora_debug_factor_solve_host(m, Lp.ctypes.data_as(_ip), Li.ctypes.data_as(_ip), Lx.ctypes.data_as(_dp),
                                           B.shape[1], B.ctypes.data_as(_dp), X.ctypes.data_as(_dp), st)
     assert rc == 0, lib.cora_last_error(None).decode()
-    return X, dict(stages=st[0], nnzW=st[1], nnzL=st[2], dense_blocks=st[3])
-
-
-def _spd(n, kind, rng):
-    if kind == "chain":          # block tridiagonal, like an odometry chain
-        A = sp.diags([np.full(n - k, -1.0 / (k + 1)) for k in range(1, 5)], list(range(1, 5)), shape=(n, n))
-    elif kind == "arrow":        # chain + a few dense trailing rows (landmarks)
-        A = sp.diags([np.full(n - 1, -1.0)], [1], shape=(n, n)).tolil()
-        for r in range(n - 6, n):
-            A[r, rng.choice(n - 6, size=(n - 6) // 2, replace=False)] = -0.01
-        A = sp.triu(A.tocsr().T + A.tocsr(), 1)
-    else:                        # random sparse graph Laplacian: no chain structure at all
-        nz = 3 * n
-        A = sp.coo_matrix((-rng.uniform(0.1, 1.0, nz), (rng.integers(0, n, nz), rng.integers(0, n, nz))), shape=(n, n))
-        A = sp.triu(A.tocsr(), 1)
-    A = (A + A.T).tocsr()
-    d = np.asarray(abs(A).sum(axis=1)).ravel() + rng.uniform(0.1, 1.0, n)
-    return (A + sp.diags(d)).tocsr()
+    plan = capi.factor_plan_host(Lp, Li, Lx)   # the same plan, in numbers (cora_debug_factor_plan_host)
+    assert (plan["stages"], plan["nnzW"], plan["nnzL"], plan["blocks"]) == (st[0], st[1], st[2], st[3])
+    return X, plan
 
 
 @pytest.mark.parametrize("kind,n", [("chain", 40), ("chain", 3000), ("arrow", 2500), ("random", 700), ("random", 2600)])
@@ -64,11 +42,13 @@ def test_staged_plan_matches_direct_solve(kind, n):
     ref = np.linalg.solve(A.toarray(), B)
     assert np.abs(X - ref).max() < 1e-11 * np.abs(ref).max()
     assert st["nnzL"] == Ls.nnz and st["stages"] >= 1
-    if kind == "chain" and n == 3000:     # a 3000-row path: its full inverse (4.5 M entries) is not worth forming
-        assert st["stages"] >= 2
-        assert st["dense_blocks"] > 0     # and its leaves fit the dense wavefront kernel
+    if kind == "chain" and n == 3000:     # a 3000-row path: its full inverse (4.5 M entries) is not worth forming,
+        assert st["stages"] >= 2          # and a path has no subtree that would leave a small remainder: no substitution
+        assert st["form"] == capi.FORM_DENSE and st["blocks"] > 0     # blocks -- its first rows fit the dense wavefront kernel
+        assert 0 < st["block_rows"] <= 64 and st["max_rows"] == 0 and st["aux_rows"] == 0
     if kind == "chain" and n == 40:
         assert st["stages"] == 1          # small factors are applied as one explicit inverse
+        assert st["form"] == capi.FORM_PLAIN and st["blocks"] == 0 and st["top_rows"] == n
 
 
 def test_rejects_malformed_factor():
@@ -123,3 +103,11 @@ def test_two_stage_plan_with_the_aux_sums_as_their_own_product(kind, n, monkeypa
     X2, st2 = _solve(Ls, B)
     assert np.abs(X2 - ref).max() < 1e-11 * np.abs(ref).max()
     assert st["stages"] == st2["stages"]
+    # What the probe shows: only the arrow takes substitution blocks here (its chain is one subtree under the dense rows).
+    # A path in its natural order has no subtree that leaves a small remainder, so the two chains stay with explicit
+    # stages and have no aux rows for the switch to move (dissected chains, where it moves them: tests/test_tri_forms_cpu.py).
+    assert st["form"] == st2["form"] == (capi.FORM_SUB if kind == "arrow" else capi.FORM_DENSE)
+    if kind == "arrow":
+        assert st["aux_sum"] == 1 and st2["aux_sum"] == 0 and st["aux_rows"] == st2["aux_rows"] > 0
+    else:
+        assert st["aux_sum"] == st2["aux_sum"] == 0 and st["aux_rows"] == st2["aux_rows"] == 0
