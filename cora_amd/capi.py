@@ -29,6 +29,9 @@ ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int)
 SHAPE_KEYS = ("stages", "form", "blocks", "block_rows", "max_rows", "max_lev", "max_level_lanes", "max_npl", "io_runs",
               "fuse_ok", "aux_rows", "aux_sum", "top_rows", "zero_row", "n8", "n64", "long_rows", "chunks", "max_chunks",
               "lds24", "nnzL", "nnzW", "mixed_products", "generation")
+# fields of cora_debug_format_shape (include/cora_hip.h), in order
+FORMAT_SHAPE_KEYS = ("chain_slices", "plain_slices", "max_general", "max_T", "max_lane_tail", "slices_T_gt_64",
+                     "remote_tail_pairs", "long_pose_rows", "long_landmark_rows", "max_chunks", "straddling_tails")
 FORM_PLAIN, FORM_DENSE, FORM_SUB = 0, 1, 2
 FACTOR_PRECOND, FACTOR_IMPLICIT, FACTOR_AUX = 0, 1, 2
 
@@ -220,6 +223,12 @@ class Context:
         b = (C.c_int64 * 4)()
         self._chk(self.L.cora_format_bytes(self.h, b))
         return dict(zip(["values", "indices", "descriptors", "total"], [int(x) for x in b]))
+
+    def format_shape(self):
+        """Shape of the handle's format of Q (cora_debug_format_shape; no GPU needed): dict over FORMAT_SHAPE_KEYS."""
+        out = (C.c_int64 * len(FORMAT_SHAPE_KEYS))()
+        self._chk(self.L.cora_debug_format_shape(self.h, out))
+        return dict(zip(FORMAT_SHAPE_KEYS, [int(v) for v in out]))
 
     def precond_entries(self):
         """Entries the installed preconditioner's solve plan stores (cora_precond_entries)."""

@@ -316,6 +316,37 @@ int cora_format_stats(const cora_ctx *c, int64_t s[8]) {
   return CORA_OK;
 }
 
+// Test hook (include/cora_hip.h): counted from the host copy of the format, the way k_spmm decodes it.
+int cora_debug_format_shape(const cora_ctx *c, int64_t out[11]) {
+  if (!c || !out) return CORA_ERR_ARG;
+  const HostFormat &F = c->F;
+  for (int k = 0; k < 11; ++k) out[k] = 0;
+  for (const SliceDesc &sd : F.slices) {
+    if ((sd.type & kSliceTypeMask) != kSliceStiefel) continue;
+    if (!(sd.type & kSliceChainFlag)) { ++out[1]; continue; }
+    ++out[0];
+    const int64_t T = static_cast<int64_t>(static_cast<uint32_t>(sd.type) >> kSliceTailShift);
+    out[2] = std::max<int64_t>(out[2], sd.width);
+    out[3] = std::max(out[3], T);
+    out[4] = std::max<int64_t>(out[4], (sd.type >> kSliceTailMaxShift) & kSliceTailMaxMask);
+    if (T > kWave) ++out[5];
+    for (int lane = 0; lane < (sd.nrows & kSliceRowsMask); ++lane) {
+      const uint32_t info = static_cast<uint32_t>(F.scol[static_cast<size_t>(sd.coff) + lane]);
+      const uint32_t start = info & 0xffffu, count = (info >> 16) & 0x7fu;
+      out[6] += static_cast<int64_t>(count) - static_cast<int64_t>((info >> 24) & 0x7fu);
+      if (count > 0 && start / kWave != (start + count - 1) / kWave) ++out[10];
+    }
+  }
+  const int64_t first_trans = static_cast<int64_t>(F.L.d) * F.L.n + F.L.r;
+  for (size_t ci = 0; ci < F.chunks.size(); ci += static_cast<size_t>(std::max(F.chunks[ci].nchunks, 1))) {
+    const LongChunk &ch = F.chunks[ci];
+    const int64_t api = F.int2api[static_cast<size_t>(ch.row)];
+    ++out[api >= first_trans && api < first_trans + F.L.n ? 7 : 8];
+    out[9] = std::max<int64_t>(out[9], ch.nchunks);
+  }
+  return CORA_OK;
+}
+
 int cora_format_bytes(const cora_ctx *c, int64_t b[4]) {
   if (!c || !b) return CORA_ERR_ARG;
   const HostFormat &F = c->F;

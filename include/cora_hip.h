@@ -678,6 +678,15 @@ int cora_debug_factor_shape(const cora_ctx *ctx, int which, int64_t out[24]);
 int cora_debug_factor_plan_host(int m, const int32_t *Lp, const int32_t *Li, const double *Lx, int aux_ok,
                                 int64_t out[24]);
 
+/* Test hook: the shape of the handle's format of Q in numbers, read from the host copy of the format (no GPU needed; no
+ * kernel and no dispatch depends on it) -- what a test asserts before it claims to have reached a path:
+ *   pose slices [0] in the chain layout, [1] in the plain layout | over the chain slices: [2] most general slots of a
+ *   lane, [3] most tail pairs T of a slice, [4] most tail pairs of a lane, [5] slices with T > 64, [6] tail pairs whose
+ *   columns another rank owns (0 on one GPU) | long rows (one or more chunks on this handle) that are [7] a pose's,
+ *   [8] a landmark's translation row | [9] most chunks of one long row | [10] lanes of chain slices whose tail pairs lie
+ *   on both sides of a multiple of 64 pairs of their slice's tail (the wavefront gathers a tail 64 pairs at a time). */
+int cora_debug_format_shape(const cora_ctx *ctx, int64_t out[11]);
+
 #ifdef __cplusplus
 }
 #endif

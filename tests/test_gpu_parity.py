@@ -85,7 +85,8 @@ def test_manifold_ops_fixture(case):
 
 
 @pytest.mark.parametrize("d,n,lm,nr,loops,p", [
-    (3, 1500, 4, 800, 0, 5),     # chain, long landmark rows (multi-chunk path)
+    (3, 1500, 4, 800, 0, 5),     # chain, long landmark rows (~400 non-zeros: one chunk each; several chunks per row:
+                                 # tests/test_gpu_topologies.py, fat_landmark)
     (3, 900, 3, 500, 60, 3),     # loop closures
     (2, 1200, 2, 700, 20, 5),    # SE(2)
     (3, 600, 0, 0, 0, 4),        # pose-graph only: no ranges / landmarks
