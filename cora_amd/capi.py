@@ -404,9 +404,12 @@ class Context:
         host = _f(host)
         self._chk(self.L.cora_upload(self.h, _d(host), host.shape[0], host.shape[1], C.c_void_p(ptr)))
 
-    def download(self, ptr, k):
-        out = self._out(k)
-        self._chk(self.L.cora_download(self.h, C.c_void_p(ptr), int(k), _d(out), self.N))
+    def download(self, ptr, k, out=None):
+        """N x k host copy of a resident vector; `out` (column-major, at least N rows: its row count is the leading
+        dimension) is filled in place when given."""
+        if out is None:
+            out = self._out(k)
+        self._chk(self.L.cora_download(self.h, C.c_void_p(ptr), int(k), _d(out), out.shape[0]))
         return out
 
     def set_point_dev(self, ptr):
@@ -457,6 +460,18 @@ class Context:
     def axpy2_dev(self, a1, x1, y1, a2, x2, y2):
         self._chk(self.L.cora_axpy2_dev(self.h, C.c_double(a1), C.c_void_p(x1), C.c_void_p(y1), C.c_double(a2),
                                         C.c_void_p(x2), C.c_void_p(y2)))
+
+    def axpby_cols_dev(self, k, a, x, b, y):
+        """y = a x + b y on vectors allocated with k columns (cora_axpby_cols_dev)."""
+        self._chk(self.L.cora_axpby_cols_dev(self.h, int(k), C.c_double(a), C.c_void_p(x), C.c_double(b), C.c_void_p(y)))
+
+    def fill_random_dev(self, k, seed, x):
+        """x (k columns) = numbers in (-1, 1) that depend on (seed, API row, column) only (cora_fill_random_dev)."""
+        self._chk(self.L.cora_fill_random_dev(self.h, int(k), C.c_ulonglong(seed), C.c_void_p(x)))
+
+    def copy_dev(self, x, k, y):
+        """y = x on vectors allocated with k columns (cora_copy_dev)."""
+        self._chk(self.L.cora_copy_dev(self.h, C.c_void_p(x), int(k), C.c_void_p(y)))
 
     def stpcg_dev(self, grad, Delta, s, r, v, p, hp, kappa_fgr=0.1, theta=0.8, max_iters=80):
         """Device-resident Steihaug-Toint PCG at the current point; returns (Hessian-vector products, ||s||_M)."""

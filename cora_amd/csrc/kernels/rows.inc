@@ -140,12 +140,47 @@ __global__ __launch_bounds__(256) void k_tangent_project(const RowArgs R, const 
   }
 }
 
+// Scale guard of the normalisations below.  The polar factor of a block and the direction of a row do not change when
+// the input is multiplied by a positive number, but their formulas square the entries: sqrt(alpha * beta) is a product
+// of two squared row norms (0 below |A| ~ 1e-77, inf above 1e77) and dot_row(a, a) leaves the range at 1e+-154.
+// Returns the exponent e for which ldexp(x, e) -- exact -- brings a block whose largest |entry| is amax to [1/2, 1),
+// and 0 (leave the block alone: the arithmetic of an ordinary block is untouched) when amax already lies in
+// [2^-250, 2^250], where a product of two squared norms of <= 24 entries stays finite, or is 0, inf or NaN.
+__device__ __forceinline__ int rescale_exponent(double amax) {
+  if ((amax >= 0x1p-250 && amax <= 0x1p250) || !(amax > 0.0) || !(amax < HUGE_VAL)) return 0;
+  int e;
+  (void)frexp(amax, &e);
+  return -e;
+}
+
 // Polar factor of a d x LD block by one-sided (Hestenes) Jacobi on its rows:
 // rotations J with (J A) having orthogonal rows;  A = J^T Sigma U  =>  polar = J^T U.
 // Works on A directly (no Gram matrix), so it is as accurate as the reference's
-// Eigen::JacobiSVD route (src/StiefelProduct.cpp:8-36: U V^T of the thin SVD).
+// Eigen::JacobiSVD route (src/StiefelProduct.cpp:8-36: U V^T of the thin SVD): within 2 x the error of a
+// float64 thin SVD in units of eps * (condition number of the polar factor), at every finite non-zero scale
+// (tests/test_gpu_rowops.py; measured figures in profiles/rowops.md).
+// RANK-DEFICIENT blocks are NOT completed to a frame as the reference's SVD route does.  A zero row takes part in no
+// rotation and is normalised to zero: a zero block returns zero, a block with one zero row returns that row zero and the
+// others orthonormal.  Two identical rows cancel in their first rotation; what is left of the second direction is zero
+// or the rounding residue of that cancellation, normalised -- a row without meaning.  The result is finite in every
+// case (tests/test_gpu_rowops.py pins exactly this), and the other blocks of the launch are not affected.  The
+// solver's iterates never get there.
 template <int LD, int D>
 __device__ __forceinline__ void polar_rows(double (&a)[D][LD]) {
+  {  // pre-pass only: the sweeps below are the same instructions for every block
+    double amax = 0.0;
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int c = 0; c < LD; ++c) amax = fmax(amax, fabs(a[i][c]));
+    const int e = rescale_exponent(amax);
+    if (e != 0) {
+#pragma unroll
+      for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int c = 0; c < LD; ++c) a[i][c] = ldexp(a[i][c], e);
+    }
+  }
   double J[D][D];
 #pragma unroll
   for (int i = 0; i < D; ++i)
@@ -238,6 +273,14 @@ __global__ __launch_bounds__(256) void k_project_manifold(const RowArgs R, const
       for (int c = 0; c < LD; ++c) a[c] = fma(alpha, v[c], a[c]);
     }
     if (un.kind == 1) {
+      double amax = 0.0;
+#pragma unroll
+      for (int c = 0; c < LD; ++c) amax = fmax(amax, fabs(a[c]));
+      const int e = rescale_exponent(amax);  // 0 for an ordinary row (and for a zero row, which stays zero)
+      if (e != 0) {
+#pragma unroll
+        for (int c = 0; c < LD; ++c) a[c] = ldexp(a[c], e);
+      }
       const double nrm = sqrt(dot_row<LD>(a, a));
       if (nrm > 0.0) {
         const double inv = 1.0 / nrm;

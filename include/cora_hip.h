@@ -159,7 +159,14 @@ int cora_riemannian_hessian_vector_product(cora_ctx *ctx, const double *Y,
                                            int ldg, const double *dotY,
                                            int ldd, double *out, int ldo);
 
-/* Problem::projectToManifold, src/CORA_problem.cpp:905-934. */
+/* Problem::projectToManifold, src/CORA_problem.cpp:905-934: polar factor of every pose block, unit range rows,
+ * translation rows unchanged.  This call, cora_retract, cora_retract_dev and cora_project_to_manifold_dev run the same
+ * kernel and return the same bits for the same input.
+ * SCALE.  Any finite non-zero scale is accepted: a block (a range row) whose largest |entry| lies outside
+ * [2^-250, 2^250] is multiplied by an exact power of two first; ordinary input takes the same arithmetic as before.
+ * RANK-DEFICIENT pose blocks are NOT completed to an orthonormal frame as the reference's SVD route does: a zero block
+ * returns zero, a zero row stays zero next to orthonormal others, and of two identical rows one comes back without
+ * meaning (zero or a normalised rounding residue).  A zero range row stays zero.  The output is finite in every case. */
 int cora_project_to_manifold(cora_ctx *ctx, const double *A, int lda,
                              double *out, int ldo);
 
