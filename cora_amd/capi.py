@@ -54,6 +54,24 @@ def factor_plan_host(Lp, Li, Lx, aux_ok=True):
     return dict(zip(SHAPE_KEYS, [int(v) for v in out]))
 
 
+def factor_plan_digest(Lp, Li, Lx, group=None, aux_ok=True):
+    """Digest of the whole solve plan of a factor that is installed nowhere: (integers and indices, bits of the doubles),
+    two 64-bit FNV-1a values (cora_debug_factor_plan_digest; no GPU needed).  group: None or one id per variable."""
+    L = load()
+    Lp, Li, Lx = _csc_factor(Lp, Li, Lx)
+    m = len(Lp) - 1
+    g = None
+    if group is not None:
+        g = np.ascontiguousarray(group, dtype=np.int32)
+        assert g.shape == (m,)
+    out = (C.c_uint64 * 2)()
+    rc = L.cora_debug_factor_plan_digest(m, Lp.ctypes.data_as(_ip), Li.ctypes.data_as(_ip), _d(Lx),
+                                         g.ctypes.data_as(_ip) if g is not None else None, int(bool(aux_ok)), out)
+    if rc:
+        raise CoraError(rc, L.cora_last_error(None).decode())
+    return int(out[0]), int(out[1])
+
+
 class CoraError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("%s: %s" % (STATUS.get(code, str(code)), msg))

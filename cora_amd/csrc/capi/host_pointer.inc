@@ -264,3 +264,20 @@ int cora_debug_factor_plan_host(int m, const int32_t *Lp, const int32_t *Li, con
   }
   return CORA_OK;
 }
+
+int cora_debug_factor_plan_digest(int m, const int32_t *Lp, const int32_t *Li, const double *Lx, const int32_t *group, int aux_ok,
+                                  uint64_t out[2]) {
+  if (m <= 0 || !Lp || !Li || !Lx || !out) return CORA_ERR_ARG;
+  try {
+    std::vector<int32_t> row_of(static_cast<size_t>(m));
+    for (int i = 0; i < m; ++i) row_of[i] = i;
+    std::vector<int32_t> g;
+    if (group) g.assign(group, group + m);
+    TriPlan P;
+    build_tri_plan(m, Lp, Li, Lx, row_of, -1, P, group ? &g : nullptr, aux_ok ? m : -1);
+    tri_plan_digest(P, out);
+  } catch (const std::exception &e) {
+    return fail(nullptr, CORA_ERR_ARG, e.what());
+  }
+  return CORA_OK;
+}

@@ -157,4 +157,8 @@ inline int64_t sub_lds_bytes(int64_t max_rows, int64_t max_lev, int tile_stride)
 }
 void tri_plan_shape(const TriPlan &plan, int64_t out[kShapeFields]);
 
+// Test hook: a digest of everything a plan holds (cora_debug_factor_plan_digest) -- out[0] over its integers, booleans,
+// indices and headers, out[1] over the bits of its doubles.  Two plans with the same digest are the same input to every kernel.
+void tri_plan_digest(const TriPlan &plan, uint64_t out[2]);
+
 }  // namespace cora

@@ -685,6 +685,14 @@ int cora_debug_factor_shape(const cora_ctx *ctx, int which, int64_t out[24]);
 int cora_debug_factor_plan_host(int m, const int32_t *Lp, const int32_t *Li, const double *Lx, int aux_ok,
                                 int64_t out[24]);
 
+/* Test hook: a digest of the WHOLE solve plan of a factor that is not installed anywhere (built as by
+ * cora_debug_factor_plan_host; group: NULL or m ids, variables with the same id >= 0 are kept together, as a handle passes
+ * the rotation rows of a pose).  FNV-1a, members in declaration order (cora_amd/csrc/trisolve.h), every array preceded by
+ * its length: out[0] over every integer, boolean, index and header, out[1] over the bits of every double.  Equal digests:
+ * the kernels see the same plan. */
+int cora_debug_factor_plan_digest(int m, const int32_t *Lp, const int32_t *Li, const double *Lx, const int32_t *group,
+                                  int aux_ok, uint64_t out[2]);
+
 /* Test hook: the shape of the handle's format of Q in numbers, read from the host copy of the format (no GPU needed; no
  * kernel and no dispatch depends on it) -- what a test asserts before it claims to have reached a path:
  *   pose slices [0] in the chain layout, [1] in the plain layout | over the chain slices: [2] most general slots of a
