@@ -674,6 +674,54 @@ class Context:
         self._chk(self.L.cora_update_values_times(self.h, out))
         return [out[i] for i in range(5)]
 
+    # ---- Q(w) assembled from per-measurement weights (include/cora_hip.h, cora_assembly_build)
+    def assembly_build(self, rowptr, colidx):
+        """Builds the term map of Q(w) over the pattern the handle was created with; needs a measurement table."""
+        rowptr, colidx = self._csr(rowptr, colidx)
+        if len(rowptr) != self.N + 1:
+            raise CoraError(5, "rowptr must have N+1 entries")
+        if len(colidx) != rowptr[-1]:
+            raise CoraError(5, "colidx must have rowptr[N] entries")
+        self._chk(self.L.cora_assembly_build(self.h, rowptr.ctypes.data_as(_ip), colidx.ctypes.data_as(_ip)))
+        self._asm_nnz = int(rowptr[-1])
+
+    def assembly_info(self):
+        """dict n_weights, n_terms, long_entries, max_terms of the term map."""
+        out = (C.c_int64 * 4)()
+        self._chk(self.L.cora_assembly_info(self.h, out))
+        return dict(zip(["n_weights", "n_terms", "long_entries", "max_terms"], [int(x) for x in out]))
+
+    def _weights(self, w):
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if len(w) != self.assembly_info()["n_weights"]:
+            raise CoraError(5, "the weight vector must have 2 * n_edges + n_ranges entries")
+        return w
+
+    def assemble_values(self, w):
+        """Q(w) from host weights [rot | trans | range]; returns the assembled CSR values (the handle's new bits).
+        Afterwards the handle is in the state of a fresh one, with the measurement table following the weights."""
+        w = self._weights(w)
+        vals = np.zeros(max(self._asm_nnz, 1))
+        self._chk(self.L.cora_assemble_values(self.h, _d(w), _d(vals)))
+        return vals[:self._asm_nnz]
+
+    def assemble_values_dev(self, d_w, d_vals_out=None):
+        """The same from weights on the device (raw pointers as ints); d_vals_out: None or nnz device doubles."""
+        self._chk(self.L.cora_assemble_values_dev(self.h, C.c_void_p(d_w), C.c_void_p(d_vals_out)))
+
+    def debug_assemble_values_host(self, w):
+        """Test hook: the term map executed on the host in the device's order (no GPU needed, the handle is unchanged)."""
+        w = self._weights(w)
+        vals = np.zeros(max(self._asm_nnz, 1))
+        self._chk(self.L.cora_debug_assemble_values_host(self.h, _d(w), _d(vals)))
+        return vals[:self._asm_nnz]
+
+    def assemble_times(self):
+        """Milliseconds: term map build, weight check, assembly kernels (events), update passes, copies + host refresh."""
+        out = (C.c_double * 5)()
+        self._chk(self.L.cora_assemble_times(self.h, out))
+        return [out[i] for i in range(5)]
+
     # ---- test hook
     def debug_format_spmm_host(self, X):
         X = _f(X)

@@ -2,7 +2,7 @@
 // device memory and stream; every compute entry point ends in a HIP kernel of
 // kernels.hip -- there is no CPU fallback.
 //
-// ONE translation unit in twelve pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
+// ONE translation unit in thirteen pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
 // error / device macros and the helpers every part uses; the entry points live in capi/*.inc, included at the end in this order:
 //   handle.inc          creation of (partitioned) handles, destruction, rank state, row maps, statistics
 //   resident.inc        device vectors, the current point, the trust-region trial / accept pair, products, projections
@@ -14,6 +14,7 @@
 //   host_pointer.inc    the host-pointer operator API (one entry per reference method), host-side debug hooks
 //   measurements.inc    the measurement table of a handle and the per-measurement residuals
 //   values.inc          in-place update of Q's values: source map, host-pointer and device-pointer update
+//   assembly.inc        Q(w) from per-measurement weights: term map, host-pointer, device-pointer and host-mirror assembly
 //   comm.inc            native communication: RCCL, in-process and device-side (p2p.h) transports
 #include <hip/hip_runtime.h>
 // RCCL's types and the few enumerators used, declared here (NCCL's public ABI: they have not changed since 2.0): the
@@ -81,6 +82,8 @@ struct MeasurementTable {
   bool set = false;
   int64_t n_edges = 0, n_ranges = 0;
   std::vector<int32_t> edge_rows, range_rows;  // [4][n_edges], [3][n_ranges]
+  std::vector<int32_t> api_edge_rows, api_range_rows;  // [n_edges][4], [n_ranges][3] as given (API rows): the term map of Q(w) is over the CSR
+  bool host_stale = false;  // cora_assemble_values_dev rescaled the device's kappa, tau and omega only
   std::vector<double> edge_data, range_data;   // [d*d + d + 2][n_edges], [2][n_ranges]
   int32_t *d_edge_rows = nullptr, *d_range_rows = nullptr;
   double *d_edge_data = nullptr, *d_range_data = nullptr;
@@ -222,6 +225,13 @@ struct cora_ctx {
   bool dist_long = true;            // the handle was created with distributed long rows (no CORA_PART_WHOLE_LONG_ROWS)
   bool host_values_stale = false;   // cora_update_values_dev moved the device's values only: F's value arrays are old
   double values_ms[5] = {0, 0, 0, 0, 0};  // cora_update_values_times
+  // assembly of Q(w) from per-measurement weights (capi/assembly.inc): the term map, its device copy, a device weight
+  // vector for the host-pointer form, events around the assembly kernels and the times of the last call
+  TermMap tmap;
+  int32_t *d_tptr = nullptr, *d_tweight = nullptr, *d_tlong = nullptr;
+  double *d_tcoef = nullptr, *d_tbase = nullptr, *d_asm_w = nullptr;
+  hipEvent_t asm_ev[2] = {nullptr, nullptr};
+  double asm_ms[5] = {0, 0, 0, 0, 0};  // cora_assemble_times
   std::vector<std::pair<double *, size_t>> user_allocs;  // live vectors of cora_dev_alloc (pointer, bytes)
   std::vector<std::pair<double *, size_t>> pool;         // released ones, kept for the next request of the same size
   std::string err;
@@ -510,7 +520,17 @@ int set_point_dev_impl(cora_ctx *c, const double *dY) {
   return point_finish(c);
 }
 
+void free_assembly(cora_ctx *c) {  // (the device must be current where there is one)
+  for (void *p : {static_cast<void *>(c->d_tptr), static_cast<void *>(c->d_tweight), static_cast<void *>(c->d_tlong),
+                  static_cast<void *>(c->d_tcoef), static_cast<void *>(c->d_tbase), static_cast<void *>(c->d_asm_w)})
+    if (p) (void)hipFree(p);
+  c->d_tptr = c->d_tweight = c->d_tlong = nullptr;
+  c->d_tcoef = c->d_tbase = c->d_asm_w = nullptr;
+  c->tmap = TermMap();
+}
+
 void free_measurements(cora_ctx *c) {  // (the device must be current)
+  free_assembly(c);  // (the term map belongs to the table)
   MeasurementTable &M = c->meas;
   for (void *p : {static_cast<void *>(M.d_edge_rows), static_cast<void *>(M.d_range_rows), static_cast<void *>(M.d_edge_data),
                   static_cast<void *>(M.d_range_data), static_cast<void *>(M.d_out)})
@@ -540,6 +560,7 @@ extern "C" {
 #include "capi/host_pointer.inc"
 #include "capi/measurements.inc"
 #include "capi/values.inc"
+#include "capi/assembly.inc"
 
 }  // extern "C"
 

@@ -203,6 +203,8 @@ void cora_ctx_destroy(cora_ctx *c) {
     if (c->h_flag) (void)hipHostFree(c->h_flag);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
+    for (hipEvent_t e : c->asm_ev)
+      if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->prof_events) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->phase_events) (void)hipEventDestroy(e);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);

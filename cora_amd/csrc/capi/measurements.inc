@@ -29,6 +29,8 @@ int cora_set_measurements(cora_ctx *c, int64_t n_edges, const int32_t *edge_rows
   T.edge_data.resize(static_cast<size_t>(nf) * n_edges);
   T.range_rows.resize(static_cast<size_t>(3 * n_ranges));
   T.range_data.resize(static_cast<size_t>(2 * n_ranges));
+  T.api_edge_rows.assign(edge_rows, edge_rows + 4 * n_edges);
+  T.api_range_rows.assign(range_rows, range_rows + 3 * n_ranges);
   for (int64_t e = 0; e < n_edges; ++e) {
     const int32_t *row = edge_rows + 4 * e;
     int32_t ra = 0, rb = -1;
@@ -73,6 +75,7 @@ int cora_set_measurements(cora_ctx *c, int64_t n_edges, const int32_t *edge_rows
     HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&M.d_out), static_cast<size_t>(2 * n_edges + n_ranges + 3) * sizeof(double)));
     M.set = true;
   } else {
+    c->tmap = TermMap();  // (a term map belongs to the table it was built from)
     c->meas = std::move(T);
     c->meas.set = true;
   }
@@ -150,6 +153,8 @@ int cora_debug_measurement_residuals_host(cora_ctx *c, const double *X, int ldx,
                                           double *edge_trans, double *range_res, double sums[3]) {
   if (!c) return CORA_ERR_ARG;
   if (!c->meas.set) return fail(c, CORA_ERR_NOT_READY, "no measurement table (cora_set_measurements)");
+  if (c->meas.host_stale)
+    return fail(c, CORA_ERR_NOT_READY, "the host copy of the measurement table is stale (cora_assemble_values_dev rescaled the device's only)");
   if (k <= 0 || k > kMaxLD) return fail(c, CORA_ERR_SHAPE, "column count must be in [1, 24]");
   if (!X) return fail(c, CORA_ERR_ARG, "null pointer");
   const HostFormat &F = c->F;

@@ -192,6 +192,42 @@ const char *value_map_check_host(const ValueMap &M, const double *val);
 // F's five value arrays from `val` through the map: the bits build_format would have produced.
 void value_map_apply_host(const ValueMap &M, const double *val, HostFormat &F);
 
+// Q(w) as a fixed sum of per-measurement terms (cora_assembly_build / cora_assemble_values, capi/assembly.inc).  Q is
+// linear in the measurement weights: CSR entry q is the sum over t in [tptr[q], tptr[q + 1]) of tcoef[t] * w[tweight[t]],
+// w = [rot of every edge | trans of every edge | range] (the layout of the residuals).  A coefficient carries the
+// precision (kappa, tau, omega) the table held when the map was built; `base` keeps those 2 * n_edges + n_ranges numbers.
+// ORDER of an entry's terms: ascending weight index, and for one weight index the enumeration order of the measurement
+//   rotation of edge e (second rotation row >= 0):  (ra+k, ra+k) k < d;  (rb+k, rb+k) k < d;  then for a < d, c < d:
+//       (ra+a, rb+c);  then for a < d, c < d: (rb+c, ra+a)                        -- kappa on the diagonals, -kappa R[a,c]
+//   translation of edge e:  rows u = (ra .. ra+d-1, ta, tb), v = (-t, -1, +1): (u_i, u_j) for i, then j   -- tau (v_i v_j)
+//   range m:                rows u = (q, ta, tb),            v = (r, -1, +1):  (u_i, u_j) for i, then j   -- omega (v_i v_j)
+// (v_i v_j is formed first, so the coefficients of (i, j) and (j, i) have the same bits and Q(w) is bitwise symmetric.)
+// SUM of an entry, on the device and in the host mirror alike, acc = fma(coef, w, acc) from +0.0:
+//   at most kLongEntry terms: in map order, one accumulator;
+//   more ("long" entries, listed in long_entries): 64 accumulators, number l takes terms l, l + 64, ... in order; then
+//   acc[l] += acc[l + off] for l < off, off = 32, 16, 8, 4, 2, 1; the entry is acc[0].
+// An entry no term reaches is +0.0.
+// kLongEntry = 2 waves of terms: up to there a lane's serial loop is shorter than the launch of a wavefront per entry
+// would be; beyond it (a landmark's diagonal collects a term per measurement: thousands) one lane would hold its wave up.
+constexpr int kLongEntry = 2 * kWave;
+struct TermMap {
+  bool built = false;
+  int64_t nnz = 0, n_edges = 0, n_ranges = 0, n_weights = 0, n_terms = 0, max_terms = 0;
+  std::vector<int32_t> tptr;          // nnz + 1
+  std::vector<int32_t> tweight;       // n_terms
+  std::vector<double> tcoef;          // n_terms
+  std::vector<int32_t> long_entries;  // CSR positions with more than kLongEntry terms, ascending
+  std::vector<double> base;           // n_weights: kappa of every edge | tau of every edge | omega of every range
+};
+// The table in API rows as cora_set_measurements takes it, except edge_data / range_data, which are field-major
+// ([field][measurement], the handle's copy).  Throws std::runtime_error: a row with a repeated column, a term with a
+// nonzero coefficient outside the pattern (names the measurement), 2^31 terms or more.
+void build_term_map(int d, int64_t N, const int32_t *rowptr, const int32_t *col, int64_t n_edges, const int32_t *edge_rows,
+                    const double *edge_data, int64_t n_ranges, const int32_t *range_rows, const double *range_data,
+                    TermMap &M);
+// The map executed on the host in the device's order (see above): vals[nnz].
+void term_map_apply_host(const TermMap &M, const double *w, double *vals);
+
 // Every column index a slice stores (general slots and tail of a chain slice; all slots of the others); the implied
 // columns of a chain slice are rows of the local shard.
 void slice_columns(const HostFormat &F, const SliceDesc &sd, std::vector<int32_t> &out);

@@ -342,6 +342,66 @@ void Problem::setMeasurementWeights(const MeasurementWeights &w) {
   if (had_table) ensureMeasurementTable();  // kappa, tau, omega of the table follow the weights
 }
 
+// Q(w) assembled on the device through the handle's term map (cora_assemble_values, include/cora_hip.h): no host sparse
+// algebra after the first call per handle.
+void Problem::reweight(const MeasurementWeights &w) {
+  validateWeights(w);
+  if (!ctx_ || !problem_data_up_to_date_ || data_matrix_.nonZeros() == 0 || part_world_ > 1) {
+    setMeasurementWeights(w);  // no live handle to keep (or a partitioned one, which has no measurement table)
+    return;
+  }
+  int64_t info[4];
+  if (!measurements_ready_ || cora_assembly_info(ctx_.get(), info) != CORA_OK) {
+    // the term map multiplies the UNWEIGHTED precisions: the table goes up with unit weights first
+    const MeasurementWeights kept = weights();
+    weights() = MeasurementWeights();
+    measurements_ready_ = false;
+    try {
+      ensureMeasurementTable();
+    } catch (...) {
+      weights() = kept;
+      throw;
+    }
+    weights() = kept;
+    const int rc = cora_assembly_build(ctx_.get(), data_matrix_.outerIndexPtr(), data_matrix_.innerIndexPtr());
+    if (rc != CORA_OK) {
+      measurements_ready_ = false;  // (the unit-weight table is not the one measurementResiduals expects)
+      throwLast(rc, "Problem::reweight");
+    }
+  }
+  // the seven kinds in table order: [rot | trans] of pose-pose, pose priors, pose-landmark, landmark priors; then ranges
+  const size_t npp = rel_pose_pose_measurements_.size(), nprior = pose_priors_.size();
+  const size_t npl = rel_pose_landmark_measurements_.size(), nlp = landmark_priors_.size(), nr = range_measurements_.size();
+  const size_t m = npp + nprior + npl + nlp;
+  std::vector<double> flat(2 * m + nr, 1.0);
+  auto put = [&flat](size_t at, const std::vector<Scalar> &v) { std::copy(v.begin(), v.end(), flat.begin() + static_cast<std::ptrdiff_t>(at)); };
+  put(0, w.rel_pose_rot);
+  put(npp, w.pose_prior_rot);
+  put(m, w.rel_pose_trans);
+  put(m + npp, w.pose_prior_trans);
+  put(m + npp + nprior, w.pose_landmark);
+  put(m + npp + nprior + npl, w.landmark_prior);
+  put(2 * m, w.range);
+  {
+    std::vector<Scalar> vals(data_matrix_.values.size());
+    const int rc = cora_assemble_values(ctx_.get(), flat.data(), vals.data());
+    if (rc != CORA_OK) {  // refused: the handle's values, the weights and Q are as before
+      measurements_ready_ = false;  // (the table may be the unit-weight one: the next use installs the weighted one)
+      throwLast(rc, "Problem::reweight");
+    }
+    data_matrix_.values.swap(vals);  // the device's bits: certification and the host Cholesky read them
+  }
+  weights() = w;
+  // the handle is back in the state of a fresh one at the same rank; its table follows the weights and stays
+  precond_ready_ = false;
+  implicit_ready_ = false;
+  cert_block_.reset();
+  std::lock_guard<std::recursive_mutex> lock(*cert_mutex_);
+  cert_S_ = SparseMatrix();
+  cert_lambda_pos_.clear();
+  cert_lambda_q_.clear();
+}
+
 const SparseMatrix &Problem::getDataMatrix() {
   if (data_matrix_.nonZeros() == 0 || !problem_data_up_to_date_) updateProblemData();
   return data_matrix_;

@@ -286,6 +286,17 @@ class Problem {
    * Throws std::invalid_argument for a wrong length, a negative or a non-finite weight (nothing is changed then). */
   void setMeasurementWeights(const MeasurementWeights &w);
   const MeasurementWeights &getMeasurementWeights() const;
+  /** EXTENSION beyond the reference: the same re-weighting with Q(w) ASSEMBLED ON THE DEVICE.  Same validation, same
+   * stored weights and the same things redone on next use as setMeasurementWeights.  With a live, up-to-date,
+   * unpartitioned handle the first call installs the measurement table with unit weights and builds the handle's term
+   * map (cora_assembly_build, include/cora_hip.h); every call then flattens the seven kinds into table order (pose-pose,
+   * pose priors, pose-landmark, landmark priors, then ranges) and runs cora_assemble_values: no host sparse algebra, and
+   * getDataMatrix() holds the values the device computed, bit for bit.  Without such a handle it IS
+   * setMeasurementWeights.
+   * The two methods sum the same terms in different orders: their matrices agree to rounding (a few ulp of the sum of
+   * the terms' magnitudes per entry), not to the bit.  reweight is reproducible in itself: the same weights give the same
+   * bits on every call, on the device and in the host mirror of a plan-only handle. */
+  void reweight(const MeasurementWeights &w);
 
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;

@@ -312,6 +312,17 @@ int cora_problem_set_measurement_weights(cora_problem *p, const double *const we
   });
 }
 
+int cora_problem_reweight(cora_problem *p, const double *const weights[7], const int64_t lengths[7]) {
+  return guarded([&] {
+    MeasurementWeights w;
+    std::vector<Scalar> *dst[7] = {&w.rel_pose_rot, &w.rel_pose_trans, &w.pose_prior_rot, &w.pose_prior_trans,
+                                   &w.pose_landmark, &w.landmark_prior, &w.range};
+    for (int k = 0; k < 7; ++k)
+      if (weights && weights[k] && lengths && lengths[k] > 0) dst[k]->assign(weights[k], weights[k] + lengths[k]);
+    p->problem.reweight(w);
+  });
+}
+
 int cora_problem_get_measurement_weights(const cora_problem *p, double *const weights[7]) {
   return guarded([&] {
     const Problem &q = p->problem;

@@ -352,4 +352,18 @@ hipError_t launch_values_gather(int64_t n, const int32_t *src, const double *val
 hipError_t launch_values_gather_sym(int64_t n, const int32_t *src, const double *vals, double *dst0, double *dst1,
                                     hipStream_t st);
 
+// Assembly of Q(w) from per-measurement weights (kernels/assemble.inc): the device copy of a TermMap (cora_internal.h).
+struct AssembleArgs {
+  int64_t nnz = 0;
+  int n_long = 0;
+  const int32_t *tptr = nullptr, *tweight = nullptr, *long_entries = nullptr;
+  const double *tcoef = nullptr;
+};
+// flag |= 1 where a weight is negative or not finite
+hipError_t launch_weights_check(int64_t n, const double *w, int *flag, hipStream_t st);
+// vals[q] = sum of tcoef[t] * w[tweight[t]] over the terms of entry q (order: TermMap); vals: 16-byte aligned
+hipError_t launch_assemble(const AssembleArgs &A, const double *w, double *vals, hipStream_t st);
+// dst[i] = base[i] * w[i]
+hipError_t launch_scale_precisions(int64_t n, const double *base, const double *w, double *dst, hipStream_t st);
+
 }  // namespace cora

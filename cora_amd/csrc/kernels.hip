@@ -33,6 +33,7 @@
 //   kernels/rows.inc     row-unit, vector, reduction, exchange and LOBPCG block kernels                           CORA_TU & 2
 //   kernels/residuals.inc  per-measurement residuals: one gather pass over the measurement table                   CORA_TU & 2
 //   kernels/update_values.inc  in-place update of Q's values: check of the new values, gather passes                CORA_TU & 2
+//   kernels/assemble.inc  Q(w) from per-measurement weights through the term map: check, short and long entries     CORA_TU & 2
 //   kernels/tri.inc      the staged Cholesky solve: k_rowop, k_blockop, k_subblock                                 CORA_TU & 4
 //   kernels/launch.inc   host-side launch wrappers (kernels.h), per translation unit and row-stride group
 namespace cora {
@@ -41,6 +42,7 @@ namespace cora {
 #include "kernels/rows.inc"
 #include "kernels/residuals.inc"
 #include "kernels/update_values.inc"
+#include "kernels/assemble.inc"
 #include "kernels/tri.inc"
 #include "kernels/launch.inc"
 }  // namespace cora

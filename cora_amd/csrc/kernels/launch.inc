@@ -406,6 +406,28 @@ hipError_t launch_values_gather_sym(int64_t n, const int32_t *src, const double 
   return hipGetLastError();
 }
 
+// assembly of Q(w) (kernels/assemble.inc)
+hipError_t launch_weights_check(int64_t n, const double *w, int *flag, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_weights_check, dim3(grid_for(n)), dim3(256), 0, st, n, w, flag);
+  return hipGetLastError();
+}
+
+hipError_t launch_assemble(const AssembleArgs &A, const double *w, double *vals, hipStream_t st) {
+  if (A.nnz <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_assemble_short, dim3(grid_for((A.nnz + 1) / 2)), dim3(256), 0, st, A.nnz, A.tptr, A.tweight, A.tcoef, w, vals);
+  if (A.n_long > 0)  // (after the short pass on the same stream: it leaves 0.0 in the long entries)
+    hipLaunchKernelGGL(k_assemble_long, dim3(grid_for(A.n_long, 256 / kWave)), dim3(256), 0, st, A.n_long, A.long_entries, A.tptr,
+                       A.tweight, A.tcoef, w, vals);
+  return hipGetLastError();
+}
+
+hipError_t launch_scale_precisions(int64_t n, const double *base, const double *w, double *dst, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_scale_precisions, dim3(grid_for(n)), dim3(256), 0, st, n, base, w, dst);
+  return hipGetLastError();
+}
+
 #endif  // CORA_TU & 2
 #if CORA_TU & 4
 

@@ -253,6 +253,17 @@ class Problem:
         lens = (C.c_int64 * 7)(*[a.size for a in arrs])
         self._chk(self.L.cora_problem_set_measurement_weights(self.h, ptrs, lens))
 
+    def reweight(self, weights):
+        """Problem::reweight: set_measurement_weights with Q(w) assembled on the device through the handle's term map
+        (falls back to set_measurement_weights without a live handle).  The two agree to rounding, not to the bit."""
+        unknown = set(weights) - set(self.WEIGHT_KINDS)
+        if unknown:
+            raise HostError("unknown measurement kinds: %s" % sorted(unknown))
+        arrs = [np.ascontiguousarray(weights.get(k, ()), dtype=np.float64).reshape(-1) for k in self.WEIGHT_KINDS]
+        ptrs = (_dp * 7)(*[a.ctypes.data_as(_dp) if a.size else None for a in arrs])
+        lens = (C.c_int64 * 7)(*[a.size for a in arrs])
+        self._chk(self.L.cora_problem_reweight(self.h, ptrs, lens))
+
     def get_measurement_weights(self):
         cnt = (C.c_int64 * 5)()
         self._chk(self.L.cora_problem_measurement_counts(self.h, cnt))

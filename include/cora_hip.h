@@ -408,7 +408,8 @@ int cora_debug_measurement_residuals_host(cora_ctx *ctx, const double *X, int ld
  *                         device staging buffer of nnz doubles.
  * cora_update_values      vals: the new values on the HOST, CSR order, with the pattern passed again.  Also works on a
  *                         plan-only handle (device < 0): the host format is refreshed through the same map.
- * cora_update_values_dev  d_vals: nnz doubles in CSR order ON THE DEVICE (assembled there by the caller).  Needs the map
+ * cora_update_values_dev  d_vals: nnz doubles in CSR order ON THE DEVICE (cora_assemble_values_dev below forms Q(w)
+ *                         there; any other values are the caller's).  Needs the map
  *                         (CORA_ERR_NOT_READY before).  The host copy of the format is NOT refreshed:
  *                         cora_debug_format_spmm_host answers CORA_ERR_NOT_READY until the next cora_update_values.
  * Partitioned handles: every rank passes the WHOLE matrix, as to cora_ctx_create_part; the map is per rank and the call
@@ -439,6 +440,63 @@ int cora_values_map_build(cora_ctx *ctx, const int32_t *rowptr, const int32_t *c
 int cora_update_values(cora_ctx *ctx, const int32_t *rowptr, const int32_t *colidx, const double *vals);
 int cora_update_values_dev(cora_ctx *ctx, const double *d_vals);
 int cora_update_values_times(const cora_ctx *ctx, double ms[5]);
+
+/* ---- Q(w): the values of Q ASSEMBLED ON THE DEVICE from per-measurement weights ------------------------------------------
+ * Q is linear in the weights of the measurements.  With the table of cora_set_measurements -- rows (ra, rb, ta, tb) and
+ * data (R, t, kappa, tau) of an edge, rows (q, ta, tb) and data (r, omega) of a range -- every stored entry of Q is a
+ * fixed sum of terms coef * w[i], the ones the reference's assembly produces (src/CORA_problem.cpp:115-377, 625-712):
+ *   rotation of edge e (rb >= 0), weight e:    kappa at (ra+k, ra+k) and (rb+k, rb+k), k < d;
+ *                                              -kappa R[a,c] at (ra+a, rb+c) and at (rb+c, ra+a)
+ *   translation of edge e, weight n_edges + e: tau v_i v_j at every pair of the rows (ra .. ra+d-1, ta, tb), v = (-t, -1, +1)
+ *   range m, weight 2 n_edges + m:             omega v_i v_j at every pair of the rows (q, ta, tb), v = (r, -1, +1)
+ * (the rotation part is the connection Laplacian as the reference forms it, kappa on the diagonals -- not the expansion
+ * of the residual, which differs wherever R is not exactly orthonormal).
+ * WEIGHTS: 2 n_edges + n_ranges doubles, [rot of every edge | trans of every edge | range], the layout of the residuals
+ * of cora_measurement_residuals_dev, so that a re-weighting loop reads residuals and writes weights at the same index.
+ * Every weight must be finite and >= 0.  The rot weight of an edge without a rotation part (rb = -1) multiplies nothing
+ * but is validated like the others.  A weight MULTIPLIES the precision the table held when the map was built: build with
+ * the unweighted precisions and w = 1 reproduces Q.
+ *
+ * cora_assembly_build    (rowptr, colidx): the pattern the handle was created with (checked as cora_values_map_build
+ *                        checks it; the source map of cora_update_values is built too when it is absent).  Builds the
+ *                        TERM MAP -- for every CSR entry the list of (weight index, coefficient) -- and uploads it:
+ *                        12 bytes per term and 4 per entry.  Needs a measurement table (CORA_ERR_NOT_READY).  Works on a
+ *                        plan-only handle (device < 0).  CORA_ERR_ARG: a term with a nonzero coefficient outside the
+ *                        pattern (the message names the measurement; terms whose coefficient is exactly 0.0 are
+ *                        dropped), a row that repeats a column, 2^31 terms or more, a partitioned handle.
+ *                        A later cora_set_measurements drops the map.
+ * cora_assemble_values   w: the weights on the HOST.  vals_out: NULL or nnz host doubles that receive the assembled CSR
+ *                        values (the bits the handle now holds).  The host copy of the format and the host copy of the
+ *                        table are refreshed; on a plan-only handle the map is executed on the host.
+ * cora_assemble_values_dev  d_w: the weights ON THE DEVICE; d_vals_out: NULL or nnz device doubles.  No host memory is
+ *                        touched: the host copy of the format is stale as after cora_update_values_dev, and so is the
+ *                        host copy of the table (cora_debug_measurement_residuals_host answers CORA_ERR_NOT_READY).
+ * cora_debug_assemble_values_host  test hook: the map executed on the host in the device's order.  Never used by a compute
+ *                        entry point; changes nothing of the handle.
+ * cora_assembly_info     out = { number of weights, number of terms, long entries, most terms of one entry };
+ *                        CORA_ERR_NOT_READY without a map.
+ * cora_assemble_times    milliseconds of the last calls: [0] term map build, [1] weight check, [2] the assembly kernels
+ *                        (events), [3] cora_update_values_dev's passes, [4] copies and host refresh.
+ *
+ * SUMMATION ORDER.  An entry's terms are ordered by ascending weight index and, for one measurement, as listed above
+ * (diagonals of a, of b, the block (a, b) row by row, the block (b, a) in the same (a, c) order; pairs (i, j) row by
+ * row).  An entry of at most 128 terms is summed by one thread: acc = fma(coef, w, acc) from +0.0 in that order.  A
+ * longer one (a landmark's diagonal collects a term per measurement) by one wavefront: lane l sums terms l, l + 64, ...
+ * the same way, then lane l += lane l + off for off = 32, 16, 8, 4, 2, 1, and lane 0 holds the entry.  No atomics: the
+ * values are a function of the map and the weights, two calls give the same bits, and the host mirror gives the
+ * device's bits.  An entry no term reaches is +0.0.  v_i v_j is formed before the precision multiplies it, so Q(w) is
+ * bitwise symmetric and passes the symmetry check of an update.
+ *
+ * STATE after a successful call: that of cora_update_values* (above) -- the values go through the same check and gather
+ * passes -- except that the measurement table FOLLOWS the weights: kappa, tau and omega become base * w (device copy
+ * always, host copy by cora_assemble_values), so cora_measurement_residuals* return weighted residuals and 1/2 of their
+ * sum stays the cost.  A refused call (a bad weight, no map, values the update refuses) leaves the handle as it was. */
+int cora_assembly_build(cora_ctx *ctx, const int32_t *rowptr, const int32_t *colidx);
+int cora_assemble_values(cora_ctx *ctx, const double *w, double *vals_out);
+int cora_assemble_values_dev(cora_ctx *ctx, const double *d_w, double *d_vals_out);
+int cora_debug_assemble_values_host(cora_ctx *ctx, const double *w, double *vals_out);
+int cora_assembly_info(const cora_ctx *ctx, int64_t out[4]);
+int cora_assemble_times(const cora_ctx *ctx, double ms[5]);
 
 /* Timing helpers: HIP events on the handle's stream. */
 int cora_timer_start(cora_ctx *ctx);

@@ -116,6 +116,10 @@ int cora_problem_measurement_residuals(cora_problem *p, const double *Y, int col
  * (cora_update_values) and stays the same handle.  Afterwards cora_problem_measurement_residuals returns WEIGHTED
  * residuals.  get: every non-NULL array receives the count of its kind (ones where none were set). */
 int cora_problem_set_measurement_weights(cora_problem *p, const double *const weights[7], const int64_t lengths[7]);
+/* Problem::reweight: the same arguments and the same result to rounding, with Q(w) assembled on the device through the
+ * handle's term map (cora_assembly_build / cora_assemble_values, cora_hip.h) when a live unpartitioned handle exists:
+ * the data matrix then holds the device's bits.  Without such a handle it is cora_problem_set_measurement_weights. */
+int cora_problem_reweight(cora_problem *p, const double *const weights[7], const int64_t lengths[7]);
 int cora_problem_get_measurement_weights(const cora_problem *p, double *const weights[7]);
 
 /* Riemannian TNT (the call of src/CORA.cpp:139-140 with the parameters of :95-109) from x0
