@@ -722,6 +722,43 @@ class Context:
         self._chk(self.L.cora_assemble_times(self.h, out))
         return [out[i] for i in range(5)]
 
+    # ---- the weight step of a robust-cost (GNC) loop (include/cora_hip.h, cora_gnc_weights_dev)
+    GNC_COSTS = {"none": 0, "tls": 1, "gm": 2}
+
+    @staticmethod
+    def _gnc_stats(st):
+        names = ("sum_wr2", "max_rho", "n_mid", "n_out")
+        return {seg: dict(zip(names, st[4 * i:4 * i + 4])) for i, seg in enumerate(("rot", "trans", "range"))}
+
+    def _gnc_host(self, fn, X, barc2, cost, mu, couple_edges):
+        X = _f(X)
+        barc2 = self._weights(barc2)
+        w, r2, st = np.zeros(max(len(barc2), 1)), np.zeros(max(len(barc2), 1)), np.zeros(12)
+        self._chk(fn(self.h, _d(X), X.shape[0], X.shape[1], _d(barc2), int(self.GNC_COSTS.get(cost, cost)),
+                     int(bool(couple_edges)), C.c_double(mu), _d(w), _d(r2), _d(st)))
+        return dict(w=w[:len(barc2)], r2=r2[:len(barc2)], stats=self._gnc_stats(st), stats_raw=st)
+
+    def gnc_weights(self, X, barc2, cost, mu=1.0, couple_edges=False):
+        """Weight step at the host matrix X (N x k).  barc2: thresholds in the weight layout [rot | trans | range] (+inf:
+        trusted); cost: 'none' | 'tls' | 'gm' (or the integer).  Returns dict w, r2 (unweighted residuals), stats
+        ({'rot' | 'trans' | 'range': sum_wr2, max_rho, n_mid, n_out}) and stats_raw (the 12 doubles)."""
+        return self._gnc_host(self.L.cora_gnc_weights, X, barc2, cost, mu, couple_edges)
+
+    def debug_gnc_weights_host(self, X, barc2, cost, mu=1.0, couple_edges=False):
+        """Test hook: the same sequence on the host (no GPU needed, the handle is unchanged)."""
+        return self._gnc_host(self.L.cora_debug_gnc_weights_host, X, barc2, cost, mu, couple_edges)
+
+    def gnc_weights_dev(self, x, k, d_barc2, cost, mu, couple_edges, d_w_out, d_r2_out=None):
+        """The same on device vectors (raw pointers as ints): x a resident vector of k columns, d_barc2 / d_w_out /
+        d_r2_out (or None) n_weights device doubles.  Returns the statistics (dict, 'raw': the 12 doubles)."""
+        st = np.zeros(12)
+        self._chk(self.L.cora_gnc_weights_dev(self.h, C.c_void_p(x), int(k), C.c_void_p(d_barc2),
+                                              int(self.GNC_COSTS.get(cost, cost)), int(bool(couple_edges)), C.c_double(mu),
+                                              C.c_void_p(d_w_out), C.c_void_p(d_r2_out), _d(st)))
+        out = self._gnc_stats(st)
+        out["raw"] = st
+        return out
+
     # ---- test hook
     def debug_format_spmm_host(self, X):
         X = _f(X)

@@ -15,6 +15,7 @@
 //   measurements.inc    the measurement table of a handle and the per-measurement residuals
 //   values.inc          in-place update of Q's values: source map, host-pointer and device-pointer update
 //   assembly.inc        Q(w) from per-measurement weights: term map, host-pointer, device-pointer and host-mirror assembly
+//   gnc.inc             the weight step of a robust-cost (GNC) loop: device-pointer, host-pointer and host-mirror form
 //   comm.inc            native communication: RCCL, in-process and device-side (p2p.h) transports
 #include <hip/hip_runtime.h>
 // RCCL's types and the few enumerators used, declared here (NCCL's public ABI: they have not changed since 2.0): the
@@ -232,6 +233,7 @@ struct cora_ctx {
   double *d_tcoef = nullptr, *d_tbase = nullptr, *d_asm_w = nullptr;
   hipEvent_t asm_ev[2] = {nullptr, nullptr};
   double asm_ms[5] = {0, 0, 0, 0, 0};  // cora_assemble_times
+  double *d_gnc = nullptr;  // cora_gnc_weights (capi/gnc.inc): thresholds | weights | residuals of the host-pointer form, 3 n_weights
   std::vector<std::pair<double *, size_t>> user_allocs;  // live vectors of cora_dev_alloc (pointer, bytes)
   std::vector<std::pair<double *, size_t>> pool;         // released ones, kept for the next request of the same size
   std::string err;
@@ -522,8 +524,10 @@ int set_point_dev_impl(cora_ctx *c, const double *dY) {
 
 void free_assembly(cora_ctx *c) {  // (the device must be current where there is one)
   for (void *p : {static_cast<void *>(c->d_tptr), static_cast<void *>(c->d_tweight), static_cast<void *>(c->d_tlong),
-                  static_cast<void *>(c->d_tcoef), static_cast<void *>(c->d_tbase), static_cast<void *>(c->d_asm_w)})
+                  static_cast<void *>(c->d_tcoef), static_cast<void *>(c->d_tbase), static_cast<void *>(c->d_asm_w),
+                  static_cast<void *>(c->d_gnc)})
     if (p) (void)hipFree(p);
+  c->d_gnc = nullptr;
   c->d_tptr = c->d_tweight = c->d_tlong = nullptr;
   c->d_tcoef = c->d_tbase = c->d_asm_w = nullptr;
   c->tmap = TermMap();
@@ -561,6 +565,7 @@ extern "C" {
 #include "capi/measurements.inc"
 #include "capi/values.inc"
 #include "capi/assembly.inc"
+#include "capi/gnc.inc"
 
 }  // extern "C"
 

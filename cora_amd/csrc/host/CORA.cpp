@@ -187,6 +187,59 @@ CoraResult solveCORA(Problem &problem, const Matrix &x0, int max_relaxation_rank
   return std::make_pair(result, iterates);
 }
 
+CoraResult solveRobustCORA(Problem &problem, const Matrix &x0, const GncParams &params, int max_relaxation_rank, bool verbose,
+                           RobustInfo *info) {
+  if (params.cost != GncCost::TruncatedLeastSquares && params.cost != GncCost::GemanMcClure)
+    throw std::invalid_argument("solveRobustCORA: the cost must be TruncatedLeastSquares or GemanMcClure");
+  if (!(params.mu_factor > 1.0) || !std::isfinite(params.mu_factor))
+    throw std::invalid_argument("solveRobustCORA: mu_factor must be finite and > 1");
+  const bool tls = params.cost == GncCost::TruncatedLeastSquares;
+  RobustInfo R;
+  auto same = [](const MeasurementWeights &a, const MeasurementWeights &b) {
+    return a.rel_pose_rot == b.rel_pose_rot && a.rel_pose_trans == b.rel_pose_trans && a.pose_prior_rot == b.pose_prior_rot &&
+           a.pose_prior_trans == b.pose_prior_trans && a.pose_landmark == b.pose_landmark && a.landmark_prior == b.landmark_prior &&
+           a.range == b.range;
+  };
+  problem.reweight(MeasurementWeights());
+  CoraResult res = solveCORA(problem, x0, max_relaxation_rank, verbose, false, false, &R.last_solve);
+  auto step = problem.gncWeights(res.first.x, params.thresholds, GncCost::None, 1.0, params.couple_edges);
+  R.weights = step.first;
+  const Scalar rho_max = step.second.maxRho();
+  printIfVerbose(verbose, "solveRobustCORA: largest ratio to a threshold after the unweighted solve: " + std::to_string(rho_max));
+  if (!(rho_max > 1.0)) {
+    R.converged = true;
+  } else {
+    Scalar mu = tls ? 1.0 / (2.0 * rho_max - 1.0) : 2.0 * rho_max;
+    MeasurementWeights prev;
+    bool have_prev = false;
+    while (true) {
+      step = problem.gncWeights(res.first.x, params.thresholds, params.cost, mu, params.couple_edges);
+      R.mu_history.push_back(mu);
+      R.sum_wr2_history.push_back(step.second.sumWr2());
+      if (tls && have_prev && step.second.nMid() == 0 && same(step.first, prev)) {  // the solution already is the one of these weights
+        R.converged = true;
+        break;
+      }
+      if (R.outer_iterations >= params.max_outer) break;
+      problem.reweight(step.first);
+      res = solveCORA(problem, res.first.x, max_relaxation_rank, verbose, false, false, &R.last_solve);
+      ++R.outer_iterations;
+      R.weights = step.first;
+      printIfVerbose(verbose, "solveRobustCORA: round " + std::to_string(R.outer_iterations) + ", mu " + std::to_string(mu) +
+                                  ", sum of w r2 " + std::to_string(step.second.sumWr2()) + ", f " + std::to_string(res.first.f));
+      if (!tls && mu == 1.0) {
+        R.converged = true;
+        break;
+      }
+      mu = tls ? mu * params.mu_factor : std::max<Scalar>(1.0, mu / params.mu_factor);
+      prev = step.first;
+      have_prev = true;
+    }
+  }
+  if (info) *info = R;
+  return res;
+}
+
 Matrix saddleEscape(const Problem &problem, const Matrix &Y, Scalar theta, const Vector &v,
                     Scalar gradient_tolerance, Scalar preconditioned_gradient_tolerance) {
   // src/CORA.cpp:245-350

@@ -7,7 +7,9 @@
 #include <thread>
 #include <cstdio>
 
+#include <algorithm>
 #include <cmath>
+#include <limits>
 #include <iostream>
 
 #include <cstdlib>
@@ -342,6 +344,29 @@ void Problem::setMeasurementWeights(const MeasurementWeights &w) {
   if (had_table) ensureMeasurementTable();  // kappa, tau, omega of the table follow the weights
 }
 
+// The measurement table with UNIT weights and the term map of Q(w) on the live handle (reweight, gncWeights): the term
+// map multiplies the unweighted precisions, so the table goes up without the stored weights first.
+bool Problem::ensureTermMap(const char *who) {
+  int64_t info[4];
+  if (measurements_ready_ && cora_assembly_info(ctx_.get(), info) == CORA_OK) return false;
+  const MeasurementWeights kept = weights();
+  weights() = MeasurementWeights();
+  measurements_ready_ = false;
+  try {
+    ensureMeasurementTable();
+  } catch (...) {
+    weights() = kept;
+    throw;
+  }
+  weights() = kept;
+  const int rc = cora_assembly_build(ctx_.get(), data_matrix_.outerIndexPtr(), data_matrix_.innerIndexPtr());
+  if (rc != CORA_OK) {
+    measurements_ready_ = false;  // (the unit-weight table is not the one measurementResiduals expects)
+    throwLast(rc, who);
+  }
+  return true;
+}
+
 // Q(w) assembled on the device through the handle's term map (cora_assemble_values, include/cora_hip.h): no host sparse
 // algebra after the first call per handle.
 void Problem::reweight(const MeasurementWeights &w) {
@@ -350,25 +375,7 @@ void Problem::reweight(const MeasurementWeights &w) {
     setMeasurementWeights(w);  // no live handle to keep (or a partitioned one, which has no measurement table)
     return;
   }
-  int64_t info[4];
-  if (!measurements_ready_ || cora_assembly_info(ctx_.get(), info) != CORA_OK) {
-    // the term map multiplies the UNWEIGHTED precisions: the table goes up with unit weights first
-    const MeasurementWeights kept = weights();
-    weights() = MeasurementWeights();
-    measurements_ready_ = false;
-    try {
-      ensureMeasurementTable();
-    } catch (...) {
-      weights() = kept;
-      throw;
-    }
-    weights() = kept;
-    const int rc = cora_assembly_build(ctx_.get(), data_matrix_.outerIndexPtr(), data_matrix_.innerIndexPtr());
-    if (rc != CORA_OK) {
-      measurements_ready_ = false;  // (the unit-weight table is not the one measurementResiduals expects)
-      throwLast(rc, "Problem::reweight");
-    }
-  }
+  ensureTermMap("Problem::reweight");
   // the seven kinds in table order: [rot | trans] of pose-pose, pose priors, pose-landmark, landmark priors; then ranges
   const size_t npp = rel_pose_pose_measurements_.size(), nprior = pose_priors_.size();
   const size_t npl = rel_pose_landmark_measurements_.size(), nlp = landmark_priors_.size(), nr = range_measurements_.size();
@@ -400,6 +407,67 @@ void Problem::reweight(const MeasurementWeights &w) {
   cert_S_ = SparseMatrix();
   cert_lambda_pos_.clear();
   cert_lambda_q_.clear();
+}
+
+// One GNC weight step (cora_gnc_weights, include/cora_hip.h): thresholds flattened into table order like reweight's
+// weights (+inf where a kind has none), the weights split back into the seven kinds.
+std::pair<MeasurementWeights, GncStats> Problem::gncWeights(const Matrix &Y, const MeasurementWeights &thresholds, GncCost cost,
+                                                            Scalar mu, bool couple_edges) {
+  if (part_world_ > 1) throw std::runtime_error("Problem::gncWeights: not supported on a partitioned handle");
+  if (!ctx_ || !problem_data_up_to_date_ || data_matrix_.nonZeros() == 0)
+    throw std::runtime_error("Problem::gncWeights: no live device handle (run a solve or an operator after updateProblemData first)");
+  checkMatrixShape("Problem::gncWeights::Y", getExpectedVariableSize(), Y.cols(), Y.rows(), Y.cols());
+  const size_t npp = rel_pose_pose_measurements_.size(), nprior = pose_priors_.size();
+  const size_t npl = rel_pose_landmark_measurements_.size(), nlp = landmark_priors_.size(), nr = range_measurements_.size();
+  const size_t m = npp + nprior + npl + nlp;
+  std::vector<double> barc2(2 * m + nr, std::numeric_limits<double>::infinity());
+  auto put = [&barc2](size_t at, const std::vector<Scalar> &v, size_t n, const char *kind) {
+    if (v.empty()) return;
+    if (v.size() != n)
+      throw std::invalid_argument(std::string("Problem::gncWeights: thresholds: ") + kind + " has " + std::to_string(v.size()) +
+                                  " values for " + std::to_string(n) + " measurements");
+    std::copy(v.begin(), v.end(), barc2.begin() + static_cast<std::ptrdiff_t>(at));
+  };
+  if (!couple_edges) {
+    put(0, thresholds.rel_pose_rot, npp, "rel_pose_rot");
+    put(npp, thresholds.pose_prior_rot, nprior, "pose_prior_rot");
+  }
+  put(m, thresholds.rel_pose_trans, npp, "rel_pose_trans");
+  put(m + npp, thresholds.pose_prior_trans, nprior, "pose_prior_trans");
+  put(m + npp + nprior, thresholds.pose_landmark, npl, "pose_landmark");
+  put(m + npp + nprior + npl, thresholds.landmark_prior, nlp, "landmark_prior");
+  put(2 * m, thresholds.range, nr, "range");
+  if (ensureTermMap("Problem::gncWeights")) {
+    const MeasurementWeights kept = weights();  // set by setMeasurementWeights: the table must follow them again
+    const std::vector<Scalar> *k[7] = {&kept.rel_pose_rot, &kept.rel_pose_trans, &kept.pose_prior_rot, &kept.pose_prior_trans,
+                                       &kept.pose_landmark, &kept.landmark_prior, &kept.range};
+    if (std::any_of(k, k + 7, [](const std::vector<Scalar> *v) { return !v->empty(); })) reweight(kept);
+  }
+  Matrix full_tmp;
+  if (formulation_ == Formulation::Implicit) full_tmp = getTranslationExplicitSolution(Y);
+  const Matrix &X = formulation_ == Formulation::Implicit ? full_tmp : Y;
+  std::vector<double> w(std::max<size_t>(barc2.size(), 1));
+  double st[12];
+  const int rc = cora_gnc_weights(ctx_.get(), X.data(), static_cast<int>(X.rows()), static_cast<int>(X.cols()), barc2.data(),
+                                  static_cast<int>(cost), couple_edges ? 1 : 0, mu, w.data(), nullptr, st);
+  if (rc != CORA_OK) throwLast(rc, "Problem::gncWeights");
+  std::pair<MeasurementWeights, GncStats> out;
+  MeasurementWeights &W = out.first;
+  W.rel_pose_rot.assign(w.begin(), w.begin() + npp);
+  W.pose_prior_rot.assign(w.begin() + npp, w.begin() + npp + nprior);
+  W.rel_pose_trans.assign(w.begin() + m, w.begin() + m + npp);
+  W.pose_prior_trans.assign(w.begin() + m + npp, w.begin() + m + npp + nprior);
+  W.pose_landmark.assign(w.begin() + m + npp + nprior, w.begin() + m + npp + nprior + npl);
+  W.landmark_prior.assign(w.begin() + m + npp + nprior + npl, w.begin() + 2 * m);
+  W.range.assign(w.begin() + 2 * m, w.begin() + 2 * m + nr);
+  GncStats::Segment *seg[3] = {&out.second.rot, &out.second.trans, &out.second.range};
+  for (int i = 0; i < 3; ++i) {
+    seg[i]->sum_wr2 = st[4 * i];
+    seg[i]->max_rho = st[4 * i + 1];
+    seg[i]->n_mid = static_cast<long>(st[4 * i + 2]);
+    seg[i]->n_out = static_cast<long>(st[4 * i + 3]);
+  }
+  return out;
 }
 
 const SparseMatrix &Problem::getDataMatrix() {

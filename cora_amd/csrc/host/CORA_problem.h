@@ -6,6 +6,7 @@
 // operators in this class: without a usable gfx950 device they throw.
 #pragma once
 
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -69,6 +70,27 @@ struct MeasurementWeights {
   std::vector<Scalar> range;
 };
 
+/** EXTENSION beyond the reference: the weight step of a graduated non-convexity (GNC) loop, Problem::gncWeights below.
+ * The robust costs (include/cora_hip.h, cora_gnc_weights_dev): with rho = r2 / barc2 the ratio of a measurement's
+ * UNWEIGHTED residual to its threshold,
+ *   TruncatedLeastSquares  w = 1 for rho <= mu / (mu + 1), 0 for rho >= (mu + 1) / mu, sqrt(mu (mu + 1) / rho) - mu between
+ *   GemanMcClure           w = (mu / (rho + mu))^2
+ *   None                   w = 1 (only the statistics are of interest: the largest rho starts the schedule of mu). */
+enum class GncCost { None = 0, TruncatedLeastSquares = 1, GemanMcClure = 2 };
+/** Statistics of a weight step per segment (rotation parts, translation parts, ranges).  With coupled edges a relative
+ * pose or pose prior is counted and maximised in `trans` only; `rot` then carries only its sum. */
+struct GncStats {
+  struct Segment {
+    Scalar sum_wr2 = 0;  // sum of w r2
+    Scalar max_rho = 0;  // largest ratio (0 for an empty segment)
+    long n_mid = 0;      // measurements with 0 < w < 1
+    long n_out = 0;      // measurements with w < 0.5
+  } rot, trans, range;
+  Scalar maxRho() const { return std::max(rot.max_rho, std::max(trans.max_rho, range.max_rho)); }
+  Scalar sumWr2() const { return rot.sum_wr2 + trans.sum_wr2 + range.sum_wr2; }
+  long nMid() const { return rot.n_mid + trans.n_mid + range.n_mid; }
+};
+
 class Problem {
  private:
   int dim_;
@@ -102,6 +124,7 @@ class Problem {
   void *comm_user_ = nullptr;
   mutable std::shared_ptr<cora_ctx> ctx_;
   void validateWeights(const MeasurementWeights &w) const;  // lengths and values, std::invalid_argument
+  bool ensureTermMap(const char *who);  // unit-weight table + term map on the live handle; true when it installed them
   // the Ritz block of the last certify_solution_resident, on the device (declared after ctx_: released before the handle)
   mutable std::shared_ptr<class LOBPCGSolver> cert_block_;
   CertResults certifyImpl(const Matrix &Y, Scalar eta, size_t nx, const Matrix &eigvec_bootstrap, size_t max_LOBPCG_iters,
@@ -297,6 +320,20 @@ class Problem {
    * the terms' magnitudes per entry), not to the bit.  reweight is reproducible in itself: the same weights give the same
    * bits on every call, on the device and in the host mirror of a plan-only handle. */
   void reweight(const MeasurementWeights &w);
+  /** EXTENSION beyond the reference: one GNC weight step on the device (cora_gnc_weights, include/cora_hip.h) at Y
+   * (getExpectedVariableSize() rows, 1..24 columns; completed first in the implicit formulation).  `thresholds` holds
+   * barc2 per measurement in the seven vectors of MeasurementWeights: an EMPTY vector means trusted (+inf: weight 1),
+   * otherwise its length must be the count of the kind and every value > 0 or +inf (std::invalid_argument /
+   * std::runtime_error otherwise).  The residuals are UNWEIGHTED: they are formed with the measurements' own precisions
+   * whatever the current weights are.  couple_edges: a relative pose or pose prior is one measurement (rot + trans
+   * against its *_trans threshold, one weight for both parts; the *_rot thresholds are ignored).
+   * Returns the weights, ready for reweight(), and the statistics.  The handle's state is untouched, except on the first
+   * use per handle, which installs the unit-weight measurement table and the term map exactly as reweight does (and,
+   * where weights had been set by setMeasurementWeights, re-assembles Q with them so that the table follows them).
+   * Needs a live handle (one solve or operator call after updateProblemData): std::runtime_error without one, and with a
+   * partitioned one, which has no measurement table. */
+  std::pair<MeasurementWeights, GncStats> gncWeights(const Matrix &Y, const MeasurementWeights &thresholds, GncCost cost,
+                                                     Scalar mu, bool couple_edges);
 
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;

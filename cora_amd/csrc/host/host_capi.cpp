@@ -586,6 +586,81 @@ int cora_problem_solve(cora_problem *p, const double *x0, int max_rank, int verb
   });
 }
 
+namespace {
+MeasurementWeights sevenKinds(const double *const arrays[7], const int64_t lengths[7]) {
+  MeasurementWeights w;
+  std::vector<Scalar> *dst[7] = {&w.rel_pose_rot, &w.rel_pose_trans, &w.pose_prior_rot, &w.pose_prior_trans,
+                                 &w.pose_landmark, &w.landmark_prior, &w.range};
+  for (int k = 0; k < 7; ++k)
+    if (arrays && arrays[k] && lengths && lengths[k] > 0) dst[k]->assign(arrays[k], arrays[k] + lengths[k]);
+  return w;
+}
+}  // namespace
+
+int cora_problem_gnc_weights(cora_problem *p, const double *Y, int cols, const double *const thresholds[7],
+                             const int64_t lengths[7], int cost, double mu, int couple_edges, double *const weights_out[7],
+                             double stats[12]) {
+  return guarded([&] {
+    Problem &q = p->problem;
+    if (cost < 0 || cost > 2) throw std::invalid_argument("cora_problem_gnc_weights: unknown cost");
+    const auto r = q.gncWeights(wrap(Y, q.getExpectedVariableSize(), cols), sevenKinds(thresholds, lengths),
+                                static_cast<GncCost>(cost), mu, couple_edges != 0);
+    const MeasurementWeights &w = r.first;
+    const std::vector<Scalar> *src[7] = {&w.rel_pose_rot, &w.rel_pose_trans, &w.pose_prior_rot, &w.pose_prior_trans,
+                                         &w.pose_landmark, &w.landmark_prior, &w.range};
+    for (int k = 0; k < 7; ++k)
+      if (weights_out && weights_out[k] && !src[k]->empty()) std::memcpy(weights_out[k], src[k]->data(), sizeof(double) * src[k]->size());
+    if (stats) {
+      const GncStats::Segment *seg[3] = {&r.second.rot, &r.second.trans, &r.second.range};
+      for (int i = 0; i < 3; ++i) {
+        stats[4 * i] = seg[i]->sum_wr2;
+        stats[4 * i + 1] = seg[i]->max_rho;
+        stats[4 * i + 2] = static_cast<double>(seg[i]->n_mid);
+        stats[4 * i + 3] = static_cast<double>(seg[i]->n_out);
+      }
+    }
+  });
+}
+
+int cora_problem_solve_robust(cora_problem *p, const double *x0, int max_rank, int verbose,
+                              const double *const thresholds[7], const int64_t lengths[7], int cost, int couple_edges,
+                              double mu_factor, int max_outer, double *x_out, double stats[11], double robust[3],
+                              double *mu_hist, double *sum_wr2_hist) {
+  return guarded([&] {
+    Problem &q = p->problem;
+    if (cost != 1 && cost != 2) throw std::invalid_argument("cora_problem_solve_robust: the cost must be 1 (TLS) or 2 (GM)");
+    const Index N = q.getExpectedVariableSize(), r = static_cast<Index>(q.getRelaxationRank());
+    GncParams prm;
+    prm.cost = static_cast<GncCost>(cost);
+    prm.thresholds = sevenKinds(thresholds, lengths);
+    prm.couple_edges = couple_edges != 0;
+    prm.mu_factor = mu_factor;
+    prm.max_outer = max_outer;
+    RobustInfo info;
+    const auto t0 = std::chrono::steady_clock::now();
+    const CoraResult res = solveRobustCORA(q, wrap(x0, N, r), prm, max_rank, verbose != 0, &info);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::memcpy(x_out, res.first.x.data(), sizeof(double) * static_cast<size_t>(res.first.x.size()));
+    const CoraSolveInfo &si = info.last_solve;
+    stats[0] = res.first.f;
+    stats[1] = res.first.gradfx_norm;
+    stats[2] = si.certified ? 1.0 : 0.0;
+    stats[3] = si.eta;
+    stats[4] = si.theta;
+    stats[5] = si.final_rank;
+    stats[6] = si.staircase_levels;
+    stats[7] = static_cast<double>(si.hessian_vector_products);
+    stats[8] = secs;
+    stats[9] = si.relaxation_certified ? 1.0 : 0.0;
+    stats[10] = si.relaxation_rank;
+    robust[0] = info.outer_iterations;
+    robust[1] = info.converged ? 1.0 : 0.0;
+    robust[2] = static_cast<double>(info.mu_history.size());
+    if (mu_hist) std::copy(info.mu_history.begin(), info.mu_history.end(), mu_hist);
+    if (sum_wr2_hist) std::copy(info.sum_wr2_history.begin(), info.sum_wr2_history.end(), sum_wr2_hist);
+  });
+}
+
 int cora_problem_precond_info(cora_problem *p, double info[3]) {
   return guarded([&] {
     p->problem.ensurePreconditionerReady();

@@ -340,6 +340,59 @@ inline int residual_blocks(int64_t n) {  // blocks of a launch over n measuremen
 hipError_t launch_edge_residuals(const ResidualArgs &A, hipStream_t st);   // n == 0: no launch
 hipError_t launch_range_residuals(const ResidualArgs &A, hipStream_t st);  // n == 0: no launch
 
+// The weight step of a robust-cost (GNC) loop (kernels/gnc.inc; include/cora_hip.h, cora_gnc_weights_dev).  One launch per
+// kind of measurement: R is the table of that kind as the residual kernels take it (out0, out1 and partial unused),
+//   edges : base = [kappa | tau], barc2, w, r2 = [rot | trans], each 2 n doubles;  partial [8][blocks]
+//   ranges: base = omega,         barc2, w, r2 = n doubles;                          partial [4][blocks]
+// partial: per segment (edges: rot, trans) three sums -- sum of w r^2, count of 0 < w < 1, count of w < 0.5 -- then one
+// row of maxima of rho per segment.  r2 may be nullptr.  flag |= 1: an r^2 that is not finite, |= 2: a threshold that
+// is NaN or <= 0.
+constexpr int kGncNone = 0, kGncTls = 1, kGncGm = 2;
+struct GncArgs {
+  ResidualArgs R;
+  const double *base = nullptr, *barc2 = nullptr;
+  double *w = nullptr, *r2 = nullptr, *partial = nullptr;
+  int *flag = nullptr;
+  int cost = kGncNone, couple = 0;
+  double mu = 1.0;
+};
+// The arithmetic of one slot, shared by the kernels and the host mirror (cora_debug_gnc_weights_host): every operation
+// is a single correctly rounded fp64 one, in this order, never contracted.
+// rho = r2 / barc2 (0 for a trusted slot: barc2 = +inf);  bad |= 1: r2 not finite, |= 2: barc2 NaN or <= 0
+__host__ __device__ inline double gnc_ratio(double r2, double barc2, int &bad) {
+  if (!(fabs(r2) <= 1.79769313486231570815e308)) bad |= 1;
+  if (!(barc2 > 0.0)) bad |= 2;
+  return barc2 > 1.79769313486231570815e308 ? 0.0 : r2 / barc2;
+}
+// a coupled edge is one measurement: one addition, rot first
+__host__ __device__ inline double gnc_coupled_r2(double rot, double trn) {
+#pragma clang fp contract(off)
+  return rot + trn;
+}
+// TLS: 1 up to rho = mu / (mu + 1), 0 from (mu + 1) / mu on, sqrt(mu (mu + 1) / rho) - mu between;  GM: (mu / (rho + mu))^2.
+// The middle band of TLS lies in (0, 1); rounding can leave it an ulp outside, so it is clamped (a weight below zero
+// would be refused by the assembly).
+__host__ __device__ inline double gnc_weight(int cost, double mu, double rho) {
+#pragma clang fp contract(off)
+  if (cost == kGncTls) {
+    const double m1 = mu + 1.0;
+    if (rho <= mu / m1) return 1.0;
+    if (rho >= m1 / mu) return 0.0;
+    const double q = mu * m1 / rho;
+    const double w = sqrt(q) - mu;
+    return w < 0.0 ? 0.0 : (w > 1.0 ? 1.0 : w);
+  }
+  if (cost == kGncGm) {
+    const double t = mu / (rho + mu);
+    return t * t;
+  }
+  return 1.0;
+}
+hipError_t launch_gnc_edges(const GncArgs &A, hipStream_t st);   // n == 0: no launch
+hipError_t launch_gnc_ranges(const GncArgs &A, hipStream_t st);  // n == 0: no launch
+// out[j] = max over b of partial[j * nblocks + b] (values >= 0), one block, fixed order
+hipError_t launch_reduce_max_partials(const double *partial, int nblocks, int count, double *out, hipStream_t st);
+
 // In-place update of Q's values (kernels/update_values.inc).  src: the sources of ValueMap (cora_internal.h), vals: the
 // new CSR values on the device.
 // check: flag |= 1 where a value is not finite, |= 2 where a mirror pair (mirror[2j], mirror[2j + 1]) differs.

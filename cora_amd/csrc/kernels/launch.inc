@@ -382,6 +382,38 @@ hipError_t launch_range_residuals(const ResidualArgs &A, hipStream_t st) {
   return hipGetLastError();
 }
 
+// the GNC weight step (kernels/gnc.inc): the residual kernels' grid and piece width
+hipError_t launch_gnc_edges(const GncArgs &A, hipStream_t st) {
+  const ResidualArgs &R = A.R;
+  if (R.n <= 0) return hipSuccess;
+  if ((R.d != 2 && R.d != 3) || R.k < 1 || R.k > R.ld) return hipErrorInvalidValue;
+  const dim3 grid(residual_blocks(R.n)), block(256);
+  const bool wide = R.ld % 2 == 0;
+  if (R.d == 2) {
+    if (wide) hipLaunchKernelGGL((k_gnc_edges<2, 2>), grid, block, 0, st, A);
+    else hipLaunchKernelGGL((k_gnc_edges<2, 1>), grid, block, 0, st, A);
+  } else {
+    if (wide) hipLaunchKernelGGL((k_gnc_edges<3, 2>), grid, block, 0, st, A);
+    else hipLaunchKernelGGL((k_gnc_edges<3, 1>), grid, block, 0, st, A);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_gnc_ranges(const GncArgs &A, hipStream_t st) {
+  const ResidualArgs &R = A.R;
+  if (R.n <= 0) return hipSuccess;
+  if (R.k < 1 || R.k > R.ld) return hipErrorInvalidValue;
+  const dim3 grid(residual_blocks(R.n)), block(256);
+  if (R.ld % 2 == 0) hipLaunchKernelGGL((k_gnc_ranges<2>), grid, block, 0, st, A);
+  else hipLaunchKernelGGL((k_gnc_ranges<1>), grid, block, 0, st, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_reduce_max_partials(const double *partial, int nblocks, int count, double *out, hipStream_t st) {
+  hipLaunchKernelGGL(k_reduce_max_partials, dim3(1), dim3(256), 0, st, partial, nblocks, count, out);
+  return hipGetLastError();
+}
+
 // in-place update of Q's values (kernels/update_values.inc): two slots per thread
 hipError_t launch_values_check(int64_t nnz, const double *vals, int64_t n_pairs, const int32_t *mirror, int *flag,
                                hipStream_t st) {

@@ -31,6 +31,73 @@ __device__ __forceinline__ double group_sum_8(double v) {
   return v;
 }
 
+// What lane g of its group adds to the two sums of edge e (before the precisions):  rot += |X_b - R^T X_a|^2,
+// trn += |x_t(b) - x_t(a) - sum_c t_c X_a[c, :]|^2 over the lane's pieces of the columns.  Shared with the robust-cost
+// weight step (kernels/gnc.inc), whose residuals are these bits.
+template <int D, int W>
+__device__ __forceinline__ void edge_lane_sums(const ResidualArgs &A, int64_t n, int64_t e, int g, int pieces, bool &has_rot,
+                                               double &rot, double &trn) {
+  const int32_t ra = A.rows[e], rb = A.rows[n + e], ta = A.rows[2 * n + e], tb = A.rows[3 * n + e];
+  has_rot = rb >= 0;
+  double R[D][D] = {}, t[D];
+#pragma unroll
+  for (int c = 0; c < D; ++c) t[c] = A.data[static_cast<size_t>(D * D + c) * n + e];
+  if (has_rot) {
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+      for (int b = 0; b < D; ++b) R[a][b] = A.data[static_cast<size_t>(a * D + b) * n + e];
+  }
+  for (int v = g; v < pieces; v += kResidualLanes) {
+    const int c0 = v * W;
+    double xa[D][W], xta[W], xtb[W];
+#pragma unroll
+    for (int c = 0; c < D; ++c) res_load<W>(A.X, ra + c, A.ld, c0, A.k, xa[c]);
+    res_load<W>(A.X, ta, A.ld, c0, A.k, xta);
+    res_load<W>(A.X, tb, A.ld, c0, A.k, xtb);
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      double diff = xtb[j] - xta[j];
+#pragma unroll
+      for (int c = 0; c < D; ++c) diff = fma(-t[c], xa[c][j], diff);
+      trn = fma(diff, diff, trn);
+    }
+    if (has_rot) {
+#pragma unroll
+      for (int b = 0; b < D; ++b) {  // row b of X_b - R^T X_a
+        double xb[W];
+        res_load<W>(A.X, rb + b, A.ld, c0, A.k, xb);
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+          double diff = xb[j];
+#pragma unroll
+          for (int a = 0; a < D; ++a) diff = fma(-R[a][b], xa[a][j], diff);
+          rot = fma(diff, diff, rot);
+        }
+      }
+    }
+  }
+}
+
+// the same for range m:  res += |x_t(b) - x_t(a) + r x_rho|^2
+template <int W>
+__device__ __forceinline__ void range_lane_sum(const ResidualArgs &A, int64_t n, int64_t m, int g, int pieces, double &res) {
+  const int32_t rr = A.rows[m], ta = A.rows[n + m], tb = A.rows[2 * n + m];
+  const double r = A.data[m];
+  for (int v = g; v < pieces; v += kResidualLanes) {
+    const int c0 = v * W;
+    double xr[W], xta[W], xtb[W];
+    res_load<W>(A.X, rr, A.ld, c0, A.k, xr);
+    res_load<W>(A.X, ta, A.ld, c0, A.k, xta);
+    res_load<W>(A.X, tb, A.ld, c0, A.k, xtb);
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      const double diff = fma(r, xr[j], xtb[j] - xta[j]);
+      res = fma(diff, diff, res);
+    }
+  }
+}
+
 // rot = kappa |X_b - R^T X_a|_F^2,  trans = tau |x_t(b) - x_t(a) - sum_c t_c X_a[c, :]|^2
 template <int D, int W>
 __global__ __launch_bounds__(256) void k_edge_residuals(ResidualArgs A) {
@@ -47,48 +114,9 @@ __global__ __launch_bounds__(256) void k_edge_residuals(ResidualArgs A) {
     double rot = 0.0, trn = 0.0, kappa = 0.0, tau = 0.0;
     bool has_rot = false;
     if (live) {
-      const int32_t ra = A.rows[e], rb = A.rows[n + e], ta = A.rows[2 * n + e], tb = A.rows[3 * n + e];
-      has_rot = rb >= 0;
-      double R[D][D] = {}, t[D];
-#pragma unroll
-      for (int c = 0; c < D; ++c) t[c] = A.data[static_cast<size_t>(D * D + c) * n + e];
       kappa = A.data[static_cast<size_t>(D * D + D) * n + e];
       tau = A.data[static_cast<size_t>(D * D + D + 1) * n + e];
-      if (has_rot) {
-#pragma unroll
-        for (int a = 0; a < D; ++a)
-#pragma unroll
-          for (int b = 0; b < D; ++b) R[a][b] = A.data[static_cast<size_t>(a * D + b) * n + e];
-      }
-      for (int v = g; v < pieces; v += G) {
-        const int c0 = v * W;
-        double xa[D][W], xta[W], xtb[W];
-#pragma unroll
-        for (int c = 0; c < D; ++c) res_load<W>(A.X, ra + c, A.ld, c0, A.k, xa[c]);
-        res_load<W>(A.X, ta, A.ld, c0, A.k, xta);
-        res_load<W>(A.X, tb, A.ld, c0, A.k, xtb);
-#pragma unroll
-        for (int j = 0; j < W; ++j) {
-          double diff = xtb[j] - xta[j];
-#pragma unroll
-          for (int c = 0; c < D; ++c) diff = fma(-t[c], xa[c][j], diff);
-          trn = fma(diff, diff, trn);
-        }
-        if (has_rot) {
-#pragma unroll
-          for (int b = 0; b < D; ++b) {  // row b of X_b - R^T X_a
-            double xb[W];
-            res_load<W>(A.X, rb + b, A.ld, c0, A.k, xb);
-#pragma unroll
-            for (int j = 0; j < W; ++j) {
-              double diff = xb[j];
-#pragma unroll
-              for (int a = 0; a < D; ++a) diff = fma(-R[a][b], xa[a][j], diff);
-              rot = fma(diff, diff, rot);
-            }
-          }
-        }
-      }
+      edge_lane_sums<D, W>(A, n, e, g, pieces, has_rot, rot, trn);
     }
     rot = group_sum_8(rot);
     trn = group_sum_8(trn);
@@ -123,21 +151,8 @@ __global__ __launch_bounds__(256) void k_range_residuals(ResidualArgs A) {
     const bool live = e < n;
     double res = 0.0, omega = 0.0;
     if (live) {
-      const int32_t rr = A.rows[e], ta = A.rows[n + e], tb = A.rows[2 * n + e];
-      const double r = A.data[e];
       omega = A.data[n + e];
-      for (int v = g; v < pieces; v += G) {
-        const int c0 = v * W;
-        double xr[W], xta[W], xtb[W];
-        res_load<W>(A.X, rr, A.ld, c0, A.k, xr);
-        res_load<W>(A.X, ta, A.ld, c0, A.k, xta);
-        res_load<W>(A.X, tb, A.ld, c0, A.k, xtb);
-#pragma unroll
-        for (int j = 0; j < W; ++j) {
-          const double diff = fma(r, xr[j], xtb[j] - xta[j]);
-          res = fma(diff, diff, res);
-        }
-      }
+      range_lane_sum<W>(A, n, e, g, pieces, res);
     }
     res = group_sum_8(res);
     if (live && g == 0) {

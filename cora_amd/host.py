@@ -273,6 +273,61 @@ class Problem:
         self._chk(self.L.cora_problem_get_measurement_weights(self.h, ptrs))
         return {k: a[:int(n)] for k, a, n in zip(self.WEIGHT_KINDS, arrs, sizes)}
 
+    GNC_COSTS = {"none": 0, "tls": 1, "gm": 2}
+
+    def _seven(self, arrays, what):
+        unknown = set(arrays) - set(self.WEIGHT_KINDS)
+        if unknown:
+            raise HostError("unknown measurement kinds in %s: %s" % (what, sorted(unknown)))
+        arrs = [np.ascontiguousarray(arrays.get(k, ()), dtype=np.float64).reshape(-1) for k in self.WEIGHT_KINDS]
+        ptrs = (_dp * 7)(*[a.ctypes.data_as(_dp) if a.size else None for a in arrs])
+        lens = (C.c_int64 * 7)(*[a.size for a in arrs])
+        return arrs, ptrs, lens
+
+    def gnc_weights(self, Y, thresholds, cost, mu=1.0, couple_edges=True):
+        """Problem::gncWeights: one weight step of a robust-cost loop on the device at Y.  thresholds: dict kind -> array
+        of barc2 (kinds as in reweight; a missing kind is trusted), cost 'none' | 'tls' | 'gm'.  The residuals behind the
+        weights are UNWEIGHTED whatever the current weights.  Returns (weights, stats): weights a dict for reweight(),
+        stats {'rot' | 'trans' | 'range': dict sum_wr2, max_rho, n_mid, n_out}.  Needs a live handle (HostError)."""
+        Y = np.asfortranarray(np.asarray(Y, dtype=np.float64))
+        if Y.ndim != 2 or Y.shape[0] != self.variable_size():
+            raise HostError("expected %d rows, got shape %s" % (self.variable_size(), Y.shape))
+        keep, ptrs, lens = self._seven(thresholds, "thresholds")
+        cnt = (C.c_int64 * 5)()
+        self._chk(self.L.cora_problem_measurement_counts(self.h, cnt))
+        sizes = [cnt[0], cnt[0], cnt[1], cnt[1], cnt[2], cnt[3], cnt[4]]
+        arrs = [np.zeros(max(int(n), 1)) for n in sizes]
+        out = (_dp * 7)(*[a.ctypes.data_as(_dp) for a in arrs])
+        st = np.zeros(12)
+        self._chk(self.L.cora_problem_gnc_weights(self.h, Y.ctypes.data_as(_dp), int(Y.shape[1]), ptrs, lens,
+                                                  int(self.GNC_COSTS[cost]), C.c_double(mu), int(bool(couple_edges)), out,
+                                                  st.ctypes.data_as(_dp)))
+        names = ("sum_wr2", "max_rho", "n_mid", "n_out")
+        stats = {seg: dict(zip(names, st[4 * i:4 * i + 4])) for i, seg in enumerate(("rot", "trans", "range"))}
+        return {k: a[:int(n)] for k, a, n in zip(self.WEIGHT_KINDS, arrs, sizes)}, stats
+
+    def solve_robust(self, x0, thresholds, cost="tls", couple_edges=True, mu_factor=1.4, max_outer=100, max_rank=10,
+                     verbose=False):
+        """solveRobustCORA: graduated non-convexity over solve().  Returns solve()'s dict (of the last solve) plus
+        outer_iterations, converged, mu_history, sum_wr2_history and weights (the final ones: the problem stays weighted
+        with them)."""
+        dm = self.dims()
+        x0 = np.asfortranarray(np.asarray(x0, dtype=np.float64))
+        keep, ptrs, lens = self._seven(thresholds, "thresholds")
+        out = np.zeros((self.variable_size(), dm["d"]), order="F")
+        st, rb = np.zeros(11), np.zeros(3)
+        mu_h, sum_h = np.zeros(max_outer + 1), np.zeros(max_outer + 1)
+        self._chk(self.L.cora_problem_solve_robust(self.h, x0.ctypes.data_as(_dp), int(max_rank), int(verbose), ptrs, lens,
+                                                   int(self.GNC_COSTS[cost]), int(bool(couple_edges)), C.c_double(mu_factor),
+                                                   int(max_outer), out.ctypes.data_as(_dp), st.ctypes.data_as(_dp),
+                                                   rb.ctypes.data_as(_dp), mu_h.ctypes.data_as(_dp), sum_h.ctypes.data_as(_dp)))
+        nh = int(rb[2])
+        return dict(x=out, f=st[0], grad_norm=st[1], certified=bool(st[2]), eta=st[3], theta=st[4],
+                    final_rank=int(st[5]), levels=int(st[6]), hvps=int(st[7]), seconds=st[8],
+                    relaxation_certified=bool(st[9]), relaxation_rank=int(st[10]), outer_iterations=int(rb[0]),
+                    converged=bool(rb[1]), mu_history=mu_h[:nh].copy(), sum_wr2_history=sum_h[:nh].copy(),
+                    weights=self.get_measurement_weights())
+
     def tnt(self, x0, max_iterations=0, max_inner=0, grad_tol=0, pgrad_tol=0, max_seconds=0, verbose=False,
             host_stpcg=False):
         dm = self.dims()

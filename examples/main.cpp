@@ -19,11 +19,11 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv]" << std::endl;
+    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]]" << std::endl;
     return 1;
   }
   int max_rank = 10;
-  std::string tum, save_dir, residuals, weights;
+  std::string tum, save_dir, residuals, weights, robust, barc2, weights_out;
   bool jacobi = false, implicit = false, odom = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
@@ -38,6 +38,11 @@ int main(int argc, char **argv) {
     // measurement weights, one line each: kind,index,weight -- kind one of rel_pose_rot, rel_pose_trans, pose_prior_rot,
     // pose_prior_trans, pose_landmark, landmark_prior, range; index in the order of the file's measurements of that kind
     else if (a == "--weights" && i + 1 < argc) weights = argv[++i];
+    // outlier-robust solve (solveRobustCORA): the cost, one threshold barc2 per kind named as in --weights (kinds not
+    // named are trusted), and a file for the final weights in the --weights format
+    else if (a == "--robust" && i + 1 < argc) robust = argv[++i];
+    else if (a == "--barc2" && i + 1 < argc) barc2 = argv[++i];
+    else if (a == "--weights-out" && i + 1 < argc) weights_out = argv[++i];
   }
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
@@ -92,7 +97,61 @@ int main(int argc, char **argv) {
     if (odom && implicit)  // examples/paper_experiments.cpp:623-625
       x0 = x0.block(0, 0, problem.rotAndRangeMatrixSize(), x0.cols());
     CORA::CoraSolveInfo info;
-    const CORA::CoraResult soln = CORA::solveCORA(problem, x0, max_rank, /*verbose=*/true, false, false, &info);
+    CORA::CoraResult soln;
+    if (robust.empty()) {
+      if (!barc2.empty() || !weights_out.empty()) throw std::runtime_error("--barc2 and --weights-out need --robust tls|gm");
+      soln = CORA::solveCORA(problem, x0, max_rank, /*verbose=*/true, false, false, &info);
+    } else {  // (an extension beyond the reference: solveRobustCORA)
+      CORA::GncParams gnc;
+      if (robust == "tls") gnc.cost = CORA::GncCost::TruncatedLeastSquares;
+      else if (robust == "gm") gnc.cost = CORA::GncCost::GemanMcClure;
+      else throw std::runtime_error("--robust: expected tls or gm, got '" + robust + "'");
+      const size_t npp = problem.getRPMs().size(), npr = problem.getPosePriors().size();
+      const std::pair<const char *, std::pair<std::vector<CORA::Scalar> *, size_t>> kinds[] = {
+          {"rel_pose_rot", {&gnc.thresholds.rel_pose_rot, npp}},     {"rel_pose_trans", {&gnc.thresholds.rel_pose_trans, npp}},
+          {"pose_prior_rot", {&gnc.thresholds.pose_prior_rot, npr}}, {"pose_prior_trans", {&gnc.thresholds.pose_prior_trans, npr}},
+          {"pose_landmark", {&gnc.thresholds.pose_landmark, problem.getRPLMs().size()}},
+          {"landmark_prior", {&gnc.thresholds.landmark_prior, problem.getLandmarkPriors().size()}},
+          {"range", {&gnc.thresholds.range, problem.getRangeMeasurements().size()}}};
+      for (size_t at = 0; at < barc2.size();) {
+        const size_t end = std::min(barc2.find(',', at), barc2.size()), eq = barc2.find('=', at);
+        if (eq == std::string::npos || eq >= end) throw std::runtime_error("--barc2: expected kind=value, got '" + barc2.substr(at, end - at) + "'");
+        const std::string kind = barc2.substr(at, eq - at);
+        const double value = std::stod(barc2.substr(eq + 1, end - eq - 1));
+        bool known = false;
+        for (const auto &k : kinds)
+          if (kind == k.first) {
+            known = true;
+            k.second.first->assign(k.second.second, value);
+          }
+        if (!known) throw std::runtime_error("--barc2: unknown kind '" + kind + "'");
+        at = end + 1;
+      }
+      CORA::RobustInfo rinfo;
+      soln = CORA::solveRobustCORA(problem, x0, gnc, max_rank, /*verbose=*/true, &rinfo);
+      info = rinfo.last_solve;
+      const CORA::MeasurementWeights &w = rinfo.weights;
+      const std::pair<const char *, const std::vector<CORA::Scalar> *> out_kinds[] = {
+          {"rel_pose_rot", &w.rel_pose_rot}, {"rel_pose_trans", &w.rel_pose_trans}, {"pose_prior_rot", &w.pose_prior_rot},
+          {"pose_prior_trans", &w.pose_prior_trans}, {"pose_landmark", &w.pose_landmark}, {"landmark_prior", &w.landmark_prior},
+          {"range", &w.range}};
+      size_t below_half = 0, total = 0;
+      for (const auto &k : out_kinds)
+        for (const CORA::Scalar v : *k.second) {
+          ++total;
+          if (v < 0.5) ++below_half;
+        }
+      std::printf("robust solve (%s): %d rounds, %s, %zu of %zu weights below 1/2\n", robust.c_str(), rinfo.outer_iterations,
+                  rinfo.converged ? "converged" : "stopped at the cap", below_half, total);
+      if (!weights_out.empty()) {
+        std::ofstream csv(weights_out);
+        if (!csv) throw std::runtime_error("cannot write " + weights_out);
+        csv.precision(17);
+        for (const auto &k : out_kinds)
+          for (size_t i = 0; i < k.second->size(); ++i) csv << k.first << ',' << i << ',' << (*k.second)[i] << '\n';
+        std::cout << "wrote " << weights_out << " (" << total << " weights)" << std::endl;
+      }
+    }
     const auto t_solved = clk::now();
     const CORA::Matrix aligned = problem.alignEstimateToOrigin(soln.first.x);
     std::printf("final cost %.9g  |grad| %.3e  certified %d  theta %.3e  staircase levels %d  Hvps %ld  %.3f s\n",

@@ -498,6 +498,47 @@ int cora_debug_assemble_values_host(cora_ctx *ctx, const double *w, double *vals
 int cora_assembly_info(const cora_ctx *ctx, int64_t out[4]);
 int cora_assemble_times(const cora_ctx *ctx, double ms[5]);
 
+/* ---- The WEIGHT STEP of a robust-cost loop (graduated non-convexity) on the device -------------------------------------
+ * One pass over the measurement table at a point X: the UNWEIGHTED residual r2 of every slot, its ratio rho = r2 / barc2 to
+ * a threshold, the weight w(rho, mu) of the chosen cost, and the statistics a GNC schedule needs.  All vectors have the
+ * weight layout of cora_assemble_values -- n_w = 2 n_edges + n_ranges doubles, [rot of every edge | trans of every edge |
+ * range] -- so d_w_out is directly an argument of cora_assemble_values_dev and the loop never leaves the device.
+ *   r2     the value cora_measurement_residuals* returns for the slot when the table holds the BASE precisions (the ones
+ *          it held at cora_assembly_build): read from the term map, not from the table, whose kappa, tau and omega are
+ *          base * w after a re-weighting -- a weight of 0 could never be undone from those.  It does not depend on the
+ *          current weights, and has the bits of the residual kernels.  The rot slot of an edge without a rotation part is 0.
+ *   barc2  one threshold per slot: finite and > 0, or +inf = trusted (rho = 0, w = 1).
+ *   cost   CORA_GNC_NONE  w = 1, mu ignored (the statistics for mu_0)
+ *          CORA_GNC_TLS   w = 1 for rho <= mu / (mu + 1);  0 for rho >= (mu + 1) / mu;  else sqrt(mu (mu + 1) / rho) - mu
+ *          CORA_GNC_GM    t = mu / (rho + mu), w = t t
+ *          each operation one plain fp64 operation in the order written (no contraction); the middle band of TLS is
+ *          clamped to [0, 1], which rounding can leave by an ulp.
+ *   couple_edges != 0: an edge is ONE measurement, r2 = rot + trans (one addition), its threshold is the one of its TRANS
+ *          slot (the rot slots of barc2 are not read), and the same w goes to both slots.  Ranges are unaffected.
+ *   stats  12 host doubles [3][4] for the segments rot, trans, range: { sum of w r2, largest rho (0 for an empty segment),
+ *          number of 0 < w < 1, number of w < 0.5 }; counts are exact.  Coupled: an edge is counted and maximised in the
+ *          trans segment only, the rot segment carries only its sum.  May be NULL.
+ * cora_gnc_weights_dev  dX: a resident vector of k columns (1 <= k <= 24); d_barc2, d_w_out: n_w device doubles;
+ *          d_r2_out: NULL or n_w device doubles.  Synchronises.
+ * cora_gnc_weights      the host-pointer form (X: N x k column-major, uploaded first).
+ * cora_debug_gnc_weights_host  test hook: the same sequence of operations on the host (no GPU needed): r2 and w have the
+ *          device's bits; the statistics' sums are added in measurement order instead of per block.
+ * No atomics on the outputs: block partials in fixed slots, one block adds them (the maxima likewise), so two calls give
+ * the same bits, statistics included.
+ * ERRORS.  CORA_ERR_NOT_READY without a table or without a term map (cora_assembly_build).  CORA_ERR_SHAPE for k outside
+ * 1..24.  CORA_ERR_ARG: a null pointer, an unknown cost, mu not finite or <= 0 with a cost other than NONE, a threshold
+ * that is NaN or <= 0, a partitioned handle.  CORA_ERR_NAN: a residual that is not finite.  On an error the contents of
+ * the outputs are unspecified.
+ * STATE.  The call never changes the handle: the current point, the preconditioner, the values, the table and the
+ * staleness flags stay as they were. */
+enum { CORA_GNC_NONE = 0, CORA_GNC_TLS = 1, CORA_GNC_GM = 2 };
+int cora_gnc_weights_dev(cora_ctx *ctx, const double *dX, int k, const double *d_barc2, int cost, int couple_edges,
+                         double mu, double *d_w_out, double *d_r2_out, double stats[12]);
+int cora_gnc_weights(cora_ctx *ctx, const double *X, int ldx, int k, const double *barc2, int cost, int couple_edges,
+                     double mu, double *w_out, double *r2_out, double stats[12]);
+int cora_debug_gnc_weights_host(cora_ctx *ctx, const double *X, int ldx, int k, const double *barc2, int cost,
+                                int couple_edges, double mu, double *w_out, double *r2_out, double stats[12]);
+
 /* Timing helpers: HIP events on the handle's stream. */
 int cora_timer_start(cora_ctx *ctx);
 int cora_timer_stop_ms(cora_ctx *ctx, float *ms); /* synchronises */

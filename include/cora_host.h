@@ -121,6 +121,26 @@ int cora_problem_set_measurement_weights(cora_problem *p, const double *const we
  * the data matrix then holds the device's bits.  Without such a handle it is cora_problem_set_measurement_weights. */
 int cora_problem_reweight(cora_problem *p, const double *const weights[7], const int64_t lengths[7]);
 int cora_problem_get_measurement_weights(const cora_problem *p, double *const weights[7]);
+/* Problem::gncWeights (an extension beyond the reference; CORA/CORA_problem.h): one weight step of a robust-cost (GNC)
+ * loop on the device at Y (N x cols).  thresholds / lengths: barc2 per measurement in the seven arrays of
+ * cora_problem_set_measurement_weights (NULL or length 0: the kind is trusted, weight 1).  cost: 0 none, 1 truncated
+ * least squares, 2 Geman-McClure (cora_hip.h, CORA_GNC_*).  The residuals are UNWEIGHTED whatever the current weights.
+ * couple_edges != 0: a relative pose / pose prior is one measurement judged against its *_trans threshold.
+ * weights_out: every non-NULL array receives the count of its kind -- valid arguments of cora_problem_reweight.
+ * stats: 12 doubles [rot | trans | range] x { sum w r2, max rho, n_mid, n_out } (may be NULL).
+ * Needs a live, unpartitioned device handle (CORA_HOST_ERR otherwise). */
+int cora_problem_gnc_weights(cora_problem *p, const double *Y, int cols, const double *const thresholds[7],
+                             const int64_t lengths[7], int cost, double mu, int couple_edges, double *const weights_out[7],
+                             double stats[12]);
+/* solveRobustCORA (an extension beyond the reference; CORA/CORA.h): graduated non-convexity over solveCORA from x0
+ * (N x rank).  thresholds / lengths / cost (1 or 2) / couple_edges as above; mu_factor > 1; max_outer: cap on the rounds.
+ * x_out: N x d.  stats: as cora_problem_solve, of the last solve.  robust: [0] rounds, [1] 1 = converged (0: the cap),
+ * [2] number of weight steps recorded in the histories.  mu_hist / sum_wr2_hist: NULL or max_outer + 1 doubles each.
+ * The problem is left weighted with the final weights (cora_problem_get_measurement_weights). */
+int cora_problem_solve_robust(cora_problem *p, const double *x0, int max_rank, int verbose,
+                              const double *const thresholds[7], const int64_t lengths[7], int cost, int couple_edges,
+                              double mu_factor, int max_outer, double *x_out, double stats[11], double robust[3],
+                              double *mu_hist, double *sum_wr2_hist);
 
 /* Riemannian TNT (the call of src/CORA.cpp:139-140 with the parameters of :95-109) from x0
  * (N x rank).  opts (may be NULL): [0] max_iterations, [1] max_TPCG_iterations, [2] gradient
