@@ -248,6 +248,19 @@ class Context:
         self._chk(self.L.cora_debug_format_shape(self.h, out))
         return dict(zip(FORMAT_SHAPE_KEYS, [int(v) for v in out]))
 
+    def format_digest(self):
+        """Digest of the handle's whole format of Q: (integers and indices, bits of the doubles), two 64-bit FNV-1a
+        values (cora_debug_format_digest; no GPU needed)."""
+        out = (C.c_uint64 * 2)()
+        self._chk(self.L.cora_debug_format_digest(self.h, out))
+        return int(out[0]), int(out[1])
+
+    def value_map_digest(self):
+        """Digest of the handle's source map (values_map_build): (sources, mirror pairs); CoraError while there is none."""
+        out = (C.c_uint64 * 2)()
+        self._chk(self.L.cora_debug_value_map_digest(self.h, out))
+        return int(out[0]), int(out[1])
+
     def precond_entries(self):
         """Entries the installed preconditioner's solve plan stores (cora_precond_entries)."""
         s = (C.c_int64 * 6)()

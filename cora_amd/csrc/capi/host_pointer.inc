@@ -221,6 +221,19 @@ int cora_debug_format_spmm_host(const cora_ctx *c, const double *X, int ldx, int
   return CORA_OK;
 }
 
+int cora_debug_format_digest(const cora_ctx *c, uint64_t out[2]) {
+  if (!c || !out) return CORA_ERR_ARG;
+  format_digest(c->F, out);
+  return CORA_OK;
+}
+
+int cora_debug_value_map_digest(cora_ctx *c, uint64_t out[2]) {
+  if (!c || !out) return CORA_ERR_ARG;
+  if (!c->vmap.built) return fail(c, CORA_ERR_NOT_READY, "no source map yet: call cora_values_map_build or cora_update_values first");
+  value_map_digest(c->vmap, out);
+  return CORA_OK;
+}
+
 int cora_debug_factor_solve_host(int m, const int32_t *Lp, const int32_t *Li, const double *Lx, int k,
                                  const double *B, double *X, int64_t stats[4]) {
   if (m <= 0 || !Lp || !Li || !Lx || !B || !X || k <= 0) return CORA_ERR_ARG;

@@ -11,23 +11,15 @@ namespace cora {
 
 constexpr int kWave = 64;         // CDNA4 wavefront
 constexpr int kLongRow = 96;      // translation rows longer than this -> long path
-constexpr int kLongChunk = 1024;  // default nnz per long-row chunk (one wavefront each)
-extern int g_long_chunk;
-extern int g_interleave;            // pose-slice slot order (see format_build.cpp)
-constexpr int kSigma = 256;       // default sorting window (rows) for translation slices
-extern int g_sigma;               // tunable copy of kSigma (format_build.cpp)
-extern int g_chain_slices;        // pose slices in the chain layout (kSliceChainFlag, format_build.cpp); 0: plain layout
+constexpr int kLongChunk = 1024;  // nnz per long-row chunk (one wavefront each)
+constexpr int kSigma = 256;       // sorting window (rows) for translation slices
 constexpr int kMaxLD = 24;
 
 // Row stride (doubles) used for a k-column resident vector: the number of columns itself, whatever k (<= kMaxLD).  Odd
 // strides cost 8-byte instead of 16-byte row accesses but save the padding traffic (Hvp at p = 5 measured 24.45 ->
 // 23.28 us against a stride of 6); rounds 1-2 padded 13..24 columns to 16 / 20 / 24 -- the certificate block of rank
 // p >= 11 has max(10, p + 2) >= 13 columns (src/CORA_problem.cpp:1062-1063) and paid up to 23 % of padding.
-extern int g_pad_even;  // lab switch: 1 = round odd k up to even (format_build.cpp)
-inline int ld_for(int k) {
-  if (g_pad_even && k > 1) return (k + 1) & ~1;
-  return k < 2 ? 2 : k;
-}
+inline int ld_for(int k) { return k < 2 ? 2 : k; }
 
 enum SliceType : int32_t {
   kSliceStiefel = 0,   // lane = one pose (its d rotation rows); d x 1 column blocks
@@ -121,6 +113,7 @@ struct Layout {
   int64_t local_rows = 0;
 };
 
+// (A new member of HostFormat or Layout has to enter format_digest, format_build.cpp: the digest is what pins the format.)
 struct HostFormat {
   Layout L;
   std::vector<int32_t> api2int;   // N: internal row of API row
@@ -235,5 +228,12 @@ void slice_columns(const HostFormat &F, const SliceDesc &sd, std::vector<int32_t
 // Host execution of the FORMAT (test hook, see cora_debug_format_spmm_host).
 void format_spmm_host(const HostFormat &F, const double *X_int, int ld,
                       double *out_int);
+
+// Digests (test hooks, cora_debug_format_digest / cora_debug_value_map_digest): FNV-1a over 64-bit words, every array
+// preceded by its length.  format_digest: out[0] every integer of the format (Layout, counters, row maps, slice and chunk
+// descriptors, indices, work orders), out[1] the bits of every double.  value_map_digest: out[0] the sources, out[1] the
+// mirror pairs.  Equal digests: the kernels see the same format.
+void format_digest(const HostFormat &F, uint64_t out[2]);
+void value_map_digest(const ValueMap &M, uint64_t out[2]);
 
 }  // namespace cora

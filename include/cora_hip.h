@@ -801,6 +801,16 @@ int cora_debug_factor_plan_digest(int m, const int32_t *Lp, const int32_t *Li, c
  *   on both sides of a multiple of 64 pairs of their slice's tail (the wavefront gathers a tail 64 pairs at a time). */
 int cora_debug_format_shape(const cora_ctx *ctx, int64_t out[11]);
 
+/* Test hooks: digests of the handle's WHOLE format of Q and of its source map (cora_values_map_build), read from the host
+ * copies (no GPU needed; plan-only handles too).  FNV-1a over 64-bit words, every array preceded by its length.
+ * cora_debug_format_digest: out[0] over every integer -- the layout, the counters, the row maps, every slice and chunk
+ * descriptor, the column indices, both work orders --, out[1] over the bits of every double (slice and long-row values,
+ * head values, sym(Q_PP), the diagonal).  Equal digests: the kernels see the same format.
+ * cora_debug_value_map_digest: out[0] over the sources of the five value arrays, out[1] over the mirror pairs;
+ * CORA_ERR_NOT_READY while the handle has no map. */
+int cora_debug_format_digest(const cora_ctx *ctx, uint64_t out[2]);
+int cora_debug_value_map_digest(cora_ctx *ctx, uint64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif
