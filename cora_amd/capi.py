@@ -72,6 +72,29 @@ def factor_plan_digest(Lp, Li, Lx, group=None, aux_ok=True):
     return int(out[0]), int(out[1])
 
 
+def factor_image(Lp, Li, Lx, row_map=None, group=None, aux_ok=True, d=0, rot0=0, rot1=0, rows=0, zero_row=-1):
+    """What an install of a factor would upload, for a factor that is installed nowhere (cora_debug_factor_image; no GPU
+    needed): (digest, shape) -- the digest of plan + device image in upload order (integers, doubles) and the dict over
+    SHAPE_KEYS with io_runs and fuse_ok as an install decides them.  row_map: None (identity) or the internal row of every
+    variable; rows: rows of a vector (0: the factor's order); d, rot0, rot1: the rotation rows [rot0, rot1), d per pose."""
+    L = load()
+    Lp, Li, Lx = _csc_factor(Lp, Li, Lx)
+    m = len(Lp) - 1
+    opt = []
+    for v in (row_map, group):
+        a = None if v is None else np.ascontiguousarray(v, dtype=np.int32)
+        assert a is None or a.shape == (m,)
+        opt.append(a)
+    dig, shape = (C.c_uint64 * 2)(), (C.c_int64 * len(SHAPE_KEYS))()
+    rc = L.cora_debug_factor_image(m, Lp.ctypes.data_as(_ip), Li.ctypes.data_as(_ip), _d(Lx),
+                                   *[a.ctypes.data_as(_ip) if a is not None else None for a in opt], int(bool(aux_ok)),
+                                   C.c_int64(int(rows)), C.c_int32(int(zero_row)), int(d), C.c_int64(int(rot0)),
+                                   C.c_int64(int(rot1)), dig, shape)
+    if rc:
+        raise CoraError(rc, L.cora_last_error(None).decode())
+    return (int(dig[0]), int(dig[1])), dict(zip(SHAPE_KEYS, [int(v) for v in shape]))
+
+
 class CoraError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("%s: %s" % (STATUS.get(code, str(code)), msg))

@@ -55,6 +55,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "kernels.h"
 #include "p2p.h"
 #include "parallel.h"
+#include "trisolve_image.h"
 
 using namespace cora;
 
@@ -134,26 +135,52 @@ struct cora_ctx {
   // sparse Cholesky factors resident on the device (level-scheduled triangular solves):
   // the preconditioner's (Q + lambda I)[0:m] and, for the translation-implicit formulation,
   // the translation Laplacian Q33[0:nt-1]
-  struct DevStage {
-    RowOpDev fwd_a{}, fwd_b{}, bwd_a{}, bwd_b{};
-    BlockOpDev blocks{};
-    SubOpDev sub{};
-    bool has_fwd_a = false, has_bwd_a = false, dense = false, is_sub = false, aux_sum = false;
-  };
-  struct DevFactor {
-    TriPlan plan;  // host copy is dropped after upload (only the counts are kept)
-    std::vector<DevStage> stages;
-    // the plan's arrays live in a few large device chunks handed out front to back (60 arrays per factor: one hipMalloc
-    // / hipFree each cost more than the copies); a re-installed factor writes over the chunks of the one before
+  using DevStage = cora::DevStage;
+  // The device sink of walk_tri_image.  A factor's arrays live in a few large device chunks handed out front to back (60
+  // arrays per factor: one hipMalloc / hipFree each cost more than the copies); a re-installed factor writes over the
+  // chunks of the one before (rewind).  After a failed call `error` is set and put does nothing more.
+  struct DevArena {
     std::vector<void *> allocs;
     std::vector<size_t> chunk_bytes;
     size_t chunk_at = 0, chunk_used = 0;
+    hipError_t error = hipSuccess;
+    void rewind() {
+      chunk_at = 0;
+      chunk_used = 0;
+      error = hipSuccess;
+    }
+    void scalar(int64_t) {}
+    template <class T>
+    const T *put(const std::vector<T> &vec) {
+      if (error != hipSuccess) return nullptr;
+      const size_t bytes = (std::max<size_t>(vec.size(), 1) * sizeof(T) + 255) & ~static_cast<size_t>(255);
+      while (chunk_at < allocs.size() && chunk_used + bytes > chunk_bytes[chunk_at]) {
+        ++chunk_at;
+        chunk_used = 0;
+      }
+      if (chunk_at == allocs.size()) {
+        const size_t cb = std::max<size_t>(bytes, static_cast<size_t>(64) << 20);
+        void *q = nullptr;
+        if ((error = hipMalloc(&q, cb)) != hipSuccess) return nullptr;
+        allocs.push_back(q);
+        chunk_bytes.push_back(cb);
+        chunk_used = 0;
+      }
+      T *p = reinterpret_cast<T *>(static_cast<char *>(allocs[chunk_at]) + chunk_used);
+      chunk_used += bytes;
+      if (!vec.empty()) error = hipMemcpy(p, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice);  // (vec may be a temporary)
+      return p;
+    }
+  };
+  struct DevFactor {
+    std::vector<DevStage> stages;
+    DevArena arena;
     int aux_rows = 0;  // two-stage plans: rows appended to the work vector
     bool fuse_ok = false;  // substitution blocks whose tiles hold every pose's rotation rows at consecutive positions:
                            // the STPCG passes can be fused into the sweeps (SubFuse, kernels.h)
     bool ready = false;
-    int64_t entries[6] = {0, 0, 0, 0, 0, 0};  // cora_precond_entries (counted at install, before the host copy is dropped)
-    int64_t shape[kShapeFields] = {0};        // cora_debug_factor_shape (the same)
+    int64_t entries[6] = {0, 0, 0, 0, 0, 0};  // cora_precond_entries (counted at install, from the host plan)
+    int64_t shape[kShapeFields] = {0};        // cora_debug_factor_shape, cora_precond_stats (the same)
     unsigned long long generation = 0;  // counts installs: a captured STPCG graph carries the plan's arrays and sizes
   };
   DevFactor precond_f, implicit_f, aux_f;  // aux_f: the caller's own factor (cora_aux_set_cholesky)

@@ -191,7 +191,7 @@ void cora_ctx_destroy(cora_ctx *c) {
     for (auto &p : c->pool)
       if (p.first) (void)hipFree(p.first);
     for (auto *f : {&c->precond_f, &c->implicit_f, &c->aux_f})
-      for (void *p : f->allocs)
+      for (void *p : f->arena.allocs)
         if (p) (void)hipFree(p);
     for (int i = 0; i < 2; ++i) {
       if (c->h_pin[i]) (void)hipHostFree(c->h_pin[i]);
@@ -289,10 +289,10 @@ int cora_long_rows(const cora_ctx *c, int32_t *api_rows, int64_t *count) {
 int cora_precond_stats(const cora_ctx *c, int64_t s[4]) {
   if (!c || !s) return CORA_ERR_ARG;
   const auto &f = c->precond_f;
-  s[0] = f.ready ? static_cast<int64_t>(f.plan.stages.size()) : 0;
-  s[1] = f.ready ? f.plan.nnzW : 0;
-  s[2] = f.ready ? f.plan.nnzL : 0;
-  s[3] = f.ready && !f.plan.stages.empty() ? f.plan.stages.back().rows : 0;
+  s[0] = f.ready ? f.shape[kShapeStages] : 0;
+  s[1] = f.ready ? f.shape[kShapeNnzW] : 0;
+  s[2] = f.ready ? f.shape[kShapeNnzL] : 0;
+  s[3] = f.ready ? f.shape[kShapeTopRows] : 0;
   return CORA_OK;
 }
 

@@ -294,3 +294,32 @@ int cora_debug_factor_plan_digest(int m, const int32_t *Lp, const int32_t *Li, c
   }
   return CORA_OK;
 }
+
+int cora_debug_factor_image(int m, const int32_t *Lp, const int32_t *Li, const double *Lx, const int32_t *row_of,
+                            const int32_t *group, int aux_ok, int64_t rows, int32_t zero_row, int d, int64_t rot0, int64_t rot1,
+                            uint64_t digest[2], int64_t shape[24]) {
+  if (m <= 0 || !Lp || !Li || !Lx || !digest || !shape) return CORA_ERR_ARG;
+  if (rows <= 0) rows = m;
+  if (rows < m || rows > INT32_MAX || zero_row >= rows || rot0 < 0 || rot1 < rot0 || rot1 > rows ||
+      (rot1 > rot0 && (d <= 0 || (rot1 - rot0) % d != 0)))
+    return fail(nullptr, CORA_ERR_ARG, "cora_debug_factor_image: layout outside the vector");
+  try {
+    std::vector<int32_t> map(static_cast<size_t>(m));
+    for (int i = 0; i < m; ++i) {
+      map[i] = row_of ? row_of[i] : i;
+      if (map[i] < 0 || map[i] >= rows) return fail(nullptr, CORA_ERR_ARG, "cora_debug_factor_image: row map outside the vector");
+    }
+    std::vector<int32_t> g;
+    if (group) g.assign(group, group + m);
+    TriPlan P;
+    TriImage I;
+    PhaseTimer tick(false, "", 0, 0);
+    build_tri_plan(m, Lp, Li, Lx, map, zero_row, P, group ? &g : nullptr, aux_ok ? static_cast<int32_t>(rows) : -1);
+    build_tri_image(P, ImageLayout{d, rot0, rot1, rows, group != nullptr}, I, tick);
+    tri_image_digest(P, I, digest);
+    tri_image_shape(P, I, shape);
+  } catch (const std::exception &e) {
+    return fail(nullptr, CORA_ERR_ARG, e.what());
+  }
+  return CORA_OK;
+}

@@ -26,309 +26,71 @@ int cora_precond_setup(cora_ctx *c, int kind) {
   return fail(c, CORA_ERR_ARG, "unknown preconditioner kind");
 }
 
-// Builds the level schedule of a factor and uploads it.  row_of[i] = internal row of permuted variable i.
+// cora_precond_entries: counted from the plan as built (before the image appends the over-read tails to its arrays)
+static void plan_entries(const TriPlan &plan, int64_t e[6]) {
+  std::fill(e, e + 6, int64_t{0});
+  if (plan.stages.empty()) return;
+  const TriStage &top = plan.stages.back();
+  e[0] = static_cast<int64_t>(top.fwd_b.val.size());
+  e[1] = static_cast<int64_t>(top.bwd_b.val.size());
+  if (!plan.stages[0].sub) return;
+  const SubBlockOpHost &o = plan.stages[0].sub_op;
+  e[2] = static_cast<int64_t>(o.f_val.size());
+  e[3] = static_cast<int64_t>(o.b_val.size());
+  e[4] = static_cast<int64_t>(o.nrows.size());
+  e[5] = o.n_aux;
+}
+
+// Installs a host factor as a device solve plan: the plan (build_tri_plan), its device image (build_tri_image), both
+// uploaded through the factor's arena (walk_tri_image).  row_of[i] = internal row of permuted variable i.
 static int install_factor(cora_ctx *c, cora_ctx::DevFactor &f, int m, const int32_t *Lp, const int32_t *Li,
                           const double *Lx, const std::vector<int32_t> &row_of, int32_t zero_row,
                           const std::vector<int32_t> *group = nullptr) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   cora::PhaseTimer tick(cora::env_flag(cora::Env::TriTiming), "  [install]", 26, 3);
-  f.chunk_at = 0;
-  f.chunk_used = 0;
+  f.arena.rewind();
   f.stages.clear();
   f.ready = false;
   f.aux_rows = 0;
   f.fuse_ok = false;
+  const Layout &L = c->F.L;
+  TriPlan plan;
+  TriImage image;
   try {
-    build_tri_plan(m, Lp, Li, Lx, row_of, zero_row, f.plan, group, static_cast<int32_t>(c->F.L.rows));
+    build_tri_plan(m, Lp, Li, Lx, row_of, zero_row, plan, group, static_cast<int32_t>(L.rows));
+    tick("plan (host)");
+    plan_entries(plan, f.entries);
+    build_tri_image(plan, ImageLayout{L.d, L.rot_base, L.rot_base + static_cast<int64_t>(L.d) * L.nl_poses, L.rows, group != nullptr},
+                    image, tick);
   } catch (const std::exception &e) {
     return fail(c, CORA_ERR_ARG, e.what());
   }
-  tick("plan (host)");
-  tri_plan_shape(f.plan, f.shape);
-  auto up = [&](auto **dst, const auto &vec) -> hipError_t {
-    using T = typename std::remove_reference<decltype(vec)>::type::value_type;
-    const size_t bytes = (std::max<size_t>(vec.size(), 1) * sizeof(T) + 255) & ~static_cast<size_t>(255);
-    while (f.chunk_at < f.allocs.size() && f.chunk_used + bytes > f.chunk_bytes[f.chunk_at]) {
-      ++f.chunk_at;
-      f.chunk_used = 0;
-    }
-    if (f.chunk_at == f.allocs.size()) {
-      const size_t cb = std::max<size_t>(bytes, static_cast<size_t>(64) << 20);
-      void *q = nullptr;
-      const hipError_t e = hipMalloc(&q, cb);
-      if (e != hipSuccess) return e;
-      f.allocs.push_back(q);
-      f.chunk_bytes.push_back(cb);
-      f.chunk_used = 0;
-    }
-    T *p = reinterpret_cast<T *>(static_cast<char *>(f.allocs[f.chunk_at]) + f.chunk_used);
-    f.chunk_used += bytes;
-    *dst = p;
-    if (vec.empty()) return hipSuccess;
-    return hipMemcpy(p, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice);  // (vec may be a temporary)
-  };
-  auto up_op = [&](RowOpDev &D, RowOpHost &H) -> hipError_t {
-    hipError_t e;
-    D.n8 = H.n8;
-    D.n64 = H.n64;
-    D.nlong = static_cast<int>(H.long_out.size());
-    D.nchunks = static_cast<int>(H.chunk_begin.size());
-    if ((e = up(&D.out_row, H.out_row)) != hipSuccess) return e;
-    if ((e = up(&D.begin, H.begin)) != hipSuccess) return e;
-    if ((e = up(&D.end, H.end)) != hipSuccess) return e;
-    if ((e = up(&D.long_out, H.long_out)) != hipSuccess) return e;
-    if ((e = up(&D.long_chunk_ptr, H.long_chunk_ptr)) != hipSuccess) return e;
-    if ((e = up(&D.chunk_begin, H.chunk_begin)) != hipSuccess) return e;
-    if ((e = up(&D.chunk_end, H.chunk_end)) != hipSuccess) return e;
-    if ((e = up(&D.col, H.col)) != hipSuccess) return e;
-    if ((e = up(&D.val, H.val)) != hipSuccess) return e;
-    std::vector<int32_t> chunk_row(static_cast<size_t>(D.nchunks), 0);
-    for (int r = 0; r < D.nlong; ++r)
-      for (int32_t ch = H.long_chunk_ptr[r]; ch < H.long_chunk_ptr[r + 1]; ++ch) chunk_row[ch] = r;
-    if ((e = up(&D.chunk_row, chunk_row)) != hipSuccess) return e;
-    const std::vector<unsigned> tick(static_cast<size_t>(std::max(D.nlong, 1)), 0u);
-    const unsigned *tp = nullptr;
-    if ((e = up(&tp, tick)) != hipSuccess) return e;
-    D.tickets = const_cast<unsigned *>(tp);
-    const std::vector<double> part(static_cast<size_t>(std::max(D.nchunks, 1)) * kMaxLD, 0.0);
-    const double *pp = nullptr;
-    if ((e = up(&pp, part)) != hipSuccess) return e;
-    D.partial = const_cast<double *>(pp);
-    H = RowOpHost();  // the host copy is not needed any more
-    return hipSuccess;
-  };
-  const size_t K = f.plan.stages.size();
-  f.stages.resize(K);
-  std::shared_ptr<SubBlockOpHost> dead_sub;
-  for (int64_t &e : f.entries) e = 0;
-  if (K > 0) {
-    const TriStage &top = f.plan.stages.back();
-    f.entries[0] = static_cast<int64_t>(top.fwd_b.val.size());
-    f.entries[1] = static_cast<int64_t>(top.bwd_b.val.size());
-    if (f.plan.stages[0].sub) {
-      const SubBlockOpHost &o = f.plan.stages[0].sub_op;
-      f.entries[2] = static_cast<int64_t>(o.f_val.size());
-      f.entries[3] = static_cast<int64_t>(o.b_val.size());
-      f.entries[4] = static_cast<int64_t>(o.nrows.size());
-      f.entries[5] = o.n_aux;
-    }
-  }
-  for (size_t k = 0; k < K; ++k) {
-    TriStage &S = f.plan.stages[k];
+  tri_image_shape(plan, image, f.shape);
+  walk_tri_image(f.arena, plan, image, f.stages);
+  HIP_TRY(c, f.arena.error);
+  for (size_t k = 0; k < f.stages.size(); ++k) {
+    const StageImage &I = image.stages[k];
     cora_ctx::DevStage &D = f.stages[k];
-    D.has_fwd_a = k > 0;
-    D.has_bwd_a = k + 1 < K;
-    D.dense = S.dense;
-    if (S.sub) {
-      SubBlockOpHost &H = S.sub_op;
-      D.is_sub = true;
-      std::vector<SubDesc> desc(H.nrows.size());
-      for (size_t b = 0; b < desc.size(); ++b) {
-        SubDesc &d = desc[b];
-        d.row_begin = H.row_begin[b];
-        d.nrows = H.nrows[b];
-        d.f_ent_begin = H.f_ent_begin[b];
-        d.f_nent = H.f_nent[b];
-        d.b_ent_begin = H.b_ent_begin[b];
-        d.b_nent = H.b_nent[b];
-        d.f_lev_begin = H.f_lev_begin[b];
-        d.f_nlev = (H.f_lev_begin[b + 1] - H.f_lev_begin[b]) / 4 - 1;  // barrier levels: one header per wavefront (4) each, + the closing one
-        d.b_lev_begin = H.b_lev_begin[b];
-        d.b_nlev = (H.b_lev_begin[b + 1] - H.b_lev_begin[b]) / 4 - 1;
-        d.tgt_begin = H.tgt_begin[b];
-        d.ntgt = H.tgt_begin[b + 1] - H.tgt_begin[b];
-      }
-      SubOpDev &Q = D.sub;
-      Q.nblocks = static_cast<int>(desc.size());
-      Q.ntop = static_cast<int>(f.plan.top_rows.size());
-      Q.max_rows = H.max_rows;
-      Q.max_ent = H.max_ent;
-      Q.max_lev = H.max_lev;
-      Q.max_level_lanes = H.max_level_lanes;
-      Q.max_npl = H.max_npl;
-      Q.aux_base = f.plan.aux_base;
-      HIP_TRY(c, up(&Q.fwd.rows, H.rows));
-      H.f_hdr.resize(H.f_hdr.size() + 8, 0);  // the kernel reads one header ahead
-      H.f_idx.resize(H.f_idx.size() + 8, 0);  // ... and an entry past a block without entries
-      H.f_val.resize(H.f_val.size() + 8, 0.0);
-      H.b_idx.resize(H.b_idx.size() + 8, 0);
-      H.b_val.resize(H.b_val.size() + 8, 0.0);
-      H.b_hdr.resize(H.b_hdr.size() + 8, 0);
-      HIP_TRY(c, up(&Q.fwd.hdr, H.f_hdr));
-      HIP_TRY(c, up(&Q.fwd.idx, H.f_idx));
-      HIP_TRY(c, up(&Q.fwd.val, H.f_val));
-      HIP_TRY(c, up(&Q.bwd.rows, H.b_rows));
-      HIP_TRY(c, up(&Q.bwd.hdr, H.b_hdr));
-      HIP_TRY(c, up(&Q.bwd.idx, H.b_idx));
-      HIP_TRY(c, up(&Q.bwd.val, H.b_val));
-      HIP_TRY(c, up(&Q.tgt_row, H.tgt_row));
-      HIP_TRY(c, up(&Q.tgt_slot, H.tgt_slot));
-      HIP_TRY(c, up(&Q.c_ptr, H.c_ptr));
-      HIP_TRY(c, up(&Q.c_idx, H.c_idx));
-      HIP_TRY(c, up(&Q.c_val, H.c_val));
-      HIP_TRY(c, up(&Q.top_rows, f.plan.top_rows));
-      f.aux_rows = H.n_aux;
-      tick("  sub: desc + arrays");
-      {
-        // memory-order I/O lists of both sweeps: {internal row, tile position} of every block row, sorted by row
-        auto io_of = [&](const std::vector<int32_t> &rows) {
-          std::vector<int2> io(rows.size() + 1);  // (+ 1: a block without rows still forms an address)
-          const size_t nblk = desc.size();
-          const unsigned nth = nblk < 64 ? 1u : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-          auto part = [&](unsigned t) {  // blocks are independent: a range of them per thread
-            std::vector<int32_t> ord;
-            for (size_t b = nblk * t / nth; b < nblk * (t + 1) / nth; ++b) {
-              const int32_t r0 = desc[b].row_begin, nb = desc[b].nrows;
-              ord.resize(static_cast<size_t>(nb));
-              for (int k = 0; k < nb; ++k) ord[k] = k;
-              std::sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return rows[r0 + x] < rows[r0 + y]; });
-              for (int k = 0; k < nb; ++k) io[static_cast<size_t>(r0) + k] = make_int2(rows[r0 + ord[k]], ord[k]);
-            }
-          };
-          cora::parallel_parts(nth, part);
-          io.back() = make_int2(0, 0);
-          return io;
-        };
-        // (the rows of a block in memory order are the same set for both sweeps: the runs are found once, from the
-        // forward list; only the tile positions differ)
-        {
-          const std::vector<int2> iof = io_of(H.rows), iob = io_of(H.b_rows);
-          bool runs_ok = !cora::env_flag(cora::Env::SubIoLists);  // (lab switch: the 8-byte index lists)
-          std::vector<uint16_t> tpf(iof.size() + 8, 0), tpb(iob.size() + 8, 0);
-          for (size_t b = 0; b < desc.size(); ++b) {
-            SubDesc &d = desc[b];
-            const int32_t r0 = d.row_begin, nb = d.nrows;
-            int nr = 0;
-            for (int q = 0; q < kSubMaxRuns; ++q) { d.run_off[q] = 0; d.run_end[q] = INT32_MAX; }
-            for (int k = 0; k < nb; ++k) {
-              const int2 a = iof[static_cast<size_t>(r0) + k], bb = iob[static_cast<size_t>(r0) + k];
-              if (a.x != bb.x || a.y > 0xffff || bb.y > 0xffff) runs_ok = false;
-              tpf[static_cast<size_t>(r0) + k] = static_cast<uint16_t>(a.y);
-              tpb[static_cast<size_t>(r0) + k] = static_cast<uint16_t>(bb.y);
-              if (k == 0 || a.x != iof[static_cast<size_t>(r0) + k - 1].x + 1) {  // a new run starts at k
-                if (nr > 0 && nr <= kSubMaxRuns) d.run_end[nr - 1] = k;
-                if (nr < kSubMaxRuns) d.run_off[nr] = a.x - k;
-                ++nr;
-              }
-            }
-            if (nr > kSubMaxRuns) runs_ok = false;
-          }
-          Q.io_runs = runs_ok ? 1 : 0;
-          f.shape[kShapeIoRuns] = Q.io_runs;
-          HIP_TRY(c, up(&Q.fwd.io, iof));
-          HIP_TRY(c, up(&Q.bwd.io, iob));
-          HIP_TRY(c, up(&Q.fwd.tpos, tpf));
-          HIP_TRY(c, up(&Q.bwd.tpos, tpb));
-        }
-        tick("  sub: io lists");
-        // fused projection in the backward sweep: the first rotation row of a pose finds the others right behind it
-        // in the tile, and a pose of the last stage has all its rows there.  Row units of a block: {tile position, row}
-        const Layout &L = c->F.L;
-        const int64_t rot0 = L.rot_base, rot1 = L.rot_base + static_cast<int64_t>(L.d) * L.nl_poses;
-        bool ok = group != nullptr;  // (a shard's rows are rotations | ranges | translations in this order too: the same tests on the row index)
-        std::vector<int2> units;
-        for (size_t b = 0; b < desc.size(); ++b) {
-          const int32_t *rows = H.b_rows.data() + desc[b].row_begin;
-          const int nb = desc[b].nrows;
-          int64_t leaders = 0, rot_rows = 0;
-          desc[b].unit_begin = static_cast<int32_t>(units.size());
-          for (int k = 0; k < nb; ++k) {
-            if (rows[k] < rot0 || rows[k] >= rot1) {
-              units.push_back(make_int2(k, rows[k]));
-              continue;
-            }
-            ++rot_rows;
-            if ((rows[k] - rot0) % L.d != 0) continue;
-            ++leaders;
-            units.push_back(make_int2(k, rows[k]));
-            for (int a = 1; a < L.d && ok; ++a) ok = k + a < nb && rows[k + a] == rows[k] + a;
-          }
-          desc[b].nunits = static_cast<int32_t>(units.size()) - desc[b].unit_begin;
-          ok = ok && rot_rows == leaders * L.d;
-        }
-        units.push_back(make_int2(0, 0));
-        HIP_TRY(c, up(&Q.b_unit, units));
-        if (ok) {
-          std::vector<char> in_top(static_cast<size_t>(L.rows), 0);
-          for (int32_t r : f.plan.top_rows) in_top[r] = 1;
-          for (int32_t r : f.plan.top_rows)
-            if (r >= rot0 && r < rot1) {
-              const int64_t lead = r - (r - rot0) % L.d;
-              for (int a = 0; a < L.d && ok; ++a) ok = in_top[lead + a] != 0;
-            }
-        }
-        f.fuse_ok = ok;
-        if (tick.on()) std::fprintf(stderr, "  [tri plan] sweep fusion possible: %d\n", int(ok));
-      }
-      HIP_TRY(c, up(&Q.desc, desc));
-      tick("  sub: units");
-      // the host copy is not needed any more: 130 MB of vectors, 16 ms to hand back at 10^5 poses and 0.1 s at 10^6 -- on
-      // a thread of its own (joined before the next factor is installed and when the handle goes), started AFTER the
-      // last stage's uploads: a thread that unmaps 130 MB holds the address space's lock, and the next copy from pageable
-      // memory waited 12 ms for it (measured: a 2.3 MB copy, 0.0122 s)
-      dead_sub = std::make_shared<SubBlockOpHost>(std::move(H));
-      H = SubBlockOpHost();
-      continue;
-    }
-    if (k == 1 && f.stages[0].is_sub) {  // the last stage of a two-stage plan: only its two explicit-inverse products
-      D.aux_sum = !S.fwd_a.empty();      // (+ the sum of the aux rows as a product of its own on large plans)
-      if (D.aux_sum) HIP_TRY(c, up_op(D.fwd_a, S.fwd_a));
-      HIP_TRY(c, up_op(D.fwd_b, S.fwd_b));
-      tick("  top: forward product");
-      HIP_TRY(c, up_op(D.bwd_b, S.bwd_b));
-      tick("  top: backward product");
-      continue;
-    }
-    if (D.has_fwd_a) HIP_TRY(c, up_op(D.fwd_a, S.fwd_a));
-    if (S.dense) {
-      BlockOpHost &H = S.blocks_op;
-      D.blocks.nblocks = static_cast<int>(H.nrows.size());
-      {
-        // per-row records, padded per block to a multiple of eight (empty masks) + one spare round at the end; the
-        // value arrays get 64 * 65 zero entries: the kernel's prefetch of the next round reads past a block's end
-        std::vector<BlockDesc> desc(H.nrows.size());
-        std::vector<BlockLane> bc, br;
-        for (size_t b = 0; b < desc.size(); ++b) {
-          desc[b] = BlockDesc{H.row_begin[b], H.nrows[b], static_cast<int32_t>(bc.size()), 0, H.w_off[b], 0};
-          for (int l = 0; l < H.nrows[b]; ++l) {
-            const size_t i = static_cast<size_t>(H.row_begin[b]) + l;
-            bc.push_back(BlockLane{H.mask_col[i], H.off_col[i], H.rows[i]});
-            br.push_back(BlockLane{H.mask_row[i], H.off_row[i], H.rows[i]});
-          }
-          while (bc.size() % 8) {
-            bc.push_back(BlockLane{0, 0, 0});
-            br.push_back(BlockLane{0, 0, 0});
-          }
-        }
-        bc.resize(bc.size() + 24, BlockLane{0, 0, 0});
-        br.resize(br.size() + 24, BlockLane{0, 0, 0});
-        H.w_by_col.resize(H.w_by_col.size() + 64 * 65, 0.0);
-        H.w_by_row.resize(H.w_by_row.size() + 64 * 65, 0.0);
-        HIP_TRY(c, up(&D.blocks.desc, desc));
-        HIP_TRY(c, up(&D.blocks.by_col, bc));
-        HIP_TRY(c, up(&D.blocks.by_row, br));
-      }
-      HIP_TRY(c, up(&D.blocks.w_by_col, H.w_by_col));
-      HIP_TRY(c, up(&D.blocks.w_by_row, H.w_by_row));
-      HIP_TRY(c, up(&D.blocks.ext_ptr, H.ext_ptr));
-      HIP_TRY(c, up(&D.blocks.ext_col, H.ext_col));
-      HIP_TRY(c, up(&D.blocks.ext_val, H.ext_val));
-      H = BlockOpHost();
-      continue;
-    }
-    HIP_TRY(c, up_op(D.fwd_b, S.fwd_b));
-    if (D.has_bwd_a) HIP_TRY(c, up_op(D.bwd_a, S.bwd_a));
-    HIP_TRY(c, up_op(D.bwd_b, S.bwd_b));
+    D.has_fwd_a = I.has_fwd_a, D.has_bwd_a = I.has_bwd_a, D.dense = I.dense, D.is_sub = I.is_sub, D.aux_sum = I.aux_sum;
   }
-  if (dead_sub) {
-    if (c->deferred_free.valid()) c->deferred_free.get();
-    c->deferred_free = std::async(std::launch::async, [dead = std::move(dead_sub)]() mutable { dead.reset(); });
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  f.aux_rows = image.aux_rows;
+  f.fuse_ok = image.fuse_ok;
   tick("upload");
+  if (!plan.stages.empty() && plan.stages[0].sub) {
+    // the substitution arrays are not needed any more: 130 MB of vectors, 16 ms to hand back at 10^5 poses and 0.1 s at
+    // 10^6 -- on a thread of its own (joined before the next factor is installed and when the handle goes), started AFTER
+    // the last stage's uploads: a thread that unmaps 130 MB holds the address space's lock, and the next copy from
+    // pageable memory waited 12 ms for it (measured: a 2.3 MB copy, 0.0122 s)
+    auto dead = std::make_shared<SubBlockOpHost>(std::move(plan.stages[0].sub_op));
+    if (c->deferred_free.valid()) c->deferred_free.get();
+    c->deferred_free = std::async(std::launch::async, [dead = std::move(dead)]() mutable { dead.reset(); });
+  }
+  image = TriImage();  // (the rest of the host copy goes here, inside the install's reported time)
+  plan = TriPlan();
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  tick("host copy dropped");
   f.ready = true;
   ++f.generation;
-  f.shape[kShapeFuseOk] = f.fuse_ok ? 1 : 0;
   f.shape[kShapeGeneration] = static_cast<int64_t>(f.generation);
   return CORA_OK;
 }

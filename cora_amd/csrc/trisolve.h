@@ -143,8 +143,10 @@ void build_tri_plan(int m, const int32_t *Lp, const int32_t *Li, const double *L
 void tri_plan_solve_host(const TriPlan &plan, int64_t rows, const double *rhs, double *out);
 
 // Test hook: the shape of a plan in numbers (cora_debug_factor_shape / cora_debug_factor_plan_host, include/cora_hip.h
-// lists the fields).  Taken while the host arrays still exist: install_factor drops them after the upload.  The fields
-// only a device install knows (kShapeIoRuns, kShapeFuseOk, kShapeGeneration) are left at -1.
+// lists the fields).  Taken while the host arrays still exist: install_factor drops them after the upload.  Two fields
+// are decided by the device image of the plan, not by the plan (kShapeIoRuns, kShapeFuseOk: tri_image_shape,
+// trisolve_image.h, fills them in -- the shape of an install is that one) and one by the handle (kShapeGeneration): they
+// are left at -1 here.
 constexpr int kShapeFields = 24;
 enum TriShapeField : int {
   kShapeStages = 0, kShapeForm, kShapeBlocks, kShapeBlockRows, kShapeMaxRows, kShapeMaxLev, kShapeMaxLevelLanes, kShapeMaxNpl,
@@ -158,7 +160,8 @@ inline int64_t sub_lds_bytes(int64_t max_rows, int64_t max_lev, int tile_stride)
 void tri_plan_shape(const TriPlan &plan, int64_t out[kShapeFields]);
 
 // Test hook: a digest of everything a plan holds (cora_debug_factor_plan_digest) -- out[0] over its integers, booleans,
-// indices and headers, out[1] over the bits of its doubles.  Two plans with the same digest are the same input to every kernel.
+// indices and headers, out[1] over the bits of its doubles.  Two plans with the same digest are the same plan; what the
+// kernels read is the plan and its device image, and tri_image_digest (trisolve_image.h) is the digest of that.
 void tri_plan_digest(const TriPlan &plan, uint64_t out[2]);
 
 }  // namespace cora

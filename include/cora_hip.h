@@ -792,6 +792,19 @@ int cora_debug_factor_plan_host(int m, const int32_t *Lp, const int32_t *Li, con
 int cora_debug_factor_plan_digest(int m, const int32_t *Lp, const int32_t *Li, const double *Lx, const int32_t *group,
                                   int aux_ok, uint64_t out[2]);
 
+/* Test hook: what an INSTALL of a factor uploads, for a factor that is installed nowhere (no GPU needed): the solve plan
+ * as above plus its device image (cora_amd/csrc/trisolve_image.h: block descriptors, I/O lists, tile positions, run tables,
+ * row units, packed block lanes, chunk rows, over-read tails), walked in upload order.  row_of: NULL (variable i lives in
+ * row i) or m internal rows; group as above; rows: rows of a vector (0: m) -- the aux rows of a substitution plan start
+ * there; zero_row: the pinned row or -1; d, [rot0, rot1): the rows that are the d rotation rows of a pose each (the fused
+ * projection's row units; rot0 == rot1: none).  digest: FNV-1a, per array its element size, its length and its bytes --
+ * [0] integers, indices, descriptors and the scalar members of the kernels' argument blocks, [1] the bits of the doubles.
+ * shape: the 24 fields of cora_debug_factor_shape, [8] and [9] as an install decides them, [23] = -1.  An install with the
+ * same factor, rows, groups and layout reports the same shape and uploads arrays with this digest. */
+int cora_debug_factor_image(int m, const int32_t *Lp, const int32_t *Li, const double *Lx, const int32_t *row_of,
+                            const int32_t *group, int aux_ok, int64_t rows, int32_t zero_row, int d, int64_t rot0, int64_t rot1,
+                            uint64_t digest[2], int64_t shape[24]);
+
 /* Test hook: the shape of the handle's format of Q in numbers, read from the host copy of the format (no GPU needed; no
  * kernel and no dispatch depends on it) -- what a test asserts before it claims to have reached a path:
  *   pose slices [0] in the chain layout, [1] in the plain layout | over the chain slices: [2] most general slots of a

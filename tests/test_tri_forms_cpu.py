@@ -3,7 +3,9 @@ and the plans solve their systems -- without a GPU: every case of tests/tri_form
 process per environment set (the sets of tests/test_gpu_tri_forms.py: the switches that decide a plan's form are read
 once, when the library loads).  Per case
   - the host probe (cora_debug_factor_plan_host) reports the intended form: stages, kind of stage-0 blocks, where the aux
-    sums go, tile size, row classes, chunks per row -- a fixture that drifts to another form fails here;
+    sums go, tile size, row classes, chunks per row -- a fixture that drifts to another form fails here; and the device
+    image of the plan under the case's row map, groups and layout (cora_debug_factor_image, on a plan-only handle) takes
+    the decisions the case names: row I/O from run tables or index lists (io_runs), the projection in the sweeps (fuse_ok);
   - the plan's products executed on the host (cora_debug_factor_solve_host) meet the bound of the GPU test: 1e-11 for
     complete factors, 1e-10 for the incomplete one, 1e-8 for the regularised Q + lambda I (tests/test_trisolve_cpu.py,
     tests/test_gpu_stpcg_forms.py), relative to the reference's largest entry;
@@ -60,7 +62,8 @@ def test_fixture_takes_its_form_and_the_plan_solves_it(which, cid):
 def test_every_form_is_among_the_cases():
     """Over all sets: one inverse, substitution blocks with the aux sums folded and as their own product, dense blocks
     in 2 and in 3 stages, substitution blocks on a structure that is no chain, an incomplete factor, a product with all
-    three row classes, a row of more than 64 chunks, a tile above 64 KB -- and 8 entries per lane in a level."""
+    three row classes, a row of more than 64 chunks, a tile above 64 KB, 8 entries per lane in a level -- and both
+    answers of either decision of the device image."""
     shapes = {(s, cid): _child(s)[cid] for s, cid in CASES if not cid.startswith(("proj-", "stpcg-"))}
     sh = {k: c["shape"] for k, c in shapes.items()}
     fx = {k: c["fixture"] for k, c in shapes.items()}
@@ -79,3 +82,6 @@ def test_every_form_is_among_the_cases():
     assert some(lambda s, f: s["max_chunks"] > 64)
     assert some(lambda s, f: s["form"] == W.SUB and s["lds24"] > W.TILE_LIMIT and s["max_rows"] >= 342)
     assert some(lambda s, f: s["form"] == W.SUB and s["max_npl"] == 8)
+    for key in W.IMAGE_KEYS:
+        for answer in (0, 1):
+            assert some(lambda s, f: s["form"] == W.SUB and s[key] == answer), (key, answer)

@@ -4,7 +4,8 @@ plan and on factors of arbitrary structure, as a PROCESS of its own: python test
 A process per ENVIRONMENT SET, because the switches that decide a plan's form and its row classes are read once, when
 the library loads; the switches read per call (CORA_TRI_SUB, CORA_TRI_UNFOLD_MIN, CORA_SUB_IO_LISTS) are flipped around
 single installs.  The child prints one line `CASE {json}` per case -- its id, the plan's shape as the probe reports it
-(cora_debug_factor_shape on the handle; `host`: cora_debug_factor_plan_host), discrete mismatches (`fail`) and the worst
+(cora_debug_factor_shape on the handle; `host`: cora_debug_factor_image for the same factor, row map, groups and layout on
+a plan-only handle -- and on the device the two must agree in every field but the install count), discrete mismatches (`fail`) and the worst
 deviations (`checks`: [name, value, kind]; the bound of each kind lives in BOUND below) -- and ends with `DONE`.  Any error
 of the library that a case does not expect is an exception nothing catches: the exit status is non-zero.
 
@@ -92,7 +93,8 @@ AUX_CASES = {
          dict(form=DENSE, stages=2, blocks=(50, None), mixed_products=(3, None), max_chunks=(33, None))),
     ],
 }
-HOST_KEYS = ("io_runs", "fuse_ok", "generation")   # what only an install on a device knows
+HOST_KEYS = ("generation",)   # what only an install on a device knows
+IMAGE_KEYS = ("io_runs", "fuse_ok")   # what the device image of a plan decides (cora_debug_factor_image), not the plan
 
 
 def case_ids(which):
@@ -189,16 +191,40 @@ def host_solve(L, B, env):
 _handles = {}
 
 
-def handle(N):
-    """A device handle whose vectors have N rows (d = 2: N = 3 n + l + r with l = 3), one per N and process."""
+def handle(N, device=True):
+    """A handle whose vectors have N rows (d = 2: N = 3 n + l + r with l = 3), one per N and process; on the device, or
+    plan-only (the same format and row order, no GPU)."""
     if N not in _handles:
         from cora_amd import capi
         from synth import make_problem
         n = N // 4
         A, Q, dm = make_problem(d=2, n=n, n_landmarks=3, n_ranges=N - 3 * n - 3, n_loops=3, seed=N)
         assert dm.N == N
-        _handles[N] = capi.Context(dm.d, dm.n, dm.r, dm.n_trans, Q.rowptr, Q.col, Q.val)
+        _handles[N] = capi.Context(dm.d, dm.n, dm.r, dm.n_trans, Q.rowptr, Q.col, Q.val, device=0 if device else -1)
     return _handles[N]
+
+
+def image_shape(h, L, perm, env, grouped=False):
+    """The shape cora_debug_factor_image gives an install of L on h under perm (API rows, new -> old): the handle's row
+    map, its rotation rows and vector length; grouped: the groups cora_precond_set_cholesky forms (a pose's rotation
+    rows), and the pinned row where the factor leaves one out."""
+    from cora_amd import capi
+    rm, dn = h.row_map(), h.d * h.n
+    rot0 = int(rm[:dn].min())
+    assert np.array_equal(rm[:dn], rot0 + np.arange(dn)), "rotation rows are not one run of the internal order"
+    left = np.setdiff1d(np.arange(h.N), perm)
+    assert len(left) <= 1
+    with switches(env):
+        return capi.factor_image(L.indptr, L.indices, L.data, row_map=rm[perm], group=np.where(perm < dn, perm // h.d, -1) if grouped else None,
+                                 d=h.d, rot0=rot0, rot1=rot0 + dn, rows=h.rows, zero_row=int(rm[left[0]]) if len(left) else -1)[1]
+
+
+def expect_image(C, shape, img):
+    """an install reports what the image hook derives without a device"""
+    from cora_amd import capi
+    for key in capi.SHAPE_KEYS:
+        if key not in HOST_KEYS:
+            C.expect("installed plan %s against cora_debug_factor_image" % key, shape[key], img[key])
 
 
 def permutation(h, fx, how):
@@ -270,11 +296,16 @@ def aux_case(spec, device, state):
     Xhost = host_solve(L, B, env)
     C.add("host", rel(Xhost, X), kind)
     C.add("reference", rel(fx["ref"].plain(B), X), "spread-" + kind)
-    if not device:
-        C.shape(hp, {k: v for k, v in want.items() if k not in HOST_KEYS})
-        return dict(shape=hp, fixture=name, **C.out())
-    h = handle(fx["n"])
+    h = handle(fx["n"], device)
     perm = permutation(h, fx, how)
+    img = image_shape(h, L, perm, env)
+    if not device:
+        C.shape(hp, {k: v for k, v in want.items() if k not in HOST_KEYS + IMAGE_KEYS})
+        C.shape(img, {k: v for k, v in want.items() if k not in HOST_KEYS})
+        for key in capi.SHAPE_KEYS:   # the image's plan is the plan the host probe builds
+            if key not in HOST_KEYS + IMAGE_KEYS:
+                C.expect("image plan %s against the host probe" % key, img[key], hp[key])
+        return dict(shape=img, fixture=name, **C.out())
     before = state.get(fx["n"], 0)
     with switches(env):
         h.aux_set_cholesky(L.indptr, L.indices, L.data, perm)
@@ -282,8 +313,9 @@ def aux_case(spec, device, state):
     state[fx["n"]] = shape["generation"]
     C.shape(shape, want)
     C.expect("installs on the handle", shape["generation"], before + 1)
+    expect_image(C, shape, img)
     for key in capi.SHAPE_KEYS:   # the device's plan is the plan the host probe builds
-        if key not in HOST_KEYS:
+        if key not in HOST_KEYS + IMAGE_KEYS:
             C.expect("device plan %s against the host probe" % key, shape[key], hp[key])
     if not C.fail:   # (a plan of another form would be compared under the wrong name)
         vec = Vectors(h)
@@ -309,6 +341,7 @@ def reinstall_case(device, state):
         with switches(env):
             h.aux_set_cholesky(fx["L"].indptr, fx["L"].indices, fx["L"].data, perm)
         shape = h.factor_shape(capi.FACTOR_AUX)
+        expect_image(C, shape, image_shape(h, fx["L"], perm, env))
         C.expect("form after installing %s" % fx["name"], shape["form"], form)
         C.expect("nnz(L) after installing %s" % fx["name"], shape["nnzL"], fx["L"].nnz)
         C.expect("installs", shape["generation"], state[2600] + 1)
@@ -442,9 +475,7 @@ def precond_cases(device):
     forms = (("sub", False, {}, dict(form=SUB, stages=2, blocks=(3, None), zero_row=(0, None))),
              ("sub-split", True, {}, dict(form=SUB, stages=2, blocks=(3, None), fuse_ok=0)),
              ("dense", False, SUB0, dict(form=DENSE, stages=2, blocks=(10, None), fuse_ok=0)))
-    h = None
-    if device:
-        h = capi.Context(dm.d, dm.n, dm.r, dm.n_trans, R.Q.rowptr, R.Q.col, R.Q.val)
+    h = capi.Context(dm.d, dm.n, dm.r, dm.n_trans, R.Q.rowptr, R.Q.col, R.Q.val, device=0 if device else -1)
     rng = np.random.default_rng(5)
     points = {p: orc.project_manifold(dm, rng.uniform(-1, 1, (N, p))) for p in PROJ_RANKS}
     for name, split, env, want in forms:
@@ -457,21 +488,25 @@ def precond_cases(device):
         xh[perm] = host_solve(L, V[perm], env)
         C.add("host", rel(xh, want_x), "reg")
         C.add("reference", rel(R.chol_plain.full_solve(V), want_x), "spread-reg")
-        shape = hp
+        shape = img = image_shape(h, L, perm, env, grouped=True)
+        if name == "sub":
+            C.expect("the sweeps can take the projection", img["fuse_ok"], 1)
         if not device:
-            C.shape(hp, {k: v for k, v in want.items() if k not in HOST_KEYS + ("zero_row",)})
+            C.shape(hp, {k: v for k, v in want.items() if k not in HOST_KEYS + IMAGE_KEYS + ("zero_row",)})
+            C.shape(img, {k: v for k, v in want.items() if k not in HOST_KEYS})
         else:
             with switches(env):
                 h.precond_set_cholesky(L.indptr, L.indices, L.data, perm)
             h.precond_setup(capi.PRECOND_REGULARIZED_CHOLESKY)
             shape = h.factor_shape(capi.FACTOR_PRECOND)
             C.shape(shape, want)
+            expect_image(C, shape, img)
             C.expect("cora_precond_stats", h.precond_stats(),
                      dict(stages=shape["stages"], nnzW=shape["nnzW"], nnzL=L.nnz, top_rows=shape["top_rows"]))
             C.expect("substitution blocks of cora_precond_entries", h.precond_entries()["sub_blocks"],
                      shape["blocks"] if shape["form"] == SUB else 0)
             if name == "sub":
-                C.expect("the sweeps can take the projection", shape["fuse_ok"], 1)
+                C.expect("the sweeps take the projection", shape["fuse_ok"], 1)
             for p in (2, 3, 7, 24):   # cora_precondition: the pinned row exactly zero, the others the solve
                 h.set_rank(p)
                 x = h.precondition(V[:, :p])
