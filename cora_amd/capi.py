@@ -795,6 +795,65 @@ class Context:
         out["raw"] = st
         return out
 
+    # ---- trajectory error against a reference after an orthogonal alignment (include/cora_hip.h, cora_compare_dev)
+    COMPARE_PROPER = 1
+
+    def _select(self, select):
+        if select is None:
+            return None, None
+        s = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8)
+        if s.shape != (self.nt,):
+            raise CoraError(1, "select must have n_trans = %d entries" % self.nt)
+        return s, s.ctypes.data_as(C.c_void_p)
+
+    def _compare_result(self, k, kr, et, er, el, out, aligned=None):
+        o = 8 + kr
+        names = ("m", "sum_et2", "max_et", "sum_er2", "max_er", "n_landmarks", "sum_el2", "max_el")
+        res = dict(zip(names, out[:8]))
+        res.update(pose_trans_err=et[:self.n], pose_rot_err=er[:self.n], landmark_err=el[:self.nt - self.n], sigma=out[8:o],
+                   xbar=out[o:o + k], gbar=out[o + k:o + k + kr], A=out[o + k + kr:].reshape(kr, k).T.copy(), raw=out)
+        if aligned is not None:
+            res["aligned"] = aligned
+        return res
+
+    def _compare_host(self, fn, X, Ref, select, proper, aligned):
+        X, Ref = _f(X), _f(Ref)
+        k, kr = X.shape[1], Ref.shape[1]
+        sel, selp = self._select(select)
+        et, er, el = np.zeros(max(self.n, 1)), np.zeros(max(self.n, 1)), np.zeros(max(self.nt - self.n, 1))
+        out = np.zeros(8 + kr + k + kr + k * kr)
+        al = self._out(kr) if aligned else None
+        self._chk(fn(self.h, _d(X), X.shape[0], k, _d(Ref), Ref.shape[0], kr, selp, self.COMPARE_PROPER if proper else 0,
+                     _d(et), _d(er), _d(el), _d(al) if aligned else None, self.N, _d(out)))
+        return self._compare_result(k, kr, et, er, el, out, al)
+
+    def compare(self, X, Ref, select=None, proper=False, aligned=False):
+        """Errors of the host matrix X (N x k) against Ref (N x kr) after the alignment on the selected poses' positions.
+        select: n_trans flags (poses, then landmarks) or None = all.  Returns dict m, sum_et2, max_et, sum_er2, max_er,
+        n_landmarks, sum_el2, max_el, pose_trans_err, pose_rot_err, landmark_err, sigma, xbar, gbar, A (k x kr), raw, and
+        aligned (N x kr) when asked for."""
+        return self._compare_host(self.L.cora_compare, X, Ref, select, proper, aligned)
+
+    def debug_compare_host(self, X, Ref, select=None, proper=False, aligned=False):
+        """The same operations on the host (no GPU needed, the handle is unchanged)."""
+        return self._compare_host(self.L.cora_debug_compare_host, X, Ref, select, proper, aligned)
+
+    def compare_dev(self, x, k, ref, kr, select=None, proper=False, d_aligned=None):
+        """The same on resident vectors (raw pointers as ints); d_aligned: a resident vector of kr columns or None."""
+        sel, selp = self._select(select)
+        et, er, el = np.zeros(max(self.n, 1)), np.zeros(max(self.n, 1)), np.zeros(max(self.nt - self.n, 1))
+        out = np.zeros(8 + kr + k + kr + k * kr)
+        self._chk(self.L.cora_compare_dev(self.h, C.c_void_p(x), int(k), C.c_void_p(ref), int(kr), selp,
+                                          self.COMPARE_PROPER if proper else 0, _d(et), _d(er), _d(el), C.c_void_p(d_aligned),
+                                          _d(out)))
+        return self._compare_result(k, kr, et, er, el, out)
+
+    def debug_compare_H(self, k, kr):
+        """Test hook: H (k x kr) of the last comparison on this handle."""
+        H = np.zeros((k, kr), order="F")
+        self._chk(self.L.cora_debug_compare_H(self.h, int(k), int(kr), _d(H)))
+        return H
+
     # ---- test hook
     def debug_format_spmm_host(self, X):
         X = _f(X)

@@ -2,7 +2,7 @@
 // device memory and stream; every compute entry point ends in a HIP kernel of
 // kernels.hip -- there is no CPU fallback.
 //
-// ONE translation unit in thirteen pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
+// ONE translation unit in fourteen pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
 // error / device macros and the helpers every part uses; the entry points live in capi/*.inc, included at the end in this order:
 //   handle.inc          creation of (partitioned) handles, destruction, rank state, row maps, statistics
 //   resident.inc        device vectors, the current point, the trust-region trial / accept pair, products, projections
@@ -16,6 +16,7 @@
 //   values.inc          in-place update of Q's values: source map, host-pointer and device-pointer update
 //   assembly.inc        Q(w) from per-measurement weights: term map, host-pointer, device-pointer and host-mirror assembly
 //   gnc.inc             the weight step of a robust-cost (GNC) loop: device-pointer, host-pointer and host-mirror form
+//   compare.inc         trajectory comparison after an orthogonal alignment: device-pointer, host-pointer and host form
 //   comm.inc            native communication: RCCL, in-process and device-side (p2p.h) transports
 #include <hip/hip_runtime.h>
 // RCCL's types and the few enumerators used, declared here (NCCL's public ABI: they have not changed since 2.0): the
@@ -261,6 +262,20 @@ struct cora_ctx {
   hipEvent_t asm_ev[2] = {nullptr, nullptr};
   double asm_ms[5] = {0, 0, 0, 0, 0};  // cora_assemble_times
   double *d_gnc = nullptr;  // cora_gnc_weights (capi/gnc.inc): thresholds | weights | residuals of the host-pointer form, 3 n_weights
+  // trajectory comparison (capi/compare.inc): the pose table (internal rows: first rotation row of every pose | translation
+  // row of every pose, then landmark | range rows), built at the first call, its device copy, the selection bytes, one
+  // block of doubles (pose translation errors | pose rotation errors | landmark errors | 48 column sums | 6 statistics |
+  // A) and the vectors of the pass (centred X, centred Ref; X, Ref, aligned of the host-pointer form) -- its own, so that a
+  // call moves none of the handle's scratch vectors
+  std::vector<int32_t> cmp_rows;
+  std::vector<unsigned char> cmp_sel_host;
+  std::vector<double> cmp_H;  // H of the last comparison, k x kr row-major (test hook cora_debug_compare_H)
+  int cmp_H_k = 0, cmp_H_kr = 0;
+  int32_t *d_cmp_rows = nullptr;
+  unsigned char *d_cmp_sel = nullptr;
+  double *d_cmp = nullptr;
+  double *cmp_vec[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t cmp_vec_bytes[5] = {0, 0, 0, 0, 0};
   std::vector<std::pair<double *, size_t>> user_allocs;  // live vectors of cora_dev_alloc (pointer, bytes)
   std::vector<std::pair<double *, size_t>> pool;         // released ones, kept for the next request of the same size
   std::string err;
@@ -593,6 +608,7 @@ extern "C" {
 #include "capi/values.inc"
 #include "capi/assembly.inc"
 #include "capi/gnc.inc"
+#include "capi/compare.inc"
 
 }  // extern "C"
 

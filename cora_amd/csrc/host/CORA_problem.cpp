@@ -986,6 +986,58 @@ MeasurementResiduals Problem::measurementResiduals(const Matrix &Y) const {
   return out;
 }
 
+TrajectoryComparison Problem::compareToReference(const Matrix &Y, const Matrix &Ref, const std::vector<unsigned char> &select,
+                                                 bool proper, bool want_aligned) const {
+  checkUpToDate();
+  if (part_world_ > 1) throw std::runtime_error("Problem::compareToReference: not supported on a partitioned handle");
+  checkMatrixShape("Problem::compareToReference::Y", getExpectedVariableSize(), Y.cols(), Y.rows(), Y.cols());
+  checkMatrixShape("Problem::compareToReference::Ref", getDataMatrixSize(), Ref.cols(), Ref.rows(), Ref.cols());
+  const int n = numPoses(), nt = numTranslationalStates(), N = getDataMatrixSize();
+  std::vector<unsigned char> sel(select);
+  if (sel.empty()) {
+    sel.assign(static_cast<size_t>(nt), 1);
+    if (has_priors_) sel[static_cast<size_t>(getRotationIdx(origin_symbol_))] = 0;
+  } else if (static_cast<int>(sel.size()) != nt) {
+    throw std::invalid_argument("Problem::compareToReference: select needs one flag per pose and landmark");
+  }
+  ensureContext();
+  Matrix full_tmp;
+  if (formulation_ == Formulation::Implicit) full_tmp = getTranslationExplicitSolution(Y);
+  const Matrix &X = formulation_ == Formulation::Implicit ? full_tmp : Y;
+  const int k = static_cast<int>(X.cols()), kr = static_cast<int>(Ref.cols());
+  TrajectoryComparison out;
+  out.pose_trans_err.resize(static_cast<size_t>(n));
+  out.pose_rot_err.resize(static_cast<size_t>(n));
+  out.landmark_err.resize(static_cast<size_t>(std::max(nt - n, 1)));
+  if (want_aligned) out.aligned = Matrix(N, kr);
+  std::vector<double> st(static_cast<size_t>(8 + 2 * kr + k + std::max(k, 1) * std::max(kr, 1)) + 64);
+  CORA_CALL(cora_compare(ctx_.get(), X.data(), static_cast<int>(X.rows()), k, Ref.data(), static_cast<int>(Ref.rows()), kr, sel.data(),
+                         proper ? CORA_COMPARE_PROPER : 0, out.pose_trans_err.data(), out.pose_rot_err.data(), out.landmark_err.data(),
+                         want_aligned ? out.aligned.data() : nullptr, N, st.data()),
+            "Problem::compareToReference");
+  out.landmark_err.resize(static_cast<size_t>(nt - n));
+  out.num_poses = static_cast<long>(st[0]);
+  out.sum_trans_err2 = st[1];
+  out.max_trans_err = st[2];
+  out.sum_rot_err2 = st[3];
+  out.max_rot_err = st[4];
+  out.num_landmarks = static_cast<long>(st[5]);
+  out.sum_landmark_err2 = st[6];
+  out.max_landmark_err = st[7];
+  const double *o = st.data() + 8;
+  out.singular_values.assign(o, o + kr);
+  o += kr;
+  out.xbar = Vector(k);
+  out.gbar = Vector(kr);
+  for (int a = 0; a < k; ++a) out.xbar(a) = o[a];
+  o += k;
+  for (int b = 0; b < kr; ++b) out.gbar(b) = o[b];
+  o += kr;
+  out.A = Matrix(k, kr);
+  std::copy(o, o + static_cast<size_t>(k) * kr, out.A.data());
+  return out;
+}
+
 // src/CORA_problem.cpp:1168-1197: [Y; -chol(Q33red) \ (B^T Y); 0], computed on the device
 Matrix Problem::getTranslationExplicitSolution(const Matrix &Y) const {
   checkMatrixShape("Problem::getTranslationExplicitSolution::Y", rotAndRangeMatrixSize(), Y.cols(), Y.rows(), Y.cols());

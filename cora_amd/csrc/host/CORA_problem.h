@@ -91,6 +91,24 @@ struct GncStats {
   long nMid() const { return rot.n_mid + trans.n_mid + range.n_mid; }
 };
 
+/** EXTENSION beyond the reference: how far an estimate is from a reference point (normally the ground truth of
+ * parsePyfgGroundTruth) after an orthogonal alignment on the selected poses' positions, Problem::compareToReference below
+ * (definitions: include/cora_hip.h, cora_compare_dev).  Errors of entries that were not selected are 0. */
+struct TrajectoryComparison {
+  long num_poses = 0, num_landmarks = 0;  // selected
+  std::vector<Scalar> pose_trans_err;     // |(x_i - xbar) A - (g_i - gbar)| per pose, pose order
+  std::vector<Scalar> pose_rot_err;       // |X_i A - G_i|_F per pose (chordal; angle = 2 asin(e / (2 sqrt 2)) for a d-column reference)
+  std::vector<Scalar> landmark_err;       // per landmark
+  Scalar sum_trans_err2 = 0, max_trans_err = 0, sum_rot_err2 = 0, max_rot_err = 0, sum_landmark_err2 = 0, max_landmark_err = 0;
+  std::vector<Scalar> singular_values;    // of H, descending: a small last one says the alignment is not determined
+  Matrix A;                               // k x kr, A^T A = I
+  Vector xbar, gbar;                      // the selected poses' mean positions
+  Matrix aligned;                         // the estimate in the reference's frame (N x kr), empty unless asked for
+  Scalar transRmse() const { return num_poses > 0 ? std::sqrt(sum_trans_err2 / static_cast<Scalar>(num_poses)) : 0; }
+  Scalar rotRmse() const { return num_poses > 0 ? std::sqrt(sum_rot_err2 / static_cast<Scalar>(num_poses)) : 0; }
+  Scalar landmarkRmse() const { return num_landmarks > 0 ? std::sqrt(sum_landmark_err2 / static_cast<Scalar>(num_landmarks)) : 0; }
+};
+
 class Problem {
  private:
   int dim_;
@@ -334,6 +352,14 @@ class Problem {
    * partitioned one, which has no measurement table. */
   std::pair<MeasurementWeights, GncStats> gncWeights(const Matrix &Y, const MeasurementWeights &thresholds, GncCost cost,
                                                      Scalar mu, bool couple_edges);
+
+  /** EXTENSION beyond the reference: the errors of Y against Ref on the device (cora_compare, include/cora_hip.h).
+   * Y: getExpectedVariableSize() rows, k = 1..24 columns (completed first in the implicit formulation); Ref:
+   * getDataMatrixSize() rows, kr <= k columns.  select: one flag per translational state (poses, then landmarks); EMPTY
+   * means every pose and landmark except the origin pose of a problem with priors.  proper (needs k == kr): det A = +1.
+   * Changes nothing of the Problem or its handle.  Single-GPU handles only. */
+  TrajectoryComparison compareToReference(const Matrix &Y, const Matrix &Ref, const std::vector<unsigned char> &select = {},
+                                          bool proper = true, bool want_aligned = false) const;
 
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;

@@ -622,6 +622,39 @@ int cora_problem_gnc_weights(cora_problem *p, const double *Y, int cols, const d
   });
 }
 
+int cora_problem_ground_truth(const cora_problem *p, const char *path, double *X_out) {
+  return guarded([&] {
+    const Matrix X = parsePyfgGroundTruth(path, p->problem);
+    std::memcpy(X_out, X.data(), sizeof(double) * static_cast<size_t>(X.size()));
+  });
+}
+
+int cora_problem_compare(const cora_problem *p, const double *Y, int cols, const double *Ref, int ref_cols,
+                         const unsigned char *select, int proper, double *pose_trans_err, double *pose_rot_err,
+                         double *landmark_err, double *aligned_out, double *out) {
+  return guarded([&] {
+    const Problem &q = p->problem;
+    std::vector<unsigned char> sel;
+    if (select) sel.assign(select, select + q.numTranslationalStates());
+    const TrajectoryComparison c = q.compareToReference(wrap(Y, q.getExpectedVariableSize(), cols), wrap(Ref, q.getDataMatrixSize(), ref_cols),
+                                                        sel, proper != 0, aligned_out != nullptr);
+    auto put = [](double *dst, const std::vector<Scalar> &v) {
+      if (dst && !v.empty()) std::memcpy(dst, v.data(), sizeof(double) * v.size());
+    };
+    put(pose_trans_err, c.pose_trans_err);
+    put(pose_rot_err, c.pose_rot_err);
+    put(landmark_err, c.landmark_err);
+    if (aligned_out) std::memcpy(aligned_out, c.aligned.data(), sizeof(double) * static_cast<size_t>(c.aligned.size()));
+    const double head[8] = {static_cast<double>(c.num_poses), c.sum_trans_err2, c.max_trans_err, c.sum_rot_err2, c.max_rot_err,
+                            static_cast<double>(c.num_landmarks), c.sum_landmark_err2, c.max_landmark_err};
+    double *o = std::copy(head, head + 8, out);
+    o = std::copy(c.singular_values.begin(), c.singular_values.end(), o);
+    o = std::copy(c.xbar.data(), c.xbar.data() + c.xbar.size(), o);
+    o = std::copy(c.gbar.data(), c.gbar.data() + c.gbar.size(), o);
+    std::copy(c.A.data(), c.A.data() + c.A.size(), o);
+  });
+}
+
 int cora_problem_solve_robust(cora_problem *p, const double *x0, int max_rank, int verbose,
                               const double *const thresholds[7], const int64_t lengths[7], int cost, int couple_edges,
                               double mu_factor, int max_outer, double *x_out, double stats[11], double robust[3],

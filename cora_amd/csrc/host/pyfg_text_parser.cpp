@@ -1,5 +1,7 @@
 #include "pyfg_text_parser.h"
 
+#include "CORA_utils.h"
+
 #include <cmath>
 #include <fstream>
 #include <iostream>
@@ -185,6 +187,65 @@ Problem parsePyfgTextToProblem(const std::string &filename) {  // :112-321
     }
   }
   return problem;
+}
+
+// The vertices' own values as a point of the problem.  A second pass over the file: parsePyfgTextToProblem keeps dropping
+// them, as the reference does (:162-175).
+Matrix parsePyfgGroundTruth(const std::string &filename, const Problem &problem) {
+  const int dim = getDimFromPyfgFirstLine(filename);
+  if (dim != problem.dim()) throw std::invalid_argument("parsePyfgGroundTruth: the file's dimension is not the problem's");
+  const Index n = problem.numPoses(), nt = problem.numTranslationalStates();
+  const Index dn = problem.numPosesDim(), t0 = problem.rotAndRangeMatrixSize();
+  Matrix X(problem.getDataMatrixSize(), dim);
+  std::vector<char> seen(static_cast<size_t>(nt), 0);
+  const std::map<Symbol, int> poses = problem.getPoseSymbolMap(), landmarks = problem.getLandmarkSymbolMap();
+  if (problem.getNumPosePriors() + problem.getNumLandmarkPriors() > 0) {  // the origin pose the priors added: identity, zero
+    const auto it = poses.find(problem.getOriginSymbol());
+    if (it != poses.end()) {
+      for (int a = 0; a < dim; ++a) X(static_cast<Index>(it->second) * dim + a, a) = 1.0;
+      seen[static_cast<size_t>(it->second)] = 1;
+    }
+  }
+  std::ifstream in(filename);
+  if (!in.good()) throw std::runtime_error("Could not open file " + filename);
+  std::string line, s1;
+  double ts;
+  while (std::getline(in, line)) {
+    std::istringstream iss(line);
+    const PyFGType type = typeOf(line, iss);
+    if (type == POSE_TYPE_2D || type == POSE_TYPE_3D) {
+      if (!(iss >> ts >> s1)) throw std::runtime_error("Could not read pose variable from line " + line);
+      const auto it = poses.find(Symbol(s1));
+      if (it == poses.end()) continue;  // (a vertex the problem does not know)
+      const Vector t = readVector(iss, dim);
+      const Matrix R = projectToSOd(type == POSE_TYPE_2D ? fromAngle(readScalar(iss)) : readQuat(iss));
+      for (int a = 0; a < dim; ++a) {
+        X(t0 + it->second, a) = t(a);
+        for (int b = 0; b < dim; ++b) X(static_cast<Index>(it->second) * dim + a, b) = R(b, a);  // R^T
+      }
+      seen[static_cast<size_t>(it->second)] = 1;
+    } else if (type == LANDMARK_TYPE_2D || type == LANDMARK_TYPE_3D) {
+      if (!(iss >> s1)) throw std::runtime_error("Could not read landmark variable from line " + line);
+      const auto it = landmarks.find(Symbol(s1));
+      if (it == landmarks.end()) continue;
+      const Vector t = readVector(iss, dim);
+      for (int a = 0; a < dim; ++a) X(t0 + n + it->second, a) = t(a);
+      seen[static_cast<size_t>(n + it->second)] = 1;
+    }
+  }
+  for (Index i = 0; i < nt; ++i)
+    if (!seen[static_cast<size_t>(i)])
+      throw std::runtime_error("parsePyfgGroundTruth: translational state " + std::to_string(i) + " of the problem has no VERTEX record in " + filename);
+  // range row m: the unit vector from the second endpoint to the first, so that x_t(b) - x_t(a) + r x_rho vanishes at r = |.|
+  const std::vector<RangeMeasurement> &ranges = problem.getRangeMeasurements();
+  for (size_t m = 0; m < ranges.size(); ++m) {
+    const Index ta = problem.getTranslationIdx(ranges[m].first_id), tb = problem.getTranslationIdx(ranges[m].second_id);
+    Scalar nrm = 0;
+    for (int a = 0; a < dim; ++a) nrm += (X(ta, a) - X(tb, a)) * (X(ta, a) - X(tb, a));
+    nrm = std::sqrt(nrm);
+    for (int a = 0; a < dim; ++a) X(dn + static_cast<Index>(m), a) = nrm > 0 ? (X(ta, a) - X(tb, a)) / nrm : (a == 0 ? 1.0 : 0.0);
+  }
+  return X;
 }
 
 }  // namespace CORA

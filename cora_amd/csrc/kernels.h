@@ -393,6 +393,38 @@ hipError_t launch_gnc_ranges(const GncArgs &A, hipStream_t st);  // n == 0: no l
 // out[j] = max over b of partial[j * nblocks + b] (values >= 0), one block, fixed order
 hipError_t launch_reduce_max_partials(const double *partial, int nblocks, int count, double *out, hipStream_t st);
 
+// Comparison of a resident estimate X (k columns) with a resident reference Ref (kr <= k columns) after an orthogonal
+// alignment on the selected poses' positions (kernels/compare.inc; include/cora_hip.h, cora_compare_dev).  An entity
+// -- pose i < n, landmark n <= i < nt, range row -- belongs to a group of kResidualLanes lanes; the pose table holds
+// INTERNAL rows: rot_row[n] (first rotation row; the d rows are consecutive), trn_row[nt] (poses, then landmarks),
+// rng_row[nr].  sel: nt bytes, API order.  Three steps:
+//   sums   : partial[k + kr][blocks] = column sums of X | Ref over the selected poses' translation rows
+//   centre : Xc, Gc (zeroed by the caller) get x_i - mean, g_i - mean in the selected poses' translation rows; the caller
+//            forms H = Xc^T Gc with launch_gram: the other rows add exact zeros.  mean_c = sums[c] / m, formed by every
+//            lane that needs it (one division, the same bits everywhere)
+//   errors : et, er [n], el [nt - n] (0.0 where not selected), aligned (may be nullptr: all rows, kr columns),
+//            partial[6][blocks] = sum et^2, sum er^2, sum el^2 | max et, max er, max el.  A: [k][kr] row-major.
+//            flag |= 1 where an error is not finite.
+// Every grid is sized by the count (32 entities per block, no grid-stride loop).
+struct CompareArgs {
+  int d = 0, n = 0, nt = 0, nr = 0;
+  int k = 0, ldx = 0, kr = 0, ldr = 0;
+  const double *X = nullptr, *Ref = nullptr;
+  const int32_t *rot_row = nullptr, *trn_row = nullptr, *rng_row = nullptr;
+  const unsigned char *sel = nullptr;
+  double m = 0.0;               // number of selected poses
+  const double *sums = nullptr; // [k + kr]
+  const double *A = nullptr;
+  double *Xc = nullptr, *Gc = nullptr;
+  double *et = nullptr, *er = nullptr, *el = nullptr, *aligned = nullptr;
+  double *partial = nullptr;
+  int *flag = nullptr;
+};
+inline int compare_blocks(int64_t entities) { return static_cast<int>((entities + 256 / kResidualLanes - 1) / (256 / kResidualLanes)); }
+hipError_t launch_compare_sums(const CompareArgs &A, hipStream_t st);    // compare_blocks(n) blocks
+hipError_t launch_compare_centre(const CompareArgs &A, hipStream_t st);  // compare_blocks(n) blocks
+hipError_t launch_compare_errors(const CompareArgs &A, hipStream_t st);  // compare_blocks(nt + (aligned ? nr : 0)) blocks
+
 // In-place update of Q's values (kernels/update_values.inc).  src: the sources of ValueMap (cora_internal.h), vals: the
 // new CSR values on the device.
 // check: flag |= 1 where a value is not finite, |= 2 where a mirror pair (mirror[2j], mirror[2j + 1]) differs.

@@ -414,6 +414,44 @@ hipError_t launch_reduce_max_partials(const double *partial, int nblocks, int co
   return hipGetLastError();
 }
 
+// the trajectory comparison (kernels/compare.inc): grids sized by the count, piece widths by the parity of the two strides
+static bool compare_args_ok(const CompareArgs &A) {
+  return (A.d == 2 || A.d == 3) && A.k >= 1 && A.k <= A.ldx && A.kr >= 1 && A.kr <= A.ldr && A.k <= kMaxLD && A.kr <= A.k &&
+         A.n >= 0 && A.nt >= A.n && A.nr >= 0;
+}
+#define COMPARE_BY_WIDTH(kernel, grid)                                                         \
+  do {                                                                                          \
+    const bool wx = A.ldx % 2 == 0, wr = A.ldr % 2 == 0;                                        \
+    if (wx && wr) hipLaunchKernelGGL((kernel<2, 2>), dim3(grid), dim3(256), 0, st, A);          \
+    else if (wx) hipLaunchKernelGGL((kernel<2, 1>), dim3(grid), dim3(256), 0, st, A);           \
+    else if (wr) hipLaunchKernelGGL((kernel<1, 2>), dim3(grid), dim3(256), 0, st, A);           \
+    else hipLaunchKernelGGL((kernel<1, 1>), dim3(grid), dim3(256), 0, st, A);                   \
+  } while (0)
+hipError_t launch_compare_sums(const CompareArgs &A, hipStream_t st) {
+  if (!compare_args_ok(A) || A.n < 1) return hipErrorInvalidValue;
+  COMPARE_BY_WIDTH(k_compare_sums, compare_blocks(A.n));
+  return hipGetLastError();
+}
+hipError_t launch_compare_centre(const CompareArgs &A, hipStream_t st) {
+  if (!compare_args_ok(A) || A.n < 1) return hipErrorInvalidValue;
+  COMPARE_BY_WIDTH(k_compare_centre, compare_blocks(A.n));
+  return hipGetLastError();
+}
+#undef COMPARE_BY_WIDTH
+hipError_t launch_compare_errors(const CompareArgs &A, hipStream_t st) {
+  if (!compare_args_ok(A) || A.nt < 1) return hipErrorInvalidValue;
+  const dim3 grid(compare_blocks(static_cast<int64_t>(A.nt) + (A.aligned ? A.nr : 0))), block(256);
+  const bool wide = A.ldr % 2 == 0;
+  if (A.d == 2) {
+    if (wide) hipLaunchKernelGGL((k_compare_errors<2, 2>), grid, block, 0, st, A);
+    else hipLaunchKernelGGL((k_compare_errors<2, 1>), grid, block, 0, st, A);
+  } else {
+    if (wide) hipLaunchKernelGGL((k_compare_errors<3, 2>), grid, block, 0, st, A);
+    else hipLaunchKernelGGL((k_compare_errors<3, 1>), grid, block, 0, st, A);
+  }
+  return hipGetLastError();
+}
+
 // in-place update of Q's values (kernels/update_values.inc): two slots per thread
 hipError_t launch_values_check(int64_t nnz, const double *vals, int64_t n_pairs, const int32_t *mirror, int *flag,
                                hipStream_t st) {

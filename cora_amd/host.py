@@ -306,6 +306,51 @@ class Problem:
         stats = {seg: dict(zip(names, st[4 * i:4 * i + 4])) for i, seg in enumerate(("rot", "trans", "range"))}
         return {k: a[:int(n)] for k, a, n in zip(self.WEIGHT_KINDS, arrs, sizes)}, stats
 
+    def ground_truth(self, path):
+        """parsePyfgGroundTruth: the VERTEX_* values of a PyFG file as a point of this problem (N x d: rotation rows
+        R_i^T, unit range rows, positions), the reference of compare()."""
+        dm = self.dims()
+        X = np.zeros((dm["N"], dm["d"]), order="F")
+        self._chk(self.L.cora_problem_ground_truth(self.h, str(path).encode(), X.ctypes.data_as(_dp)))
+        return X
+
+    def compare(self, Y, Ref, select=None, proper=True, aligned=False):
+        """Problem::compareToReference: errors of Y (variable_size() x k) against Ref (N x kr, kr <= k) after the
+        orthogonal alignment on the selected poses' positions (include/cora_hip.h, cora_compare_dev).  select: None
+        (every pose and landmark but the origin pose of a problem with priors) or n + l flags; proper needs k == kr.
+        Returns dict m, n_landmarks, pose_trans_err, pose_rot_err, landmark_err, sum_et2, max_et, sum_er2, max_er,
+        sum_el2, max_el, trans_rmse, rot_rmse, landmark_rmse, sigma, xbar, gbar, A (k x kr), and aligned (N x kr) when
+        asked for."""
+        Y = np.asfortranarray(np.asarray(Y, dtype=np.float64))
+        Ref = np.asfortranarray(np.asarray(Ref, dtype=np.float64))
+        dm = self.dims()
+        if Y.ndim != 2 or Y.shape[0] != self.variable_size():
+            raise HostError("expected %d rows, got shape %s" % (self.variable_size(), Y.shape))
+        if Ref.ndim != 2 or Ref.shape[0] != dm["N"]:
+            raise HostError("the reference needs %d rows, got shape %s" % (dm["N"], Ref.shape))
+        k, kr, n, nl = Y.shape[1], Ref.shape[1], dm["n"], dm["l"]
+        sel = None
+        if select is not None:
+            sel = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8)
+            if sel.shape != (n + nl,):
+                raise HostError("select needs %d flags" % (n + nl))
+        et, er, el = np.zeros(max(n, 1)), np.zeros(max(n, 1)), np.zeros(max(nl, 1))
+        al = np.zeros((dm["N"], kr), order="F") if aligned else None
+        out = np.zeros(8 + kr + k + kr + k * kr)
+        self._chk(self.L.cora_problem_compare(self.h, Y.ctypes.data_as(_dp), int(k), Ref.ctypes.data_as(_dp), int(kr),
+                                              sel.ctypes.data_as(C.c_void_p) if sel is not None else None, int(bool(proper)),
+                                              et.ctypes.data_as(_dp), er.ctypes.data_as(_dp), el.ctypes.data_as(_dp),
+                                              al.ctypes.data_as(_dp) if aligned else None, out.ctypes.data_as(_dp)))
+        o = 8 + kr
+        res = dict(zip(("m", "sum_et2", "max_et", "sum_er2", "max_er", "n_landmarks", "sum_el2", "max_el"), out[:8]))
+        res.update(pose_trans_err=et[:n], pose_rot_err=er[:n], landmark_err=el[:nl], sigma=out[8:o], xbar=out[o:o + k],
+                   gbar=out[o + k:o + k + kr], A=out[o + k + kr:].reshape(kr, k).T.copy(),
+                   trans_rmse=float(np.sqrt(out[1] / max(out[0], 1))), rot_rmse=float(np.sqrt(out[3] / max(out[0], 1))),
+                   landmark_rmse=float(np.sqrt(out[6] / max(out[5], 1))))
+        if aligned:
+            res["aligned"] = al
+        return res
+
     def solve_robust(self, x0, thresholds, cost="tls", couple_edges=True, mu_factor=1.4, max_outer=100, max_rank=10,
                      verbose=False):
         """solveRobustCORA: graduated non-convexity over solve().  Returns solve()'s dict (of the last solve) plus

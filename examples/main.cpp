@@ -5,6 +5,7 @@
 //               -Lcora_amd/lib -lcora_hip -Wl,-rpath,$PWD/cora_amd/lib -o cora_main
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -19,12 +20,12 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]]" << std::endl;
+    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum]" << std::endl;
     return 1;
   }
   int max_rank = 10;
-  std::string tum, save_dir, residuals, weights, robust, barc2, weights_out;
-  bool jacobi = false, implicit = false, odom = false;
+  std::string tum, save_dir, residuals, weights, robust, barc2, weights_out, aligned_tum;
+  bool jacobi = false, implicit = false, odom = false, evaluate = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--jacobi") jacobi = true;
@@ -43,6 +44,10 @@ int main(int argc, char **argv) {
     else if (a == "--robust" && i + 1 < argc) robust = argv[++i];
     else if (a == "--barc2" && i + 1 < argc) barc2 = argv[++i];
     else if (a == "--weights-out" && i + 1 < argc) weights_out = argv[++i];
+    // error of the solution against the input file's own VERTEX_* values after the alignment on all poses' positions;
+    // the estimate in the ground truth's frame as a TUM trajectory
+    else if (a == "--evaluate") evaluate = true;
+    else if (a == "--aligned-tum" && i + 1 < argc) aligned_tum = argv[++i];
   }
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
@@ -188,6 +193,48 @@ int main(int argc, char **argv) {
       std::printf("residuals: rotation %.9g  translation %.9g  range %.9g  half of their total %.9g  (final cost %.9g)\n",
                   res.rot_sum, res.trans_sum, res.range_sum, 0.5 * (res.rot_sum + res.trans_sum + res.range_sum), soln.first.f);
       std::cout << "wrote " << residuals << " (" << lines << " measurements)" << std::endl;
+    }
+    if (evaluate || !aligned_tum.empty()) {  // (an extension beyond the reference: Problem::compareToReference)
+      const CORA::Matrix truth = CORA::parsePyfgGroundTruth(argv[1], problem);
+      const CORA::TrajectoryComparison cmp = problem.compareToReference(soln.first.x, truth, {}, true, !aligned_tum.empty());
+      // a pose's rotation error as an angle: 2 asin(e / (2 sqrt 2)) of its chordal error e; the RMSE is over these angles
+      const auto degrees = [](double chordal) { return 2.0 * std::asin(std::min(1.0, chordal / (2.0 * std::sqrt(2.0)))) * 180.0 / 3.14159265358979323846; };
+      if (evaluate) {
+        // the origin pose that priors add is no pose of a robot (compareToReference leaves it out under the same condition)
+        const bool has_origin = problem.getNumPosePriors() + problem.getNumLandmarkPriors() > 0;
+        // one line from the per-pose errors of the poses with symbol character chr (0: all), under the joint alignment
+        const auto line = [&](unsigned char chr) {
+          double t2 = 0, a2 = 0, tmax = 0, amax = 0;
+          long count = 0;
+          for (const auto &kv : problem.getPoseSymbolMap()) {
+            if ((chr && kv.first.chr() != chr) || (has_origin && kv.first == problem.getOriginSymbol())) continue;
+            const double et = cmp.pose_trans_err[static_cast<size_t>(kv.second)];
+            const double ang = degrees(cmp.pose_rot_err[static_cast<size_t>(kv.second)]);
+            t2 += et * et;
+            a2 += ang * ang;
+            tmax = std::max(tmax, et);
+            amax = std::max(amax, ang);
+            ++count;
+          }
+          const double n = static_cast<double>(std::max(count, 1L));
+          if (chr) std::printf("evaluate: robot '%c' ", chr);
+          else std::printf("evaluate: ");
+          std::printf("%ld poses  translation RMSE %.6g max %.6g  rotation RMSE %.6g deg max %.6g deg\n", count, std::sqrt(t2 / n), tmax,
+                      std::sqrt(a2 / n), amax);
+        };
+        line(0);
+        std::vector<unsigned char> robots;
+        for (const auto &kv : problem.getPoseSymbolMap())
+          if (!(has_origin && kv.first == problem.getOriginSymbol()) && std::find(robots.begin(), robots.end(), kv.first.chr()) == robots.end())
+            robots.push_back(kv.first.chr());
+        if (robots.size() > 1)
+          for (const unsigned char chr : robots) line(chr);
+        std::printf("evaluate: %ld landmarks  position RMSE %.6g max %.6g\n", cmp.num_landmarks, cmp.landmarkRmse(), cmp.max_landmark_err);
+      }
+      if (!aligned_tum.empty()) {
+        CORA::saveSolnToTum(problem, cmp.aligned, aligned_tum);
+        std::cout << "wrote " << aligned_tum << std::endl;
+      }
     }
     if (!tum.empty()) {
       CORA::saveSolnToTum(problem, aligned, tum);

@@ -539,6 +539,70 @@ int cora_gnc_weights(cora_ctx *ctx, const double *X, int ldx, int k, const doubl
 int cora_debug_gnc_weights_host(cora_ctx *ctx, const double *X, int ldx, int k, const double *barc2, int cost,
                                 int couple_edges, double mu, double *w_out, double *r2_out, double stats[12]);
 
+/* ---- TRAJECTORY ERROR against a reference (normally ground truth), aligned on the device ------------------------------
+ * Compares a resident estimate X (k columns) with a resident reference Ref (kr <= k columns, normally kr = d).  A relaxed
+ * solution is defined up to X -> X G, G in O(p), and a common shift of the translation rows, a rounded one up to a rigid
+ * motion, so the two are aligned first: orthogonal Procrustes (Kabsch) on the selected poses' positions.
+ * DEFINITIONS.  n poses, l = n_trans - n landmarks, dimension d.  For pose i: x_i in R^k its translation row of X, g_i in
+ * R^kr its translation row of Ref, X_i (d x k) and G_i (d x kr) its rotation blocks.
+ *   select   host array of n_trans bytes in API order (poses, then landmarks); NULL = all ones.  P = the selected poses,
+ *            m = |P|; m = 0 is CORA_ERR_ARG.
+ *   means    xbar = (1/m) sum_P x_i, gbar likewise.
+ *   H        = sum_P (x_i - xbar)^T (g_i - gbar), k x kr, formed from CENTRED rows in two passes (the one-pass form cancels
+ *            for a trajectory far from the origin).
+ *   A        = U D V^T of the thin SVD H = U Sigma V^T (host, fp64, one-sided Jacobi), D = I; with CORA_COMPARE_PROPER
+ *            (needs k == kr) D = diag(1, .., 1, det(U V^T)), so det A = +1 and a rounded solution is not matched by a
+ *            reflection.  A minimises sum_P |(x_i - xbar) A - (g_i - gbar)|^2 over A^T A = I.  Where H is rank deficient
+ *            (one pose; a collinear walk in 3-D) A is any such minimiser; the singular values are returned so that the
+ *            caller can see it; it is not an error.
+ *   et_i     = |(x_i - xbar) A - (g_i - gbar)|_2 per selected pose
+ *   er_i     = |X_i A - G_i|_F per selected pose: the chordal distance; for kr = d the angle is 2 asin(er_i / (2 sqrt 2)).
+ *   el_j     = the same as et with the rows of landmark j, per selected landmark.  Landmarks never enter xbar, gbar or H.
+ *   Entries of the three arrays that are not selected are 0.0.
+ *   out      8 + kr + k + kr + k kr host doubles: m, sum et^2, max et, sum er^2, max er, number of selected landmarks,
+ *            sum el^2, max el | the kr singular values, descending | xbar | gbar | A column-major (k x kr).
+ *   dAligned optional resident vector of kr columns, EVERY row whatever the selection: rotation and range rows times A,
+ *            translation rows (x - xbar) A + gbar; padding rows are zero.  Must not overlap dX or dRef (checked).
+ * cora_compare_dev   dX, dRef (and dAligned) resident vectors; pose_trans_err, pose_rot_err (n) and landmark_err (l) host
+ *            arrays, each may be NULL.  Three device steps -- column sums, centred rows and H (the Gram kernel), errors --
+ *            with the SVD on the host between the second and the third.  Synchronises.
+ * cora_compare       the host-pointer form: X is N x k, Ref N x kr, Aligned (may be NULL) N x kr, column-major with leading
+ *            dimensions; uploaded first.
+ * cora_debug_compare_host  the same operations on the host; works on a plan-only handle (device < 0).  It does NOT mirror
+ *            the device's lane order, so its sums, its H and with H its A have other last bits.  What holds for EACH form,
+ *            against exact arithmetic on the same inputs, wherever D = I and H has full column rank:
+ *              means   |xbar_c - exact| <= eps sum_P |x_ic|, gbar likewise
+ *              H       |H_ab - exact| <= tol_ab = (m + 4) eps sum_P |x_ia - xbar_a| |g_ib - gbar_b|
+ *              A       |A - exact|_F <= dA = 4 |tol|_F / sigma_min(H) + 64 k eps   (perturbation of the polar factor)
+ *              entry   within 8 (k + kr) eps (|x_i - xbar| + |g_i - gbar| + |xbar| + |gbar|) of the exact error for ITS A,
+ *                      xbar, gbar.
+ *            Hence the two forms' A differ by at most 2 dA in the Frobenius norm, and an entry of the two by at most
+ *            twice the entry bound plus |x_i - xbar| 2 dA + dm for a position (dm = twice the norms of the two vectors of
+ *            mean bounds), sqrt(d) 2 dA for a rotation block -- bounds fixed by the inputs, not bit for bit.
+ * No atomics on doubles: block partials in fixed slots, one block finishes them, so two calls give the same bits.
+ * ERRORS.  CORA_ERR_SHAPE: k or kr outside 1..24, kr > k, a leading dimension below N.  CORA_ERR_ARG: a null dX, dRef or out,
+ * an unknown flag, CORA_COMPARE_PROPER with k != kr, m = 0, an aligned vector that overlaps an input, a partitioned handle,
+ * a handle whose row order does not keep a pose's d rotation rows consecutive.  CORA_ERR_NAN: a mean, H or an error that is
+ * not finite.  On an error the contents of the outputs are unspecified.
+ * STATE.  The call never changes what the handle computes with: the current point, the preconditioner, the values, the
+ * tables and the staleness flags stay as they were.  Kept on the handle until it is destroyed: the pose table, the
+ * per-entry error arrays, and the two centred vectors of cora_compare_dev (rows x k and rows x kr doubles, grown to the
+ * widest k and kr seen) while they are at most 256 MiB each -- a larger one (10^6 poses at 24 columns: 0.86 GB) is
+ * released before the call returns and allocated again by the next; cora_compare releases its three upload / download
+ * vectors before it returns.  Every form also keeps H of its last call (k kr doubles) for cora_debug_compare_H. */
+enum { CORA_COMPARE_PROPER = 1 };
+int cora_compare_dev(cora_ctx *ctx, const double *dX, int k, const double *dRef, int kr, const unsigned char *select,
+                     int flags, double *pose_trans_err, double *pose_rot_err, double *landmark_err, double *dAligned,
+                     double *out);
+int cora_compare(cora_ctx *ctx, const double *X, int ldx, int k, const double *Ref, int ldref, int kr,
+                 const unsigned char *select, int flags, double *pose_trans_err, double *pose_rot_err, double *landmark_err,
+                 double *Aligned, int ldal, double *out);
+int cora_debug_compare_host(cora_ctx *ctx, const double *X, int ldx, int k, const double *Ref, int ldref, int kr,
+                            const unsigned char *select, int flags, double *pose_trans_err, double *pose_rot_err,
+                            double *landmark_err, double *Aligned, int ldal, double *out);
+/* Test hook: H of the handle's last comparison (any of the three forms) with these k, kr; k x kr column-major. */
+int cora_debug_compare_H(const cora_ctx *ctx, int k, int kr, double *H);
+
 /* Timing helpers: HIP events on the handle's stream. */
 int cora_timer_start(cora_ctx *ctx);
 int cora_timer_stop_ms(cora_ctx *ctx, float *ms); /* synchronises */

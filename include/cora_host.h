@@ -132,6 +132,18 @@ int cora_problem_get_measurement_weights(const cora_problem *p, double *const we
 int cora_problem_gnc_weights(cora_problem *p, const double *Y, int cols, const double *const thresholds[7],
                              const int64_t lengths[7], int cost, double mu, int couple_edges, double *const weights_out[7],
                              double stats[12]);
+/* parsePyfgGroundTruth (an extension beyond the reference; CORA/pyfg_text_parser.h): the VERTEX_* values of a PyFG file as
+ * a point of the problem, N x d column-major with N = data-matrix size (rotation rows R_i^T, unit range rows, positions). */
+int cora_problem_ground_truth(const cora_problem *p, const char *path, double *X_out);
+/* Problem::compareToReference (an extension beyond the reference; CORA/CORA_problem.h; definitions: cora_hip.h,
+ * cora_compare_dev): errors of Y (variable size x cols) against Ref (data-matrix size x ref_cols <= cols) after the
+ * orthogonal alignment on the selected poses' positions.  select: NULL (every pose and landmark but the origin pose of a
+ * problem with priors) or n_poses + n_landmarks bytes.  proper != 0 needs cols == ref_cols.  pose_trans_err, pose_rot_err
+ * (n_poses), landmark_err (n_landmarks), aligned_out (data-matrix size x ref_cols) may be NULL.  out: 8 + ref_cols + cols
+ * + ref_cols + cols * ref_cols doubles in the order of cora_compare_dev. */
+int cora_problem_compare(const cora_problem *p, const double *Y, int cols, const double *Ref, int ref_cols,
+                         const unsigned char *select, int proper, double *pose_trans_err, double *pose_rot_err,
+                         double *landmark_err, double *aligned_out, double *out);
 /* solveRobustCORA (an extension beyond the reference; CORA/CORA.h): graduated non-convexity over solveCORA from x0
  * (N x rank).  thresholds / lengths / cost (1 or 2) / couple_edges as above; mu_factor > 1; max_outer: cap on the rounds.
  * x_out: N x d.  stats: as cora_problem_solve, of the last solve.  robust: [0] rounds, [1] 1 = converged (0: the cap),
