@@ -854,6 +854,62 @@ class Context:
         self._chk(self.L.cora_debug_compare_H(self.h, int(k), int(kr), _d(H)))
         return H
 
+    # ---- relative pose error over a pair table kept on the handle (include/cora_hip.h, cora_rpe_dev)
+    def set_pose_pairs(self, pairs):
+        """Installs the table of pose pairs (m x 2 API pose indices; None or an empty table clears it)."""
+        if pairs is None:
+            self._chk(self.L.cora_set_pose_pairs(self.h, C.c_int64(0), None))
+            return
+        p = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        self._chk(self.L.cora_set_pose_pairs(self.h, C.c_int64(len(p)), p.ctypes.data_as(_ip) if len(p) else None))
+
+    def pose_pairs_count(self):
+        m = C.c_int64(0)
+        self._chk(self.L.cora_pose_pairs_count(self.h, C.byref(m)))
+        return int(m.value)
+
+    def pose_pairs_equal(self, pairs):
+        """Whether the table holds exactly these pairs in this order (None or empty: no table)."""
+        p = np.zeros((0, 2), dtype=np.int32) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        same = C.c_int(0)
+        self._chk(self.L.cora_pose_pairs_equal(self.h, C.c_int64(len(p)), p.ctypes.data_as(_ip) if len(p) else None, C.byref(same)))
+        return bool(same.value)
+
+    @staticmethod
+    def _rpe_result(m, et, er, out, arrays=True):
+        names = ("m", "sum_et2", "max_et", "sum_er2", "max_er", "argmax_et")
+        res = dict(zip(names, out))
+        res["raw"] = out
+        if arrays:
+            res.update(trans_err=et[:m], rot_err=er[:m])
+        return res
+
+    def _rpe_host(self, fn, X, Ref, arrays):
+        X, Ref = _f(X), _f(Ref)
+        m = self.pose_pairs_count()
+        et, er, out = np.zeros(max(m, 1)), np.zeros(max(m, 1)), np.zeros(6)
+        self._chk(fn(self.h, _d(X), X.shape[0], X.shape[1], _d(Ref), Ref.shape[0], Ref.shape[1], _d(et) if arrays else None,
+                     _d(er) if arrays else None, _d(out)))
+        return self._rpe_result(m, et, er, out, arrays)
+
+    def rpe(self, X, Ref, arrays=True):
+        """Relative pose errors of the host matrix X (N x k) against Ref (N x kr; k and kr independent) over the pair
+        table.  Returns dict m, sum_et2, max_et, sum_er2, max_er, argmax_et (first pair that attains max_et), raw, and
+        trans_err, rot_err (m each) unless arrays is False."""
+        return self._rpe_host(self.L.cora_rpe, X, Ref, arrays)
+
+    def debug_rpe_host(self, X, Ref, arrays=True):
+        """The same definitions on the host in the device's lane and tree order (no GPU needed, the handle is unchanged)."""
+        return self._rpe_host(self.L.cora_debug_rpe_host, X, Ref, arrays)
+
+    def rpe_dev(self, x, k, ref, kr, arrays=True):
+        """The same on resident vectors (raw pointers as ints); arrays=False reads back the six statistics only."""
+        m = self.pose_pairs_count()
+        et, er, out = np.zeros(max(m, 1)), np.zeros(max(m, 1)), np.zeros(6)
+        self._chk(self.L.cora_rpe_dev(self.h, C.c_void_p(x), int(k), C.c_void_p(ref), int(kr), _d(et) if arrays else None,
+                                      _d(er) if arrays else None, _d(out)))
+        return self._rpe_result(m, et, er, out, arrays)
+
     # ---- test hook
     def debug_format_spmm_host(self, X):
         X = _f(X)

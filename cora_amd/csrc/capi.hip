@@ -2,7 +2,7 @@
 // device memory and stream; every compute entry point ends in a HIP kernel of
 // kernels.hip -- there is no CPU fallback.
 //
-// ONE translation unit in fourteen pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
+// ONE translation unit in fifteen pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
 // error / device macros and the helpers every part uses; the entry points live in capi/*.inc, included at the end in this order:
 //   handle.inc          creation of (partitioned) handles, destruction, rank state, row maps, statistics
 //   resident.inc        device vectors, the current point, the trust-region trial / accept pair, products, projections
@@ -17,6 +17,7 @@
 //   assembly.inc        Q(w) from per-measurement weights: term map, host-pointer, device-pointer and host-mirror assembly
 //   gnc.inc             the weight step of a robust-cost (GNC) loop: device-pointer, host-pointer and host-mirror form
 //   compare.inc         trajectory comparison after an orthogonal alignment: device-pointer, host-pointer and host form
+//   rpe.inc             relative pose error over a pair table of the handle: table, device-pointer, host-pointer and host-mirror form
 //   comm.inc            native communication: RCCL, in-process and device-side (p2p.h) transports
 #include <hip/hip_runtime.h>
 // RCCL's types and the few enumerators used, declared here (NCCL's public ABI: they have not changed since 2.0): the
@@ -92,9 +93,21 @@ struct MeasurementTable {
   double *d_edge_data = nullptr, *d_range_data = nullptr;
   double *d_out = nullptr;  // [n_edges] rotation | [n_edges] translation | [n_ranges] range | 3 sums
 };
+// The pair table of cora_set_pose_pairs (capi/rpe.inc): the pairs as given (API pose indices) and translated to internal
+// rows, structure-of-arrays [first rotation row of i | translation row of i | first rotation row of j | translation row
+// of j][pair] (RpeArgs, kernels.h), and the device's error arrays
+struct PosePairTable {
+  bool set = false;
+  int64_t m = 0;
+  std::vector<int32_t> api;   // [m][2]
+  std::vector<int32_t> rows;  // [4][m]
+  int32_t *d_rows = nullptr;
+  double *d_err = nullptr;  // [m] translation | [m] rotation | 5 statistics
+};
 struct cora_ctx {
   HostFormat F;
   MeasurementTable meas;
+  PosePairTable pairs;
   cora_native_comm *native_comm = nullptr;  // owned: the library's own communication (cora_comm_create_*)
   cora::P2PState *p2p_pending = nullptr;    // a mailbox exported by cora_comm_p2p_handle, not yet connected
   int device = -1;
@@ -609,6 +622,7 @@ extern "C" {
 #include "capi/assembly.inc"
 #include "capi/gnc.inc"
 #include "capi/compare.inc"
+#include "capi/rpe.inc"
 
 }  // extern "C"
 

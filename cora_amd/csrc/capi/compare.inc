@@ -159,8 +159,8 @@ void compare_tail_out(int k, int kr, const double *sigma, const double *xbar, co
     for (int a = 0; a < k; ++a) *o++ = A[static_cast<size_t>(a) * kr + b];
 }
 
-// the pose table and the buffers of the device forms, built at the first call
-int compare_prepare(cora_ctx *c) {
+// the pose table (host copy), built at the first call; shared with the pair table of capi/rpe.inc
+int compare_pose_table(cora_ctx *c) {
   const Layout &L = c->F.L;
   const int d = L.d;
   if (c->cmp_rows.empty()) {
@@ -180,6 +180,13 @@ int compare_prepare(cora_ctx *c) {
       if (rows[i] < 0 || rows[i] >= L.rows) return fail(c, CORA_ERR_ARG, "row map out of range");
     c->cmp_rows = std::move(rows);
   }
+  return CORA_OK;
+}
+
+// the pose table and the buffers of the device forms, built at the first call
+int compare_prepare(cora_ctx *c) {
+  const Layout &L = c->F.L;
+  if (const int rc = compare_pose_table(c)) return rc;
   if (!c->d_cmp_rows) HIP_TRY(c, to_device(&c->d_cmp_rows, c->cmp_rows));
   if (!c->d_cmp_sel) HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_cmp_sel), std::max<size_t>(L.nt, 1)));
   if (!c->d_cmp)

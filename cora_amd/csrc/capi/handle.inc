@@ -181,7 +181,7 @@ void cora_ctx_destroy(cora_ctx *c) {
                     c->d_partials, c->d_tickets, c->d_api2int, c->d_diag_inv, c->d_lam_st, c->d_lam_ob, c->d_own_sym, c->d_S,
                     c->d_stage, c->d_red, c->d_scalars, c->d_flag, c->d_ticket, c->d_stpcg, c->d_seq_counter,
                     c->d_vmap_src, c->d_vmap_mirror, c->d_vmap_vals, c->d_cmp_rows, c->d_cmp_sel, c->d_cmp,
-                    c->cmp_vec[0], c->cmp_vec[1], c->cmp_vec[2], c->cmp_vec[3], c->cmp_vec[4]};
+                    c->cmp_vec[0], c->cmp_vec[1], c->cmp_vec[2], c->cmp_vec[3], c->cmp_vec[4], c->pairs.d_rows, c->pairs.d_err};
     if (c->stpcg_graph) (void)hipGraphExecDestroy(c->stpcg_graph);
     for (void *p : ptrs)
       if (p) (void)hipFree(p);

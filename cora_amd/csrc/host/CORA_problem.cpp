@@ -1038,6 +1038,90 @@ TrajectoryComparison Problem::compareToReference(const Matrix &Y, const Matrix &
   return out;
 }
 
+namespace {
+// the pose indices of every robot's chain: robots in the order of their characters, poses in symbol order
+std::vector<std::vector<int32_t>> poseChains(const std::map<Symbol, int> &poses) {
+  std::map<unsigned char, std::vector<int32_t>> by_chr;
+  for (const auto &kv : poses) by_chr[kv.first.chr()].push_back(static_cast<int32_t>(kv.second));
+  std::vector<std::vector<int32_t>> chains;
+  for (auto &kv : by_chr) chains.push_back(std::move(kv.second));
+  return chains;
+}
+}  // namespace
+
+PosePairs Problem::posePairsByStep(int step) const {
+  if (step < 1) throw std::invalid_argument("Problem::posePairsByStep: the step must be at least 1");
+  PosePairs out;
+  for (const std::vector<int32_t> &c : poseChains(pose_symbol_idxs_))
+    for (size_t a = 0; a + static_cast<size_t>(step) < c.size(); ++a) {
+      out.pairs.push_back(c[a]);
+      out.pairs.push_back(c[a + static_cast<size_t>(step)]);
+      out.path_length.push_back(static_cast<Scalar>(step));
+    }
+  return out;
+}
+
+PosePairs Problem::posePairsByDistance(const Matrix &Ref, Scalar L) const {
+  if (!(L > 0)) throw std::invalid_argument("Problem::posePairsByDistance: the distance must be positive");
+  checkMatrixShape("Problem::posePairsByDistance::Ref", getDataMatrixSize(), Ref.cols(), Ref.rows(), Ref.cols());
+  const Index t0 = rotAndRangeMatrixSize();
+  PosePairs out;
+  for (const std::vector<int32_t> &c : poseChains(pose_symbol_idxs_)) {
+    std::vector<Scalar> s(c.size(), 0);  // path length from the chain's first pose
+    for (size_t a = 0; a + 1 < c.size(); ++a) {
+      Scalar sq = 0;
+      for (Index col = 0; col < Ref.cols(); ++col) {
+        const Scalar diff = Ref(t0 + c[a + 1], col) - Ref(t0 + c[a], col);
+        sq += diff * diff;
+      }
+      s[a + 1] = s[a] + std::sqrt(sq);
+    }
+    size_t b = 0;
+    for (size_t a = 0; a < c.size(); ++a) {
+      if (b <= a) b = a + 1;
+      while (b < c.size() && s[b] - s[a] < L) ++b;  // (s grows with b: the end never moves back)
+      if (b >= c.size()) break;                      // (nor does any later start reach L)
+      out.pairs.push_back(c[a]);
+      out.pairs.push_back(c[b]);
+      out.path_length.push_back(s[b] - s[a]);
+    }
+  }
+  return out;
+}
+
+RelativeError Problem::relativeError(const Matrix &Y, const Matrix &Ref, const PosePairs &pairs) {
+  if (part_world_ > 1) throw std::runtime_error("Problem::relativeError: not supported on a partitioned handle");
+  checkMatrixShape("Problem::relativeError::Y", getExpectedVariableSize(), Y.cols(), Y.rows(), Y.cols());
+  checkMatrixShape("Problem::relativeError::Ref", getDataMatrixSize(), Ref.cols(), Ref.rows(), Ref.cols());
+  if (pairs.pairs.size() != 2 * pairs.path_length.size())
+    throw std::invalid_argument("Problem::relativeError: the pairs need two indices and one path length each");
+  RelativeError out;
+  out.path_length = pairs.path_length;
+  if (pairs.size() == 0) return out;
+  if (!ctx_ || !problem_data_up_to_date_ || data_matrix_.nonZeros() == 0)
+    throw std::runtime_error("Problem::relativeError: no live device handle (run a solve or an operator after updateProblemData first)");
+  const int64_t m = static_cast<int64_t>(pairs.size());
+  int same = 0;  // (the handle keeps the table as given: a rebuilt handle has none)
+  if (cora_pose_pairs_equal(ctx_.get(), m, pairs.pairs.data(), &same) != CORA_OK || !same)
+    CORA_CALL(cora_set_pose_pairs(ctx_.get(), m, pairs.pairs.data()), "Problem::relativeError");
+  Matrix full_tmp;
+  if (formulation_ == Formulation::Implicit) full_tmp = getTranslationExplicitSolution(Y);
+  const Matrix &X = formulation_ == Formulation::Implicit ? full_tmp : Y;
+  out.trans_err.resize(static_cast<size_t>(m));
+  out.rot_err.resize(static_cast<size_t>(m));
+  double st[6];
+  CORA_CALL(cora_rpe(ctx_.get(), X.data(), static_cast<int>(X.rows()), static_cast<int>(X.cols()), Ref.data(),
+                     static_cast<int>(Ref.rows()), static_cast<int>(Ref.cols()), out.trans_err.data(), out.rot_err.data(), st),
+            "Problem::relativeError");
+  out.num_pairs = static_cast<long>(st[0]);
+  out.sum_trans_err2 = st[1];
+  out.max_trans_err = st[2];
+  out.sum_rot_err2 = st[3];
+  out.max_rot_err = st[4];
+  out.argmax_trans_err = static_cast<long>(st[5]);
+  return out;
+}
+
 // src/CORA_problem.cpp:1168-1197: [Y; -chol(Q33red) \ (B^T Y); 0], computed on the device
 Matrix Problem::getTranslationExplicitSolution(const Matrix &Y) const {
   checkMatrixShape("Problem::getTranslationExplicitSolution::Y", rotAndRangeMatrixSize(), Y.cols(), Y.rows(), Y.cols());

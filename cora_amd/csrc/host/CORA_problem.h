@@ -109,6 +109,43 @@ struct TrajectoryComparison {
   Scalar landmarkRmse() const { return num_landmarks > 0 ? std::sqrt(sum_landmark_err2 / static_cast<Scalar>(num_landmarks)) : 0; }
 };
 
+/** EXTENSION beyond the reference: pairs of poses (i, j) in pose order for the relative pose error, Problem::relativeError
+ * below, with the length of the path between the two.  posePairsByStep: the number of steps; posePairsByDistance: the
+ * length along the reference's positions. */
+struct PosePairs {
+  std::vector<int32_t> pairs;       // (i, j) of every pair, one after the other
+  std::vector<Scalar> path_length;  // one per pair
+  size_t size() const { return path_length.size(); }
+};
+
+/** EXTENSION beyond the reference: the error of the motion between the two poses of every pair, estimate against
+ * reference (definitions: include/cora_hip.h, cora_rpe_dev).  It needs no alignment and no common column count. */
+struct RelativeError {
+  long num_pairs = 0;
+  std::vector<Scalar> trans_err;    // |X_i (x_j - x_i)^T - G_i (g_j - g_i)^T| per pair
+  std::vector<Scalar> rot_err;      // |X_i X_j^T - G_i G_j^T|_F per pair (chordal; angle = 2 asin(e / (2 sqrt 2)) on the manifold)
+  std::vector<Scalar> path_length;  // of the pairs the errors were computed for
+  Scalar sum_trans_err2 = 0, max_trans_err = 0, sum_rot_err2 = 0, max_rot_err = 0;
+  long argmax_trans_err = 0;  // the first pair that attains max_trans_err
+  Scalar transRmse() const { return num_pairs > 0 ? std::sqrt(sum_trans_err2 / static_cast<Scalar>(num_pairs)) : 0; }
+  Scalar rotRmse() const { return num_pairs > 0 ? std::sqrt(sum_rot_err2 / static_cast<Scalar>(num_pairs)) : 0; }
+  /** mean of error / path_length over the pairs with a positive length (0 without one) */
+  Scalar meanTransDrift() const { return meanDrift(trans_err); }
+  Scalar meanRotDrift() const { return meanDrift(rot_err); }
+
+ private:
+  Scalar meanDrift(const std::vector<Scalar> &err) const {
+    Scalar sum = 0;
+    long count = 0;
+    for (size_t p = 0; p < err.size() && p < path_length.size(); ++p)
+      if (path_length[p] > 0) {
+        sum += err[p] / path_length[p];
+        ++count;
+      }
+    return count > 0 ? sum / static_cast<Scalar>(count) : 0;
+  }
+};
+
 class Problem {
  private:
   int dim_;
@@ -360,6 +397,22 @@ class Problem {
    * Changes nothing of the Problem or its handle.  Single-GPU handles only. */
   TrajectoryComparison compareToReference(const Matrix &Y, const Matrix &Ref, const std::vector<unsigned char> &select = {},
                                           bool proper = true, bool want_aligned = false) const;
+
+  /** EXTENSION beyond the reference: the pairs (c[a], c[a + step]) of every robot's chain c (getPoseSymbols(chr), the
+   * robots in the order of their characters), step >= 1; path_length = step.  A step of the chain's length or more gives
+   * no pair of that robot. */
+  PosePairs posePairsByStep(int step) const;
+  /** For every start pose the first later pose of the same robot whose path length along Ref's positions -- the
+   * cumulative sum of |g_{a+1} - g_a| over the chain, formed here on the host -- is at least L (> 0); starts that never
+   * reach L are left out.  Ref: getDataMatrixSize() rows, any number of columns. */
+  PosePairs posePairsByDistance(const Matrix &Ref, Scalar L) const;
+  /** The relative pose errors of Y against Ref over the pairs, on the device (cora_rpe, include/cora_hip.h).  Y:
+   * getExpectedVariableSize() rows, k = 1..24 columns (completed first in the implicit formulation); Ref:
+   * getDataMatrixSize() rows, kr = 1..24 columns, independent of k.  The pair table is installed on the handle only when the
+   * pairs differ from the ones the handle holds (cora_pose_pairs_equal; Problem keeps no copy and gains no member); nothing
+   * else of the handle changes.  No pairs: zeros.  std::runtime_error on a
+   * partitioned handle and without a live device handle (run a solve or an operator after updateProblemData first). */
+  RelativeError relativeError(const Matrix &Y, const Matrix &Ref, const PosePairs &pairs);
 
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;

@@ -655,6 +655,37 @@ int cora_problem_compare(const cora_problem *p, const double *Y, int cols, const
   });
 }
 
+int cora_problem_pose_pairs(const cora_problem *p, int step, const double *Ref, int ref_cols, double L, int32_t *pairs_out,
+                            double *path_out, int64_t *m_out) {
+  return guarded([&] {
+    const Problem &q = p->problem;
+    const PosePairs pp = Ref ? q.posePairsByDistance(wrap(Ref, q.getDataMatrixSize(), ref_cols), L) : q.posePairsByStep(step);
+    if (pairs_out && !pp.pairs.empty()) std::memcpy(pairs_out, pp.pairs.data(), sizeof(int32_t) * pp.pairs.size());
+    if (path_out && !pp.path_length.empty()) std::memcpy(path_out, pp.path_length.data(), sizeof(double) * pp.path_length.size());
+    *m_out = static_cast<int64_t>(pp.size());
+  });
+}
+
+int cora_problem_relative_error(cora_problem *p, const double *Y, int cols, const double *Ref, int ref_cols, int64_t m,
+                                const int32_t *pairs, const double *path_length, double *trans_err, double *rot_err,
+                                double out[8]) {
+  return guarded([&] {
+    Problem &q = p->problem;
+    if (m < 0 || (m > 0 && (!pairs || !path_length))) throw std::invalid_argument("cora_problem_relative_error: null pair table");
+    PosePairs pp;
+    if (m > 0) {
+      pp.pairs.assign(pairs, pairs + 2 * m);
+      pp.path_length.assign(path_length, path_length + m);
+    }
+    const RelativeError e = q.relativeError(wrap(Y, q.getExpectedVariableSize(), cols), wrap(Ref, q.getDataMatrixSize(), ref_cols), pp);
+    if (trans_err && !e.trans_err.empty()) std::memcpy(trans_err, e.trans_err.data(), sizeof(double) * e.trans_err.size());
+    if (rot_err && !e.rot_err.empty()) std::memcpy(rot_err, e.rot_err.data(), sizeof(double) * e.rot_err.size());
+    const double head[8] = {static_cast<double>(e.num_pairs), e.sum_trans_err2, e.max_trans_err, e.sum_rot_err2, e.max_rot_err,
+                            static_cast<double>(e.argmax_trans_err), e.meanTransDrift(), e.meanRotDrift()};
+    std::copy(head, head + 8, out);
+  });
+}
+
 int cora_problem_solve_robust(cora_problem *p, const double *x0, int max_rank, int verbose,
                               const double *const thresholds[7], const int64_t lengths[7], int cost, int couple_edges,
                               double mu_factor, int max_outer, double *x_out, double stats[11], double robust[3],

@@ -425,6 +425,26 @@ hipError_t launch_compare_sums(const CompareArgs &A, hipStream_t st);    // comp
 hipError_t launch_compare_centre(const CompareArgs &A, hipStream_t st);  // compare_blocks(n) blocks
 hipError_t launch_compare_errors(const CompareArgs &A, hipStream_t st);  // compare_blocks(nt + (aligned ? nr : 0)) blocks
 
+// Relative pose error of a resident estimate X (k columns) against a resident reference Ref (kr columns, independent of
+// k) over m pairs of poses (kernels/rpe.inc; include/cora_hip.h, cora_rpe_dev).  rows: [4][m] INTERNAL rows -- first
+// rotation row of i | translation row of i | first rotation row of j | translation row of j (a pose's d rotation rows
+// are consecutive).  et, er: m doubles each.  partial[5][rpe_blocks(m)]: sum et^2, sum er^2 | max et, max er | m - (first
+// pair of the block that attains the block's max et).  flag |= 1 where an error is not finite.
+struct RpeArgs {
+  int64_t m = 0;
+  int d = 0, k = 0, ldx = 0, kr = 0, ldr = 0;
+  const double *X = nullptr, *Ref = nullptr;
+  const int32_t *rows = nullptr;
+  double *et = nullptr, *er = nullptr;
+  double *partial = nullptr;
+  int *flag = nullptr;
+};
+constexpr int64_t kRpeMaxPairs = static_cast<int64_t>(1) << 30;  // (32 pairs per block: the grid stays far below 2^31)
+inline int rpe_blocks(int64_t m) { return compare_blocks(m); }
+hipError_t launch_rpe(const RpeArgs &A, hipStream_t st);  // rpe_blocks(m) blocks; m == 0: invalid
+// stats[5] = sum et^2, sum er^2, max et, max er, first pair that attains max et, from the partials of launch_rpe
+hipError_t launch_rpe_finish(const double *partial, int nblocks, int64_t m, double *stats, hipStream_t st);
+
 // In-place update of Q's values (kernels/update_values.inc).  src: the sources of ValueMap (cora_internal.h), vals: the
 // new CSR values on the device.
 // check: flag |= 1 where a value is not finite, |= 2 where a mirror pair (mirror[2j], mirror[2j + 1]) differs.

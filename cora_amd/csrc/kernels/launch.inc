@@ -452,6 +452,33 @@ hipError_t launch_compare_errors(const CompareArgs &A, hipStream_t st) {
   return hipGetLastError();
 }
 
+// the relative pose error (kernels/rpe.inc): grid sized by the count, piece widths by the parity of the two strides
+template <int D>
+static void launch_rpe_d(const RpeArgs &A, hipStream_t st) {
+  const dim3 grid(rpe_blocks(A.m)), block(256);
+  const bool wx = A.ldx % 2 == 0, wr = A.ldr % 2 == 0;
+  if (wx && wr) hipLaunchKernelGGL((k_rpe<D, 2, 2>), grid, block, 0, st, A);
+  else if (wx) hipLaunchKernelGGL((k_rpe<D, 2, 1>), grid, block, 0, st, A);
+  else if (wr) hipLaunchKernelGGL((k_rpe<D, 1, 2>), grid, block, 0, st, A);
+  else hipLaunchKernelGGL((k_rpe<D, 1, 1>), grid, block, 0, st, A);
+}
+hipError_t launch_rpe(const RpeArgs &A, hipStream_t st) {
+  if ((A.d != 2 && A.d != 3) || A.k < 1 || A.k > A.ldx || A.kr < 1 || A.kr > A.ldr || A.ldx > kMaxLD || A.ldr > kMaxLD || A.m < 1 ||
+      A.m > kRpeMaxPairs)
+    return hipErrorInvalidValue;
+  if (A.d == 2) launch_rpe_d<2>(A, st);
+  else launch_rpe_d<3>(A, st);
+  return hipGetLastError();
+}
+hipError_t launch_rpe_finish(const double *partial, int nblocks, int64_t m, double *stats, hipStream_t st) {
+  const size_t nb = static_cast<size_t>(nblocks);
+  hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, st, partial, nblocks, 2, stats);
+  hipLaunchKernelGGL(k_reduce_max_partials, dim3(1), dim3(256), 0, st, partial + 2 * nb, nblocks, 2, stats + 2);
+  hipLaunchKernelGGL(k_rpe_argmax, dim3(1), dim3(256), 0, st, partial + 2 * nb, partial + 4 * nb, nblocks, stats + 2,
+                     static_cast<double>(m), stats + 4);
+  return hipGetLastError();
+}
+
 // in-place update of Q's values (kernels/update_values.inc): two slots per thread
 hipError_t launch_values_check(int64_t nnz, const double *vals, int64_t n_pairs, const int32_t *mirror, int *flag,
                                hipStream_t st) {

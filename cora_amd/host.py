@@ -351,6 +351,58 @@ class Problem:
             res["aligned"] = al
         return res
 
+    def _pose_pairs(self, step, Ref, L):
+        n = self.dims()["n"]
+        pairs, path, m = np.zeros((max(n, 1), 2), dtype=np.int32), np.zeros(max(n, 1)), C.c_int64(0)
+        refp, cols = None, 0
+        if Ref is not None:
+            Ref = np.asfortranarray(np.asarray(Ref, dtype=np.float64))
+            if Ref.ndim != 2 or Ref.shape[0] != self.dims()["N"]:
+                raise HostError("the reference needs %d rows, got shape %s" % (self.dims()["N"], Ref.shape))
+            refp, cols = Ref.ctypes.data_as(_dp), Ref.shape[1]
+        self._chk(self.L.cora_problem_pose_pairs(self.h, int(step), refp, int(cols), C.c_double(L),
+                                                 pairs.ctypes.data_as(C.POINTER(C.c_int32)), path.ctypes.data_as(_dp), C.byref(m)))
+        return pairs[:m.value].copy(), path[:m.value].copy()
+
+    def pose_pairs_by_step(self, step):
+        """Problem::posePairsByStep: (pairs [m, 2] of pose indices, path_length [m] = step) -- (c[a], c[a + step]) for
+        every robot's chain c."""
+        return self._pose_pairs(step, None, 0.0)
+
+    def pose_pairs_by_distance(self, Ref, L):
+        """Problem::posePairsByDistance: for every start the first later pose of the same robot at least L along Ref's
+        positions; (pairs [m, 2], path_length [m])."""
+        return self._pose_pairs(0, Ref, L)
+
+    def relative_error(self, Y, Ref, pairs, path_length=None):
+        """Problem::relativeError: relative pose errors of Y (variable_size() x k) against Ref (N x kr; k and kr
+        independent) over the pairs (include/cora_hip.h, cora_rpe_dev).  pairs: [m, 2] or the tuple a pair builder
+        returned.  Returns dict m, trans_err, rot_err, sum_et2, max_et, sum_er2, max_er, argmax_et, trans_rmse, rot_rmse,
+        mean_trans_drift, mean_rot_drift (means of error / path_length over pairs with a positive length)."""
+        if isinstance(pairs, tuple):
+            pairs, path_length = pairs
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        m = len(pairs)
+        path = np.ones(m) if path_length is None else np.ascontiguousarray(path_length, dtype=np.float64).reshape(-1)
+        if len(path) != m:
+            raise HostError("path_length needs one value per pair")
+        Y = np.asfortranarray(np.asarray(Y, dtype=np.float64))
+        Ref = np.asfortranarray(np.asarray(Ref, dtype=np.float64))
+        if Y.ndim != 2 or Y.shape[0] != self.variable_size():
+            raise HostError("expected %d rows, got shape %s" % (self.variable_size(), Y.shape))
+        if Ref.ndim != 2 or Ref.shape[0] != self.dims()["N"]:
+            raise HostError("the reference needs %d rows, got shape %s" % (self.dims()["N"], Ref.shape))
+        et, er, out = np.zeros(max(m, 1)), np.zeros(max(m, 1)), np.zeros(8)
+        self._chk(self.L.cora_problem_relative_error(self.h, Y.ctypes.data_as(_dp), int(Y.shape[1]), Ref.ctypes.data_as(_dp),
+                                                     int(Ref.shape[1]), C.c_int64(m),
+                                                     pairs.ctypes.data_as(C.POINTER(C.c_int32)) if m else None,
+                                                     path.ctypes.data_as(_dp) if m else None, et.ctypes.data_as(_dp),
+                                                     er.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
+        res = dict(zip(("m", "sum_et2", "max_et", "sum_er2", "max_er", "argmax_et", "mean_trans_drift", "mean_rot_drift"), out))
+        res.update(trans_err=et[:m], rot_err=er[:m], trans_rmse=float(np.sqrt(out[1] / max(out[0], 1))),
+                   rot_rmse=float(np.sqrt(out[3] / max(out[0], 1))))
+        return res
+
     def solve_robust(self, x0, thresholds, cost="tls", couple_edges=True, mu_factor=1.4, max_outer=100, max_rank=10,
                      verbose=False):
         """solveRobustCORA: graduated non-convexity over solve().  Returns solve()'s dict (of the last solve) plus

@@ -9,7 +9,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
+#include <functional>
 #include <iostream>
+#include <sstream>
 #include <string>
 #include <utility>
 #include <vector>
@@ -20,11 +22,11 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum]" << std::endl;
+    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]]" << std::endl;
     return 1;
   }
   int max_rank = 10;
-  std::string tum, save_dir, residuals, weights, robust, barc2, weights_out, aligned_tum;
+  std::string tum, save_dir, residuals, weights, robust, barc2, weights_out, aligned_tum, rpe_steps, rpe_dists;
   bool jacobi = false, implicit = false, odom = false, evaluate = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
@@ -48,6 +50,10 @@ int main(int argc, char **argv) {
     // the estimate in the ground truth's frame as a TUM trajectory
     else if (a == "--evaluate") evaluate = true;
     else if (a == "--aligned-tum" && i + 1 < argc) aligned_tum = argv[++i];
+    // relative pose error of the solution against the file's own VERTEX_* values (no alignment needed): pairs a fixed
+    // number of steps apart, pairs at least a path length apart along the ground truth
+    else if (a == "--rpe" && i + 1 < argc) rpe_steps = argv[++i];
+    else if (a == "--rpe-dist" && i + 1 < argc) rpe_dists = argv[++i];
   }
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
@@ -235,6 +241,37 @@ int main(int argc, char **argv) {
         CORA::saveSolnToTum(problem, cmp.aligned, aligned_tum);
         std::cout << "wrote " << aligned_tum << std::endl;
       }
+    }
+    if (!rpe_steps.empty() || !rpe_dists.empty()) {  // (an extension beyond the reference: Problem::relativeError)
+      const CORA::Matrix truth = CORA::parsePyfgGroundTruth(argv[1], problem);
+      const auto degrees = [](double chordal) { return 2.0 * std::asin(std::min(1.0, chordal / (2.0 * std::sqrt(2.0)))) * 180.0 / 3.14159265358979323846; };
+      // the rotation RMSE is over the pairs' angles, as in --evaluate; the drift is the mean of error / path length
+      const auto line = [&](const std::string &setting, const CORA::PosePairs &pairs) {
+        const CORA::RelativeError e = problem.relativeError(soln.first.x, truth, pairs);
+        double a2 = 0, amax = 0, adrift = 0;
+        long with_length = 0;
+        for (size_t p = 0; p < e.rot_err.size(); ++p) {
+          const double ang = degrees(e.rot_err[p]);
+          a2 += ang * ang;
+          amax = std::max(amax, ang);
+          if (e.path_length[p] > 0) {
+            adrift += ang / e.path_length[p];
+            ++with_length;
+          }
+        }
+        const double n = static_cast<double>(std::max(e.num_pairs, 1L));
+        std::printf("rpe: %s %ld pairs  translation RMSE %.6g max %.6g  rotation RMSE %.6g deg max %.6g deg  drift %.6g per unit %.6g deg per unit\n",
+                    setting.c_str(), e.num_pairs, e.transRmse(), e.max_trans_err, std::sqrt(a2 / n), amax, e.meanTransDrift(),
+                    with_length > 0 ? adrift / static_cast<double>(with_length) : 0.0);
+      };
+      const auto each = [](const std::string &list, const std::function<void(const std::string &)> &fn) {
+        std::stringstream ss(list);
+        std::string item;
+        while (std::getline(ss, item, ','))
+          if (!item.empty()) fn(item);
+      };
+      each(rpe_steps, [&](const std::string &v) { line("step " + v, problem.posePairsByStep(std::atoi(v.c_str()))); });
+      each(rpe_dists, [&](const std::string &v) { line("distance " + v, problem.posePairsByDistance(truth, std::atof(v.c_str()))); });
     }
     if (!tum.empty()) {
       CORA::saveSolnToTum(problem, aligned, tum);

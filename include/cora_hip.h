@@ -603,6 +603,70 @@ int cora_debug_compare_host(cora_ctx *ctx, const double *X, int ldx, int k, cons
 /* Test hook: H of the handle's last comparison (any of the three forms) with these k, kr; k x kr column-major. */
 int cora_debug_compare_H(const cora_ctx *ctx, int k, int kr, double *H);
 
+/* ---- RELATIVE POSE ERROR against a reference (normally ground truth), evaluated on the device ---------------------------
+ * The error of the MOTION between two poses i -> j, for a table of pairs kept on the handle.  It needs no alignment: with
+ * X_i the d x k rotation block of pose i and x_i its translation row, X_i X_j^T and X_i (x_j - x_i)^T are invariant under
+ * X -> X G, G in O(k), and under a common shift of the translation rows.  So the estimate X (k columns) and the reference
+ * Ref (kr columns) may have ANY column counts 1 <= k, kr <= 24, independent of each other and of the handle's rank: a
+ * relaxed level of the staircase is compared with a d-column ground truth directly.
+ * DEFINITIONS.  n poses, dimension d.  For pose i: X_i (d x k), x_i in R^k from X; G_i (d x kr), g_i in R^kr from Ref.
+ * For a pair (i, j) of pose indices in API pose order, 0 <= i, j < n:
+ *   E_ij = X_i X_j^T (d x d)        u_ij = X_i (x_j - x_i)^T (d)
+ *   S_ij = G_i G_j^T                v_ij = G_i (g_j - g_i)^T
+ *   et_ij = |u_ij - v_ij|_2         er_ij = |E_ij - S_ij|_F
+ * er is the chordal distance cora_compare reports for a pose; for on-manifold d-column inputs the angle of the error
+ * rotation is 2 asin(er / (2 sqrt 2)), and et is the length of the translation part of (S, v)^-1 (E, u), the usual RPE.
+ * Any pair is allowed: i > j, repeated pairs, pairs across robots.  i == j is the identity motion in both vectors and
+ * both errors are exactly 0.0 (the rows are not looked at: off the manifold X_i X_i^T and G_i G_i^T differ).  Landmarks
+ * have no rotation and are not pairable.
+ *   out      6 host doubles: m, sum et^2, max et, sum er^2, max er, the index of the first pair that attains max et.
+ * SUMMATION ORDER.  A pair belongs to a group of 8 lanes.  A dot product over the columns of a vector is split over the
+ * lanes in pieces of 16 bytes (8 at an odd row stride, i.e. an odd column count of 3 or more), piece v going to lane
+ * v mod 8; a lane adds its pieces in column order with one fma per term from +0.0 (x_j - x_i is one subtraction per
+ * column); the lanes are added by the butterfly over the distances 4, 2, 1, X and Ref separately; the d^2 + d differences
+ * are taken afterwards, squared and added with one fma each in row-major order, E before u.  A pair's errors are a function
+ * of its 2 d + 2 rows of each vector alone: the same bits on every call and at every place in the table.  No atomics on
+ * doubles: block totals in fixed slots, one block finishes the sums, the maxima and the first maximum.
+ * cora_set_pose_pairs   pairs: m x 2 int32 (i, j).  Validates, translates through the pose table the comparison keeps
+ *            (first internal rotation row, translation row) and uploads structure-of-arrays.  A second call replaces the
+ *            table; m = 0 clears it.  Works on a plan-only handle (device < 0) except for the upload.  A refused call
+ *            leaves the table as it was.
+ * cora_pose_pairs_count m of the table (0 without one).
+ * cora_pose_pairs_equal *equal = 1 when the table holds exactly these m pairs in this order (m = 0: no table), else 0: a
+ *            caller that evaluates in a loop installs a table only when it changed.
+ * cora_rpe_dev          dX, dRef resident vectors of k and kr columns; trans_err, rot_err: host arrays of m doubles, each
+ *            may be NULL -- with both NULL only `out` is read back.  Synchronises.
+ * cora_rpe              the host-pointer form: X is N x k, Ref N x kr, column-major with leading dimensions; uploaded
+ *            first, and the two vectors are released before it returns.
+ * cora_debug_rpe_host   the same definitions on the host through the translated table; works on a plan-only handle.  It
+ *            MIRRORS the lane pieces, the fma order and the butterfly: trans_err and rot_err have the device's bits, and
+ *            with them the two maxima and the first maximum.  The two sums of squares are added in pair order, not in the
+ *            device's block order: they agree with the device's within m eps times the sum, not bit for bit.
+ * ROUNDING.  With a = |X_i|_F |x_j - x_i|, b = |G_i|_F |g_j - g_i|, A = |X_i|_F |X_j|_F, B = |G_i|_F |G_j|_F, eps = 2^-52,
+ * exact double inputs, and any summation order of a length-k dot product within (k + 1) eps sum |p| |q|:
+ *   |et - exact| <= 2 (k + kr + d + 8) eps (a + b)        |er - exact| <= 2 (k + kr + d + 8) eps (A + B)
+ * x_j - x_i carries one relative eps, so a trajectory far from the origin does not cancel beyond it; the norm of an error
+ * vector is bounded through the triangle inequality, so the bounds hold at et = 0 and er = 0 too; the factor 2 covers the
+ * second-order terms and the final square root.  Both forms stay inside them against exact arithmetic.
+ * ERRORS.  cora_set_pose_pairs: CORA_ERR_ARG for m < 0 or above 2^30, a null table with m > 0, an index outside [0, n) (the
+ * message names the first bad pair), a partitioned handle, a handle whose row order does not keep a pose's d rotation rows
+ * consecutive.  The three forms: CORA_ERR_ARG for a partitioned handle or a null X, Ref or out; CORA_ERR_SHAPE for k or kr
+ * outside 1..24 or a leading dimension below N; CORA_ERR_NOT_READY without a table; CORA_ERR_NAN for an error or a sum that
+ * is not finite.  On an error the contents of the outputs are unspecified.
+ * STATE.  The calls never change what the handle computes with: the current point, the values, the preconditioner, the
+ * measurement table, the term map and the staleness flags stay as they were.  Kept on the handle until replaced or
+ * destroyed: the pair table (as given and translated, 24 bytes per pair on the host, 16 on the device) and two error
+ * arrays of m doubles on the device. */
+int cora_set_pose_pairs(cora_ctx *ctx, int64_t m, const int32_t *pairs /* [m][2] */);
+int cora_pose_pairs_count(const cora_ctx *ctx, int64_t *m);
+int cora_pose_pairs_equal(const cora_ctx *ctx, int64_t m, const int32_t *pairs, int *equal);
+int cora_rpe_dev(cora_ctx *ctx, const double *dX, int k, const double *dRef, int kr, double *trans_err, double *rot_err,
+                 double out[6]);
+int cora_rpe(cora_ctx *ctx, const double *X, int ldx, int k, const double *Ref, int ldref, int kr, double *trans_err,
+             double *rot_err, double out[6]);
+int cora_debug_rpe_host(cora_ctx *ctx, const double *X, int ldx, int k, const double *Ref, int ldref, int kr,
+                        double *trans_err, double *rot_err, double out[6]);
+
 /* Timing helpers: HIP events on the handle's stream. */
 int cora_timer_start(cora_ctx *ctx);
 int cora_timer_stop_ms(cora_ctx *ctx, float *ms); /* synchronises */

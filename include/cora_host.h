@@ -144,6 +144,18 @@ int cora_problem_ground_truth(const cora_problem *p, const char *path, double *X
 int cora_problem_compare(const cora_problem *p, const double *Y, int cols, const double *Ref, int ref_cols,
                          const unsigned char *select, int proper, double *pose_trans_err, double *pose_rot_err,
                          double *landmark_err, double *aligned_out, double *out);
+/* Problem::posePairsByStep (Ref == NULL: the pairs (c[a], c[a + step]) of every robot's chain) or
+ * Problem::posePairsByDistance (Ref: data-matrix size x ref_cols; for every start the first later pose of the same robot at
+ * least L along Ref's positions).  pairs_out: 2 * n_poses int32 (a start appears at most once), path_out: n_poses doubles;
+ * *m_out: the number of pairs. */
+int cora_problem_pose_pairs(const cora_problem *p, int step, const double *Ref, int ref_cols, double L, int32_t *pairs_out,
+                            double *path_out, int64_t *m_out);
+/* Problem::relativeError: the relative pose errors of Y (variable size x cols) against Ref (data-matrix size x ref_cols,
+ * independent of cols) over m pairs (include/cora_hip.h, cora_rpe_dev).  trans_err, rot_err: m doubles or NULL.  out: m,
+ * sum et^2, max et, sum er^2, max er, first pair that attains max et, mean of et / path_length, mean of er / path_length. */
+int cora_problem_relative_error(cora_problem *p, const double *Y, int cols, const double *Ref, int ref_cols, int64_t m,
+                                const int32_t *pairs, const double *path_length, double *trans_err, double *rot_err,
+                                double out[8]);
 /* solveRobustCORA (an extension beyond the reference; CORA/CORA.h): graduated non-convexity over solveCORA from x0
  * (N x rank).  thresholds / lengths / cost (1 or 2) / couple_edges as above; mu_factor > 1; max_outer: cap on the rounds.
  * x_out: N x d.  stats: as cora_problem_solve, of the last solve.  robust: [0] rounds, [1] 1 = converged (0: the cap),
