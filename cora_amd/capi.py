@@ -910,6 +910,43 @@ class Context:
                                       _d(er) if arrays else None, _d(out)))
         return self._rpe_result(m, et, er, out, arrays)
 
+    # ---- rounding of a relaxed point to SE(d) (include/cora_hip.h, cora_round_dev)
+    def _round_result(self, k, out, rounded=None):
+        d = self.d
+        res = dict(count=int(out[0]), flipped=bool(out[1]), sigma=out[2:2 + k].copy(),
+                   Vd=out[2 + k:2 + k + k * d].reshape(d, k).T.copy(), raw=out)
+        if rounded is not None:
+            res["X"] = rounded
+        return res
+
+    def round(self, Y):
+        """Rounds the host matrix Y (N x k, d <= k <= 24) to SE(d) on the device.  Returns dict X (N x d), count (pose
+        blocks of positive determinant), flipped, sigma (k singular values), Vd (k x d), raw."""
+        Y = _f(Y)
+        k = Y.shape[1]
+        X, out = np.zeros((Y.shape[0], self.d), order="F"), np.zeros(2 + k + k * self.d)
+        self._chk(self.L.cora_round(self.h, _d(Y), Y.shape[0], int(k), _d(X), X.shape[0], _d(out)))
+        return self._round_result(k, out, X)
+
+    def debug_round_host(self, Y, basis=None):
+        """The same on the host through the functions the kernels call (no GPU needed).  basis: a k x d matrix to use in
+        place of the eigenvectors of this form's own Gram matrix (the Vd of a device call: the rows, the count and the flip
+        then have the device's bits)."""
+        Y = _f(Y)
+        k = Y.shape[1]
+        X, out = np.zeros((Y.shape[0], self.d), order="F"), np.zeros(2 + k + k * self.d)
+        B = None if basis is None else np.asfortranarray(np.asarray(basis, dtype=np.float64).reshape(k, self.d))
+        self._chk(self.L.cora_debug_round_host(self.h, _d(Y), Y.shape[0], int(k), None if B is None else _d(B), _d(X),
+                                               X.shape[0], _d(out)))
+        return self._round_result(k, out, X)
+
+    def round_dev(self, y, k, out_ptr):
+        """The same on resident vectors (raw pointers as ints): y has k columns, out_ptr d columns; they must not overlap.
+        Returns the dict of round() without X."""
+        out = np.zeros(2 + k + k * self.d)
+        self._chk(self.L.cora_round_dev(self.h, C.c_void_p(y), int(k), C.c_void_p(out_ptr), _d(out)))
+        return self._round_result(k, out)
+
     # ---- test hook
     def debug_format_spmm_host(self, X):
         X = _f(X)

@@ -2,7 +2,7 @@
 // device memory and stream; every compute entry point ends in a HIP kernel of
 // kernels.hip -- there is no CPU fallback.
 //
-// ONE translation unit in fifteen pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
+// ONE translation unit in sixteen pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
 // error / device macros and the helpers every part uses; the entry points live in capi/*.inc, included at the end in this order:
 //   handle.inc          creation of (partitioned) handles, destruction, rank state, row maps, statistics
 //   resident.inc        device vectors, the current point, the trust-region trial / accept pair, products, projections
@@ -18,6 +18,7 @@
 //   gnc.inc             the weight step of a robust-cost (GNC) loop: device-pointer, host-pointer and host-mirror form
 //   compare.inc         trajectory comparison after an orthogonal alignment: device-pointer, host-pointer and host form
 //   rpe.inc             relative pose error over a pair table of the handle: table, device-pointer, host-pointer and host-mirror form
+//   round.inc           rounding of a relaxed point to SE(d): device-pointer, host-pointer and host-mirror form
 //   comm.inc            native communication: RCCL, in-process and device-side (p2p.h) transports
 #include <hip/hip_runtime.h>
 // RCCL's types and the few enumerators used, declared here (NCCL's public ABI: they have not changed since 2.0): the
@@ -623,6 +624,7 @@ extern "C" {
 #include "capi/gnc.inc"
 #include "capi/compare.inc"
 #include "capi/rpe.inc"
+#include "capi/round.inc"
 
 }  // extern "C"
 

@@ -29,14 +29,13 @@ bool all_finite(const double *v, size_t n) {
   return true;
 }
 
-// A = U D V^T of the thin SVD H = U Sigma V^T (H: k x kr row-major, k >= kr, finite), D = I or, with `proper` (k == kr),
-// diag(1, .., 1, det(U V^T)); sigma: the kr singular values, descending; A: k x kr row-major.  One-sided Jacobi on the
-// columns of H (rotations until every pair is orthogonal to working precision), which also leaves the columns that
-// belong to tiny singular values orthogonal to the others to working precision; a column that is exactly null (one pose:
-// H = 0) is replaced by the unit vector with the largest remainder against the columns already there, so A^T A = I
-// whatever the rank.
-void compare_align(int k, int kr, const double *H, bool proper, double *A, double *sigma) {
-  std::vector<double> U(H, H + static_cast<size_t>(k) * kr), V(static_cast<size_t>(kr) * kr, 0.0);
+// The one-sided Jacobi both compare_align and the rounding's basis (capi/round.inc) run: H (k x kr row-major, k >= kr,
+// finite) is divided by its largest |entry| (returned) and its columns are rotated until every pair is orthogonal to
+// working precision; U: the rotated columns (k x kr row-major), V: the accumulated rotations (kr x kr row-major), so that
+// H / scale = U V^T with the columns of U orthogonal.
+double compare_jacobi(int k, int kr, const double *H, std::vector<double> &U, std::vector<double> &V) {
+  U.assign(H, H + static_cast<size_t>(k) * kr);
+  V.assign(static_cast<size_t>(kr) * kr, 0.0);
   for (int j = 0; j < kr; ++j) V[static_cast<size_t>(j) * kr + j] = 1.0;
   double scale = 0.0;
   for (double v : U) scale = std::max(scale, std::fabs(v));
@@ -74,6 +73,18 @@ void compare_align(int k, int kr, const double *H, bool proper, double *A, doubl
       }
     if (!rotated) break;
   }
+  return scale;
+}
+
+// A = U D V^T of the thin SVD H = U Sigma V^T (H: k x kr row-major, k >= kr, finite), D = I or, with `proper` (k == kr),
+// diag(1, .., 1, det(U V^T)); sigma: the kr singular values, descending; A: k x kr row-major.  One-sided Jacobi on the
+// columns of H (rotations until every pair is orthogonal to working precision), which also leaves the columns that
+// belong to tiny singular values orthogonal to the others to working precision; a column that is exactly null (one pose:
+// H = 0) is replaced by the unit vector with the largest remainder against the columns already there, so A^T A = I
+// whatever the rank.
+void compare_align(int k, int kr, const double *H, bool proper, double *A, double *sigma) {
+  std::vector<double> U, V;
+  const double scale = compare_jacobi(k, kr, H, U, V);
   std::vector<double> norm(static_cast<size_t>(kr));
   std::vector<int> order(static_cast<size_t>(kr));
   for (int j = 0; j < kr; ++j) {

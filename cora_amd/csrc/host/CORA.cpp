@@ -150,7 +150,14 @@ CoraResult solveCORA(Problem &problem, const Matrix &x0, int max_relaxation_rank
   if (X.cols() > problem.dim()) {
     printIfVerbose(verbose, "\nProjecting solution to rank " + std::to_string(problem.dim()) + " and refining.");
     auto tp = clk::now();
-    X = projectSolution(problem, X, verbose);
+    if (info && info->device_rounding) {
+      RoundingInfo rounding;
+      X = problem.roundSolution(X, &rounding);
+      printIfVerbose(verbose, "Out of " + std::to_string(problem.numPoses()) + " blocks, " +
+                                  std::to_string(rounding.positive_determinants) + " have positive determinant (device rounding).");
+    } else {
+      X = projectSolution(problem, X, verbose);
+    }
     t_project = since(tp);
     traceBits("projectSolution", X);
     problem.setRank(problem.dim());

@@ -27,6 +27,9 @@ struct CoraSolveInfo {  // extra observability (the reference only prints these)
   int staircase_levels = 0;
   long hessian_vector_products = 0;
   double tnt_seconds = 0, certify_seconds = 0, escape_seconds = 0;  // wall-clock split of the staircase
+  // INPUT (the only one; everything above is written by solveCORA): round the certified point with
+  // Problem::roundSolution -- on the device -- in place of projectSolution.  Without it nothing changes, down to the bit.
+  bool device_rounding = false;
 };
 
 CoraResult solveCORA(Problem &problem, const Matrix &x0, int max_relaxation_rank = 20, bool verbose = false,

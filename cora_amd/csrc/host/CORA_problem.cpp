@@ -1122,6 +1122,27 @@ RelativeError Problem::relativeError(const Matrix &Y, const Matrix &Ref, const P
   return out;
 }
 
+Matrix Problem::roundSolution(const Matrix &Y, RoundingInfo *info) const {
+  checkUpToDate();
+  if (part_world_ > 1) throw std::runtime_error("Problem::roundSolution: not supported on a partitioned handle");
+  checkMatrixShape("Problem::roundSolution::Y", getExpectedVariableSize(), Y.cols(), Y.rows(), Y.cols());
+  ensureContext();
+  Matrix lift_tmp;
+  const Matrix &Yl = lifted(Y, lift_tmp);  // implicit formulation: [Y; 0] on the device, as in saddleEscape
+  const int N = getDataMatrixSize(), k = static_cast<int>(Y.cols());
+  Matrix out(N, dim_);
+  double st[CORA_ROUND_OUT_MAX];
+  CORA_CALL(cora_round(ctx_.get(), Yl.data(), static_cast<int>(Yl.rows()), k, out.data(), N, st), "Problem::roundSolution");
+  if (info) {
+    info->positive_determinants = static_cast<long>(st[0]);
+    info->flipped = st[1] != 0;
+    info->singular_values.assign(st + 2, st + 2 + k);
+  }
+  Matrix Xd = lowered(std::move(out));
+  checkVariablesAreValid(Xd);
+  return Xd;
+}
+
 // src/CORA_problem.cpp:1168-1197: [Y; -chol(Q33red) \ (B^T Y); 0], computed on the device
 Matrix Problem::getTranslationExplicitSolution(const Matrix &Y) const {
   checkMatrixShape("Problem::getTranslationExplicitSolution::Y", rotAndRangeMatrixSize(), Y.cols(), Y.rows(), Y.cols());

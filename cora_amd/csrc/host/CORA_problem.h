@@ -146,6 +146,14 @@ struct RelativeError {
   }
 };
 
+/** EXTENSION beyond the reference: what Problem::roundSolution reports beside the rounded point (include/cora_hip.h,
+ * cora_round_dev). */
+struct RoundingInfo {
+  std::vector<Scalar> singular_values;  // of the relaxed point, descending, one per column
+  long positive_determinants = 0;       // pose blocks of Y Vd with a positive determinant
+  bool flipped = false;                 // fewer than half: the last column was negated
+};
+
 class Problem {
  private:
   int dim_;
@@ -413,6 +421,14 @@ class Problem {
    * else of the handle changes.  No pairs: zeros.  std::runtime_error on a
    * partitioned handle and without a live device handle (run a solve or an operator after updateProblemData first). */
   RelativeError relativeError(const Matrix &Y, const Matrix &Ref, const PosePairs &pairs);
+
+  /** EXTENSION beyond the reference: projectSolution on the device (cora_round, include/cora_hip.h) -- the d dominant
+   * singular directions of Y from its Gram matrix, the majority rule on the determinants, every pose block projected to
+   * SO(d) by a one-sided Jacobi on the block itself, range rows normalised.  Y: getExpectedVariableSize() rows, d..24
+   * columns (lifted to [Y; 0] and lowered again in the implicit formulation); returns the same rows, d columns, and ends
+   * with checkVariablesAreValid.  Changes nothing of the handle; Problem gains no member.  std::runtime_error on a
+   * partitioned handle. */
+  Matrix roundSolution(const Matrix &Y, RoundingInfo *info = nullptr) const;
 
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;

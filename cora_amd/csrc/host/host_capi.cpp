@@ -447,6 +447,20 @@ int cora_problem_project_solution(cora_problem *p, const double *Y, double *y_ou
   });
 }
 
+int cora_problem_round_solution(const cora_problem *p, const double *Y, int cols, double *y_out, double *info) {
+  return guarded([&] {
+    const Problem &q = p->problem;
+    RoundingInfo ri;
+    const Matrix out = q.roundSolution(wrap(Y, q.getExpectedVariableSize(), cols), &ri);
+    std::memcpy(y_out, out.data(), sizeof(double) * static_cast<size_t>(out.size()));
+    if (info) {
+      info[0] = static_cast<double>(ri.positive_determinants);
+      info[1] = ri.flipped ? 1.0 : 0.0;
+      std::copy(ri.singular_values.begin(), ri.singular_values.end(), info + 2);
+    }
+  });
+}
+
 int cora_problem_certify_chain(cora_problem *p, const double *Y, double eta, int nx, int resident, double out[6], double *x) {
   return guarded([&] {
     // two certifications in a row at the same point, the second one started from the first one's Ritz block: handed over
@@ -556,7 +570,13 @@ int cora_host_fast_verification_pieces(int n, const int32_t *rowptr, const int32
 
 int cora_problem_solve(cora_problem *p, const double *x0, int max_rank, int verbose, const double *opts,
                        double *x_out, double stats[11]) {
+  return cora_problem_solve_flags(p, x0, max_rank, verbose, opts, 0, x_out, stats);
+}
+
+int cora_problem_solve_flags(cora_problem *p, const double *x0, int max_rank, int verbose, const double *opts, int flags,
+                             double *x_out, double stats[11]) {
   return guarded([&] {
+    if (flags & ~CORA_SOLVE_DEVICE_ROUNDING) throw std::invalid_argument("cora_problem_solve_flags: unknown flag");
     Problem &q = p->problem;
     const Index N = q.getExpectedVariableSize(), r = static_cast<Index>(q.getRelaxationRank());
     TNTParams prm;
@@ -568,6 +588,7 @@ int cora_problem_solve(cora_problem *p, const double *x0, int max_rank, int verb
       if (opts[4] > 0) prm.max_computation_time = opts[4];
     }
     CoraSolveInfo info;
+    info.device_rounding = (flags & CORA_SOLVE_DEVICE_ROUNDING) != 0;
     const auto t0 = std::chrono::steady_clock::now();
     const CoraResult res = solveCORA(q, wrap(x0, N, r), max_rank, verbose != 0, false, false, &info, &prm);
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

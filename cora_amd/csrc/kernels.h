@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 
 #include "cora_internal.h"
@@ -444,6 +445,298 @@ inline int rpe_blocks(int64_t m) { return compare_blocks(m); }
 hipError_t launch_rpe(const RpeArgs &A, hipStream_t st);  // rpe_blocks(m) blocks; m == 0: invalid
 // stats[5] = sum et^2, sum er^2, max et, max er, first pair that attains max et, from the partials of launch_rpe
 hipError_t launch_rpe_finish(const double *partial, int nblocks, int64_t m, double *stats, hipStream_t st);
+
+// Scale guard of the normalisations of rows.inc and of the rounding below.  The polar factor of a block and the direction
+// of a row do not change when the input is multiplied by a positive number, but their formulas square the entries:
+// sqrt(alpha * beta) is a product of two squared row norms (0 below |A| ~ 1e-77, inf above 1e77) and dot_row(a, a) leaves
+// the range at 1e+-154.  Returns the exponent e for which ldexp(x, e) -- exact -- brings a block whose largest |entry| is
+// amax to [1/2, 1), and 0 (leave the block alone: the arithmetic of an ordinary block is untouched) when amax already
+// lies in [2^-250, 2^250], where a product of two squared norms of <= 24 entries stays finite, or is 0, inf or NaN.
+__host__ __device__ inline int rescale_exponent(double amax) {
+  if ((amax >= 0x1p-250 && amax <= 0x1p250) || !(amax > 0.0) || !(amax < HUGE_VAL)) return 0;
+  int e;
+  (void)frexp(amax, &e);
+  return -e;
+}
+
+// Rounding of a resident vector Y (k columns, d <= k <= 24) to SE(d): out = d columns at stride ld_for(d)
+// (kernels/round.inc; include/cora_hip.h, cora_round_dev).  One thread per unit of RowArgs (pose block, range row,
+// translation row).  vd: the basis, column-major k x d, for the translation rows; vd_dir: the same basis times the power
+// of two that brings an extreme-scale Y into range (equal to vd otherwise), for the pose blocks and the range rows, whose
+// results do not depend on a positive scale.  Three launches without a host step between them:
+//   count  : partial[round_count_blocks] = number of pose blocks of the block with det(Y_i Vd) > 0 (fixed slots)
+//   finish : words[0] = their sum, words[1] = 1 when the sum < n / 2 (integer division): the last column is negated
+//   apply  : every unit's rows of out; reads words[1]; flag |= 1 where a product is not finite
+struct RoundArgs {
+  RowArgs R;
+  int k = 0, ldy = 0;
+  const double *Y = nullptr;
+  double *out = nullptr;
+  int *partial = nullptr, *words = nullptr, *flag = nullptr;
+  double vd[kMaxLD * 3], vd_dir[kMaxLD * 3];
+};
+constexpr int kRoundCountBlock = 64;  // poses per block of the count pass: one wavefront, its partial is a ballot
+inline int round_count_blocks(int64_t poses) { return static_cast<int>((poses + kRoundCountBlock - 1) / kRoundCountBlock); }
+hipError_t launch_round_count(const RoundArgs &A, hipStream_t st);  // + the finish; no poses: words = {0, 0}
+hipError_t launch_round_apply(const RoundArgs &A, hipStream_t st);
+// the rare path of an input whose Gram matrix leaves the range: partial[blocks] = max |y| (finish: launch_reduce_max_partials),
+// flag |= 1 where an entry is not finite;  out = ldexp(y, e)
+hipError_t launch_round_amax(int64_t n, const double *y, double *partial, int nblocks, int *flag, hipStream_t st);
+hipError_t launch_round_scale(int64_t n, const double *y, int e, double *out, hipStream_t st);
+
+// The arithmetic of one unit (round_pose, round_row and their parts), shared by the kernels and the host mirror
+// (cora_debug_round_host): every operation is a
+// single correctly rounded fp64 one in the order written, never contracted; a fused one is an explicit fma.
+// m[b] = sum over a = 0 .. k - 1 of row[a] vd[b k + a], one fma per term from +0.0, b < D
+template <int D>
+__host__ __device__ inline void round_product(const double *row, int k, const double *vd, double *m) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int b = 0; b < D; ++b) m[b] = 0.0;
+  for (int a = 0; a < k; ++a) {
+    const double y = row[a];
+#pragma unroll
+    for (int b = 0; b < D; ++b) m[b] = fma(y, vd[b * k + a], m[b]);
+  }
+}
+// ldexp by rescale_exponent of the largest |entry| (exact; nothing for an ordinary block)
+template <int N>
+__host__ __device__ inline void round_rescale(double *m) {
+  double amax = 0.0;
+#pragma unroll
+  for (int i = 0; i < N; ++i) amax = fmax(amax, fabs(m[i]));
+  const int e = rescale_exponent(amax);
+  if (e != 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) m[i] = ldexp(m[i], e);
+  }
+}
+template <int D>
+__host__ __device__ inline double round_det(const double (&m)[D][D]) {
+#pragma clang fp contract(off)
+  if constexpr (D == 2) {
+    return fma(m[0][0], m[1][1], -(m[0][1] * m[1][0]));
+  } else {
+    const double c0 = fma(m[1][1], m[2][2], -(m[1][2] * m[2][1]));
+    const double c1 = fma(m[1][2], m[2][0], -(m[1][0] * m[2][2]));
+    const double c2 = fma(m[1][0], m[2][1], -(m[1][1] * m[2][0]));
+    return fma(m[0][0], c0, fma(m[0][1], c1, m[0][2] * c2));
+  }
+}
+// whether det(M) > 0, on the rescaled block (the sign does not depend on a positive scale; the determinant of an
+// extreme-scale block would leave the range)
+template <int D>
+__host__ __device__ inline bool round_det_positive(double (&m)[D][D]) {
+  round_rescale<D * D>(&m[0][0]);
+  return round_det<D>(m) > 0.0;
+}
+template <int D>
+__host__ __device__ inline void round_cross(const double *a, const double *b, double *c) {
+#pragma clang fp contract(off)
+  static_assert(D == 3, "cross products complete frames at d = 3");
+  c[0] = fma(a[1], b[2], -(a[2] * b[1]));
+  c[1] = fma(a[2], b[0], -(a[0] * b[2]));
+  c[2] = fma(a[0], b[1], -(a[1] * b[0]));
+}
+// The rotation R in SO(D) that maximises tr(R^T M), in place; M finite.  One-sided (Hestenes) Jacobi on the rows as in
+// polar_rows (rows.inc): rotations J, a product of proper rotations, leave J M = diag(n) Q with orthogonal rows n_i q_i;
+// polar(M) = J^T Q and det(polar) = det(Q).  With all rows there and det(Q) < 0 the row of smallest norm is negated: the
+// correction sits on the smallest singular value.  A row whose squared norm is below 2^-960 after the rescaling -- below
+// 2^-355 of the largest entry at the least, where eps times the condition number is beyond every bound -- counts as
+// missing, takes part in no rotation and is completed: the perpendicular at D = 2, cross products at D = 3 (one row left:
+// the frame built from the axis it is furthest from), so that det = +1; no row left: J is the identity, and so is R.
+template <int D>
+__host__ __device__ inline void round_rotation(double (&a)[D][D]) {
+#pragma clang fp contract(off)
+  constexpr double kTiny = 0x1p-960;
+  round_rescale<D * D>(&a[0][0]);
+  double J[D][D];
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int j = 0; j < D; ++j) J[i][j] = (i == j) ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    double off = 0.0;
+#pragma unroll
+    for (int p = 0; p < D - 1; ++p)
+#pragma unroll
+      for (int q = p + 1; q < D; ++q) {
+        double alpha = 0.0, beta = 0.0, gamma = 0.0;
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+          alpha = fma(a[p][c], a[p][c], alpha);
+          beta = fma(a[q][c], a[q][c], beta);
+          gamma = fma(a[p][c], a[q][c], gamma);
+        }
+        if (gamma != 0.0 && alpha >= kTiny && beta >= kTiny) {
+          const double denom = sqrt(alpha * beta);
+          off = fmax(off, fabs(gamma) / denom);
+          const double zeta = (beta - alpha) / (2.0 * gamma);
+          const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(fma(zeta, zeta, 1.0)));
+          const double cs = 1.0 / sqrt(fma(t, t, 1.0)), sn = cs * t;
+#pragma unroll
+          for (int c = 0; c < D; ++c) {
+            const double x = a[p][c], y = a[q][c];
+            a[p][c] = fma(cs, x, -(sn * y));
+            a[q][c] = fma(sn, x, cs * y);
+          }
+#pragma unroll
+          for (int c = 0; c < D; ++c) {
+            const double x = J[p][c], y = J[q][c];
+            J[p][c] = fma(cs, x, -(sn * y));
+            J[q][c] = fma(sn, x, cs * y);
+          }
+        }
+      }
+    if (off < 1e-15) break;
+  }
+  double nrm2[D];
+  double least = 0.0;
+  int present = 0, smallest = 0;  // (the first of equal norms)
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < D; ++c) s = fma(a[i][c], a[i][c], s);
+    nrm2[i] = s;
+    if (i == 0 || s < least) {
+      least = s;
+      smallest = i;
+    }
+    if (s >= kTiny) {
+      ++present;
+      const double nrm = sqrt(s);
+#pragma unroll
+      for (int c = 0; c < D; ++c) a[i][c] = a[i][c] / nrm;
+    } else {
+#pragma unroll
+      for (int c = 0; c < D; ++c) a[i][c] = 0.0;
+    }
+  }
+  if (present == D) {
+    if (round_det<D>(a) < 0.0) {
+#pragma unroll
+      for (int i = 0; i < D; ++i)
+        if (i == smallest) {
+#pragma unroll
+          for (int c = 0; c < D; ++c) a[i][c] = -a[i][c];
+        }
+    }
+  } else if (present == 0) {
+#pragma unroll
+    for (int i = 0; i < D; ++i) a[i][i] = 1.0;
+  } else if constexpr (D == 2) {
+    if (nrm2[0] >= kTiny) {  // det [x y; -y x] = 1
+      a[1][0] = -a[0][1];
+      a[1][1] = a[0][0];
+    } else {
+      a[0][0] = a[1][1];
+      a[0][1] = -a[1][0];
+    }
+  } else {
+    if (present == 1) {
+      // the row that is there, u, at place p; the axis e it is furthest from; v = (u x e) / |u x e|, then w = u x v:
+      // (u, v, w) at the places (p, p + 1, p + 2) mod 3, an even permutation
+      const int p = nrm2[0] >= kTiny ? 0 : (nrm2[1] >= kTiny ? 1 : 2);
+      double u[3], e[3] = {0.0, 0.0, 0.0}, v[3], w[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        if (i == p) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) u[c] = a[i][c];
+        }
+      const int ax = (fabs(u[0]) <= fabs(u[1]) && fabs(u[0]) <= fabs(u[2])) ? 0 : (fabs(u[1]) <= fabs(u[2]) ? 1 : 2);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) e[c] = c == ax ? 1.0 : 0.0;
+      round_cross<3>(u, e, v);
+      const double nv = sqrt(fma(v[0], v[0], fma(v[1], v[1], v[2] * v[2])));
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c] = v[c] / nv;
+      round_cross<3>(u, v, w);
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          if (i == (p + 1) % 3) a[i][c] = v[c];
+          if (i == (p + 2) % 3) a[i][c] = w[c];
+        }
+    } else {
+      // two rows there: the third is the cross product of the other two in cyclic order (det = +1), normalised (the two
+      // are orthogonal to working precision only)
+      const int z = nrm2[0] < kTiny ? 0 : (nrm2[1] < kTiny ? 1 : 2);
+      double x[3], y[3], w[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          if (i == (z + 1) % 3) x[c] = a[i][c];
+          if (i == (z + 2) % 3) y[c] = a[i][c];
+        }
+      round_cross<3>(x, y, w);
+      const double nw = sqrt(fma(w[0], w[0], fma(w[1], w[1], w[2] * w[2])));
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        if (i == z) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) a[i][c] = w[c] / nw;
+        }
+    }
+  }
+  double o[D][D];
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int j = 0; j < D; ++j) s = fma(J[j][i], a[j][c], s);
+      o[i][c] = s;
+    }
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int c = 0; c < D; ++c) a[i][c] = o[i][c];
+}
+// a range row: the direction of m (D entries), a zero row stays zero
+template <int D>
+__host__ __device__ inline void round_direction(double *m) {
+#pragma clang fp contract(off)
+  round_rescale<D>(m);
+  double s = 0.0;
+#pragma unroll
+  for (int c = 0; c < D; ++c) s = fma(m[c], m[c], s);
+  const double nrm = sqrt(s);
+  if (nrm > 0.0) {
+#pragma unroll
+    for (int c = 0; c < D; ++c) m[c] = m[c] / nrm;
+  }
+}
+// One unit.  round_pose: the D rows of a pose block (row, row + ldy, ..) through vd_dir, the flip, then round_rotation;
+// round_row: a range row (through vd_dir, then its direction) or a translation row (through vd).  Both return whether every
+// product was finite; a unit that is not keeps its products.
+template <int D>
+__host__ __device__ inline bool round_pose(const double *row, int ldy, int k, const double *vd_dir, bool flip, double (&m)[D][D]) {
+  bool finite = true;
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    round_product<D>(row + static_cast<size_t>(i) * ldy, k, vd_dir, m[i]);
+    if (flip) m[i][D - 1] = -m[i][D - 1];
+#pragma unroll
+    for (int c = 0; c < D; ++c) finite = finite && fabs(m[i][c]) <= 1.79769313486231570815e308;
+  }
+  if (finite) round_rotation<D>(m);
+  return finite;
+}
+template <int D>
+__host__ __device__ inline bool round_row(bool range, const double *row, int k, const double *vd, bool flip, double (&m)[D]) {
+  bool finite = true;
+  round_product<D>(row, k, vd, m);
+  if (flip) m[D - 1] = -m[D - 1];
+#pragma unroll
+  for (int c = 0; c < D; ++c) finite = finite && fabs(m[c]) <= 1.79769313486231570815e308;
+  if (range && finite) round_direction<D>(m);
+  return finite;
+}
 
 // In-place update of Q's values (kernels/update_values.inc).  src: the sources of ValueMap (cora_internal.h), vals: the
 // new CSR values on the device.

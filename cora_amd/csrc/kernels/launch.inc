@@ -479,6 +479,42 @@ hipError_t launch_rpe_finish(const double *partial, int nblocks, int64_t m, doub
   return hipGetLastError();
 }
 
+// the rounding to SE(d) (kernels/round.inc): the count pass by wavefronts of poses with its one-wavefront finish, the apply
+// pass by blocks of 256 units
+static bool round_args_ok(const RoundArgs &A) {
+  return (A.R.d == 2 || A.R.d == 3) && A.k >= A.R.d && A.k <= A.ldy && A.ldy <= kMaxLD && A.R.nl_poses >= 0 && A.R.nl_ranges >= 0 &&
+         A.R.nl_trans >= 0;
+}
+hipError_t launch_round_count(const RoundArgs &A, hipStream_t st) {
+  if (!round_args_ok(A)) return hipErrorInvalidValue;
+  const int nb = round_count_blocks(A.R.nl_poses);
+  if (nb > 0) {
+    if (A.R.d == 2) hipLaunchKernelGGL(k_round_count<2>, dim3(nb), dim3(kRoundCountBlock), 0, st, A);
+    else hipLaunchKernelGGL(k_round_count<3>, dim3(nb), dim3(kRoundCountBlock), 0, st, A);
+  }
+  hipLaunchKernelGGL(k_round_finish, dim3(1), dim3(64), 0, st, A.partial, nb, A.R.nl_poses, A.words);
+  return hipGetLastError();
+}
+hipError_t launch_round_apply(const RoundArgs &A, hipStream_t st) {
+  if (!round_args_ok(A)) return hipErrorInvalidValue;
+  const int64_t units = static_cast<int64_t>(A.R.nl_poses) + A.R.nl_ranges + A.R.nl_trans;
+  const int grid = static_cast<int>((units + 255) / 256);
+  if (grid == 0) return hipSuccess;
+  if (A.R.d == 2) hipLaunchKernelGGL(k_round_apply<2>, dim3(grid), dim3(256), 0, st, A);
+  else hipLaunchKernelGGL(k_round_apply<3>, dim3(grid), dim3(256), 0, st, A);
+  return hipGetLastError();
+}
+hipError_t launch_round_amax(int64_t n, const double *y, double *partial, int nblocks, int *flag, hipStream_t st) {
+  if (n < 1 || nblocks < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_round_amax, dim3(nblocks), dim3(256), 0, st, n, y, partial, flag);
+  return hipGetLastError();
+}
+hipError_t launch_round_scale(int64_t n, const double *y, int e, double *out, hipStream_t st) {
+  if (n < 1) return hipSuccess;
+  hipLaunchKernelGGL(k_round_scale, dim3(grid_for(n)), dim3(256), 0, st, n, y, e, out);
+  return hipGetLastError();
+}
+
 // in-place update of Q's values (kernels/update_values.inc): two slots per thread
 hipError_t launch_values_check(int64_t nnz, const double *vals, int64_t n_pairs, const int32_t *mirror, int *flag,
                                hipStream_t st) {

@@ -140,18 +140,7 @@ __global__ __launch_bounds__(256) void k_tangent_project(const RowArgs R, const 
   }
 }
 
-// Scale guard of the normalisations below.  The polar factor of a block and the direction of a row do not change when
-// the input is multiplied by a positive number, but their formulas square the entries: sqrt(alpha * beta) is a product
-// of two squared row norms (0 below |A| ~ 1e-77, inf above 1e77) and dot_row(a, a) leaves the range at 1e+-154.
-// Returns the exponent e for which ldexp(x, e) -- exact -- brings a block whose largest |entry| is amax to [1/2, 1),
-// and 0 (leave the block alone: the arithmetic of an ordinary block is untouched) when amax already lies in
-// [2^-250, 2^250], where a product of two squared norms of <= 24 entries stays finite, or is 0, inf or NaN.
-__device__ __forceinline__ int rescale_exponent(double amax) {
-  if ((amax >= 0x1p-250 && amax <= 0x1p250) || !(amax > 0.0) || !(amax < HUGE_VAL)) return 0;
-  int e;
-  (void)frexp(amax, &e);
-  return -e;
-}
+// (the scale guard of the normalisations below, rescale_exponent, lives in kernels.h: the rounding and its host mirror use it too)
 
 // Polar factor of a d x LD block by one-sided (Hestenes) Jacobi on its rows:
 // rotations J with (J A) having orthogonal rows;  A = J^T Sigma U  =>  polar = J^T U.

@@ -7,6 +7,7 @@ from . import capi
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
+SOLVE_DEVICE_ROUNDING = 1  # CORA_SOLVE_DEVICE_ROUNDING (include/cora_host.h): a flag of cora_problem_solve_flags
 
 
 class HostError(RuntimeError):
@@ -494,6 +495,22 @@ class Problem:
         self._chk(self.L.cora_problem_project_solution(self.h, Y.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
         return out
 
+    def round_solution(self, Y, info=False):
+        """Problem::roundSolution: projectSolution on the device (include/cora_hip.h, cora_round) -- variable_size() x k,
+        d <= k <= 24, to variable_size() x d.  info=True: (X, dict count, flipped, sigma)."""
+        dm = self.dims()
+        Y = np.asfortranarray(np.asarray(Y, dtype=np.float64))
+        if Y.ndim != 2 or Y.shape[0] != self.variable_size():
+            raise HostError("expected %d rows, got shape %s" % (self.variable_size(), Y.shape))
+        k = Y.shape[1]
+        out = np.zeros((self.variable_size(), dm["d"]), order="F")
+        st = np.zeros(2 + max(k, 1))
+        self._chk(self.L.cora_problem_round_solution(self.h, Y.ctypes.data_as(_dp), int(k), out.ctypes.data_as(_dp),
+                                                     st.ctypes.data_as(_dp)))
+        if not info:
+            return out
+        return out, dict(count=int(st[0]), flipped=bool(st[1]), sigma=st[2:2 + k].copy())
+
     def certify_chain(self, Y, eta, nx=10, resident=False):
         """Two certifications in a row, the second started from the first one's Ritz block (host hand-over or resident)."""
         dm = self.dims()
@@ -514,15 +531,22 @@ class Problem:
         self._chk(self.L.cora_problem_certification_reached_step3(self.h, C.byref(v)))
         return bool(v.value)
 
-    def solve(self, x0, max_rank=10, verbose=False, max_seconds=0, max_iterations=0):
+    def solve(self, x0, max_rank=10, verbose=False, max_seconds=0, max_iterations=0, device_rounding=False):
+        """solveCORA.  device_rounding: round the certified point with round_solution (on the device) in place of
+        project_solution (CoraSolveInfo::device_rounding)."""
         dm = self.dims()
         x0 = np.asfortranarray(np.asarray(x0, dtype=np.float64))
         opts = np.array([max_iterations, 0, 0, 0, max_seconds, 0.0])
         out = np.zeros((self.variable_size(), dm["d"]), order="F")
         st = np.zeros(11)
-        self._chk(self.L.cora_problem_solve(self.h, x0.ctypes.data_as(_dp), int(max_rank), int(verbose),
-                                            opts.ctypes.data_as(_dp), out.ctypes.data_as(_dp),
-                                            st.ctypes.data_as(_dp)))
+        if device_rounding:
+            self._chk(self.L.cora_problem_solve_flags(self.h, x0.ctypes.data_as(_dp), int(max_rank), int(verbose),
+                                                      opts.ctypes.data_as(_dp), SOLVE_DEVICE_ROUNDING, out.ctypes.data_as(_dp),
+                                                      st.ctypes.data_as(_dp)))
+        else:
+            self._chk(self.L.cora_problem_solve(self.h, x0.ctypes.data_as(_dp), int(max_rank), int(verbose),
+                                                opts.ctypes.data_as(_dp), out.ctypes.data_as(_dp),
+                                                st.ctypes.data_as(_dp)))
         return dict(x=out, f=st[0], grad_norm=st[1], certified=bool(st[2]), eta=st[3], theta=st[4],
                     final_rank=int(st[5]), levels=int(st[6]), hvps=int(st[7]), seconds=st[8],
                     relaxation_certified=bool(st[9]), relaxation_rank=int(st[10]))

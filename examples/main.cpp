@@ -22,12 +22,12 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]]" << std::endl;
+    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding]" << std::endl;
     return 1;
   }
   int max_rank = 10;
   std::string tum, save_dir, residuals, weights, robust, barc2, weights_out, aligned_tum, rpe_steps, rpe_dists;
-  bool jacobi = false, implicit = false, odom = false, evaluate = false;
+  bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--jacobi") jacobi = true;
@@ -54,6 +54,8 @@ int main(int argc, char **argv) {
     // number of steps apart, pairs at least a path length apart along the ground truth
     else if (a == "--rpe" && i + 1 < argc) rpe_steps = argv[++i];
     else if (a == "--rpe-dist" && i + 1 < argc) rpe_dists = argv[++i];
+    // the certified point is rounded on the device (Problem::roundSolution) in place of projectSolution
+    else if (a == "--device-rounding") device_rounding = true;
   }
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
@@ -108,7 +110,9 @@ int main(int argc, char **argv) {
     if (odom && implicit)  // examples/paper_experiments.cpp:623-625
       x0 = x0.block(0, 0, problem.rotAndRangeMatrixSize(), x0.cols());
     CORA::CoraSolveInfo info;
+    info.device_rounding = device_rounding;  // (an extension beyond the reference: CoraSolveInfo::device_rounding)
     CORA::CoraResult soln;
+    if (device_rounding && !robust.empty()) throw std::runtime_error("--device-rounding applies to the plain solve, not to --robust");
     if (robust.empty()) {
       if (!barc2.empty() || !weights_out.empty()) throw std::runtime_error("--barc2 and --weights-out need --robust tls|gm");
       soln = CORA::solveCORA(problem, x0, max_rank, /*verbose=*/true, false, false, &info);

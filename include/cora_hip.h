@@ -667,6 +667,54 @@ int cora_rpe(cora_ctx *ctx, const double *X, int ldx, int k, const double *Ref, 
 int cora_debug_rpe_host(cora_ctx *ctx, const double *X, int ldx, int k, const double *Ref, int ldref, int kr,
                         double *trans_err, double *rot_err, double out[6]);
 
+/* ---- ROUNDING of a relaxed point to SE(d), on the device -------------------------------------------------------------------
+ * The step between a certified point of rank k and the rank-d estimate (projectSolution on the host): the input is a
+ * resident vector Y of k columns, d <= k <= 24; the output a resident vector of d columns at stride cora_ld_for(d).  The
+ * two must not overlap.
+ * 1. BASIS.  G = Y^T Y over all rows (the Gram kernel of cora_gram_dev).  The k x k symmetric eigenproblem runs on the host
+ *    (the comparison's one-sided Jacobi).  Vd (k x d): the eigenvectors of the d largest eigenvalues in descending order, each signed so that
+ *    its entry of largest magnitude is positive (the first such entry on a tie).  Singular values: sqrt(max(lambda, 0)),
+ *    descending, all k of them.
+ * 2. COUNT.  M_i = Y_i Vd (d x d) for every pose block; count = the number of blocks with det(M_i) > 0.  When
+ *    count < n / 2 (integer division; the host's rule) the last column of Y Vd is negated for every row of every kind.
+ * 3. APPLY, one unit at a time:
+ *    pose block        the R in SO(d) that maximises tr(R^T M_i): with M_i = U Sigma V^T it is U diag(1, .., 1, det(U V^T)) V^T,
+ *                      the correction on the smallest singular value.  One-sided Jacobi on the block itself (no Gram matrix
+ *                      of the block).  The result is a rotation -- orthonormal, determinant +1 -- for EVERY finite input: a
+ *                      rank-deficient block is completed to a frame (the perpendicular at d = 2, cross products at d = 3),
+ *                      a zero block gives exactly the identity.
+ *    range row         y Vd normalised to unit length; a zero row stays zero.
+ *    translation row   y Vd (poses and landmarks).
+ *    A block or row at an extreme scale is brought into range by an exact power of two first, as the retraction does.  An
+ *    input whose squares leave the range of a double altogether (|y| beyond about 1e+-150) has its Gram matrix formed from
+ *    a copy scaled by a power of two, in a second pass that ordinary inputs never take.
+ *   out      CORA_ROUND_OUT_LEN(k, d) <= CORA_ROUND_OUT_MAX host doubles: the count, flipped (0 / 1), the k singular values,
+ *            Vd column-major (k x d).
+ * ARITHMETIC.  A product y Vd is one fma per term from +0.0 in column order; every later operation of a unit is a single
+ * correctly rounded one in a fixed order, never contracted.  A unit's output is a function of its own rows, Vd and the flip:
+ * the same bits on every call.  The count is a sum of integers.  No atomics on doubles.
+ * cora_round_dev        dY: k columns, dOut: d columns (cora_dev_alloc(ctx, d, ..)).  Synchronises (twice: the basis is
+ *            formed on the host; count, its finish and the apply pass follow each other on the stream without a host step).
+ * cora_round            the host-pointer form: Y is N x k, Out N x d, column-major with leading dimensions; its two vectors
+ *            are released before it returns.
+ * cora_debug_round_host the same on the host; works on a plan-only handle.  basis == NULL: Vd from this form's own Gram
+ *            matrix (plain sums in row order).  basis != NULL (k x d column-major, e.g. the Vd a device call returned): the
+ *            units run through the very functions the kernels call, so every output row, the count and the flip have the
+ *            device's bits.  The singular values in `out` are this form's own in both cases.
+ * ACCURACY.  A pose block against exact arithmetic on the same Vd: within a small multiple of eps kappa, kappa =
+ * 2 sigma_1 / (sigma_{d-1} + s sigma_d) of M_i with s the sign of det(M_i), plus the forward error (k + 2) eps |Y_i| |Vd| of
+ * the product scaled by kappa / sigma_1 (tests/round_ref.py calibrates the multiple on a float64 SVD; profiles/round.md).
+ * ERRORS.  CORA_ERR_ARG: a partitioned handle, a null pointer, an output that overlaps the input; CORA_ERR_SHAPE: k < d or
+ * k > 24, a leading dimension below N; CORA_ERR_NAN: an input entry or a product that is not finite (the device forms report
+ * it through the handle's flag word).  On an error the contents of the outputs are unspecified.
+ * STATE.  The calls never change what the handle computes with.  Nothing is kept on the handle between calls. */
+#define CORA_ROUND_OUT_LEN(k, d) (2 + (k) + (k) * (d))
+#define CORA_ROUND_OUT_MAX 98 /* k = 24, d = 3 */
+int cora_round_dev(cora_ctx *ctx, const double *dY, int k, double *dOut, double *out);
+int cora_round(cora_ctx *ctx, const double *Y, int ldy, int k, double *Out, int ldo, double *out);
+int cora_debug_round_host(cora_ctx *ctx, const double *Y, int ldy, int k, const double *basis, double *Out, int ldo,
+                          double *out);
+
 /* Timing helpers: HIP events on the handle's stream. */
 int cora_timer_start(cora_ctx *ctx);
 int cora_timer_stop_ms(cora_ctx *ctx, float *ms); /* synchronises */

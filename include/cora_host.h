@@ -156,6 +156,10 @@ int cora_problem_pose_pairs(const cora_problem *p, int step, const double *Ref, 
 int cora_problem_relative_error(cora_problem *p, const double *Y, int cols, const double *Ref, int ref_cols, int64_t m,
                                 const int32_t *pairs, const double *path_length, double *trans_err, double *rot_err,
                                 double out[8]);
+/* Problem::roundSolution (an extension beyond the reference): projectSolution on the device (include/cora_hip.h,
+ * cora_round).  Y: variable size x cols, d <= cols <= 24; y_out: variable size x d.  info: NULL or 2 + cols doubles -- the
+ * pose blocks of positive determinant, flipped (0 / 1), the singular values of Y (descending). */
+int cora_problem_round_solution(const cora_problem *p, const double *Y, int cols, double *y_out, double *info);
 /* solveRobustCORA (an extension beyond the reference; CORA/CORA.h): graduated non-convexity over solveCORA from x0
  * (N x rank).  thresholds / lengths / cost (1 or 2) / couple_edges as above; mu_factor > 1; max_outer: cap on the rounds.
  * x_out: N x d.  stats: as cora_problem_solve, of the last solve.  robust: [0] rounds, [1] 1 = converged (0: the cap),
@@ -241,6 +245,11 @@ int cora_problem_project_solution(cora_problem *p, const double *Y, double *y_ou
  * was certified (0: it reached max_rank), [10] the rank of that level. */
 int cora_problem_solve(cora_problem *p, const double *x0, int max_rank, int verbose, const double *opts,
                        double *x_out, double stats[11]);
+/* The same with flags: CORA_SOLVE_DEVICE_ROUNDING rounds the certified point with Problem::roundSolution (on the device)
+ * in place of projectSolution (CoraSolveInfo::device_rounding); 0 is cora_problem_solve. */
+#define CORA_SOLVE_DEVICE_ROUNDING 1
+int cora_problem_solve_flags(cora_problem *p, const double *x0, int max_rank, int verbose, const double *opts, int flags,
+                             double *x_out, double stats[11]);
 
 /* After a preconditioned call: [0] regularisation lambda used, [1] nnz(L), [2] elimination-tree height. */
 int cora_problem_precond_info(cora_problem *p, double info[3]);
