@@ -1,6 +1,6 @@
 """Builds cora_amd/lib/libcora_hip.so with hipcc for gfx950 (no GPU needed).
 
-Sources: csrc/format_build.cpp (host format builder), csrc/assembly_build.cpp
+Sources: csrc/format_build.cpp (host format builder), csrc/long_image.cpp (device image of the long rows), csrc/assembly_build.cpp
 (term map of Q(w)), csrc/trisolve_build.cpp and csrc/trisolve_image.cpp (solve plan of a Cholesky factor and its
 device image), csrc/kernels.hip (CDNA4
 kernels), csrc/capi.hip (C ABI, include/cora_hip.h), csrc/p2p.hip (device-side
@@ -27,7 +27,7 @@ KERNEL_PARTS = [("spmm_g0", 1, 1), ("spmm_g1", 1, 2), ("spmm_g2", 1, 4), ("spmm_
 
 
 def sources():
-    srcs = [os.path.join(CSRC, f) for f in ("config.cpp", "format_build.cpp", "assembly_build.cpp", "trisolve_build.cpp", "trisolve_image.cpp", "kernels.hip", "capi.hip", "p2p.hip")]
+    srcs = [os.path.join(CSRC, f) for f in ("config.cpp", "format_build.cpp", "assembly_build.cpp", "trisolve_build.cpp", "trisolve_image.cpp", "long_image.cpp", "kernels.hip", "capi.hip", "p2p.hip")]
     srcs += sorted(glob.glob(os.path.join(CSRC, "host", "*.cpp")))
     return srcs
 

@@ -284,6 +284,26 @@ class Context:
         self._chk(self.L.cora_debug_value_map_digest(self.h, out))
         return int(out[0]), int(out[1])
 
+    def debug_long_image(self, piece=0):
+        """The device image of the long rows (cora_debug_long_image; no GPU needed): dict with `placed`, `chunks`
+        (dict of int32 arrays: row, k0, k1, nchunks, first, slot), `chunk_order`, `lval`, `lcol` (internal rows), `perm`, `home`
+        and `home_pose_first` (int8 per internal row, -1 = no slice owns it).  piece <= 0: the library's piece size."""
+        s = (C.c_int64 * 5)()
+        self._chk(self.L.cora_debug_long_image(self.h, int(piece), s, None, None, None, None, None, None, None))
+        chunks = np.zeros((int(s[0]), 8), dtype=np.int32)
+        order = np.zeros(int(s[1]), dtype=np.int32)
+        lval = np.zeros(int(s[2]), dtype=np.float64)
+        lcol = np.zeros(int(s[2]), dtype=np.int32)
+        perm = np.zeros(int(s[2]), dtype=np.int32)
+        home = np.zeros(int(s[3]), dtype=np.int8)
+        home_pf = np.zeros(int(s[3]), dtype=np.int8)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._chk(self.L.cora_debug_long_image(self.h, int(piece), s, vp(chunks), vp(order), vp(lval), vp(lcol), vp(perm),
+                                               vp(home), vp(home_pf)))
+        names = ["row", "k0", "k1", "nchunks", "first", "slot"]
+        return {"placed": bool(s[4]), "chunks": {k: chunks[:, i].copy() for i, k in enumerate(names)}, "chunk_order": order,
+                "lval": lval, "lcol": lcol, "perm": perm, "home": home, "home_pose_first": home_pf}
+
     def precond_entries(self):
         """Entries the installed preconditioner's solve plan stores (cora_precond_entries)."""
         s = (C.c_int64 * 6)()

@@ -56,6 +56,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "config.h"
 #include "cora_internal.h"
 #include "kernels.h"
+#include "long_image.h"
 #include "p2p.h"
 #include "parallel.h"
 #include "trisolve_image.h"
@@ -107,6 +108,7 @@ struct PosePairTable {
 };
 struct cora_ctx {
   HostFormat F;
+  LongImage LI;  // what the long rows' device arrays hold (long_image.h); derived from F at creation, device handles only
   MeasurementTable meas;
   PosePairTable pairs;
   cora_native_comm *native_comm = nullptr;  // owned: the library's own communication (cora_comm_create_*)
@@ -411,7 +413,7 @@ SpmmArgs spmm_args(const cora_ctx *c, const double *X, double *out) {
   A.slices = c->d_slices;
   A.slices_pose_first = c->d_slices_pf;
   A.n_slices = static_cast<int>(c->F.slices.size());
-  A.n_chunks = static_cast<int>(c->F.chunks.size());
+  A.n_chunks = static_cast<int>(c->LI.chunk_order.size());  // launch positions of the image: its pieces and the padding of the XCDs' lists
   A.sval = c->d_sval;
   A.head_val = c->d_head_val;
   A.scol = c->d_scol;

@@ -116,10 +116,14 @@ int cora_ctx_create_part_opts(int device, int d, int n_poses, int n_ranges, int 
   CREATE_TRY(to_device(&c->d_sval, F.sval));
   CREATE_TRY(to_device(&c->d_scol, F.scol));
   CREATE_TRY(to_device(&c->d_perm, F.perm));
-  CREATE_TRY(to_device(&c->d_chunks, F.chunks));
-  CREATE_TRY(to_device(&c->d_chunk_order, F.chunk_order));
-  CREATE_TRY(to_device(&c->d_lval, F.lval));
-  CREATE_TRY(to_device(&c->d_lcol, F.lcol));
+  // the long rows: the image (pieces per XCD), not the format's chunks; its values and columns are not kept on the host
+  c->LI = build_long_image(F);
+  CREATE_TRY(to_device(&c->d_chunks, c->LI.chunks));
+  CREATE_TRY(to_device(&c->d_chunk_order, c->LI.chunk_order));
+  CREATE_TRY(to_device(&c->d_lval, c->LI.lval));
+  CREATE_TRY(to_device(&c->d_lcol, c->LI.lcol));
+  std::vector<double>().swap(c->LI.lval);
+  std::vector<int32_t>().swap(c->LI.lcol);
   CREATE_TRY(to_device(&c->d_api2int, F.api2int));
   {
     std::vector<double> dinv(F.diag.size());
@@ -127,7 +131,7 @@ int cora_ctx_create_part_opts(int device, int d, int n_poses, int n_ranges, int 
     CREATE_TRY(to_device(&c->d_diag_inv, dinv));
   }
   CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_partials),
-                       std::max<size_t>(F.chunks.size(), 1) * kMaxLD * sizeof(double)));
+                       std::max<size_t>(c->LI.chunks.size(), 1) * kMaxLD * sizeof(double)));
   CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_tickets),
                        std::max<size_t>(F.n_long_rows, 1) * sizeof(unsigned)));
   CREATE_TRY(hipMemset(c->d_tickets, 0, std::max<size_t>(F.n_long_rows, 1) * sizeof(unsigned)));

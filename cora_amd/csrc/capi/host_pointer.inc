@@ -227,6 +227,35 @@ int cora_debug_format_digest(const cora_ctx *c, uint64_t out[2]) {
   return CORA_OK;
 }
 
+int cora_debug_long_image(const cora_ctx *c, int piece, int64_t sizes[5], int32_t *chunks, int32_t *chunk_order, double *lval,
+                          int32_t *lcol, int32_t *perm, int8_t *home, int8_t *home_pose_first) {
+  if (!c || !sizes) return CORA_ERR_ARG;
+  if (c->host_values_stale)
+    return fail(const_cast<cora_ctx *>(c), CORA_ERR_NOT_READY,
+                "the host copy of the format holds the values from before cora_update_values_dev: update with host values first");
+  const LongImage I = build_long_image(c->F, piece > 0 ? piece : kLongPiece);
+  sizes[0] = static_cast<int64_t>(I.chunks.size());
+  sizes[1] = static_cast<int64_t>(I.chunk_order.size());
+  sizes[2] = static_cast<int64_t>(I.lval.size());
+  sizes[3] = c->F.L.rows;
+  sizes[4] = I.placed ? 1 : 0;
+  if (chunks) std::memcpy(chunks, I.chunks.data(), I.chunks.size() * sizeof(LongChunk));
+  if (chunk_order) std::copy(I.chunk_order.begin(), I.chunk_order.end(), chunk_order);
+  if (lval) std::copy(I.lval.begin(), I.lval.end(), lval);
+  if (lcol) std::copy(I.lcol.begin(), I.lcol.end(), lcol);
+  if (perm) std::copy(I.perm.begin(), I.perm.end(), perm);
+  std::vector<int8_t> h;
+  if (home) {
+    long_row_homes(c->F, c->F.slices, h);
+    std::copy(h.begin(), h.end(), home);
+  }
+  if (home_pose_first) {
+    long_row_homes(c->F, c->F.slices_pose_first.empty() ? c->F.slices : c->F.slices_pose_first, h);
+    std::copy(h.begin(), h.end(), home_pose_first);
+  }
+  return CORA_OK;
+}
+
 int cora_debug_value_map_digest(cora_ctx *c, uint64_t out[2]) {
   if (!c || !out) return CORA_ERR_ARG;
   if (!c->vmap.built) return fail(c, CORA_ERR_NOT_READY, "no source map yet: call cora_values_map_build or cora_update_values first");

@@ -20,7 +20,7 @@ struct StpcgState;
 struct SpmmArgs {
   const SliceDesc *slices;
   int n_slices;
-  int n_chunks;        // set by the caller: number of long-row chunks
+  int n_chunks;        // set by the caller: launch positions of the long rows' pieces (entries of chunk_order)
   int n_real_chunks;   // filled by launch_spmm
   int n_slice_blocks;  // filled by launch_spmm
   const double *sval;
@@ -28,10 +28,10 @@ struct SpmmArgs {
   const int32_t *scol;
   const int32_t *perm;
   const LongChunk *chunks;
-  const int32_t *chunk_order;
+  const int32_t *chunk_order;  // [n_chunks] piece at every launch position, -1: none (long_image.h)
   const double *lval;
   const int32_t *lcol;
-  double *partials;    // [n_chunks][kMaxLD]
+  double *partials;    // [pieces][kMaxLD]
   unsigned *tickets;   // [n_long_rows], zero between launches
   const double *X;     // rows x LD
   double *out;         // rows x LD (only local rows are written)

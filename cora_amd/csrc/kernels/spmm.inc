@@ -55,7 +55,7 @@ __device__ __forceinline__ void long_chunk_wave(const SpmmArgs &A, int ci) {
   // several chunks: publish the partial WRITE-THROUGH (sc1 stores, so no L2
   // release fence is needed), drain, take a ticket; the last arriver re-reads
   // all partials with sc1 loads (which bypass its L1) and sums them in chunk
-  // order, so the result is deterministic.  gfx950 inter-workgroup hand-off
+  // order (compensated, below), so the result is deterministic.  gfx950 inter-workgroup hand-off
   // recipe R1 (cdna_hip_programming.md, Guideline 16).
   if (lane < LD)
     __hip_atomic_store(A.partials + static_cast<size_t>(ci) * kMaxLD + lane, tot, __ATOMIC_RELAXED,
@@ -73,18 +73,27 @@ __device__ __forceinline__ void long_chunk_wave(const SpmmArgs &A, int ci) {
   double s = 0.0;
   if (lane < LD) {
     const double *P = A.partials + static_cast<size_t>(ch.first) * kMaxLD + lane;
-    int c = 0;
-    for (; c + 8 <= ch.nchunks; c += 8) {
+    // The image cuts a row into more pieces than the format has chunks (a short row: one chunk, up to eight pieces), and
+    // every partial added plainly is one more rounding of the row's sum.  So the partials are added with compensation
+    // (Neumaier, in a fixed order): the row is the exact sum of its partials rounded once, to second order in the unit
+    // roundoff, however many there are.
+    // Eight loads in flight at a time; a batch the row does not fill takes +0.0 for what is missing.
+    double comp = 0.0;
+    for (int c = 0; c < ch.nchunks; c += 8) {
       double t[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u)
-        t[u] = __hip_atomic_load(P + static_cast<size_t>(c + u) * kMaxLD, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
+        t[u] = c + u < ch.nchunks ? __hip_atomic_load(P + static_cast<size_t>(c + u) * kMaxLD, __ATOMIC_RELAXED,
+                                                      __HIP_MEMORY_SCOPE_AGENT)
+                                  : 0.0;
 #pragma unroll
-      for (int u = 0; u < 8; ++u) s += t[u];
+      for (int u = 0; u < 8; ++u) {
+        const double n = s + t[u];
+        comp += fabs(s) >= fabs(t[u]) ? (s - n) + t[u] : (t[u] - n) + s;
+        s = n;
+      }
     }
-    for (; c < ch.nchunks; ++c)
-      s += __hip_atomic_load(P + static_cast<size_t>(c) * kMaxLD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s += comp;
     orow[lane] = s;
   }
   publish_kappa(s);
@@ -903,11 +912,13 @@ void k_spmm(const SpmmArgs A) {
   unsigned long long dbg_meta = 0xFFull << 32;
 #endif
   if (static_cast<int>(blockIdx.x) < A.n_chunks) {
-    // chunk blocks, also one contiguous range of the (column-sorted) launch order per XCD
+    // chunk blocks, also one contiguous range of the launch order per XCD: the pieces whose columns that XCD's slices read
     const int tc = static_cast<int>(blockIdx.x);
     const int cper = A.n_chunks >> 3;  // n_chunks is a multiple of 8
     const int pos = (tc & 7) * cper + (tc >> 3);
-    if (pos < A.n_real_chunks) long_chunk_wave<LD, KAPPA>(A, A.chunk_order[pos]);
+    // (a negative entry pads an XCD's list of pieces to the longest: long_image.h)
+    const int ci = pos < A.n_real_chunks ? A.chunk_order[pos] : -1;
+    if (ci >= 0) long_chunk_wave<LD, KAPPA>(A, ci);
   } else {
     // Slice blocks: XCD x (= blockIdx % 8, observed dispatch order; speed only)
     // walks its own contiguous eighth of the slice list, so neighbouring slices

@@ -1000,6 +1000,20 @@ int cora_debug_format_shape(const cora_ctx *ctx, int64_t out[11]);
 int cora_debug_format_digest(const cora_ctx *ctx, uint64_t out[2]);
 int cora_debug_value_map_digest(cora_ctx *ctx, uint64_t out[2]);
 
+/* Test hook: the DEVICE IMAGE of the long rows -- what a handle uploads for the chunk blocks of the product kernel in
+ * place of the format's chunks --, derived from the host copy of the format (no GPU needed; plan-only handles too).  On
+ * one GPU every long row's entries are sorted by the XCD (blockIdx % 8) whose slices own the entry's row of X ("home"),
+ * cut at every change of home and into parts of at most `piece` entries (<= 0: the library's piece size), and every piece
+ * is launched on its home; partitioned handles keep the format's chunks (sizes[4] = 0).
+ *   sizes[5]: [0] pieces, [1] launch positions (8 x the longest XCD list), [2] entries, [3] rows of a vector, [4] placed
+ *   chunks[sizes[0]][8]: row, k0, k1, nchunks, first, slot, 0, 0 -- [k0, k1) in lval / lcol below
+ *   chunk_order[sizes[1]]: XCD x runs the pieces at [x cper, (x + 1) cper), cper = sizes[1] / 8; -1 = padding
+ *   lval, lcol, perm[sizes[2]]: lval[i] = (format's lval)[perm[i]];  lcol: INTERNAL rows (cora_row_map)
+ *   home, home_pose_first[sizes[3]]: home XCD of every internal row under the two slice orders, -1 = none
+ * Every array pointer may be null (call once for the sizes).  CORA_ERR_NOT_READY while the host values are stale. */
+int cora_debug_long_image(const cora_ctx *ctx, int piece, int64_t sizes[5], int32_t *chunks, int32_t *chunk_order,
+                          double *lval, int32_t *lcol, int32_t *perm, int8_t *home, int8_t *home_pose_first);
+
 #ifdef __cplusplus
 }
 #endif

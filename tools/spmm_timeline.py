@@ -33,7 +33,8 @@ for _ in range(50):
     ctx.hvp_dev(x.data_ptr(), out.data_ptr())
 torch.cuda.synchronize()
 st = ctx.format_stats()
-nb = ((st["long_chunks"] + 7) // 8) * 8 + ((st["slices"] + 7) // 8) * 8
+# chunk blocks: the launch positions of the long rows' device image (its pieces and the padding of the XCDs' lists)
+nb = ((len(ctx.debug_long_image()["chunk_order"]) + 7) // 8) * 8 + ((st["slices"] + 7) // 8) * 8
 buf = np.zeros(3 * nb, dtype=np.uint64)
 fn = ctx.L.cora_debug_spmm_times
 fn.argtypes = [C.c_void_p, C.c_int]
