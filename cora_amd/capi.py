@@ -967,6 +967,83 @@ class Context:
         self._chk(self.L.cora_round_dev(self.h, C.c_void_p(y), int(k), C.c_void_p(out_ptr), _d(out)))
         return self._round_result(k, out)
 
+    # ---- odometry initialisation by a segmented scan of SE(d) (include/cora_hip.h, cora_odometry_init_dev)
+    def set_odometry_chains(self, chains):
+        """Installs the chains (a list of lists of edge indices into the measurement table; None or [] clears them)."""
+        chains = [np.asarray(ch, dtype=np.int32).reshape(-1) for ch in (chains or [])]
+        ptr = np.zeros(len(chains) + 1, dtype=np.int64)
+        ptr[1:] = np.cumsum([len(ch) for ch in chains])
+        edges = np.ascontiguousarray(np.concatenate(chains) if chains else np.zeros(0), dtype=np.int32)
+        edges = np.concatenate([edges, np.zeros(1, dtype=np.int32)])  # (never an empty buffer)
+        self._chk(self.L.cora_set_odometry_chains(self.h, C.c_int64(len(chains)), ptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  edges.ctypes.data_as(_ip)))
+
+    def _two_int64(self, fn):
+        out = (C.c_int64 * 2)()
+        self._chk(fn(self.h, out))
+        return int(out[0]), int(out[1])
+
+    def odometry_chains_count(self):
+        """(chains, positions) of the installed tables."""
+        return self._two_int64(self.L.cora_odometry_chains_count)
+
+    def odometry_scan_shape(self):
+        """(positions per tile, tile totals per sweep of the middle pass)."""
+        return self._two_int64(self.L.cora_odometry_scan_shape)
+
+    def _odom_inputs(self, starts, landmarks):
+        n_ch = self.odometry_chains_count()[0]
+        s = np.ascontiguousarray(np.zeros((0, self.d)) if starts is None else starts, dtype=np.float64).reshape(-1, self.d)
+        if len(s) != n_ch:
+            raise CoraError(5, "one start per chain: %d chains, %d starts" % (n_ch, len(s)))
+        lm = None
+        if landmarks is not None:
+            lm = np.ascontiguousarray(landmarks, dtype=np.float64).reshape(-1, self.d)
+            if len(lm) != self.nt - self.n:
+                raise CoraError(5, "one row per landmark: %d landmarks, %d rows" % (self.nt - self.n, len(lm)))
+            lm = np.concatenate([lm.reshape(-1), np.zeros(1)])
+        return np.concatenate([s.reshape(-1), np.zeros(1)]), lm
+
+    def _odom_result(self, out, deg, X=None):
+        nr = self.measurement_counts()[1]
+        res = dict(written=int(out[0]), n_degenerate=int(out[1]), degenerate=deg[:nr].astype(bool))
+        if X is not None:
+            res["X"] = X
+        return res
+
+    def _odom_host(self, fn, starts, landmarks):
+        s, lm = self._odom_inputs(starts, landmarks)
+        X, out = self._out(self.d), (C.c_int64 * 2)()
+        deg = np.zeros(max(self.measurement_counts()[1], 1), dtype=np.uint8)
+        self._chk(fn(self.h, _d(s), None if lm is None else _d(lm), _d(X), X.shape[0], out, deg.ctypes.data_as(C.c_void_p)))
+        return self._odom_result(out, deg, X)
+
+    def odometry_init(self, starts, landmarks=None):
+        """The odometry start on the device: starts [chains][d], landmarks [nt - n][d] or None (zeros).  Returns dict X
+        (N x d), written (poses the chains wrote), n_degenerate, degenerate (bool per range measurement of the table)."""
+        return self._odom_host(self.L.cora_odometry_init, starts, landmarks)
+
+    def debug_odometry_init_host(self, starts, landmarks=None):
+        """The same on the host in the device's bracket order (no GPU needed): X has the device's bits."""
+        return self._odom_host(self.L.cora_debug_odometry_init_host, starts, landmarks)
+
+    def odometry_init_dev(self, starts, landmarks, out_ptr):
+        """The same into a resident vector of d columns (a raw pointer as an int); the dict of odometry_init without X."""
+        s, lm = self._odom_inputs(starts, landmarks)
+        out = (C.c_int64 * 2)()
+        deg = np.zeros(max(self.measurement_counts()[1], 1), dtype=np.uint8)
+        self._chk(self.L.cora_odometry_init_dev(self.h, _d(s), None if lm is None else _d(lm), C.c_void_p(out_ptr), out,
+                                                deg.ctypes.data_as(C.c_void_p)))
+        return self._odom_result(out, deg)
+
+    def odometry_set_range_rows_dev(self, range_idx, dirs, out_ptr):
+        """Writes the normalised directions (m x d) into the rows of the range measurements range_idx of a resident vector."""
+        idx = np.ascontiguousarray(range_idx, dtype=np.int32).reshape(-1)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(len(idx), self.d)
+        if len(idx):
+            self._chk(self.L.cora_odometry_set_range_rows_dev(self.h, C.c_int64(len(idx)), idx.ctypes.data_as(_ip), _d(dirs),
+                                                              C.c_void_p(out_ptr)))
+
     # ---- test hook
     def debug_format_spmm_host(self, X):
         X = _f(X)

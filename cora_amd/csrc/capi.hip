@@ -2,7 +2,7 @@
 // device memory and stream; every compute entry point ends in a HIP kernel of
 // kernels.hip -- there is no CPU fallback.
 //
-// ONE translation unit in sixteen pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
+// ONE translation unit in seventeen pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
 // error / device macros and the helpers every part uses; the entry points live in capi/*.inc, included at the end in this order:
 //   handle.inc          creation of (partitioned) handles, destruction, rank state, row maps, statistics
 //   resident.inc        device vectors, the current point, the trust-region trial / accept pair, products, projections
@@ -19,6 +19,7 @@
 //   compare.inc         trajectory comparison after an orthogonal alignment: device-pointer, host-pointer and host form
 //   rpe.inc             relative pose error over a pair table of the handle: table, device-pointer, host-pointer and host-mirror form
 //   round.inc           rounding of a relaxed point to SE(d): device-pointer, host-pointer and host-mirror form
+//   odom.inc            odometry initialisation: chain tables, device-pointer, host-pointer and host-mirror form
 //   comm.inc            native communication: RCCL, in-process and device-side (p2p.h) transports
 #include <hip/hip_runtime.h>
 // RCCL's types and the few enumerators used, declared here (NCCL's public ABI: they have not changed since 2.0): the
@@ -106,11 +107,26 @@ struct PosePairTable {
   int32_t *d_rows = nullptr;
   double *d_err = nullptr;  // [m] translation | [m] rotation | 5 statistics
 };
+// The chain tables of cora_set_odometry_chains (capi/odom.inc): one entry per chain position (a chain's head, then its
+// edges), rows already internal (OdomArgs, kernels.h); the poses in no chain and the landmarks' rows (OdomFillArgs); the
+// device copies, the scan's tile totals and carries, the staging of the starts and the landmarks, the flag bytes
+struct OdomTables {
+  bool built = false;  // (false: built at the next initialisation as "no chains", every pose free)
+  int64_t n_chains = 0, P = 0;
+  std::vector<int32_t> pos_edge, pos_chain, pos_rot, pos_trn;  // [P]
+  std::vector<int32_t> free_rot, free_trn, lm_row;
+  int32_t *d_idx = nullptr;      // pos_edge | pos_chain | pos_rot | pos_trn | free_rot | free_trn | lm_row
+  double *d_work = nullptr;      // totals | carry, kOdomFields(d) x tiles each
+  double *d_stage = nullptr;     // starts [n_chains][d] | landmarks [nt - n][d]
+  double *h_stage = nullptr;     // the same, pinned
+  unsigned char *d_deg = nullptr;  // one byte per range measurement
+};
 struct cora_ctx {
   HostFormat F;
   LongImage LI;  // what the long rows' device arrays hold (long_image.h); derived from F at creation, device handles only
   MeasurementTable meas;
   PosePairTable pairs;
+  OdomTables odom;
   cora_native_comm *native_comm = nullptr;  // owned: the library's own communication (cora_comm_create_*)
   cora::P2PState *p2p_pending = nullptr;    // a mailbox exported by cora_comm_p2p_handle, not yet connected
   int device = -1;
@@ -591,8 +607,17 @@ void free_assembly(cora_ctx *c) {  // (the device must be current where there is
   c->tmap = TermMap();
 }
 
+void free_odom(cora_ctx *c) {  // (the device must be current where there is one)
+  OdomTables &T = c->odom;
+  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_work), static_cast<void *>(T.d_stage), static_cast<void *>(T.d_deg)})
+    if (p) (void)hipFree(p);
+  if (T.h_stage) (void)hipHostFree(T.h_stage);
+  T = OdomTables();
+}
+
 void free_measurements(cora_ctx *c) {  // (the device must be current)
   free_assembly(c);  // (the term map belongs to the table)
+  free_odom(c);      // (so do the chain tables: their positions name its edges)
   MeasurementTable &M = c->meas;
   for (void *p : {static_cast<void *>(M.d_edge_rows), static_cast<void *>(M.d_range_rows), static_cast<void *>(M.d_edge_data),
                   static_cast<void *>(M.d_range_data), static_cast<void *>(M.d_out)})
@@ -627,6 +652,7 @@ extern "C" {
 #include "capi/compare.inc"
 #include "capi/rpe.inc"
 #include "capi/round.inc"
+#include "capi/odom.inc"
 
 }  // extern "C"
 

@@ -76,6 +76,7 @@ int cora_set_measurements(cora_ctx *c, int64_t n_edges, const int32_t *edge_rows
     M.set = true;
   } else {
     c->tmap = TermMap();  // (a term map belongs to the table it was built from)
+    c->odom = OdomTables();  // (so do the chain tables)
     c->meas = std::move(T);
     c->meas.set = true;
   }

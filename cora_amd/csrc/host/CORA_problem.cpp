@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "../../../include/cora_hip.h"
+#include "odometry_init.h"
 #include "dense.h"
 #include "sparse_cholesky.h"
 #include "../config.h"
@@ -1141,6 +1142,98 @@ Matrix Problem::roundSolution(const Matrix &Y, RoundingInfo *info) const {
   Matrix Xd = lowered(std::move(out));
   checkVariablesAreValid(Xd);
   return Xd;
+}
+
+// the rule of getOdomInitialization (odometry_init.cpp; examples/paper_experiments.cpp:375-424)
+std::vector<std::vector<int32_t>> Problem::odometryChains() const {
+  std::map<unsigned char, std::map<uint64_t, int32_t>> by_robot;
+  int32_t e = 0;
+  for (const RelativePoseMeasurement &m : rel_pose_pose_measurements_) {
+    if (m.first_id.chr() == m.second_id.chr() && m.second_id.index() == m.first_id.index() + 1)
+      by_robot[m.first_id.chr()][m.first_id.index()] = e;
+    ++e;
+  }
+  std::vector<std::vector<int32_t>> chains;
+  for (const auto &robot : by_robot) {
+    uint64_t expect = 0;
+    bool open = false;
+    for (const auto &kv : robot.second) {
+      if (!open || kv.first != expect) chains.emplace_back();
+      open = true;
+      chains.back().push_back(kv.second);
+      expect = kv.first + 1;
+    }
+  }
+  return chains;
+}
+
+Matrix Problem::odometryInitialization(uint64_t seed) const {
+  checkUpToDate();
+  if (part_world_ > 1) throw std::runtime_error("Problem::odometryInitialization: not supported on a partitioned handle");
+  const char *where = "Problem::odometryInitialization";
+  ensureMeasurementTable();
+  cora_ctx *c = ctx_.get();
+  const int d = dim_, n = numPoses(), nl = numLandmarks(), N = getDataMatrixSize(), p = static_cast<int>(relaxation_rank_);
+  const size_t nr = range_measurements_.size();
+  const std::vector<std::vector<int32_t>> chains = odometryChains();
+  // (the chain tables live and die with the measurement table of the handle: the same counts are the same chains)
+  size_t positions = chains.size();
+  for (const auto &ch : chains) positions += ch.size();
+  int64_t have[2] = {0, 0};
+  CORA_CALL(cora_odometry_chains_count(c, have), where);
+  if (have[0] != static_cast<int64_t>(chains.size()) || have[1] != static_cast<int64_t>(positions)) {
+    std::vector<int64_t> ptr(1, 0);
+    std::vector<int32_t> edges;
+    for (const auto &ch : chains) {
+      edges.insert(edges.end(), ch.begin(), ch.end());
+      ptr.push_back(static_cast<int64_t>(edges.size()));
+    }
+    edges.push_back(0);  // (never an empty buffer)
+    CORA_CALL(cora_set_odometry_chains(c, static_cast<int64_t>(chains.size()), ptr.data(), edges.data()), where);
+  }
+  std::mt19937_64 g(seed);
+  odom_draws::Uniform U = odom_draws::uniform();
+  std::vector<double> starts(chains.size() * d + 1, 0.0), lms(static_cast<size_t>(nl) * d + 1, 0.0);
+  for (size_t ch = 1; ch < chains.size(); ++ch) odom_draws::drawPlace(g, U, d, starts.data() + ch * d);
+  for (const auto &kv : landmark_symbol_idxs_) {
+    const Index l = getTranslationIdx(kv.first) - rotAndRangeMatrixSize() - n;
+    odom_draws::drawPlace(g, U, d, lms.data() + static_cast<size_t>(l) * d);
+  }
+  struct Vectors {
+    cora_ctx *c;
+    double *x = nullptr, *lifted = nullptr;
+    ~Vectors() {
+      if (x) cora_dev_free(c, x);
+      if (lifted) cora_dev_free(c, lifted);
+    }
+  } v{c};
+  CORA_CALL(cora_dev_alloc(c, d, &v.x), where);
+  CORA_CALL(cora_dev_alloc(c, p, &v.lifted), where);
+  int64_t counts[2] = {0, 0};
+  std::vector<unsigned char> degenerate(nr + 1, 0);
+  CORA_CALL(cora_odometry_init_dev(c, starts.data(), lms.data(), v.x, counts, degenerate.data()), where);
+  if (counts[1] > 0) {  // endpoints that coincide: a random direction each, drawn in range order
+    std::vector<int32_t> idx;
+    std::vector<double> dirs;
+    for (size_t k = 0; k < nr; ++k) {
+      if (!degenerate[k]) continue;
+      idx.push_back(static_cast<int32_t>(k));
+      dirs.resize(dirs.size() + d);
+      odom_draws::drawDirection(g, U, d, dirs.data() + dirs.size() - d);
+    }
+    CORA_CALL(cora_odometry_set_range_rows_dev(c, static_cast<int64_t>(idx.size()), idx.data(), dirs.data(), v.x), where);
+  }
+  const Matrix Qm = odom_draws::drawRotation(g, U, p);
+  std::vector<double> lift(static_cast<size_t>(d) * p);  // the first d rows of Qm, column-major d x p
+  for (int col = 0; col < p; ++col)
+    for (int a = 0; a < d; ++a) lift[static_cast<size_t>(col) * d + a] = Qm(a, col);
+  const double *xs[1] = {v.x};
+  const double *cs[1] = {lift.data()};
+  const int ks[1] = {d};
+  CORA_CALL(cora_combine_dev(c, 1, xs, ks, cs, p, v.lifted), where);
+  Matrix x0(N, p);
+  CORA_CALL(cora_download(c, v.lifted, p, x0.data(), N), where);
+  return x0;
 }
 
 // src/CORA_problem.cpp:1168-1197: [Y; -chol(Q33red) \ (B^T Y); 0], computed on the device

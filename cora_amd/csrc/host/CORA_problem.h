@@ -430,6 +430,19 @@ class Problem {
    * partitioned handle. */
   Matrix roundSolution(const Matrix &Y, RoundingInfo *info = nullptr) const;
 
+  /** EXTENSION beyond the reference: the odometry chains getOdomInitialization composes, as indices into getRPMs() (the
+   * first block of the handle's measurement table): per robot character the measurements (c, k) -> (c, k + 1) in index
+   * order, the last duplicate wins, a gap starts a new chain.  Chains in the host function's order. */
+  std::vector<std::vector<int32_t>> odometryChains() const;
+  /** EXTENSION beyond the reference: getOdomInitialization on the device (cora_odometry_init_dev, include/cora_hip.h): the
+   * chains composed by a segmented scan of SE(d) over the handle's measurement table, the lift to the relaxation rank by
+   * cora_combine_dev.  Draws from std::mt19937_64(seed) in the host function's order -- one start per chain after the
+   * first, the landmarks in map order, the fallback directions of the degenerate range rows in range order, the p x p
+   * rotation -- so that the same seed gives the host function's start up to rounding.  getDataMatrixSize() rows,
+   * getRelaxationRank() columns.  Installs the measurement table and the chain tables on the handle where they are
+   * missing; Problem gains no member.  std::runtime_error on a partitioned handle. */
+  Matrix odometryInitialization(uint64_t seed = 7) const;
+
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;
   LambdaBlocks compute_Lambda_blocks(const Matrix &Y) const;

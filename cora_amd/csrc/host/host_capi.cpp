@@ -1,6 +1,7 @@
 // Flat C view of the C++ host for ctypes (include/cora_host.h).
 #include "../../../include/cora_host.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <memory>
@@ -249,6 +250,7 @@ int cora_problem_op(cora_problem *p, const char *op, int cols, const double *A, 
     else if (o == "retract") res = q.retract(wrap(A, N, r), wrap(B, N, r));
     else if (o == "getRandomInitialGuess") res = q.getRandomInitialGuess();
     else if (o == "getOdomInitialization") res = getOdomInitialization(q);
+    else if (o == "odometryInitialization") res = q.odometryInitialization();
     else if (o == "getTranslationExplicitSolution") res = q.getTranslationExplicitSolution(wrap(A, N, r));
     else if (o == "alignEstimateToOrigin") res = q.alignEstimateToOrigin(wrap(A, N, r));
     else throw std::invalid_argument("unknown operator " + o);
@@ -263,6 +265,21 @@ int cora_problem_lambda_blocks(cora_problem *p, const double *Y, double *stiefel
     auto L = q.compute_Lambda_blocks(wrap(Y, N, r));
     std::memcpy(stiefel, L.first.data(), sizeof(double) * static_cast<size_t>(L.first.size()));
     std::memcpy(oblique, L.second.data(), sizeof(double) * static_cast<size_t>(L.second.size()));
+  });
+}
+
+int cora_problem_odometry_chains(const cora_problem *p, int64_t counts[2], int64_t *chain_ptr, int32_t *chain_edges) {
+  return guarded([&] {
+    const std::vector<std::vector<int32_t>> chains = p->problem.odometryChains();
+    int64_t at = 0;
+    if (chain_ptr) chain_ptr[0] = 0;
+    for (size_t ch = 0; ch < chains.size(); ++ch) {
+      if (chain_edges) std::copy(chains[ch].begin(), chains[ch].end(), chain_edges + at);
+      at += static_cast<int64_t>(chains[ch].size());
+      if (chain_ptr) chain_ptr[ch + 1] = at;
+    }
+    counts[0] = static_cast<int64_t>(chains.size());
+    counts[1] = at;
   });
 }
 

@@ -738,6 +738,116 @@ __host__ __device__ inline bool round_row(bool range, const double *row, int k, 
   return finite;
 }
 
+// Odometry initialisation: a segmented inclusive scan of SE(d) over the chain positions (kernels/odom.inc;
+// include/cora_hip.h, cora_odometry_init_dev).  Chain c contributes its head and then its edges as consecutive positions;
+// the element at a head is (flag = 1, I, start of the chain), at an edge (0, R_e, t_e) from the measurement table's
+// edge_data ([field][measurement]); a right operand whose flag is set wins.  Three launches, no workgroup waits for another:
+//   totals : totals[tile] = the product of the tile's kOdomTile positions           (one workgroup of kOdomTile threads per tile)
+//   middle : carry[tile] = totals[0] o .. o totals[tile], kOdomSweep tiles per sweep (ONE wavefront; the last lane's value
+//            is carried into the next sweep)
+//   scan   : every position's product, with carry[tile - 1] from the left; the rows of the pose the position writes
+// Elements travel as kOdomFields(d) doubles, structure-of-arrays [field][tile]: the flag (0.0 / 1.0), R row-major, t.
+// BRACKET ORDER, a function of (P, kOdomTile, kOdomSweep) alone and the same in the host mirror (capi/odom.inc):
+//   wavefront: Kogge-Stone, offsets 1, 2, .., 32 -- lane l >= off takes (lane l - off) o (lane l), all lanes at once;
+//   tile: wave w > 0 folds the totals of waves 0 .. w - 1 from the left, (..(W_0 o W_1) o ..) o W_{w-1}, then that o (lane);
+//   sweeps of the middle pass and the carry into a tile: (what came before) o (the wavefront's / the tile's result).
+// Positions past P are heads of nothing (flag = 1, I, 0) and write nothing.
+constexpr int kOdomTile = 256;
+constexpr int kOdomSweep = 64;
+constexpr int kOdomFields(int d) { return 1 + d * d + d; }
+template <int D>
+struct OdomEl {
+  double v[D * D + D];  // R row-major, then t
+  int flag;
+};
+struct OdomArgs {
+  int d = 0, ntiles = 0;
+  int64_t P = 0, n_edges = 0;
+  const int32_t *pos_edge = nullptr, *pos_chain = nullptr;  // [P]: edge index (-1 at a head), chain index (at a head)
+  const int32_t *pos_rot = nullptr, *pos_trn = nullptr;     // [P]: first INTERNAL rotation row, translation row of the pose written
+  const double *edge_data = nullptr;                        // the measurement table's, [d*d + d + 2][n_edges]
+  const double *starts = nullptr;                           // [chains][d]
+  double *totals = nullptr, *carry = nullptr;               // [kOdomFields(d)][ntiles] each
+  double *out = nullptr;                                    // d columns at stride ld_for(d) = d
+  int *flag = nullptr;                                      // |= 1 where a product is not finite
+};
+// the other rows of the start: identity blocks and zero translations of the n_free poses in no chain, the landmarks' rows
+// from lm ([n_lm][d] on the device; nullptr: zeros), then -- launch_odom_ranges, after everything above -- range row m =
+// the direction of x_t(b) - x_t(a) through range_rows ([3][n_ranges] internal rows: range | a | b), deg[m] = 1 and a
+// zero row where it has none (odom_range_row), partial[odom_range_blocks] = the blocks' counts of those, words[0] their sum
+struct OdomFillArgs {
+  int d = 0;
+  int64_t n_free = 0, n_lm = 0, n_ranges = 0;
+  const int32_t *free_rot = nullptr, *free_trn = nullptr, *lm_row = nullptr, *range_rows = nullptr;
+  const double *lm = nullptr;
+  unsigned char *deg = nullptr;
+  int *partial = nullptr, *words = nullptr, *flag = nullptr;
+  double *out = nullptr;
+};
+inline int odom_tiles(int64_t P) { return static_cast<int>((P + kOdomTile - 1) / kOdomTile); }
+inline int odom_range_blocks(int64_t n_ranges) { return static_cast<int>((n_ranges + kWave - 1) / kWave); }
+hipError_t launch_odom_scan(const OdomArgs &A, hipStream_t st);      // the three launches; P == 0: none
+hipError_t launch_odom_fill(const OdomFillArgs &A, hipStream_t st);  // free poses and landmarks; none of either: no launch
+hipError_t launch_odom_ranges(const OdomFillArgs &A, hipStream_t st);  // + the sum of the counts; no ranges: words[0] = 0
+// The arithmetic, shared by the kernels and the host mirror (cora_debug_odometry_init_host): single correctly rounded
+// fp64 operations in the order written, never contracted; one fma per term.
+// b = a o b:  a right operand with its flag set wins; else R = R_a R_b (every entry from +0.0, k ascending),
+// t = t_a + R_a t_b (from t_a, k ascending), flag = flag_a
+template <int D>
+__host__ __device__ inline void odom_compose(const OdomEl<D> &a, OdomEl<D> &b) {
+#pragma clang fp contract(off)
+  if (b.flag) return;
+  double r[D * D + D];
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) s = fma(a.v[i * D + k], b.v[k * D + j], s);
+      r[i * D + j] = s;
+    }
+    double s = a.v[D * D + i];
+#pragma unroll
+    for (int k = 0; k < D; ++k) s = fma(a.v[i * D + k], b.v[D * D + k], s);
+    r[D * D + i] = s;
+  }
+#pragma unroll
+  for (int i = 0; i < D * D + D; ++i) b.v[i] = r[i];
+  b.flag = a.flag;
+}
+template <int D>
+__host__ __device__ inline void odom_head(OdomEl<D> &e) {  // (1, I, 0)
+#pragma unroll
+  for (int i = 0; i < D * D + D; ++i) e.v[i] = (i < D * D && i / D == i % D) ? 1.0 : 0.0;
+  e.flag = 1;
+}
+__host__ __device__ inline bool odom_finite(const double *v, int n) {
+  bool finite = true;
+  for (int i = 0; i < n; ++i) finite = finite && fabs(v[i]) <= 1.79769313486231570815e308;
+  return finite;
+}
+// row = (tb - ta) / |tb - ta|; returns true, and a zero row, where the norm is below 1e-5 (a degenerate row)
+template <int D>
+__host__ __device__ inline bool odom_range_row(const double *ta, const double *tb, double *row) {
+#pragma clang fp contract(off)
+  double s = 0.0;
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    row[c] = tb[c] - ta[c];
+    s = fma(row[c], row[c], s);
+  }
+  const double nrm = sqrt(s);
+  if (nrm < 1e-5) {
+#pragma unroll
+    for (int c = 0; c < D; ++c) row[c] = 0.0;
+    return true;
+  }
+#pragma unroll
+  for (int c = 0; c < D; ++c) row[c] = row[c] / nrm;
+  return false;
+}
+
 // In-place update of Q's values (kernels/update_values.inc).  src: the sources of ValueMap (cora_internal.h), vals: the
 // new CSR values on the device.
 // check: flag |= 1 where a value is not finite, |= 2 where a mirror pair (mirror[2j], mirror[2j + 1]) differs.

@@ -504,6 +504,46 @@ hipError_t launch_round_apply(const RoundArgs &A, hipStream_t st) {
   else hipLaunchKernelGGL(k_round_apply<3>, dim3(grid), dim3(256), 0, st, A);
   return hipGetLastError();
 }
+// the odometry initialisation (kernels/odom.inc): the scan's three launches; the fill; the range rows with the sum of their counts
+hipError_t launch_odom_scan(const OdomArgs &A, hipStream_t st) {
+  if (A.P <= 0) return hipSuccess;
+  if ((A.d != 2 && A.d != 3) || A.ntiles != odom_tiles(A.P) || !A.pos_edge || !A.pos_chain || !A.pos_rot || !A.pos_trn || !A.starts ||
+      !A.totals || !A.carry || !A.out || !A.flag || (A.n_edges > 0 && !A.edge_data))
+    return hipErrorInvalidValue;
+  const dim3 grid(A.ntiles), block(kOdomTile);
+  if (A.d == 2) {
+    hipLaunchKernelGGL(k_odom_totals<2>, grid, block, 0, st, A);
+    hipLaunchKernelGGL(k_odom_middle<2>, dim3(1), dim3(kOdomSweep), 0, st, A);
+    hipLaunchKernelGGL(k_odom_scan<2>, grid, block, 0, st, A);
+  } else {
+    hipLaunchKernelGGL(k_odom_totals<3>, grid, block, 0, st, A);
+    hipLaunchKernelGGL(k_odom_middle<3>, dim3(1), dim3(kOdomSweep), 0, st, A);
+    hipLaunchKernelGGL(k_odom_scan<3>, grid, block, 0, st, A);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_odom_fill(const OdomFillArgs &A, hipStream_t st) {
+  const int64_t units = A.n_free + A.n_lm;
+  if (units <= 0) return hipSuccess;
+  if ((A.d != 2 && A.d != 3) || !A.out || (A.n_free > 0 && (!A.free_rot || !A.free_trn)) || (A.n_lm > 0 && !A.lm_row))
+    return hipErrorInvalidValue;
+  const int64_t grid = (units + 255) / 256;
+  if (grid >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+  if (A.d == 2) hipLaunchKernelGGL(k_odom_fill<2>, dim3(grid), dim3(256), 0, st, A);
+  else hipLaunchKernelGGL(k_odom_fill<3>, dim3(grid), dim3(256), 0, st, A);
+  return hipGetLastError();
+}
+hipError_t launch_odom_ranges(const OdomFillArgs &A, hipStream_t st) {
+  if ((A.d != 2 && A.d != 3) || !A.partial || !A.words || A.n_ranges < 0) return hipErrorInvalidValue;
+  const int nb = odom_range_blocks(A.n_ranges);
+  if (nb > 0) {
+    if (!A.out || !A.range_rows || !A.deg || !A.flag) return hipErrorInvalidValue;
+    if (A.d == 2) hipLaunchKernelGGL(k_odom_ranges<2>, dim3(nb), dim3(kWave), 0, st, A);
+    else hipLaunchKernelGGL(k_odom_ranges<3>, dim3(nb), dim3(kWave), 0, st, A);
+  }
+  hipLaunchKernelGGL(k_round_finish, dim3(1), dim3(64), 0, st, A.partial, nb, 0, A.words);  // words[0] = the sum
+  return hipGetLastError();
+}
 hipError_t launch_round_amax(int64_t n, const double *y, double *partial, int nblocks, int *flag, hipStream_t st) {
   if (n < 1 || nblocks < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_round_amax, dim3(nblocks), dim3(256), 0, st, n, y, partial, flag);

@@ -200,13 +200,24 @@ class Problem:
             out = np.zeros(1)
         pa, pb, pc = ptr(A), ptr(B), ptr(C_)
         if name != "evaluateObjective":
-            full = name in ("getOdomInitialization", "getTranslationExplicitSolution", "alignEstimateToOrigin")
+            full = name in ("getOdomInitialization", "odometryInitialization", "getTranslationExplicitSolution", "alignEstimateToOrigin")
             out = np.zeros((dm["N"] if full else N, cols[0] if cols else p), order="F")
         if len(set(cols)) > 1:
             raise HostError("operands have different column counts: %s" % cols)
         self._chk(self.L.cora_problem_op(self.h, name.encode(), cols[0] if cols else p, pa, pb, pc,
                                          out.ctypes.data_as(_dp)))
         return float(out[0]) if name == "evaluateObjective" else out
+
+    def odometry_chains(self):
+        """Problem::odometryChains: the chains getOdomInitialization composes, a list of int32 arrays of indices into the
+        relative-pose measurements in the order they were added."""
+        cnt = (C.c_int64 * 2)()
+        self._chk(self.L.cora_problem_odometry_chains(self.h, cnt, None, None))
+        ptr = np.zeros(int(cnt[0]) + 1, dtype=np.int64)
+        edges = np.zeros(max(int(cnt[1]), 1), dtype=np.int32)
+        self._chk(self.L.cora_problem_odometry_chains(self.h, cnt, ptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      edges.ctypes.data_as(C.POINTER(C.c_int32))))
+        return [edges[ptr[i]:ptr[i + 1]].copy() for i in range(int(cnt[0]))]
 
     def lambda_blocks(self, Y):
         dm = self.dims()

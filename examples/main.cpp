@@ -22,12 +22,12 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding]" << std::endl;
+    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding] [--device-init]" << std::endl;
     return 1;
   }
   int max_rank = 10;
   std::string tum, save_dir, residuals, weights, robust, barc2, weights_out, aligned_tum, rpe_steps, rpe_dists;
-  bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false;
+  bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--jacobi") jacobi = true;
@@ -56,10 +56,13 @@ int main(int argc, char **argv) {
     else if (a == "--rpe-dist" && i + 1 < argc) rpe_dists = argv[++i];
     // the certified point is rounded on the device (Problem::roundSolution) in place of projectSolution
     else if (a == "--device-rounding") device_rounding = true;
+    // with --odom-init: the start is composed on the device (Problem::odometryInitialization) in place of getOdomInitialization
+    else if (a == "--device-init") device_init = true;
   }
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
   try {
+    if (device_init && !odom) throw std::runtime_error("--device-init composes the odometry start on the device: it needs --odom-init");
     const auto t_start = clk::now();
     CORA::Problem problem = CORA::parsePyfgTextToProblem(argv[1]);
     const auto t_parsed = clk::now();
@@ -106,7 +109,8 @@ int main(int argc, char **argv) {
     std::printf("poses %d  landmarks %d  ranges %d  N %d  nnz(Q) %ld\n", problem.numPoses(), problem.numLandmarks(),
                 problem.numRangeMeasurements(), problem.getDataMatrixSize(),
                 static_cast<long>(problem.data_matrix_.nonZeros()));
-    CORA::Matrix x0 = odom ? CORA::getOdomInitialization(problem) : problem.getRandomInitialGuess();
+    CORA::Matrix x0 = !odom ? problem.getRandomInitialGuess()
+                      : device_init ? problem.odometryInitialization() : CORA::getOdomInitialization(problem);
     if (odom && implicit)  // examples/paper_experiments.cpp:623-625
       x0 = x0.block(0, 0, problem.rotAndRangeMatrixSize(), x0.cols());
     CORA::CoraSolveInfo info;

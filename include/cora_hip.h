@@ -715,6 +715,70 @@ int cora_round(cora_ctx *ctx, const double *Y, int ldy, int k, double *Out, int 
 int cora_debug_round_host(cora_ctx *ctx, const double *Y, int ldy, int k, const double *basis, double *Out, int ldo,
                           double *out);
 
+/* ---- ODOMETRY INITIALISATION, on the device -------------------------------------------------------------------------------
+ * The start the reference's experiments use by default ("init_type": "Odom"): every robot's odometry composed from a start
+ * position, as a resident vector of d columns (cora_dev_alloc(ctx, d, ..), stride cora_ld_for(d)).  The lift to p columns
+ * is cora_combine_dev with the first d rows of a p x p rotation.  Needs a measurement table (cora_set_measurements).
+ * DEFINITIONS.
+ *   chain            relative-pose edges e_1 .. e_m (m >= 1) of the measurement table, pose b of e_k being pose a of
+ *                    e_{k+1}, with a start translation s of d numbers.  The head (pose a of e_1) gets (I, s); pose b of
+ *                    e_k gets T_k = T_{k-1} o (R_k, t_k), that is R <- R R_k, t <- t + R t_k.
+ *   rows of (R, t)   the rotation block holds R^T (row a, column b = R(b, a)), the translation row holds t.
+ *   poses in no chain  an identity block and a zero translation.
+ *   landmarks        the caller's landmarks[l][d]; NULL: zeros.
+ *   range row m      (x_t(b) - x_t(a)) / |x_t(b) - x_t(a)| of the OUTPUT's translation rows, through the table's range
+ *                    measurement m.  Where the norm is below 1e-5 the row stays zero and is reported as degenerate: the
+ *                    caller supplies a direction afterwards (cora_odometry_set_range_rows_dev).  A range row no
+ *                    measurement of the table names stays zero.
+ * cora_set_odometry_chains   chain c is chain_edges[chain_ptr[c] .. chain_ptr[c + 1]), indices into the edge table.
+ *            Validates, translates to position tables (chain c contributes its head, then its edges: P = edges + chains
+ *            positions <= n) and uploads them; they stay on the handle until replaced, until the measurement table is
+ *            replaced or until the handle is destroyed.  n_chains = 0 clears them (every pose is then in no chain; a handle
+ *            that was never given chains behaves the same).  Works on a plan-only handle, except for the upload.  A refused
+ *            call leaves the tables as they were.
+ * cora_odometry_chains_count   out = {chains, positions}.
+ * cora_odometry_scan_shape     out = {positions per tile, tile totals per sweep of the middle pass}: the shape the bracket
+ *            order below depends on.
+ * cora_odometry_init_dev   starts: host [n_chains][d]; landmarks: host [nt - n][d] or NULL; dOut: d columns; out (host):
+ *            {poses written by chains, degenerate range rows}; degenerate: host bytes, one per range measurement of the
+ *            table (1: degenerate), or NULL.  Rows: the poses in no chain and the landmarks, then the scan -- per-tile
+ *            totals, one workgroup over the totals (in sweeps, carrying across them), per-tile scan with the carry-in, which
+ *            writes the pose rows -- then the range rows.  Everything on the handle's stream; synchronises once, at the end.
+ * cora_odometry_init       the host-pointer form: Out is N x d column-major with leading dimension ldo; its vector is
+ *            released before it returns.
+ * cora_odometry_set_range_rows_dev   writes dirs[i] / |dirs[i]| (host [m][d]) into the row of range measurement
+ *            range_idx[i] of dOut, i < m: the rare path for the degenerate rows.  Synchronises.
+ * cora_debug_odometry_init_host      the same on the host through the translated tables, in the device's bracket order and
+ *            through the function the kernels compose with: Out has the device's bits.  Works on a plan-only handle.
+ * ARITHMETIC.  A composition is one fma per term: an entry of R R_k from +0.0, an entry of t + R t_k from t, the inner index
+ * ascending; never contracted.  The scan is segmented (a head resets the product) and brackets the factors of a chain as a
+ * function of (P, the scan shape) alone: within a wavefront of 64 positions Kogge-Stone with offsets 1, 2, .., 32; within a
+ * tile the totals of the wavefronts before are folded from the left and applied from the left; the same for the totals of the
+ * tiles (one wavefront per sweep) and for the carry into a tile.  The same bits on every call.  A range row is the
+ * difference, its squares summed by fma from +0.0, one square root, one division per entry.  The count of degenerate rows is
+ * a sum of integers in fixed slots.  No atomics on doubles.
+ * ACCURACY.  Against exact arithmetic, at position k of a chain (k factors of spectral norm 1, in any bracket order), to
+ * first order: rotation block within k d^2 eps in Frobenius norm, translation row within k d^2 eps (|s| + sum |t_m|).
+ * ERRORS.  CORA_ERR_NOT_READY: no measurement table.  CORA_ERR_ARG: a partitioned handle; a null pointer; an edge index
+ * outside the table; an edge without a rotation part (second rotation row -1); an empty chain; two consecutive edges that do
+ * not share the pose; a pose two positions would write (the message names the first offender); two range measurements of the
+ * table that name one range row; a start, a landmark or a direction that is not finite, a direction without length.
+ * CORA_ERR_SHAPE: a leading dimension below N.  CORA_ERR_NAN: a product that is not finite (the device forms report it
+ * through the handle's flag word).  CORA_ERR_HIP: a device form on a plan-only handle.
+ * STATE.  Nothing the handle computes with changes.  The handle keeps the position tables, the staging of the starts and
+ * the landmarks, the scan's tile totals and the flag bytes. */
+int cora_set_odometry_chains(cora_ctx *ctx, int64_t n_chains, const int64_t *chain_ptr /* [n_chains + 1] */,
+                             const int32_t *chain_edges);
+int cora_odometry_chains_count(const cora_ctx *ctx, int64_t out[2]);
+int cora_odometry_scan_shape(const cora_ctx *ctx, int64_t out[2]);
+int cora_odometry_init_dev(cora_ctx *ctx, const double *starts, const double *landmarks, double *dOut, int64_t out[2],
+                           unsigned char *degenerate);
+int cora_odometry_init(cora_ctx *ctx, const double *starts, const double *landmarks, double *Out, int ldo, int64_t out[2],
+                       unsigned char *degenerate);
+int cora_odometry_set_range_rows_dev(cora_ctx *ctx, int64_t m, const int32_t *range_idx, const double *dirs, double *dOut);
+int cora_debug_odometry_init_host(cora_ctx *ctx, const double *starts, const double *landmarks, double *Out, int ldo,
+                                  int64_t out[2], unsigned char *degenerate);
+
 /* Timing helpers: HIP events on the handle's stream. */
 int cora_timer_start(cora_ctx *ctx);
 int cora_timer_stop_ms(cora_ctx *ctx, float *ms); /* synchronises */

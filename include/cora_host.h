@@ -90,6 +90,8 @@ int cora_problem_variable_size(cora_problem *p, int64_t *rows);
  *  "retract"                  A=Y, B=V           -> out
  *  "getRandomInitialGuess"    (none)             -> out
  *  "getOdomInitialization"    (none)             -> out   (examples/paper_experiments.cpp:426-534)
+ *  "odometryInitialization"   (none)             -> out   the same start composed on the device (Problem::odometryInitialization,
+ *                                                        seed 7: getOdomInitialization's start up to rounding)
  *  "getTranslationExplicitSolution" A=Y (implicit) -> out (d+1)n + r + l rows (src/CORA_problem.cpp:1168)
  *  "alignEstimateToOrigin"    A=Y (rank d)       -> out (d+1)n + r + l rows (src/CORA_problem.cpp:1234)
  * Inputs are N x cols with leading dimension N = cora_problem_variable_size() (cols is checked
@@ -97,6 +99,10 @@ int cora_problem_variable_size(cora_problem *p, int64_t *rows);
  * output is N x rank unless stated otherwise. */
 int cora_problem_op(cora_problem *p, const char *op, int cols, const double *A, const double *B,
                     const double *C, double *out);
+/* Problem::odometryChains (an extension beyond the reference): the chains getOdomInitialization composes, as indices into
+ * the relative-pose measurements in the order they were added.  counts = { chains, edges of all chains }; chain_ptr
+ * (chains + 1 entries) and chain_edges may both be NULL to ask for the counts alone. */
+int cora_problem_odometry_chains(const cora_problem *p, int64_t counts[2], int64_t *chain_ptr, int32_t *chain_edges);
 /* compute_Lambda_blocks(Y): stiefel d x dn (ld d), oblique r */
 int cora_problem_lambda_blocks(cora_problem *p, const double *Y, double *stiefel, double *oblique);
 /* Problem::measurementResiduals (an extension beyond the reference; formulas in include/cora_hip.h, "per-measurement
