@@ -1044,6 +1044,60 @@ class Context:
             self._chk(self.L.cora_odometry_set_range_rows_dev(self.h, C.c_int64(len(idx)), idx.ctypes.data_as(_ip), _d(dirs),
                                                               C.c_void_p(out_ptr)))
 
+    # ---- landmark initialisation from ranges: multilateration (include/cora_hip.h, cora_multilaterate_dev)
+    def set_multilateration(self, pose_ok=None, landmark_on=None):
+        """Groups the usable ranges of the measurement table per landmark: pose_ok [n] / landmark_on [nt - n] masks or
+        None (all)."""
+        def mask(a, m, what):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(np.asarray(a).reshape(-1) != 0, dtype=np.uint8)
+            if len(a) != m:
+                raise CoraError(5, "%s needs %d entries, not %d" % (what, m, len(a)))
+            a = np.concatenate([a, np.zeros(1, dtype=np.uint8)])  # (never an empty buffer)
+            return a, a.ctypes.data_as(C.c_void_p)
+        po, ppo = mask(pose_ok, self.n, "pose_ok")
+        lo, plo = mask(landmark_on, self.nt - self.n, "landmark_on")
+        self._chk(self.L.cora_set_multilateration(self.h, ppo, plo))
+
+    def multilateration_counts(self):
+        """(landmarks with a list, usable ranges, skipped ranges, chunks) of the installed tables."""
+        out = (C.c_int64 * 4)()
+        self._chk(self.L.cora_multilateration_counts(self.h, out))
+        return tuple(int(v) for v in out)
+
+    def _ml_call(self, fn, gn_steps):
+        nl, nr = self.nt - self.n, self.measurement_counts()[1]
+        out = (C.c_int64 * 4)()
+        status, chosen = np.zeros(nl + 1, dtype=np.uint8), np.zeros(nl + 1, dtype=np.int32)
+        cl, cf, deg = np.zeros(nl + 1), np.zeros(nl + 1), np.zeros(nr + 1, dtype=np.uint8)
+        self._chk(fn(int(gn_steps), out, status.ctypes.data_as(C.c_void_p), _d(cl), _d(cf), chosen.ctypes.data_as(_ip),
+                     deg.ctypes.data_as(C.c_void_p)))
+        return dict(solved=int(out[0]), not_solved=int(out[1]), n_degenerate=int(out[2]), steps=int(out[3]), status=status[:nl],
+                    cost_linear=cl[:nl], cost_final=cf[:nl], chosen=chosen[:nl], degenerate=deg[:nr].astype(bool))
+
+    def _ml_host(self, fn, X, gn_steps):
+        X = np.array(X, dtype=np.float64, order="F", copy=True)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise CoraError(1, "X must have d columns")
+        res = self._ml_call(lambda *a: fn(self.h, _d(X), X.shape[0], *a), gn_steps)
+        res["X"] = X
+        return res
+
+    def multilaterate(self, X, gn_steps=5):
+        """The landmarks of the host matrix X (N x d) from the ranges, on the device.  Returns dict X (a copy with the
+        landmark and range rows rewritten), solved, not_solved, n_degenerate, steps, status, cost_linear, cost_final,
+        chosen (per landmark), degenerate (bool per range measurement)."""
+        return self._ml_host(self.L.cora_multilaterate, X, gn_steps)
+
+    def debug_multilaterate_host(self, X, gn_steps=5):
+        """The same on the host in the device's bracket order (no GPU needed): X has the device's bits."""
+        return self._ml_host(self.L.cora_debug_multilaterate_host, X, gn_steps)
+
+    def multilaterate_dev(self, x_ptr, gn_steps=5):
+        """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
+        return self._ml_call(lambda *a: self.L.cora_multilaterate_dev(self.h, C.c_void_p(x_ptr), *a), gn_steps)
+
     # ---- test hook
     def debug_format_spmm_host(self, X):
         X = _f(X)

@@ -20,6 +20,7 @@
 //   rpe.inc             relative pose error over a pair table of the handle: table, device-pointer, host-pointer and host-mirror form
 //   round.inc           rounding of a relaxed point to SE(d): device-pointer, host-pointer and host-mirror form
 //   odom.inc            odometry initialisation: chain tables, device-pointer, host-pointer and host-mirror form
+//   multilat.inc        landmark initialisation from ranges: list tables, device-pointer, host-pointer and host-mirror form
 //   comm.inc            native communication: RCCL, in-process and device-side (p2p.h) transports
 #include <hip/hip_runtime.h>
 // RCCL's types and the few enumerators used, declared here (NCCL's public ABI: they have not changed since 2.0): the
@@ -121,12 +122,31 @@ struct OdomTables {
   double *h_stage = nullptr;     // the same, pinned
   unsigned char *d_deg = nullptr;  // one byte per range measurement
 };
+// The tables of cora_set_multilateration (capi/multilat.inc): the usable ranges of the measurement table grouped per
+// landmark in table order (after the masks), cut into chunks of kMlChunk entries, rows already internal (MlArgs,
+// kernels.h); the device copies, the chunks' partial sums, the landmarks' state, the flag bytes of the range rows
+struct MlTables {
+  bool built = false;
+  int64_t n_with_list = 0, usable = 0, skipped = 0;
+  std::vector<int32_t> chunk_lm, chunk_begin, chunk_len;  // [chunks]
+  std::vector<int32_t> ent_row, ent_m;                    // [entries]
+  std::vector<int32_t> lm_chunk0, lm_row, lm_origin;      // [nl + 1], [nl], [nl]
+  std::vector<unsigned char> lm_init;                     // [nl]
+  int32_t *d_idx = nullptr;  // chunk_lm | chunk_begin | chunk_len | ent_row | ent_m | lm_chunk0 | lm_row | lm_origin
+  unsigned char *d_init = nullptr;
+  double *d_partial = nullptr;   // [kMlSums(d)][chunks]
+  double *d_state = nullptr;     // [nl][kMlState(d)]
+  int32_t *d_istate = nullptr;   // [nl][kMlInts]
+  unsigned char *d_deg = nullptr;  // one byte per range measurement
+  int32_t *d_range_rows = nullptr;  // [3][n_ranges] internal rows: range | b | a (the measurement table's with a and b exchanged)
+};
 struct cora_ctx {
   HostFormat F;
   LongImage LI;  // what the long rows' device arrays hold (long_image.h); derived from F at creation, device handles only
   MeasurementTable meas;
   PosePairTable pairs;
   OdomTables odom;
+  MlTables ml;
   cora_native_comm *native_comm = nullptr;  // owned: the library's own communication (cora_comm_create_*)
   cora::P2PState *p2p_pending = nullptr;    // a mailbox exported by cora_comm_p2p_handle, not yet connected
   int device = -1;
@@ -615,9 +635,18 @@ void free_odom(cora_ctx *c) {  // (the device must be current where there is one
   T = OdomTables();
 }
 
+void free_ml(cora_ctx *c) {  // (the device must be current where there is one)
+  MlTables &T = c->ml;
+  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_init), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state),
+                  static_cast<void *>(T.d_istate), static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows)})
+    if (p) (void)hipFree(p);
+  T = MlTables();
+}
+
 void free_measurements(cora_ctx *c) {  // (the device must be current)
   free_assembly(c);  // (the term map belongs to the table)
   free_odom(c);      // (so do the chain tables: their positions name its edges)
+  free_ml(c);        // (and the multilateration's lists: their entries name its ranges)
   MeasurementTable &M = c->meas;
   for (void *p : {static_cast<void *>(M.d_edge_rows), static_cast<void *>(M.d_range_rows), static_cast<void *>(M.d_edge_data),
                   static_cast<void *>(M.d_range_data), static_cast<void *>(M.d_out)})
@@ -653,6 +682,7 @@ extern "C" {
 #include "capi/rpe.inc"
 #include "capi/round.inc"
 #include "capi/odom.inc"
+#include "capi/multilat.inc"
 
 }  // extern "C"
 

@@ -77,6 +77,7 @@ int cora_set_measurements(cora_ctx *c, int64_t n_edges, const int32_t *edge_rows
   } else {
     c->tmap = TermMap();  // (a term map belongs to the table it was built from)
     c->odom = OdomTables();  // (so do the chain tables)
+    c->ml = MlTables();      // (and the multilateration's lists)
     c->meas = std::move(T);
     c->meas.set = true;
   }

@@ -1168,9 +1168,18 @@ std::vector<std::vector<int32_t>> Problem::odometryChains() const {
 }
 
 Matrix Problem::odometryInitialization(uint64_t seed) const {
+  return odometryStart(seed, -1, nullptr, "Problem::odometryInitialization");
+}
+
+Matrix Problem::rangeAidedInitialization(uint64_t seed, int gn_steps, LandmarkInitInfo *info) const {
+  if (gn_steps < 0) throw std::invalid_argument("Problem::rangeAidedInitialization: gn_steps must be in [0, 16]");
+  return odometryStart(seed, gn_steps, info, "Problem::rangeAidedInitialization");
+}
+
+// the odometry start; with gn_steps >= 0 the landmarks are then placed from the ranges (cora_multilaterate_dev)
+Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where) const {
   checkUpToDate();
-  if (part_world_ > 1) throw std::runtime_error("Problem::odometryInitialization: not supported on a partitioned handle");
-  const char *where = "Problem::odometryInitialization";
+  if (part_world_ > 1) throw std::runtime_error(std::string(where) + ": not supported on a partitioned handle");
   ensureMeasurementTable();
   cora_ctx *c = ctx_.get();
   const int d = dim_, n = numPoses(), nl = numLandmarks(), N = getDataMatrixSize(), p = static_cast<int>(relaxation_rank_);
@@ -1212,18 +1221,58 @@ Matrix Problem::odometryInitialization(uint64_t seed) const {
   int64_t counts[2] = {0, 0};
   std::vector<unsigned char> degenerate(nr + 1, 0);
   CORA_CALL(cora_odometry_init_dev(c, starts.data(), lms.data(), v.x, counts, degenerate.data()), where);
-  if (counts[1] > 0) {  // endpoints that coincide: a random direction each, drawn in range order
-    std::vector<int32_t> idx;
-    std::vector<double> dirs;
-    for (size_t k = 0; k < nr; ++k) {
-      if (!degenerate[k]) continue;
+  std::vector<int32_t> idx;
+  std::vector<double> dirs;
+  auto drawDegenerate = [&](const std::vector<unsigned char> &first, const std::vector<unsigned char> *skip) {
+    for (size_t k = 0; k < nr; ++k) {  // endpoints that coincide: a random direction each, drawn in range order
+      if (!first[k] || (skip && (*skip)[k])) continue;
       idx.push_back(static_cast<int32_t>(k));
       dirs.resize(dirs.size() + d);
       odom_draws::drawDirection(g, U, d, dirs.data() + dirs.size() - d);
     }
+  };
+  if (counts[1] > 0) drawDegenerate(degenerate, nullptr);
+  if (gn_steps < 0 && !idx.empty())
     CORA_CALL(cora_odometry_set_range_rows_dev(c, static_cast<int64_t>(idx.size()), idx.data(), dirs.data(), v.x), where);
-  }
   const Matrix Qm = odom_draws::drawRotation(g, U, p);
+  if (gn_steps >= 0) {
+    // the poses a chain wrote anchor the landmarks; the others sit at zero
+    std::vector<unsigned char> pose_ok(static_cast<size_t>(n) + 1, 0), on(static_cast<size_t>(nl) + 1, 1);
+    for (const auto &ch : chains)
+      for (const int32_t e : ch) {
+        const RelativePoseMeasurement &m = rel_pose_pose_measurements_[static_cast<size_t>(e)];
+        pose_ok[static_cast<size_t>(pose_symbol_idxs_.at(m.first_id))] = 1;
+        pose_ok[static_cast<size_t>(pose_symbol_idxs_.at(m.second_id))] = 1;
+      }
+    CORA_CALL(cora_set_multilateration(c, pose_ok.data(), on.data()), where);
+    int64_t out[4] = {0, 0, 0, 0};
+    std::vector<unsigned char> status(static_cast<size_t>(nl) + 1, 0), after(nr + 1, 0);
+    std::vector<double> cost_linear(static_cast<size_t>(nl) + 1, 0.0), cost_final(static_cast<size_t>(nl) + 1, 0.0);
+    CORA_CALL(cora_multilaterate_dev(c, v.x, gn_steps, out, status.data(), cost_linear.data(), cost_final.data(), nullptr, after.data()), where);
+    // the rows that were degenerate before keep the direction drawn for them where they still are; a row that is
+    // degenerate only now draws after everything odometryInitialization draws
+    std::vector<int32_t> keep_idx;
+    std::vector<double> keep_dirs;
+    for (size_t i = 0; i < idx.size(); ++i)
+      if (after[static_cast<size_t>(idx[i])]) {
+        keep_idx.push_back(idx[i]);
+        keep_dirs.insert(keep_dirs.end(), dirs.begin() + static_cast<std::ptrdiff_t>(i * d), dirs.begin() + static_cast<std::ptrdiff_t>((i + 1) * d));
+      }
+    idx.swap(keep_idx);
+    dirs.swap(keep_dirs);
+    if (out[2] > 0) drawDegenerate(after, &degenerate);
+    if (!idx.empty())
+      CORA_CALL(cora_odometry_set_range_rows_dev(c, static_cast<int64_t>(idx.size()), idx.data(), dirs.data(), v.x), where);
+    if (info) {
+      info->solved = static_cast<long>(out[0]);
+      info->not_solved = static_cast<long>(out[1]);
+      info->gn_steps = static_cast<long>(out[3]);
+      info->degenerate_range_rows = static_cast<long>(out[2]);
+      info->status.assign(status.begin(), status.begin() + nl);
+      info->cost_linear.assign(cost_linear.begin(), cost_linear.begin() + nl);
+      info->cost_final.assign(cost_final.begin(), cost_final.begin() + nl);
+    }
+  }
   std::vector<double> lift(static_cast<size_t>(d) * p);  // the first d rows of Qm, column-major d x p
   for (int col = 0; col < p; ++col)
     for (int a = 0; a < d; ++a) lift[static_cast<size_t>(col) * d + a] = Qm(a, col);

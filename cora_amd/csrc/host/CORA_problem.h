@@ -154,6 +154,15 @@ struct RoundingInfo {
   bool flipped = false;                 // fewer than half: the last column was negated
 };
 
+/** What Problem::rangeAidedInitialization reports (cora_multilaterate_dev, include/cora_hip.h). */
+struct LandmarkInitInfo {
+  long solved = 0, not_solved = 0;     // landmarks placed from their ranges | left at their random draw
+  long gn_steps = 0;                   // Gauss-Newton steps taken, summed over the landmarks
+  long degenerate_range_rows = 0;      // range rows that got a fallback direction
+  std::vector<unsigned char> status;   // per landmark (0 solved, 1 too few ranges, 2 degenerate geometry, 3 no range)
+  std::vector<Scalar> cost_linear, cost_final;  // per landmark: sum omega (|x - t| - r)^2 after the linear stage, at the point written
+};
+
 class Problem {
  private:
   int dim_;
@@ -234,6 +243,7 @@ class Problem {
   void ensureContext() const;
   void ensurePreconditioner() const;
   void ensureMeasurementTable() const;
+  Matrix odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where) const;  // gn_steps < 0: no multilateration
   void fillImplicitFormulationMatrices() const;
   [[noreturn]] void throwLast(int status, const char *where) const;
 
@@ -442,6 +452,13 @@ class Problem {
    * getRelaxationRank() columns.  Installs the measurement table and the chain tables on the handle where they are
    * missing; Problem gains no member.  std::runtime_error on a partitioned handle. */
   Matrix odometryInitialization(uint64_t seed = 7) const;
+  /** EXTENSION beyond the reference: odometryInitialization with the landmarks placed from the ranges
+   * (cora_multilaterate_dev): exactly the draws of odometryInitialization in the same order -- the random landmarks stay
+   * as the fallback of the landmarks that are not solved --, then the multilateration over the poses a chain wrote
+   * (pose_ok) with gn_steps Gauss-Newton steps, the range rows recomputed; a range row that is degenerate only now draws
+   * its direction after everything else, in range order.  Pose rows and the rows of unsolved landmarks have
+   * odometryInitialization's bits.  std::runtime_error on a partitioned handle. */
+  Matrix rangeAidedInitialization(uint64_t seed = 7, int gn_steps = 5, LandmarkInitInfo *info = nullptr) const;
 
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;

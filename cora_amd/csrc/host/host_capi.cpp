@@ -251,6 +251,7 @@ int cora_problem_op(cora_problem *p, const char *op, int cols, const double *A, 
     else if (o == "getRandomInitialGuess") res = q.getRandomInitialGuess();
     else if (o == "getOdomInitialization") res = getOdomInitialization(q);
     else if (o == "odometryInitialization") res = q.odometryInitialization();
+    else if (o == "rangeAidedInitialization") res = q.rangeAidedInitialization();
     else if (o == "getTranslationExplicitSolution") res = q.getTranslationExplicitSolution(wrap(A, N, r));
     else if (o == "alignEstimateToOrigin") res = q.alignEstimateToOrigin(wrap(A, N, r));
     else throw std::invalid_argument("unknown operator " + o);
@@ -280,6 +281,25 @@ int cora_problem_odometry_chains(const cora_problem *p, int64_t counts[2], int64
     }
     counts[0] = static_cast<int64_t>(chains.size());
     counts[1] = at;
+  });
+}
+
+int cora_problem_range_aided_initialization(cora_problem *p, uint64_t seed, int gn_steps, double *out, int64_t counts[4],
+                                            unsigned char *status, double *cost_linear, double *cost_final) {
+  return guarded([&] {
+    LandmarkInitInfo info;
+    const Matrix res = p->problem.rangeAidedInitialization(seed, gn_steps, &info);
+    if (res.rows() == p->problem.getExpectedVariableSize()) p->problem.checkVariablesAreValid(res);  // (throws off the manifold)
+    std::memcpy(out, res.data(), sizeof(double) * static_cast<size_t>(res.size()));
+    if (counts) {
+      counts[0] = info.solved;
+      counts[1] = info.not_solved;
+      counts[2] = info.degenerate_range_rows;
+      counts[3] = info.gn_steps;
+    }
+    if (status) std::copy(info.status.begin(), info.status.end(), status);
+    if (cost_linear) std::copy(info.cost_linear.begin(), info.cost_linear.end(), cost_linear);
+    if (cost_final) std::copy(info.cost_final.begin(), info.cost_final.end(), cost_final);
   });
 }
 

@@ -848,6 +848,234 @@ __host__ __device__ inline bool odom_range_row(const double *ta, const double *t
   return false;
 }
 
+// Landmark initialisation from ranges: multilateration (kernels/multilat.inc; include/cora_hip.h, cora_multilaterate_dev).
+// The usable ranges of the measurement table (one endpoint a landmark, the other a pose) are grouped per landmark into
+// lists in table order and cut into chunks of kMlChunk entries, none across two lists.  Every stage is two launches:
+//   pass : one workgroup of kMlChunk threads per chunk, one entry per thread: the entry's terms (ml_linear_terms,
+//          ml_gn_terms), summed over the chunk into partial[sum][chunk]
+//   fold : ONE wavefront per landmark sums its chunks' partials and runs ml_fold on the sums
+// stage 0 is the linear solve, stage j >= 1 evaluates visited point j - 1 (cost, and H, g of the Gauss-Newton step to
+// point j); the last stage evaluates only and writes the row: 2 (gn_steps + 2) launches.
+// BRACKET ORDER, a function of the list length and kMlChunk alone and the same in the host mirror (capi/multilat.inc):
+//   wavefront: a butterfly over lane exchanges, offsets 1, 2, .., 32 -- every lane takes (lane) + (lane ^ off): the
+//              balanced tree ((l0 + l1) + (l2 + l3)) + ..; lanes without an entry hold +0.0;
+//   chunk: the four wavefronts from the left, ((W_0 + W_1) + W_2) + W_3;
+//   landmark: lane j of the fold takes 0.0 + chunk j + chunk (j + 64) + .. of the list from the left, then the butterfly.
+// Every term is made of single correctly rounded fp64 operations in the order written, never contracted.
+constexpr int kMlChunk = 256;
+constexpr int kMlMaxSteps = 16;
+constexpr double kMlMinPivot = 1e-8;     // of the scaled (d + 1) x (d + 1) normal matrix of the linear stage
+constexpr double kMlGnMinPivot = 1e-12;  // of H / sum(omega)
+constexpr int kMlSums(int d) { return 2 + 2 * d + d * (d + 1) / 2; }   // sum w | w u | w u u^T (upper) | w b | w b u
+constexpr int kMlGnSums(int d) { return d * (d + 1) / 2 + d + 1; }    // sum w J J^T (upper) | w J e | w e^2
+constexpr int kMlState(int d) { return 2 * d + 3; }                   // y | least-cost y | its cost | linear cost | sum w
+constexpr int kMlInts = 4;                                            // status | chosen | steps taken | still stepping
+struct MlArgs {
+  int d = 0, stage = 0, last = 0;
+  int64_t n_lm = 0, n_chunks = 0, n_entries = 0, n_ranges = 0;
+  const int32_t *chunk_lm = nullptr, *chunk_begin = nullptr, *chunk_len = nullptr;  // [n_chunks]
+  const int32_t *ent_row = nullptr, *ent_m = nullptr;  // [n_entries]: INTERNAL row of the anchor, range measurement
+  const int32_t *lm_chunk0 = nullptr;                  // [n_lm + 1]: first chunk of a list
+  const int32_t *lm_row = nullptr, *lm_origin = nullptr;  // [n_lm]: INTERNAL row of the landmark, of its first anchor (-1: none)
+  const unsigned char *lm_init = nullptr;              // [n_lm]: 0 to be solved | 1 too few entries | 3 masked or empty
+  const double *range_data = nullptr;                  // the measurement table's, [2][n_ranges]: r | omega
+  double *partial = nullptr;                           // [kMlSums(d)][n_chunks]
+  double *state = nullptr;                             // [n_lm][kMlState(d)], positions relative to the origin
+  int32_t *istate = nullptr;                           // [n_lm][kMlInts]
+  double *x = nullptr;                                 // d columns at stride ld_for(d) = d
+  int *flag = nullptr;                                 // |= 1 where a sum is not finite
+};
+hipError_t launch_multilat_stage(const MlArgs &A, hipStream_t st);  // pass and fold of A.stage; no landmark: no launch
+// terms of one entry of the linear stage: u = t_i - t_0, b = r^2 - |u|^2
+template <int D>
+__host__ __device__ inline void ml_linear_terms(const double *t0, const double *ti, double r, double w, double *s) {
+#pragma clang fp contract(off)
+  double u[D], wu[D], n2 = 0.0;
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    u[c] = ti[c] - t0[c];
+    n2 = fma(u[c], u[c], n2);
+    wu[c] = w * u[c];
+  }
+  const double wb = w * fma(r, r, -n2);
+  int k = 0;
+  s[k++] = w;
+#pragma unroll
+  for (int c = 0; c < D; ++c) s[k++] = wu[c];
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+#pragma unroll
+    for (int b = a; b < D; ++b) s[k++] = wu[a] * u[b];
+  s[k++] = wb;
+#pragma unroll
+  for (int c = 0; c < D; ++c) s[k++] = wb * u[c];
+}
+// terms of one entry at the point t_0 + y: D = y - u, J = D / |D| (0 where |D| == 0), e = |D| - r
+template <int D>
+__host__ __device__ inline void ml_gn_terms(const double *y, const double *t0, const double *ti, double r, double w, double *s) {
+#pragma clang fp contract(off)
+  double dv[D], J[D], wJ[D], n2 = 0.0;
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    dv[c] = y[c] - (ti[c] - t0[c]);
+    n2 = fma(dv[c], dv[c], n2);
+  }
+  const double nrm = sqrt(n2), e = nrm - r;
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    J[c] = nrm == 0.0 ? 0.0 : dv[c] / nrm;
+    wJ[c] = w * J[c];
+  }
+  int k = 0;
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+#pragma unroll
+    for (int b = a; b < D; ++b) s[k++] = wJ[a] * J[b];
+#pragma unroll
+  for (int c = 0; c < D; ++c) s[k++] = wJ[c] * e;
+  s[k++] = (w * e) * e;
+}
+// Cholesky without pivoting of the symmetric M (n x n row-major, upper part read) and the solve of M z = q in place in
+// q; returns false, with q undefined, at the first pivot <= min_pivot (or not a number)
+template <int N>
+__host__ __device__ inline bool ml_cholesky_solve(const double *M, double *q, double min_pivot) {
+#pragma clang fp contract(off)
+  double G[N * N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    double p = M[j * N + j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) p = fma(-G[j * N + k], G[j * N + k], p);
+    if (!(p > min_pivot)) return false;
+    const double g = sqrt(p);
+    G[j * N + j] = g;
+#pragma unroll
+    for (int i = j + 1; i < N; ++i) {
+      double v = M[j * N + i];
+#pragma unroll
+      for (int k = 0; k < j; ++k) v = fma(-G[i * N + k], G[j * N + k], v);
+      G[i * N + j] = v / g;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    double v = q[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) v = fma(-G[i * N + k], q[k], v);
+    q[i] = v / G[i * N + i];
+  }
+#pragma unroll
+  for (int i = N - 1; i >= 0; --i) {
+    double v = q[i];
+#pragma unroll
+    for (int k = i + 1; k < N; ++k) v = fma(-G[k * N + i], q[k], v);
+    q[i] = v / G[i * N + i];
+  }
+  return true;
+}
+// The linear stage of a landmark from its sums S: the normal equations of |x|^2 - 2 u^T x = b in (x, s), lengths scaled
+// by the ONE scale L = sqrt(sum w |u|^2 / sum w), divided by sum w.  Returns the status (0 solved, 2 degenerate), y = L x'.
+template <int D>
+__host__ __device__ inline int ml_linear_solve(const double *S, double *y) {
+#pragma clang fp contract(off)
+  constexpr int N = D + 1, UU = 1 + D, B = UU + D * (D + 1) / 2;
+  const double sw = S[0];
+  if (!(sw > 0.0)) return 2;
+  double tr = 0.0;
+  {
+    int k = UU;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      tr = tr + S[k];
+      k += D - a;
+    }
+  }
+  const double L = sqrt(tr / sw);
+  if (!(L > 0.0)) return 2;
+  const double Lsw = L * sw, Ltr = L * tr;
+  double M[N * N], q[N];
+  int k = UU;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+#pragma unroll
+    for (int b = a; b < D; ++b) M[a * N + b] = M[b * N + a] = (4.0 * S[k++]) / tr;
+    M[a * N + D] = M[D * N + a] = (-2.0 * S[1 + a]) / Lsw;
+    q[a] = (-2.0 * S[B + 1 + a]) / Ltr;
+  }
+  M[D * N + D] = 1.0;
+  q[D] = S[B] / tr;
+  if (!ml_cholesky_solve<N>(M, q, kMlMinPivot)) return 2;
+#pragma unroll
+  for (int c = 0; c < D; ++c) y[c] = L * q[c];
+  return odom_finite(y, D) ? 0 : 2;
+}
+// y <- y - H^-1 g with H = sum w J J^T / sum w, g = sum w J e / sum w; false, and y kept, at a pivot <= kMlGnMinPivot
+// or a step that is not finite
+template <int D>
+__host__ __device__ inline bool ml_gn_step(const double *S, double sw, double *y) {
+#pragma clang fp contract(off)
+  double H[D * D], g[D], yn[D];
+  int k = 0;
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+#pragma unroll
+    for (int b = a; b < D; ++b) H[a * D + b] = H[b * D + a] = S[k++] / sw;
+#pragma unroll
+  for (int c = 0; c < D; ++c) g[c] = S[k++] / sw;
+  if (!ml_cholesky_solve<D>(H, g, kMlGnMinPivot)) return false;
+#pragma unroll
+  for (int c = 0; c < D; ++c) yn[c] = y[c] - g[c];
+  if (!odom_finite(yn, D)) return false;
+#pragma unroll
+  for (int c = 0; c < D; ++c) y[c] = yn[c];
+  return true;
+}
+// What the fold does with the sums S of a landmark at a stage (st: kMlState(D) doubles, ist: kMlInts integers, init: the
+// status known from the list alone).  Returns false where a sum is not finite (the landmark is then given up: status 2).
+template <int D>
+__host__ __device__ inline bool ml_fold(int stage, int last, const double *S, double *st, int32_t *ist, int init) {
+  double *y = st, *best = st + D, &cbest = st[2 * D], &clin = st[2 * D + 1], &sw = st[2 * D + 2];
+  if (stage == 0) {
+    for (int i = 0; i < kMlState(D); ++i) st[i] = 0.0;
+    ist[0] = init;
+    ist[1] = -1;
+    ist[2] = ist[3] = 0;
+    if (init != 0) return true;
+    if (!odom_finite(S, kMlSums(D))) {
+      ist[0] = 2;
+      return false;
+    }
+    ist[0] = ml_linear_solve<D>(S, y);
+    if (ist[0] != 0) {
+      for (int c = 0; c < D; ++c) y[c] = 0.0;
+      return true;
+    }
+    for (int c = 0; c < D; ++c) best[c] = y[c];
+    sw = S[0];
+    ist[3] = 1;
+    return true;
+  }
+  if (ist[0] != 0) return true;
+  if (!odom_finite(S, kMlGnSums(D))) {
+    ist[3] = 0;
+    return false;
+  }
+  const double cost = S[kMlGnSums(D) - 1];
+  if (stage == 1) {
+    clin = cbest = cost;
+    ist[1] = 0;
+  } else if (cost < cbest) {
+    cbest = cost;
+    for (int c = 0; c < D; ++c) best[c] = y[c];
+    ist[1] = stage - 1;
+  }
+  if (!last && ist[3]) {
+    if (ml_gn_step<D>(S, sw, y)) ist[2] += 1;
+    else ist[3] = 0;
+  }
+  return true;
+}
+
 // In-place update of Q's values (kernels/update_values.inc).  src: the sources of ValueMap (cora_internal.h), vals: the
 // new CSR values on the device.
 // check: flag |= 1 where a value is not finite, |= 2 where a mirror pair (mirror[2j], mirror[2j + 1]) differs.

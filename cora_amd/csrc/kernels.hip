@@ -26,7 +26,7 @@
 #define CORA_LDG 63
 #endif
 
-// ONE source in thirteen pieces (round 6: the file had grown to 3 700 lines); this file holds the switches of the translation units
+// ONE source in fourteen pieces (round 6: the file had grown to 3 700 lines); this file holds the switches of the translation units
 // and, at the end, the measurement builds' read-back hooks.  Inside namespace cora, in this order:
 //   kernels/common.inc   row loads / stores, wave reductions, the STPCG state's scalar steps
 //   kernels/spmm.inc     the sliced SpMM with fused epilogues (chain slices, row slices, long-row chunks)        CORA_TU & 1
@@ -37,6 +37,7 @@
 //   kernels/rpe.inc      relative pose error over the handle's pair table: errors, sums, maxima, first maximum       CORA_TU & 2
 //   kernels/round.inc    rounding of a resident vector to SE(d): count, finish, per-unit pass                       CORA_TU & 2
 //   kernels/odom.inc     odometry initialisation: segmented scan of SE(d) over the chain positions, fill of the other rows  CORA_TU & 2
+//   kernels/multilat.inc  landmark initialisation from ranges: pass over the chunks of the range lists, fold and solve per landmark  CORA_TU & 2
 //   kernels/update_values.inc  in-place update of Q's values: check of the new values, gather passes                CORA_TU & 2
 //   kernels/assemble.inc  Q(w) from per-measurement weights through the term map: check, short and long entries     CORA_TU & 2
 //   kernels/tri.inc      the staged Cholesky solve: k_rowop, k_blockop, k_subblock                                 CORA_TU & 4
@@ -51,6 +52,7 @@ namespace cora {
 #include "kernels/rpe.inc"
 #include "kernels/round.inc"
 #include "kernels/odom.inc"
+#include "kernels/multilat.inc"
 #include "kernels/update_values.inc"
 #include "kernels/assemble.inc"
 #include "kernels/tri.inc"

@@ -544,6 +544,32 @@ hipError_t launch_odom_ranges(const OdomFillArgs &A, hipStream_t st) {
   hipLaunchKernelGGL(k_round_finish, dim3(1), dim3(64), 0, st, A.partial, nb, 0, A.words);  // words[0] = the sum
   return hipGetLastError();
 }
+// the multilateration (kernels/multilat.inc): the pass over the chunks and the fold per landmark of one stage
+hipError_t launch_multilat_stage(const MlArgs &A, hipStream_t st) {
+  if (A.n_lm <= 0) return hipSuccess;
+  if ((A.d != 2 && A.d != 3) || A.stage < 0 || A.stage > kMlMaxSteps + 1 || (A.last && A.stage == 0) || A.n_chunks < 0 ||
+      A.n_chunks >= (int64_t(1) << 31) || A.n_lm >= (int64_t(1) << 31) || !A.lm_chunk0 || !A.lm_row || !A.lm_origin || !A.lm_init ||
+      !A.state || !A.istate || !A.x || !A.flag ||
+      (A.n_chunks > 0 && (!A.chunk_lm || !A.chunk_begin || !A.chunk_len || !A.ent_row || !A.ent_m || !A.range_data || !A.partial)))
+    return hipErrorInvalidValue;
+  const dim3 chunks(static_cast<unsigned>(A.n_chunks)), lms(static_cast<unsigned>(A.n_lm));
+  if (A.stage == 0) {
+    if (A.d == 2) {
+      if (A.n_chunks > 0) hipLaunchKernelGGL(k_ml_pass_linear<2>, chunks, dim3(kMlChunk), 0, st, A);
+      hipLaunchKernelGGL(k_ml_fold_linear<2>, lms, dim3(kWave), 0, st, A);
+    } else {
+      if (A.n_chunks > 0) hipLaunchKernelGGL(k_ml_pass_linear<3>, chunks, dim3(kMlChunk), 0, st, A);
+      hipLaunchKernelGGL(k_ml_fold_linear<3>, lms, dim3(kWave), 0, st, A);
+    }
+  } else if (A.d == 2) {
+    if (A.n_chunks > 0) hipLaunchKernelGGL(k_ml_pass_gn<2>, chunks, dim3(kMlChunk), 0, st, A);
+    hipLaunchKernelGGL(k_ml_fold_gn<2>, lms, dim3(kWave), 0, st, A);
+  } else {
+    if (A.n_chunks > 0) hipLaunchKernelGGL(k_ml_pass_gn<3>, chunks, dim3(kMlChunk), 0, st, A);
+    hipLaunchKernelGGL(k_ml_fold_gn<3>, lms, dim3(kWave), 0, st, A);
+  }
+  return hipGetLastError();
+}
 hipError_t launch_round_amax(int64_t n, const double *y, double *partial, int nblocks, int *flag, hipStream_t st) {
   if (n < 1 || nblocks < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_round_amax, dim3(nblocks), dim3(256), 0, st, n, y, partial, flag);

@@ -200,7 +200,8 @@ class Problem:
             out = np.zeros(1)
         pa, pb, pc = ptr(A), ptr(B), ptr(C_)
         if name != "evaluateObjective":
-            full = name in ("getOdomInitialization", "odometryInitialization", "getTranslationExplicitSolution", "alignEstimateToOrigin")
+            full = name in ("getOdomInitialization", "odometryInitialization", "rangeAidedInitialization",
+                            "getTranslationExplicitSolution", "alignEstimateToOrigin")
             out = np.zeros((dm["N"] if full else N, cols[0] if cols else p), order="F")
         if len(set(cols)) > 1:
             raise HostError("operands have different column counts: %s" % cols)
@@ -218,6 +219,20 @@ class Problem:
         self._chk(self.L.cora_problem_odometry_chains(self.h, cnt, ptr.ctypes.data_as(C.POINTER(C.c_int64)),
                                                       edges.ctypes.data_as(C.POINTER(C.c_int32))))
         return [edges[ptr[i]:ptr[i + 1]].copy() for i in range(int(cnt[0]))]
+
+    def range_aided_initialization(self, seed=7, gn_steps=5):
+        """Problem::rangeAidedInitialization: (x0, info) with info a dict solved, not_solved, n_degenerate, steps, status,
+        cost_linear, cost_final (per landmark).  The start has passed checkVariablesAreValid."""
+        dm = self.dims()
+        nl = dm["N"] - (dm["d"] + 1) * dm["n"] - dm["r"]
+        out = np.zeros((dm["N"], dm["rank"]), order="F")
+        cnt = (C.c_int64 * 4)()
+        status, cl, cf = np.zeros(nl + 1, dtype=np.uint8), np.zeros(nl + 1), np.zeros(nl + 1)
+        self._chk(self.L.cora_problem_range_aided_initialization(self.h, C.c_uint64(seed), int(gn_steps), out.ctypes.data_as(_dp),
+                                                                 cnt, status.ctypes.data_as(C.c_void_p), cl.ctypes.data_as(_dp),
+                                                                 cf.ctypes.data_as(_dp)))
+        return out, dict(solved=int(cnt[0]), not_solved=int(cnt[1]), n_degenerate=int(cnt[2]), steps=int(cnt[3]),
+                         status=status[:nl], cost_linear=cl[:nl], cost_final=cf[:nl])
 
     def lambda_blocks(self, Y):
         dm = self.dims()

@@ -22,12 +22,12 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding] [--device-init]" << std::endl;
+    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding] [--device-init [--landmark-init [--gn-steps k]]]" << std::endl;
     return 1;
   }
-  int max_rank = 10;
+  int max_rank = 10, gn_steps = 5;
   std::string tum, save_dir, residuals, weights, robust, barc2, weights_out, aligned_tum, rpe_steps, rpe_dists;
-  bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false;
+  bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false, landmark_init = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--jacobi") jacobi = true;
@@ -58,11 +58,15 @@ int main(int argc, char **argv) {
     else if (a == "--device-rounding") device_rounding = true;
     // with --odom-init: the start is composed on the device (Problem::odometryInitialization) in place of getOdomInitialization
     else if (a == "--device-init") device_init = true;
+    // with --odom-init --device-init: the landmarks of the start are placed from the ranges (Problem::rangeAidedInitialization)
+    else if (a == "--landmark-init") landmark_init = true;
+    else if (a == "--gn-steps" && i + 1 < argc) gn_steps = std::atoi(argv[++i]);
   }
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
   try {
     if (device_init && !odom) throw std::runtime_error("--device-init composes the odometry start on the device: it needs --odom-init");
+    if (landmark_init && !device_init) throw std::runtime_error("--landmark-init places the landmarks of the device's odometry start: it needs --odom-init --device-init");
     const auto t_start = clk::now();
     CORA::Problem problem = CORA::parsePyfgTextToProblem(argv[1]);
     const auto t_parsed = clk::now();
@@ -111,6 +115,16 @@ int main(int argc, char **argv) {
                 static_cast<long>(problem.data_matrix_.nonZeros()));
     CORA::Matrix x0 = !odom ? problem.getRandomInitialGuess()
                       : device_init ? problem.odometryInitialization() : CORA::getOdomInitialization(problem);
+    if (landmark_init) {  // (an extension beyond the reference: Problem::rangeAidedInitialization)
+      CORA::LandmarkInitInfo lm;
+      auto range_sum = [&](const CORA::Matrix &x) {  // (the implicit formulation's variable has no translation rows)
+        return problem.measurementResiduals(implicit ? CORA::Matrix(x.block(0, 0, problem.rotAndRangeMatrixSize(), x.cols())) : x).range_sum;
+      };
+      const double without = range_sum(x0);
+      x0 = problem.rangeAidedInitialization(7, gn_steps, &lm);
+      std::printf("landmark init: %ld landmarks solved, %ld not solved (%ld Gauss-Newton steps); range residual sum at the start %.6e with it, %.6e without\n",
+                  lm.solved, lm.not_solved, lm.gn_steps, range_sum(x0), without);
+    }
     if (odom && implicit)  // examples/paper_experiments.cpp:623-625
       x0 = x0.block(0, 0, problem.rotAndRangeMatrixSize(), x0.cols());
     CORA::CoraSolveInfo info;

@@ -779,6 +779,80 @@ int cora_odometry_set_range_rows_dev(cora_ctx *ctx, int64_t m, const int32_t *ra
 int cora_debug_odometry_init_host(cora_ctx *ctx, const double *starts, const double *landmarks, double *Out, int ldo,
                                   int64_t out[2], unsigned char *degenerate);
 
+/* ---- LANDMARK INITIALISATION FROM RANGES: MULTILATERATION, on the device -----------------------------------------------
+ * Places the landmarks of a resident vector of d columns (the output of cora_odometry_init_dev, stride cora_ld_for(d))
+ * from the range table of the measurement table and the pose translations the vector holds, in place.  Needs a
+ * measurement table (cora_set_measurements) and the tables of cora_set_multilateration.
+ * DEFINITIONS.
+ *   usable range     a range measurement of the table one endpoint of which is a landmark (a translation row past the n
+ *                    poses' translation rows) and the other a pose, in either order.  Pose-pose and landmark-landmark
+ *                    ranges are skipped and counted.
+ *   anchor           the pose endpoint t_i of a usable range, with the distance r_i and the precision omega_i.
+ *   list of l        the usable ranges of landmark l in table order, after the masks: pose_ok[n] keeps the anchors whose
+ *                    pose is flagged (NULL: all), landmark_on[nl] the landmarks that are solved (NULL: all), nl = nt - n.
+ *   chunk            kMlChunk = 256 consecutive entries of one list; a chunk never spans two lists.
+ *   origin           the first anchor t_0 of a list; u_i = t_i - t_0, and the landmark is kept as y = x - t_0: the digits
+ *                    stay when the trajectory is far from zero.
+ *   linear stage     sums of omega, omega u, omega u u^T, omega b, omega b u with b = r^2 - |u|^2; the normal equations of
+ *                    |y|^2 - 2 u^T y = b in (y, s), lengths scaled by the ONE scale L = sqrt(sum omega |u|^2 / sum omega),
+ *                    divided by sum omega, factored by a (d + 1) x (d + 1) Cholesky without pivoting.
+ *   status           0 solved | 1 fewer than d + 1 entries | 2 degenerate geometry: sum omega <= 0, L == 0 or a pivot
+ *                    <= 1e-8 (anchors on a line in 2-D, in a plane in 3-D, coincident anchors) | 3 masked, or an empty
+ *                    list.  A landmark whose status is not 0 keeps the row the caller wrote.
+ *   Gauss-Newton     gn_steps in [0, 16] steps y <- y - H^-1 g with D_i = y - u_i, J_i = D_i / |D_i| (0 where |D_i| == 0),
+ *                    e_i = |D_i| - r_i, H = sum omega J J^T / sum omega, g = sum omega J e / sum omega, by a d x d
+ *                    Cholesky.  A landmark stops stepping, and keeps its point, at a pivot <= 1e-12 or a step that is not
+ *                    finite.  The visited points are 0 (the linear solution), 1, 2, ..; the cost sum omega e^2 is
+ *                    evaluated at every one, the last included, and the row written is t_0 + the visited point of least
+ *                    cost, the earliest on ties (chosen): never worse than the linear solution on the range cost.
+ *   range rows       afterwards the unit range rows of ALL range measurements are recomputed from the translation rows by
+ *                    the range-row step of the odometry initialisation, its rules unchanged (below 1e-5: a zero row,
+ *                    reported degenerate; the caller supplies directions with cora_odometry_set_range_rows_dev), with
+ *                    the endpoints exchanged: row m = (x_t(a) - x_t(b)) / |x_t(a) - x_t(b)|, the direction at which the
+ *                    residual |x_t(b) - x_t(a) + r x_rho|^2 of the table is (|x_t(b) - x_t(a)| - r)^2, so that the range
+ *                    residuals of the result ARE the range cost the landmarks were placed by.  (cora_odometry_init_dev
+ *                    writes the opposite direction, as the host function it mirrors does.)
+ * cora_set_multilateration   validates, groups, translates to internal rows once and uploads the chunk table.  The tables
+ *            stay on the handle until replaced, until the measurement table is replaced or until the handle is destroyed.
+ *            Works on a plan-only handle, except for the upload.  A refused call leaves the tables as they were.
+ * cora_multilateration_counts   out = {landmarks with a non-empty list, usable ranges (before the masks), skipped ranges,
+ *            chunks}.
+ * cora_multilaterate_dev   out (host) = {landmarks solved, landmarks not solved, degenerate range rows, Gauss-Newton steps
+ *            taken, summed over the landmarks}; status, cost_linear, cost_final, chosen: host arrays of nl entries or NULL
+ *            (costs 0 and chosen -1 where the status is not 0); degenerate: host bytes, one per range measurement, or NULL.
+ *            2 (gn_steps + 2) launches -- per stage one pass over the chunks and one fold per landmark -- and the range
+ *            rows.  Everything on the handle's stream; synchronises once, at the end.
+ * cora_multilaterate       the host-pointer form, in place: X is N x d column-major with leading dimension ldx.
+ * cora_debug_multilaterate_host   the same on the host through the translated tables, in the device's bracket order and
+ *            through the functions the kernels call: X has the device's bits.  Works on a plan-only handle.  (It reads the
+ *            host's copy of the range table: after cora_assemble_values_dev rescaled the device's precisions the two differ.)
+ * ARITHMETIC.  Single correctly rounded fp64 operations in the order written, never contracted: u by subtraction, |u|^2
+ * by fma from +0.0, b = fma(r, r, -|u|^2), every term a chain of products from the left (omega u_a, then times u_b; omega
+ * b, then times u_a; omega J_a, then times J_b or e; omega e, then e).  The sums are additions bracketed as a function of the
+ * list's length and kMlChunk alone: within a wavefront of 64 entries a butterfly over lane exchanges with offsets 1, 2, ..,
+ * 32 (the balanced tree over neighbouring lanes; a lane without an entry holds +0.0); the four wavefronts of a chunk from the
+ * left; chunk sums as [sum][chunk]; one wavefront per landmark in which lane j adds chunks j, j + 64, .. of the list from the
+ * left to +0.0, then the same butterfly.  The solves use fma with the inner index ascending, one square root per pivot, one
+ * division per entry.  The same bits on every call.  No atomics on doubles.
+ * ACCURACY.  The linear solution is that of a least-squares problem in the squared ranges: its error against exact
+ * arithmetic is of the order eps kappa(M) (|y| + L) with M the scaled normal matrix, and on noisy ranges it is not the
+ * minimiser of the range cost, which the Gauss-Newton steps approach; their error is of the order eps kappa(H) (|y| + L).
+ * ERRORS.  CORA_ERR_NOT_READY: no measurement table, or no multilateration tables.  CORA_ERR_ARG: a partitioned handle;
+ * gn_steps outside [0, 16]; a null X or out; two range measurements of the table that name one range row.  CORA_ERR_SHAPE: a
+ * leading dimension below N.  CORA_ERR_NAN: a sum or a range row that is not finite (the device forms report it through
+ * the handle's flag word).  CORA_ERR_HIP: a device form on a plan-only handle.
+ * STATE.  Nothing the handle computes with changes.  The handle keeps the list and chunk tables, the chunks' partial sums,
+ * the landmarks' state and the flag bytes. */
+int cora_set_multilateration(cora_ctx *ctx, const unsigned char *pose_ok /* [n] or NULL */,
+                             const unsigned char *landmark_on /* [nt - n] or NULL */);
+int cora_multilateration_counts(const cora_ctx *ctx, int64_t out[4]);
+int cora_multilaterate_dev(cora_ctx *ctx, double *dX, int gn_steps, int64_t out[4], unsigned char *status, double *cost_linear,
+                           double *cost_final, int32_t *chosen, unsigned char *degenerate);
+int cora_multilaterate(cora_ctx *ctx, double *X, int ldx, int gn_steps, int64_t out[4], unsigned char *status,
+                       double *cost_linear, double *cost_final, int32_t *chosen, unsigned char *degenerate);
+int cora_debug_multilaterate_host(cora_ctx *ctx, double *X, int ldx, int gn_steps, int64_t out[4], unsigned char *status,
+                                  double *cost_linear, double *cost_final, int32_t *chosen, unsigned char *degenerate);
+
 /* Timing helpers: HIP events on the handle's stream. */
 int cora_timer_start(cora_ctx *ctx);
 int cora_timer_stop_ms(cora_ctx *ctx, float *ms); /* synchronises */

@@ -92,6 +92,8 @@ int cora_problem_variable_size(cora_problem *p, int64_t *rows);
  *  "getOdomInitialization"    (none)             -> out   (examples/paper_experiments.cpp:426-534)
  *  "odometryInitialization"   (none)             -> out   the same start composed on the device (Problem::odometryInitialization,
  *                                                        seed 7: getOdomInitialization's start up to rounding)
+ *  "rangeAidedInitialization" (none)             -> out   odometryInitialization with the landmarks placed from the ranges
+ *                                                        (Problem::rangeAidedInitialization, seed 7, 5 Gauss-Newton steps)
  *  "getTranslationExplicitSolution" A=Y (implicit) -> out (d+1)n + r + l rows (src/CORA_problem.cpp:1168)
  *  "alignEstimateToOrigin"    A=Y (rank d)       -> out (d+1)n + r + l rows (src/CORA_problem.cpp:1234)
  * Inputs are N x cols with leading dimension N = cora_problem_variable_size() (cols is checked
@@ -103,6 +105,12 @@ int cora_problem_op(cora_problem *p, const char *op, int cols, const double *A, 
  * the relative-pose measurements in the order they were added.  counts = { chains, edges of all chains }; chain_ptr
  * (chains + 1 entries) and chain_edges may both be NULL to ask for the counts alone. */
 int cora_problem_odometry_chains(const cora_problem *p, int64_t counts[2], int64_t *chain_ptr, int32_t *chain_edges);
+/* Problem::rangeAidedInitialization (an extension beyond the reference; include/cora_hip.h, "landmark initialisation from
+ * ranges").  out: data-matrix-size x rank.  counts = { landmarks solved, not solved, degenerate range rows, Gauss-Newton
+ * steps taken }; status, cost_linear, cost_final: one entry per landmark.  Every array but out may be NULL.  In the explicit
+ * formulation the result is passed through checkVariablesAreValid (an error off the manifold). */
+int cora_problem_range_aided_initialization(cora_problem *p, uint64_t seed, int gn_steps, double *out, int64_t counts[4],
+                                            unsigned char *status, double *cost_linear, double *cost_final);
 /* compute_Lambda_blocks(Y): stiefel d x dn (ld d), oblique r */
 int cora_problem_lambda_blocks(cora_problem *p, const double *Y, double *stiefel, double *oblique);
 /* Problem::measurementResiduals (an extension beyond the reference; formulas in include/cora_hip.h, "per-measurement
