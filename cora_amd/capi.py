@@ -1098,6 +1098,69 @@ class Context:
         """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
         return self._ml_call(lambda *a: self.L.cora_multilaterate_dev(self.h, C.c_void_p(x_ptr), *a), gn_steps)
 
+    # ---- chain placement from inter-robot ranges (include/cora_hip.h, cora_place_chains_dev)
+    def set_chain_placement(self, chain_fixed=None, min_ranges=None):
+        """Orders the odometry chains into stages from the pose-pose ranges between them: chain_fixed a mask per chain or
+        None (chain 0); min_ranges None: 4 x the unknowns of the linear stage (28 at d = 2, 64 at d = 3)."""
+        if min_ranges is None:
+            min_ranges = 4 * (7 if self.d == 2 else 16)
+        keep, ptr = None, None
+        if chain_fixed is not None:
+            nch = self.odometry_chains_count()[0]
+            a = np.ascontiguousarray(np.asarray(chain_fixed).reshape(-1) != 0, dtype=np.uint8)
+            if len(a) != nch:
+                raise CoraError(5, "chain_fixed needs %d entries, not %d" % (nch, len(a)))
+            keep = np.concatenate([a, np.zeros(1, dtype=np.uint8)])  # (never an empty buffer)
+            ptr = keep.ctypes.data_as(C.c_void_p)
+        self._chk(self.L.cora_set_chain_placement(self.h, ptr, int(min_ranges)))
+
+    def chain_placement_counts(self):
+        """(stages, entries, chunks, skipped ranges) of the installed tables."""
+        out = (C.c_int64 * 4)()
+        self._chk(self.L.cora_chain_placement_counts(self.h, out))
+        return tuple(int(v) for v in out)
+
+    def chain_placement_order(self):
+        """The chain of every stage, in the order of the stages."""
+        order = np.zeros(self.chain_placement_counts()[0] + 1, dtype=np.int32)
+        self._chk(self.L.cora_chain_placement_order(self.h, order.ctypes.data_as(_ip)))
+        return order[:-1]
+
+    def _pl_call(self, fn, gn_steps):
+        nch, nr, g = self.odometry_chains_count()[0], self.measurement_counts()[1], self.d * self.d + self.d
+        out = (C.c_int64 * 5)()
+        status, chosen = np.zeros(nch + 1, dtype=np.uint8), np.zeros(nch + 1, dtype=np.int32)
+        cs, cl, cf, tr = np.zeros(nch + 1), np.zeros(nch + 1), np.zeros(nch + 1), np.zeros((nch + 1) * g)
+        deg = np.zeros(nr + 1, dtype=np.uint8)
+        self._chk(fn(int(gn_steps), out, status.ctypes.data_as(C.c_void_p), _d(cs), _d(cl), _d(cf), chosen.ctypes.data_as(_ip), _d(tr),
+                     deg.ctypes.data_as(C.c_void_p)))
+        return dict(placed=int(out[0]), not_placed=int(out[1]), steps=int(out[2]), n_degenerate=int(out[3]), stages=int(out[4]),
+                    status=status[:nch], cost_start=cs[:nch], cost_linear=cl[:nch], cost_final=cf[:nch], chosen=chosen[:nch],
+                    transforms=tr[:nch * g].reshape(nch, g), degenerate=deg[:nr].astype(bool))
+
+    def _pl_host(self, fn, X, gn_steps):
+        X = np.array(X, dtype=np.float64, order="F", copy=True)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise CoraError(1, "X must have d columns")
+        res = self._pl_call(lambda *a: fn(self.h, _d(X), X.shape[0], *a), gn_steps)
+        res["X"] = X
+        return res
+
+    def place_chains(self, X, gn_steps=5):
+        """The chains of the host matrix X (N x d) moved rigidly onto the fixed chains from the ranges between chains, on
+        the device.  Returns dict X (a copy with the chains' rows and the range rows rewritten), placed, not_placed, steps,
+        n_degenerate, stages, status, cost_start, cost_linear, cost_final, chosen (per chain), transforms (per chain: R
+        row-major, then t), degenerate (bool per range measurement)."""
+        return self._pl_host(self.L.cora_place_chains, X, gn_steps)
+
+    def debug_place_chains_host(self, X, gn_steps=5):
+        """The same on the host in the device's bracket order (no GPU needed): X has the device's bits."""
+        return self._pl_host(self.L.cora_debug_place_chains_host, X, gn_steps)
+
+    def place_chains_dev(self, x_ptr, gn_steps=5):
+        """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
+        return self._pl_call(lambda *a: self.L.cora_place_chains_dev(self.h, C.c_void_p(x_ptr), *a), gn_steps)
+
     # ---- test hook
     def debug_format_spmm_host(self, X):
         X = _f(X)

@@ -21,6 +21,7 @@
 //   round.inc           rounding of a relaxed point to SE(d): device-pointer, host-pointer and host-mirror form
 //   odom.inc            odometry initialisation: chain tables, device-pointer, host-pointer and host-mirror form
 //   multilat.inc        landmark initialisation from ranges: list tables, device-pointer, host-pointer and host-mirror form
+//   placement.inc       chain placement from inter-robot ranges: stage tables, device-pointer, host-pointer and host-mirror form
 //   comm.inc            native communication: RCCL, in-process and device-side (p2p.h) transports
 #include <hip/hip_runtime.h>
 // RCCL's types and the few enumerators used, declared here (NCCL's public ABI: they have not changed since 2.0): the
@@ -140,6 +141,26 @@ struct MlTables {
   unsigned char *d_deg = nullptr;  // one byte per range measurement
   int32_t *d_range_rows = nullptr;  // [3][n_ranges] internal rows: range | b | a (the measurement table's with a and b exchanged)
 };
+// The tables of cora_set_chain_placement (capi/placement.inc): the order of the stages, decided from structure alone; per
+// stage the chain, its positions in the chain tables, the first entry's rows and the stage's chunks; the entry lists (row
+// of the chain's position, row of the anchor, range measurement) in table order, cut into chunks of kPlChunk entries, rows
+// already internal (PlArgs, kernels.h); the device copies, the chunks' partial sums, the stages' state, the range rows' bytes
+struct PlTables {
+  bool built = false;
+  int min_ranges = 0;
+  int64_t skipped = 0, max_chunks = 0;
+  std::vector<int32_t> stage_chain, stage_chunk0;             // [stages], [stages + 1]
+  std::vector<int32_t> stage_origin_q, stage_origin_a, stage_pos0, stage_npos;  // [stages]
+  std::vector<int32_t> chunk_begin, chunk_len;                // [chunks]
+  std::vector<int32_t> ent_q, ent_a, ent_m;                   // [entries]
+  std::vector<unsigned char> chain_init;                      // [chains]: 0 a stage | 1 too few entries | 3 no entry | 4 fixed
+  int32_t *d_idx = nullptr;      // chunk_begin | chunk_len | ent_q | ent_a | ent_m
+  double *d_partial = nullptr;   // [kPlSums(d)][max_chunks]
+  double *d_state = nullptr;     // [stages][kPlState(d)]
+  int32_t *d_istate = nullptr;   // [stages][kPlInts]
+  unsigned char *d_deg = nullptr;   // one byte per range measurement
+  int32_t *d_range_rows = nullptr;  // [3][n_ranges] internal rows: range | b | a (as MlTables')
+};
 struct cora_ctx {
   HostFormat F;
   LongImage LI;  // what the long rows' device arrays hold (long_image.h); derived from F at creation, device handles only
@@ -147,6 +168,7 @@ struct cora_ctx {
   PosePairTable pairs;
   OdomTables odom;
   MlTables ml;
+  PlTables pl;
   cora_native_comm *native_comm = nullptr;  // owned: the library's own communication (cora_comm_create_*)
   cora::P2PState *p2p_pending = nullptr;    // a mailbox exported by cora_comm_p2p_handle, not yet connected
   int device = -1;
@@ -635,6 +657,14 @@ void free_odom(cora_ctx *c) {  // (the device must be current where there is one
   T = OdomTables();
 }
 
+void free_pl(cora_ctx *c) {  // (the device must be current where there is one)
+  PlTables &T = c->pl;
+  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state), static_cast<void *>(T.d_istate),
+                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows)})
+    if (p) (void)hipFree(p);
+  T = PlTables();
+}
+
 void free_ml(cora_ctx *c) {  // (the device must be current where there is one)
   MlTables &T = c->ml;
   for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_init), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state),
@@ -647,6 +677,7 @@ void free_measurements(cora_ctx *c) {  // (the device must be current)
   free_assembly(c);  // (the term map belongs to the table)
   free_odom(c);      // (so do the chain tables: their positions name its edges)
   free_ml(c);        // (and the multilateration's lists: their entries name its ranges)
+  free_pl(c);        // (and the chain placement's stages)
   MeasurementTable &M = c->meas;
   for (void *p : {static_cast<void *>(M.d_edge_rows), static_cast<void *>(M.d_range_rows), static_cast<void *>(M.d_edge_data),
                   static_cast<void *>(M.d_range_data), static_cast<void *>(M.d_out)})
@@ -683,6 +714,7 @@ extern "C" {
 #include "capi/round.inc"
 #include "capi/odom.inc"
 #include "capi/multilat.inc"
+#include "capi/placement.inc"
 
 }  // extern "C"
 

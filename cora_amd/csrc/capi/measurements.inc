@@ -78,6 +78,7 @@ int cora_set_measurements(cora_ctx *c, int64_t n_edges, const int32_t *edge_rows
     c->tmap = TermMap();  // (a term map belongs to the table it was built from)
     c->odom = OdomTables();  // (so do the chain tables)
     c->ml = MlTables();      // (and the multilateration's lists)
+    c->pl = PlTables();      // (and the chain placement's stages)
     c->meas = std::move(T);
     c->meas.set = true;
   }

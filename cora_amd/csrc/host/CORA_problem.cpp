@@ -1176,8 +1176,15 @@ Matrix Problem::rangeAidedInitialization(uint64_t seed, int gn_steps, LandmarkIn
   return odometryStart(seed, gn_steps, info, "Problem::rangeAidedInitialization");
 }
 
-// the odometry start; with gn_steps >= 0 the landmarks are then placed from the ranges (cora_multilaterate_dev)
-Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where) const {
+Matrix Problem::multiRobotInitialization(uint64_t seed, int gn_steps, int min_ranges, ChainPlacementInfo *chains_info, LandmarkInitInfo *info) const {
+  if (gn_steps < 0) throw std::invalid_argument("Problem::multiRobotInitialization: gn_steps must be in [0, 16]");
+  return odometryStart(seed, gn_steps, info, "Problem::multiRobotInitialization", true, min_ranges, chains_info);
+}
+
+// the odometry start; with gn_steps >= 0 the landmarks are then placed from the ranges (cora_multilaterate_dev), with
+// `place` after the chains were (cora_place_chains_dev)
+Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where, bool place, int min_ranges,
+                              ChainPlacementInfo *chains_info) const {
   checkUpToDate();
   if (part_world_ > 1) throw std::runtime_error(std::string(where) + ": not supported on a partitioned handle");
   ensureMeasurementTable();
@@ -1235,6 +1242,27 @@ Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *inf
   if (gn_steps < 0 && !idx.empty())
     CORA_CALL(cora_odometry_set_range_rows_dev(c, static_cast<int64_t>(idx.size()), idx.data(), dirs.data(), v.x), where);
   const Matrix Qm = odom_draws::drawRotation(g, U, p);
+  if (place && gn_steps >= 0 && !chains.empty()) {
+    // (after every draw of odometryInitialization: the placement draws nothing.  Its range rows are recomputed by the
+    // multilateration below, which also decides the fallback directions.)
+    const size_t nch = chains.size(), G = static_cast<size_t>(d) * d + d;
+    CORA_CALL(cora_set_chain_placement(c, nullptr, min_ranges > 0 ? min_ranges : 4 * (d == 2 ? 7 : 16)), where);
+    int64_t out[5] = {0, 0, 0, 0, 0};
+    std::vector<unsigned char> status(nch + 1, 0);
+    std::vector<double> cs(nch + 1, 0.0), cl(nch + 1, 0.0), cf(nch + 1, 0.0), tr(nch * G + 1, 0.0);
+    CORA_CALL(cora_place_chains_dev(c, v.x, gn_steps, out, status.data(), cs.data(), cl.data(), cf.data(), nullptr, tr.data(), nullptr), where);
+    if (chains_info) {
+      chains_info->placed = static_cast<long>(out[0]);
+      chains_info->not_placed = static_cast<long>(out[1]);
+      chains_info->gn_steps = static_cast<long>(out[2]);
+      chains_info->stages = static_cast<long>(out[4]);
+      chains_info->status.assign(status.begin(), status.begin() + static_cast<std::ptrdiff_t>(nch));
+      chains_info->cost_start.assign(cs.begin(), cs.begin() + static_cast<std::ptrdiff_t>(nch));
+      chains_info->cost_linear.assign(cl.begin(), cl.begin() + static_cast<std::ptrdiff_t>(nch));
+      chains_info->cost_final.assign(cf.begin(), cf.begin() + static_cast<std::ptrdiff_t>(nch));
+      chains_info->transforms.assign(tr.begin(), tr.begin() + static_cast<std::ptrdiff_t>(nch * G));
+    }
+  }
   if (gn_steps >= 0) {
     // the poses a chain wrote anchor the landmarks; the others sit at zero
     std::vector<unsigned char> pose_ok(static_cast<size_t>(n) + 1, 0), on(static_cast<size_t>(nl) + 1, 1);

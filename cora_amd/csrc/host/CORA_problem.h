@@ -163,6 +163,16 @@ struct LandmarkInitInfo {
   std::vector<Scalar> cost_linear, cost_final;  // per landmark: sum omega (|x - t| - r)^2 after the linear stage, at the point written
 };
 
+/** What Problem::multiRobotInitialization reports about the chains (cora_place_chains_dev, include/cora_hip.h). */
+struct ChainPlacementInfo {
+  long placed = 0, not_placed = 0;     // chains moved onto the fixed ones | left at their random start
+  long gn_steps = 0;                   // Gauss-Newton steps taken, summed over the stages
+  long stages = 0;
+  std::vector<unsigned char> status;   // per chain (0 placed, 1 too few ranges, 2 placed without the linear stage, 3 no range, 4 fixed)
+  std::vector<Scalar> cost_start, cost_linear, cost_final;  // per chain: sum omega (|R q + t - a| - r)^2 over the stage's entries
+  std::vector<Scalar> transforms;      // per chain d * d + d: R row-major, then t, as written
+};
+
 class Problem {
  private:
   int dim_;
@@ -243,7 +253,9 @@ class Problem {
   void ensureContext() const;
   void ensurePreconditioner() const;
   void ensureMeasurementTable() const;
-  Matrix odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where) const;  // gn_steps < 0: no multilateration
+  // gn_steps < 0: no multilateration; place: the chains are first placed from the ranges between them (min_ranges <= 0: the default)
+  Matrix odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where, bool place = false, int min_ranges = 0,
+                       ChainPlacementInfo *chains_info = nullptr) const;
   void fillImplicitFormulationMatrices() const;
   [[noreturn]] void throwLast(int status, const char *where) const;
 
@@ -459,6 +471,15 @@ class Problem {
    * its direction after everything else, in range order.  Pose rows and the rows of unsolved landmarks have
    * odometryInitialization's bits.  std::runtime_error on a partitioned handle. */
   Matrix rangeAidedInitialization(uint64_t seed = 7, int gn_steps = 5, LandmarkInitInfo *info = nullptr) const;
+  /** EXTENSION beyond the reference: rangeAidedInitialization with every odometry chain after the first first moved rigidly
+   * onto the chains placed before it, from the pose-pose ranges between chains (cora_place_chains_dev): exactly the draws
+   * of odometryInitialization in the same order -- the random starts stay as the fallback of the chains that are not
+   * placed --, then the placement, the multilateration over the poses a chain wrote, the range rows and the lift.  Rows of
+   * chains that are not placed and of landmarks that are not solved have rangeAidedInitialization's bits.  min_ranges <= 0:
+   * 4 x the unknowns of the linear stage (28 at d = 2, 64 at d = 3), a judgement (profiles/chain_placement.md).  A stage
+   * never raises the range cost over its own entries; nothing else is promised.  std::runtime_error on a partitioned handle. */
+  Matrix multiRobotInitialization(uint64_t seed = 7, int gn_steps = 5, int min_ranges = 0, ChainPlacementInfo *chains_info = nullptr,
+                                  LandmarkInitInfo *info = nullptr) const;
 
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;

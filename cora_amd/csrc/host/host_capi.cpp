@@ -252,6 +252,7 @@ int cora_problem_op(cora_problem *p, const char *op, int cols, const double *A, 
     else if (o == "getOdomInitialization") res = getOdomInitialization(q);
     else if (o == "odometryInitialization") res = q.odometryInitialization();
     else if (o == "rangeAidedInitialization") res = q.rangeAidedInitialization();
+    else if (o == "multiRobotInitialization") res = q.multiRobotInitialization();
     else if (o == "getTranslationExplicitSolution") res = q.getTranslationExplicitSolution(wrap(A, N, r));
     else if (o == "alignEstimateToOrigin") res = q.alignEstimateToOrigin(wrap(A, N, r));
     else throw std::invalid_argument("unknown operator " + o);
@@ -300,6 +301,36 @@ int cora_problem_range_aided_initialization(cora_problem *p, uint64_t seed, int 
     if (status) std::copy(info.status.begin(), info.status.end(), status);
     if (cost_linear) std::copy(info.cost_linear.begin(), info.cost_linear.end(), cost_linear);
     if (cost_final) std::copy(info.cost_final.begin(), info.cost_final.end(), cost_final);
+  });
+}
+
+int cora_problem_multi_robot_initialization(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, double *out, int64_t counts[4],
+                                            unsigned char *status, double *cost_start, double *cost_linear, double *cost_final,
+                                            double *transforms, int64_t landmark_counts[4], unsigned char *landmark_status) {
+  return guarded([&] {
+    ChainPlacementInfo ci;
+    LandmarkInitInfo info;
+    const Matrix res = p->problem.multiRobotInitialization(seed, gn_steps, min_ranges, &ci, &info);
+    if (res.rows() == p->problem.getExpectedVariableSize()) p->problem.checkVariablesAreValid(res);  // (throws off the manifold)
+    std::memcpy(out, res.data(), sizeof(double) * static_cast<size_t>(res.size()));
+    if (counts) {
+      counts[0] = ci.placed;
+      counts[1] = ci.not_placed;
+      counts[2] = ci.gn_steps;
+      counts[3] = ci.stages;
+    }
+    if (status) std::copy(ci.status.begin(), ci.status.end(), status);
+    if (cost_start) std::copy(ci.cost_start.begin(), ci.cost_start.end(), cost_start);
+    if (cost_linear) std::copy(ci.cost_linear.begin(), ci.cost_linear.end(), cost_linear);
+    if (cost_final) std::copy(ci.cost_final.begin(), ci.cost_final.end(), cost_final);
+    if (transforms) std::copy(ci.transforms.begin(), ci.transforms.end(), transforms);
+    if (landmark_counts) {
+      landmark_counts[0] = info.solved;
+      landmark_counts[1] = info.not_solved;
+      landmark_counts[2] = info.degenerate_range_rows;
+      landmark_counts[3] = info.gn_steps;
+    }
+    if (landmark_status) std::copy(info.status.begin(), info.status.end(), landmark_status);
   });
 }
 

@@ -1076,6 +1076,400 @@ __host__ __device__ inline bool ml_fold(int stage, int last, const double *S, do
   return true;
 }
 
+// Chain placement from inter-robot ranges (kernels/placement.inc; include/cora_hip.h, cora_place_chains_dev): the
+// multilateration with a rigid body in place of a point.  The host orders the chains into STAGES (capi/placement.inc); a
+// stage finds g = (R, t) in SE(d) that moves one chain onto the chains placed before it, from the stage's entry list (row
+// of the chain's position q, row of the anchor a, range measurement), cut into chunks of kPlChunk entries.  The stages are
+// dependent, so every launch below serves ONE stage; per stage, with s = gn_steps:
+//   linear        : pass (one workgroup per chunk) and fold (ONE wavefront) of the linear stage in the squared ranges
+//   step 0 .. s+1 : pass and fold of a Gauss-Newton evaluation: step 0 at the identity (visited point 0), step 1 at the
+//                   linear stage's point (visited point 1), step k at the point after k - 1 Gauss-Newton steps; every
+//                   step but the last also takes the next Gauss-Newton step
+//   apply         : one thread per position of the chain
+// 2 (s + 3) + 1 launches.  Coordinates are taken relative to the first entry: q' = q - q_0, a' = a - a_0, and the
+// translation the stages carry is t' = R q_0 + t - a_0, so that |R q + t - a| = |R q' + t' - a'|; the identity is
+// (I, q_0 - a_0).  No transcendental function: the rotation update is the Cayley map, then round_rotation.
+// BRACKET ORDER, a function of the list length and kPlChunk alone and the same in the host mirror (capi/placement.inc):
+//   linear pass: the entry's kPlTerms(d) terms and its weight are staged in LDS; thread p < kPlSums(d) owns the pair (i, j)
+//                of pl_pair and sums (w_e c_i(e)) c_j(e) over the chunk's entries from the left, from +0.0 (pl_pair_sum);
+//   Gauss-Newton pass: as the multilateration's -- butterfly per wavefront, lanes without an entry hold +0.0, the four
+//                wavefronts from the left;
+//   fold: lane j takes 0.0 + chunk j + chunk (j + 64) + .. of the stage from the left, then the butterfly.
+// Every term is made of single correctly rounded fp64 operations in the order written, never contracted.
+constexpr int kPlChunk = 256;
+constexpr int kPlMaxSteps = 16;
+constexpr double kPlMinPivot = 1e-8;     // of the scaled normal matrix of the linear stage, divided by sum(omega)
+constexpr double kPlGnMinPivot = 1e-12;  // of H / sum(omega), rotations in units of the length scale
+constexpr int kPlUnknowns(int d) { return d == 2 ? 7 : 16; }  // s | v = R^T t | M (d = 2: c, s; d = 3: 9 entries) | t
+constexpr int kPlTerms(int d) { return kPlUnknowns(d) + 1; }  // the coefficients, then the right-hand side
+constexpr int kPlSums(int d) { return kPlTerms(d) * (kPlTerms(d) + 1) / 2; }  // sum w c_i c_j, i <= j: 36, 153
+constexpr int kPlDof(int d) { return d * (d + 1) / 2; }                      // rotation, then translation
+constexpr int kPlGnSums(int d) { return kPlDof(d) * (kPlDof(d) + 1) / 2 + kPlDof(d) + 1; }  // w J J^T (upper) | w J e | w e^2: 10, 28
+constexpr int kPlG(int d) { return d * d + d; }                              // R row-major | translation
+// current (R, t') | least-cost (R, t') | written (R, t) | least cost | cost at the identity | cost at the linear point | sum w | L
+constexpr int kPlState(int d) { return 3 * kPlG(d) + 5; }
+constexpr int kPlInts = 4;  // status | chosen | steps taken | still stepping
+struct PlArgs {
+  int d = 0, step = 0, last = 0;
+  int32_t chunk0 = 0, n_chunks = 0;                    // the stage's chunks in the chunk table
+  int32_t origin_q = 0, origin_a = 0;                  // INTERNAL rows of the first entry's position and anchor
+  int32_t pos0 = 0, n_pos = 0;                         // the chain's positions in the chain tables
+  int64_t n_ranges = 0, pstride = 0;
+  const int32_t *chunk_begin = nullptr, *chunk_len = nullptr;            // [chunks of all stages]
+  const int32_t *ent_q = nullptr, *ent_a = nullptr, *ent_m = nullptr;    // [entries]: INTERNAL rows, range measurement
+  const int32_t *pos_rot = nullptr, *pos_trn = nullptr;                  // the chain tables' (OdomArgs)
+  const double *range_data = nullptr;                  // the measurement table's, [2][n_ranges]: r | omega
+  double *partial = nullptr;                           // [kPlSums(d)][pstride], pstride >= the most chunks of a stage
+  double *state = nullptr;                             // kPlState(d) doubles of THIS stage
+  int32_t *istate = nullptr;                           // kPlInts integers of THIS stage
+  double *x = nullptr;                                 // d columns at stride ld_for(d) = d
+  int *flag = nullptr;                                 // |= 1 where a sum is not finite
+};
+hipError_t launch_place_linear(const PlArgs &A, hipStream_t st);  // pass and fold of the linear stage
+hipError_t launch_place_gn(const PlArgs &A, hipStream_t st);      // pass and fold of evaluation A.step
+hipError_t launch_place_apply(const PlArgs &A, hipStream_t st);
+// pair p of the upper triangle in row-major order: (0,0), (0,1), .., (0,nt-1), (1,1), ..
+__host__ __device__ inline void pl_pair(int nt, int p, int *i, int *j) {
+  int r = 0;
+  while (p >= nt - r) {
+    p -= nt - r;
+    ++r;
+  }
+  *i = r;
+  *j = r + p;
+}
+__host__ __device__ inline int pl_pair_index(int nt, int i, int j) { return i * nt - i * (i - 1) / 2 + (j - i); }  // i <= j
+// the power of the length scale a term carries: 1 | q | a q | a | right-hand side
+template <int D>
+__host__ __device__ inline int pl_degree(int i) {
+  constexpr int MM = D == 2 ? 2 : 9;
+  return i == 0 ? 0 : i <= D ? 1 : i <= D + MM ? 2 : i <= D + MM + D ? 1 : 2;
+}
+// terms of one entry of the linear stage: |q'|^2 + |a'|^2 + s + 2 q'.v - 2 a'^T M q' - 2 a'.t = r^2
+template <int D>
+__host__ __device__ inline void pl_linear_terms(const double *q0, const double *a0, const double *q, const double *a, double r, double *c) {
+#pragma clang fp contract(off)
+  double qq[D], aa[D], n2 = 0.0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    qq[k] = q[k] - q0[k];
+    aa[k] = a[k] - a0[k];
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) n2 = fma(qq[k], qq[k], n2);
+#pragma unroll
+  for (int k = 0; k < D; ++k) n2 = fma(aa[k], aa[k], n2);
+  int at = 0;
+  c[at++] = 1.0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) c[at++] = 2.0 * qq[k];
+  if constexpr (D == 2) {
+    c[at++] = -2.0 * fma(aa[0], qq[0], aa[1] * qq[1]);     // cos:  a . q
+    c[at++] = -2.0 * fma(aa[1], qq[0], -(aa[0] * qq[1]));  // sin:  a_y q_x - a_x q_y
+  } else {
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = 0; j < D; ++j) c[at++] = -2.0 * (aa[i] * qq[j]);
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) c[at++] = -2.0 * aa[k];
+  c[at++] = fma(r, r, -n2);
+}
+// sum over the chunk's entries, from the left, of (w_e c_i(e)) c_j(e); term: [len][nt]
+__host__ __device__ inline double pl_pair_sum(const double *term, const double *wt, int len, int nt, int i, int j) {
+#pragma clang fp contract(off)
+  double v = 0.0;
+  for (int e = 0; e < len; ++e) v = v + (wt[e] * term[e * nt + i]) * term[e * nt + j];
+  return v;
+}
+// Cholesky without pivoting in place in M (n x n row-major: the upper part is read, the factor is left in the lower part
+// and on the diagonal) and the solve of M z = q in place; false at the first pivot <= min_pivot (or not a number).  Loops,
+// no local array: the fold runs it on LDS.
+__host__ __device__ inline bool pl_cholesky_solve(int n, double *M, double *q, double min_pivot) {
+#pragma clang fp contract(off)
+  for (int j = 0; j < n; ++j) {
+    double p = M[j * n + j];
+    for (int k = 0; k < j; ++k) p = fma(-M[j * n + k], M[j * n + k], p);
+    if (!(p > min_pivot)) return false;
+    const double g = sqrt(p);
+    M[j * n + j] = g;
+    for (int i = j + 1; i < n; ++i) {
+      double v = M[j * n + i];
+      for (int k = 0; k < j; ++k) v = fma(-M[i * n + k], M[j * n + k], v);
+      M[i * n + j] = v / g;
+    }
+  }
+  for (int i = 0; i < n; ++i) {
+    double v = q[i];
+    for (int k = 0; k < i; ++k) v = fma(-M[i * n + k], q[k], v);
+    q[i] = v / M[i * n + i];
+  }
+  for (int i = n - 1; i >= 0; --i) {
+    double v = q[i];
+    for (int k = i + 1; k < n; ++k) v = fma(-M[k * n + i], q[k], v);
+    q[i] = v / M[i * n + i];
+  }
+  return true;
+}
+__host__ __device__ inline double pl_power(double L, int k) {
+#pragma clang fp contract(off)
+  double v = 1.0;
+  for (int i = 0; i < k; ++i) v = v * L;
+  return v;
+}
+// The linear stage from the sums S (kPlSums(D)): lengths scaled by the ONE scale L = sqrt(sum w (|q'|^2 + |a'|^2) /
+// (2 sum w)), the normal equations divided by sum w; work: kPlUnknowns(D) (kPlUnknowns(D) + 1) doubles.  Returns the
+// status (0 solved, 2 refused) and g = (R, t'); *scale = L (1 where it has none), *sum_w = S[0].
+template <int D>
+__host__ __device__ inline int pl_linear_solve(const double *S, double *work, double *g, double *scale, double *sum_w) {
+#pragma clang fp contract(off)
+  constexpr int N = kPlUnknowns(D), NT = kPlTerms(D), MM = D == 2 ? 2 : 9;
+  const double sw = S[0];
+  *scale = 1.0;
+  *sum_w = sw;
+  if (!(sw > 0.0)) return 2;
+  double tr = 0.0;
+  for (int k = 0; k < D; ++k) tr = tr + S[pl_pair_index(NT, 1 + k, 1 + k)];
+  for (int k = 0; k < D; ++k) tr = tr + S[pl_pair_index(NT, 1 + D + MM + k, 1 + D + MM + k)];
+  const double L = sqrt(tr / (8.0 * sw));
+  if (!(L > 0.0) || !(L <= 1.79769313486231570815e308)) return 2;
+  *scale = L;
+  double *M = work, *z = work + N * N;
+  for (int i = 0; i < N; ++i) {
+    for (int j = i; j < N; ++j) {
+      const double v = S[pl_pair_index(NT, i, j)] / (sw * pl_power(L, pl_degree<D>(i) + pl_degree<D>(j)));
+      M[i * N + j] = v;
+      M[j * N + i] = v;
+    }
+    z[i] = S[pl_pair_index(NT, i, N)] / (sw * pl_power(L, pl_degree<D>(i) + 2));
+  }
+  if (!pl_cholesky_solve(N, M, z, kPlMinPivot)) return 2;
+  if constexpr (D == 2) {
+    const double c = z[3], s = z[4], nrm = sqrt(fma(c, c, s * s));
+    if (!(nrm > 0.0) || !(nrm <= 1.79769313486231570815e308)) return 2;
+    g[0] = c / nrm;
+    g[1] = -(s / nrm);
+    g[2] = s / nrm;
+    g[3] = c / nrm;
+  } else {
+    double R[D][D];
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = 0; j < D; ++j) R[i][j] = z[1 + D + i * D + j];
+    if (!odom_finite(&R[0][0], D * D)) return 2;
+    round_rotation<D>(R);
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = 0; j < D; ++j) g[i * D + j] = R[i][j];
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) g[D * D + k] = L * z[1 + D + MM + k];
+  return odom_finite(g, kPlG(D)) ? 0 : 2;
+}
+// the identity in the stage's coordinates: (I, q_0 - a_0)
+template <int D>
+__host__ __device__ inline void pl_identity(const double *q0, const double *a0, double *g) {
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) g[i] = i / D == i % D ? 1.0 : 0.0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) g[D * D + k] = q0[k] - a0[k];
+}
+// What the linear fold does with the sums: every field of the stage's state, the status, the current point (the linear
+// stage's, or the identity where it is refused), the least-cost point = the identity.  False where a sum is not finite.
+template <int D>
+__host__ __device__ inline bool pl_fold_linear(const double *S, double *work, double *st, int32_t *ist, const double *q0, const double *a0) {
+  constexpr int G = kPlG(D);
+  for (int i = 0; i < kPlState(D); ++i) st[i] = 0.0;
+  pl_identity<D>(q0, a0, st + G);
+  ist[0] = 0;
+  ist[1] = -1;
+  ist[2] = 0;
+  ist[3] = 1;
+  st[3 * G + 4] = 1.0;
+  const bool finite = odom_finite(S, kPlSums(D));
+  ist[0] = finite ? pl_linear_solve<D>(S, work, st, st + 3 * G + 4, st + 3 * G + 3) : 2;
+  if (ist[0] != 0) pl_identity<D>(q0, a0, st);
+  return finite;
+}
+// terms of one entry at g = (R, t'): u = R q', p = u + t' - a', n = p / |p| (0 where |p| == 0), e = |p| - r;
+// J = ((u x n) / L | n): the rotation in units of the length scale L
+template <int D>
+__host__ __device__ inline void pl_gn_terms(const double *g, double L, const double *q0, const double *a0, const double *q, const double *a,
+                                            double r, double w, double *s) {
+#pragma clang fp contract(off)
+  constexpr int F = kPlDof(D);
+  double qq[D], u[D], p[D], n[D], J[F], wJ[F], n2 = 0.0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) qq[k] = q[k] - q0[k];
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) v = fma(g[i * D + k], qq[k], v);
+    u[i] = v;
+    p[i] = (v + g[D * D + i]) - (a[i] - a0[i]);
+    n2 = fma(p[i], p[i], n2);
+  }
+  const double nrm = sqrt(n2), e = nrm - r;
+#pragma unroll
+  for (int k = 0; k < D; ++k) n[k] = nrm == 0.0 ? 0.0 : p[k] / nrm;
+  if constexpr (D == 2) {
+    J[0] = fma(u[0], n[1], -(u[1] * n[0])) / L;
+  } else {
+    J[0] = fma(u[1], n[2], -(u[2] * n[1])) / L;
+    J[1] = fma(u[2], n[0], -(u[0] * n[2])) / L;
+    J[2] = fma(u[0], n[1], -(u[1] * n[0])) / L;
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) J[F - D + k] = n[k];
+#pragma unroll
+  for (int k = 0; k < F; ++k) wJ[k] = w * J[k];
+  int at = 0;
+#pragma unroll
+  for (int i = 0; i < F; ++i)
+#pragma unroll
+    for (int j = i; j < F; ++j) s[at++] = wJ[i] * J[j];
+#pragma unroll
+  for (int k = 0; k < F; ++k) s[at++] = wJ[k] * e;
+  s[at++] = (w * e) * e;
+}
+// g <- the Gauss-Newton step from g: delta = -H^-1 grad with H = sum w J J^T / sum w; R <- round_rotation(C R) with C the
+// Cayley map of the rotation step b = delta_rot / (2 L) (d = 3: ((1 - b.b) I + 2 b b^T + 2 [b]x) / (1 + b.b)), t' <- t' +
+// delta_t.  False, and g kept, at a pivot <= kPlGnMinPivot or a step that is not finite.
+template <int D>
+__host__ __device__ inline bool pl_gn_step(const double *S, double sw, double L, double *g) {
+#pragma clang fp contract(off)
+  constexpr int F = kPlDof(D);
+  double H[F * F], dl[F], gn[kPlG(D)];
+  int at = 0;
+#pragma unroll
+  for (int i = 0; i < F; ++i)
+#pragma unroll
+    for (int j = i; j < F; ++j) H[i * F + j] = H[j * F + i] = S[at++] / sw;
+#pragma unroll
+  for (int k = 0; k < F; ++k) dl[k] = S[at++] / sw;
+  if (!ml_cholesky_solve<F>(H, dl, kPlGnMinPivot)) return false;
+  double C[D][D], R[D][D];
+  if constexpr (D == 2) {
+    const double b = -dl[0] / (2.0 * L), den = fma(b, b, 1.0);
+    const double cs = fma(-b, b, 1.0) / den, sn = (2.0 * b) / den;
+    C[0][0] = cs;
+    C[0][1] = -sn;
+    C[1][0] = sn;
+    C[1][1] = cs;
+  } else {
+    double b[3], bb = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      b[k] = -dl[k] / (2.0 * L);
+      bb = fma(b[k], b[k], bb);
+    }
+    const double den = 1.0 + bb, dg = 1.0 - bb;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        // [b]x: (0,1) -b2, (0,2) b1, (1,2) -b0 and the opposite signs below the diagonal
+        const double cr = i == j ? 0.0 : ((j - i + 3) % 3 == 1 ? -b[(6 - i - j) % 3] : b[(6 - i - j) % 3]);
+        C[i][j] = (fma(2.0 * b[i], b[j], i == j ? dg : 0.0) + 2.0 * cr) / den;
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      double v = 0.0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) v = fma(C[i][k], g[k * D + j], v);
+      R[i][j] = v;
+    }
+  if (!odom_finite(&R[0][0], D * D)) return false;
+  round_rotation<D>(R);
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int j = 0; j < D; ++j) gn[i * D + j] = R[i][j];
+#pragma unroll
+  for (int k = 0; k < D; ++k) gn[D * D + k] = g[D * D + k] - dl[F - D + k];
+  if (!odom_finite(gn, kPlG(D))) return false;
+#pragma unroll
+  for (int i = 0; i < kPlG(D); ++i) g[i] = gn[i];
+  return true;
+}
+// What the fold of evaluation `step` does with the sums S (kPlGnSums(D)); at the last one also the transform as written:
+// the identity exactly where point 0 has the least cost, else (R, t' + a_0 - R q_0).  False where a sum is not finite
+// (the stage then stops stepping).
+template <int D>
+__host__ __device__ inline bool pl_fold_gn(int step, int last, const double *S, double *st, int32_t *ist, const double *q0, const double *a0) {
+#pragma clang fp contract(off)
+  constexpr int G = kPlG(D);
+  double *cur = st, *best = st + G, *out = st + 2 * G, &cbest = st[3 * G], &cstart = st[3 * G + 1], &clin = st[3 * G + 2];
+  const double sw = st[3 * G + 3], L = st[3 * G + 4];
+  bool finite = odom_finite(S, kPlGnSums(D));
+  if (!finite) {
+    ist[3] = 0;
+  } else {
+    const double cost = S[kPlGnSums(D) - 1];
+    if (step == 0) {
+      cstart = cbest = clin = cost;
+      ist[1] = 0;
+    } else {
+      if (step == 1) clin = cost;
+      if (cost < cbest) {
+        cbest = cost;
+        for (int i = 0; i < G; ++i) best[i] = cur[i];
+        ist[1] = step;
+      }
+      if (!last && ist[3]) {
+        if (pl_gn_step<D>(S, sw, L, cur)) ist[2] += 1;
+        else ist[3] = 0;
+      }
+    }
+  }
+  if (last) {
+    for (int i = 0; i < G; ++i) out[i] = i < D * D && i / D == i % D ? 1.0 : 0.0;
+    if (ist[1] > 0) {
+      for (int i = 0; i < D * D; ++i) out[i] = best[i];
+      for (int c = 0; c < D; ++c) {
+        double v = best[D * D + c] + a0[c];
+        for (int k = 0; k < D; ++k) v = fma(-best[c * D + k], q0[k], v);
+        out[D * D + c] = v;
+      }
+    }
+  }
+  return finite;
+}
+// one position of the chain under g = (R, t): t_i <- R t_i + t (from t, k ascending), the stored block (R_i^T, row a =
+// column a of R_i) <- R_i^T R^T (every entry from +0.0, k ascending)
+template <int D>
+__host__ __device__ inline void pl_apply(const double *g, double *rot, double *trn) {
+#pragma clang fp contract(off)
+  double nr[D * D], nt[D];
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+#pragma unroll
+    for (int b = 0; b < D; ++b) {
+      double v = 0.0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) v = fma(rot[a * D + k], g[b * D + k], v);
+      nr[a * D + b] = v;
+    }
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    double v = g[D * D + c];
+#pragma unroll
+    for (int k = 0; k < D; ++k) v = fma(g[c * D + k], trn[k], v);
+    nt[c] = v;
+  }
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) rot[i] = nr[i];
+#pragma unroll
+  for (int c = 0; c < D; ++c) trn[c] = nt[c];
+}
+
 // In-place update of Q's values (kernels/update_values.inc).  src: the sources of ValueMap (cora_internal.h), vals: the
 // new CSR values on the device.
 // check: flag |= 1 where a value is not finite, |= 2 where a mirror pair (mirror[2j], mirror[2j + 1]) differs.

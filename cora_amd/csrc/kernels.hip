@@ -38,6 +38,7 @@
 //   kernels/round.inc    rounding of a resident vector to SE(d): count, finish, per-unit pass                       CORA_TU & 2
 //   kernels/odom.inc     odometry initialisation: segmented scan of SE(d) over the chain positions, fill of the other rows  CORA_TU & 2
 //   kernels/multilat.inc  landmark initialisation from ranges: pass over the chunks of the range lists, fold and solve per landmark  CORA_TU & 2
+//   kernels/placement.inc  chain placement from inter-robot ranges: linear and Gauss-Newton pass and fold per stage, the rigid motion of a chain  CORA_TU & 2
 //   kernels/update_values.inc  in-place update of Q's values: check of the new values, gather passes                CORA_TU & 2
 //   kernels/assemble.inc  Q(w) from per-measurement weights through the term map: check, short and long entries     CORA_TU & 2
 //   kernels/tri.inc      the staged Cholesky solve: k_rowop, k_blockop, k_subblock                                 CORA_TU & 4
@@ -53,6 +54,7 @@ namespace cora {
 #include "kernels/round.inc"
 #include "kernels/odom.inc"
 #include "kernels/multilat.inc"
+#include "kernels/placement.inc"
 #include "kernels/update_values.inc"
 #include "kernels/assemble.inc"
 #include "kernels/tri.inc"

@@ -570,6 +570,43 @@ hipError_t launch_multilat_stage(const MlArgs &A, hipStream_t st) {
   }
   return hipGetLastError();
 }
+// the chain placement (kernels/placement.inc): every launch serves the one stage A describes
+static bool place_args_ok(const PlArgs &A) {
+  return (A.d == 2 || A.d == 3) && A.n_chunks > 0 && A.chunk0 >= 0 && A.pstride >= A.n_chunks && A.origin_q >= 0 && A.origin_a >= 0 &&
+         A.pos0 >= 0 && A.n_pos > 0 && A.n_ranges > 0 && A.chunk_begin && A.chunk_len && A.ent_q && A.ent_a && A.ent_m && A.pos_rot &&
+         A.pos_trn && A.range_data && A.partial && A.state && A.istate && A.x && A.flag;
+}
+hipError_t launch_place_linear(const PlArgs &A, hipStream_t st) {
+  if (!place_args_ok(A)) return hipErrorInvalidValue;
+  const dim3 chunks(static_cast<unsigned>(A.n_chunks));
+  if (A.d == 2) {
+    hipLaunchKernelGGL(k_pl_pass_linear<2>, chunks, dim3(kPlChunk), 0, st, A);
+    hipLaunchKernelGGL(k_pl_fold_linear<2>, dim3(1), dim3(kWave), 0, st, A);
+  } else {
+    hipLaunchKernelGGL(k_pl_pass_linear<3>, chunks, dim3(kPlChunk), 0, st, A);
+    hipLaunchKernelGGL(k_pl_fold_linear<3>, dim3(1), dim3(kWave), 0, st, A);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_place_gn(const PlArgs &A, hipStream_t st) {
+  if (!place_args_ok(A) || A.step < 0 || A.step > kPlMaxSteps + 1) return hipErrorInvalidValue;
+  const dim3 chunks(static_cast<unsigned>(A.n_chunks));
+  if (A.d == 2) {
+    hipLaunchKernelGGL(k_pl_pass_gn<2>, chunks, dim3(kPlChunk), 0, st, A);
+    hipLaunchKernelGGL(k_pl_fold_gn<2>, dim3(1), dim3(kWave), 0, st, A);
+  } else {
+    hipLaunchKernelGGL(k_pl_pass_gn<3>, chunks, dim3(kPlChunk), 0, st, A);
+    hipLaunchKernelGGL(k_pl_fold_gn<3>, dim3(1), dim3(kWave), 0, st, A);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_place_apply(const PlArgs &A, hipStream_t st) {
+  if (!place_args_ok(A)) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<unsigned>((A.n_pos + 255) / 256));
+  if (A.d == 2) hipLaunchKernelGGL(k_pl_apply<2>, grid, dim3(256), 0, st, A);
+  else hipLaunchKernelGGL(k_pl_apply<3>, grid, dim3(256), 0, st, A);
+  return hipGetLastError();
+}
 hipError_t launch_round_amax(int64_t n, const double *y, double *partial, int nblocks, int *flag, hipStream_t st) {
   if (n < 1 || nblocks < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_round_amax, dim3(nblocks), dim3(256), 0, st, n, y, partial, flag);

@@ -22,12 +22,12 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding] [--device-init [--landmark-init [--gn-steps k]]]" << std::endl;
+    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding] [--device-init [--landmark-init] [--place-chains] [--gn-steps k]]" << std::endl;
     return 1;
   }
   int max_rank = 10, gn_steps = 5;
   std::string tum, save_dir, residuals, weights, robust, barc2, weights_out, aligned_tum, rpe_steps, rpe_dists;
-  bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false, landmark_init = false;
+  bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false, landmark_init = false, place_chains = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--jacobi") jacobi = true;
@@ -61,11 +61,15 @@ int main(int argc, char **argv) {
     // with --odom-init --device-init: the landmarks of the start are placed from the ranges (Problem::rangeAidedInitialization)
     else if (a == "--landmark-init") landmark_init = true;
     else if (a == "--gn-steps" && i + 1 < argc) gn_steps = std::atoi(argv[++i]);
+    // with --odom-init --device-init: the chains after the first are first placed from the pose-pose ranges between chains
+    // (Problem::multiRobotInitialization, which then places the landmarks as --landmark-init does)
+    else if (a == "--place-chains") place_chains = true;
   }
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
   try {
     if (device_init && !odom) throw std::runtime_error("--device-init composes the odometry start on the device: it needs --odom-init");
+    if (place_chains && !device_init) throw std::runtime_error("--place-chains places the chains of the device's odometry start: it needs --odom-init --device-init");
     if (landmark_init && !device_init) throw std::runtime_error("--landmark-init places the landmarks of the device's odometry start: it needs --odom-init --device-init");
     const auto t_start = clk::now();
     CORA::Problem problem = CORA::parsePyfgTextToProblem(argv[1]);
@@ -124,6 +128,16 @@ int main(int argc, char **argv) {
       x0 = problem.rangeAidedInitialization(7, gn_steps, &lm);
       std::printf("landmark init: %ld landmarks solved, %ld not solved (%ld Gauss-Newton steps); range residual sum at the start %.6e with it, %.6e without\n",
                   lm.solved, lm.not_solved, lm.gn_steps, range_sum(x0), without);
+    }
+    if (place_chains) {  // (an extension beyond the reference: Problem::multiRobotInitialization)
+      CORA::ChainPlacementInfo ci;
+      auto range_sum = [&](const CORA::Matrix &x) {
+        return problem.measurementResiduals(implicit ? CORA::Matrix(x.block(0, 0, problem.rotAndRangeMatrixSize(), x.cols())) : x).range_sum;
+      };
+      const double without = range_sum(x0);  // (the start as it stands: with the landmarks placed under --landmark-init)
+      x0 = problem.multiRobotInitialization(7, gn_steps, 0, &ci);
+      std::printf("chain placement: %ld chains placed, %ld not placed (%ld Gauss-Newton steps); range residual sum at the start %.6e with it, %.6e without\n",
+                  ci.placed, ci.not_placed, ci.gn_steps, range_sum(x0), without);
     }
     if (odom && implicit)  // examples/paper_experiments.cpp:623-625
       x0 = x0.block(0, 0, problem.rotAndRangeMatrixSize(), x0.cols());

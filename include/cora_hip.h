@@ -853,6 +853,77 @@ int cora_multilaterate(cora_ctx *ctx, double *X, int ldx, int gn_steps, int64_t 
 int cora_debug_multilaterate_host(cora_ctx *ctx, double *X, int ldx, int gn_steps, int64_t out[4], unsigned char *status,
                                   double *cost_linear, double *cost_final, int32_t *chosen, unsigned char *degenerate);
 
+/* ---- CHAIN PLACEMENT FROM INTER-ROBOT RANGES, on the device ---------------------------------------------------------------
+ * Moves whole odometry chains of a resident vector of d columns (the output of cora_odometry_init_dev: every chain
+ * composed in its own frame) rigidly into the frame of the chains that are fixed, from the pose-pose ranges between
+ * chains, in place.  Needs a measurement table (cora_set_measurements), chain tables (cora_set_odometry_chains) and the
+ * tables of cora_set_chain_placement.  The multilateration with an element of SE(d) per chain in place of a point.
+ * DEFINITIONS.
+ *   entry            a range measurement one end of which is the translation row of a position of chain c and the other
+ *                    the translation row of a position of another chain c', in either order; duplicates count twice.
+ *                    Every other range (an end in a free pose or a landmark, both ends in one chain) is skipped and counted.
+ *   order            placed = the chains of chain_fixed (NULL: chain 0).  Repeatedly the unplaced chain with the most
+ *                    entries against placed chains is taken (ties: the lowest index) until that count is below min_ranges;
+ *                    a chain taken is a STAGE and counts as placed from then on.  min_ranges >= 8 (d = 2), 17 (d = 3).
+ *   stage's list     the entries of the stage's chain against the chains placed before it, in table order, as (row of the
+ *                    chain's position q, row of the anchor a, measurement), cut into chunks of 256; no chunk spans two stages.
+ *   status           0 placed | 1 never taken, fewer than min_ranges entries against placed chains | 2 placed, the linear
+ *                    stage refused (sum omega <= 0, no length scale, a pivot <= 1e-8 of the scaled normal matrix: positions
+ *                    on a line in 2-D or in a plane in 3-D, coincident points): the Gauss-Newton steps start from the
+ *                    identity | 3 never taken, no entry against any chain | 4 fixed.
+ *   a stage          finds g = (R, t) that minimises sum omega (|R q + t - a| - r)^2 over its list, q and a as the vector
+ *                    holds them (a was written by an earlier stage or belongs to a fixed chain).  Coordinates are relative to
+ *                    the first entry: q' = q - q_0, a' = a - a_0, t' = R q_0 + t - a_0.
+ *                    Visited point 0 is the identity (cost_start).  Point 1 is the linear stage in the squared ranges,
+ *                    |q'|^2 + |a'|^2 + s + 2 q'.v - 2 a'^T M q' - 2 a'.t' = r^2 in the unknowns s, v, M, t' (7 at d = 2 with
+ *                    M = (cos, sin); 16 at d = 3), lengths scaled by L = sqrt(sum omega (|q'|^2 + |a'|^2) / (2 sum omega)),
+ *                    the normal equations divided by sum omega and factored by Cholesky without pivoting, M projected to
+ *                    SO(d) (cost_linear; the identity again where the stage is refused).  Points 2 .. gn_steps + 1 follow by
+ *                    Gauss-Newton steps on the d (d + 1) / 2 degrees of freedom (rotation in units of L, then translation):
+ *                    with u = R q', p = u + t' - a', n = p / |p|, e = |p| - r and J = ((u x n) / L | n), delta = -H^-1 g,
+ *                    R <- round(Cayley(delta_rot / L) R), t' <- t' + delta_t; a stage stops stepping at a pivot <= 1e-12
+ *                    of H / sum omega or a step that is not finite.  The transform written is the visited point of least
+ *                    cost, the earliest on ties (chosen; cost_final): a stage never raises the range cost over its own
+ *                    entries.  Where point 0 wins the chain's rows are not touched.
+ *   apply            t_i <- R t_i + t and the stored block R_i^T <- R_i^T R^T for every position of the chain.
+ *   range rows       afterwards the unit range rows of ALL range measurements are recomputed in the direction of least
+ *                    residual, as cora_multilaterate_dev does, with its degenerate bytes and count.
+ * cora_set_chain_placement   decides the order, builds and uploads the tables.  They stay on the handle until replaced,
+ *            until the measurement table or the chain tables are replaced or until the handle is destroyed.  Works on a
+ *            plan-only handle, except for the upload.  A refused call leaves the tables as they were.
+ * cora_chain_placement_counts   out = {stages, entries, chunks, skipped ranges}.
+ * cora_chain_placement_order    stage_chain[stages] = the chain of every stage, in the order of the stages.
+ * cora_place_chains_dev   out (host) = {chains placed, chains not placed, Gauss-Newton steps taken, degenerate range rows,
+ *            stages}; status, cost_start, cost_linear, cost_final, chosen: host arrays with one entry per chain or NULL
+ *            (costs 0 and chosen -1 where the chain is no stage); transforms: [chains][d * d + d], R row-major then t as
+ *            written, the identity where the chain is no stage or point 0 won; degenerate: host bytes, one per range
+ *            measurement, or NULL.  Per stage 2 (gn_steps + 3) + 1 launches, one stage after the other, then the range
+ *            rows.  Everything on the handle's stream; synchronises once, at the end.
+ * cora_place_chains       the host-pointer form, in place: X is N x d column-major with leading dimension ldx.
+ * cora_debug_place_chains_host   the same on the host in the device's bracket order and through the functions the kernels
+ *            call: X has the device's bits.  Works on a plan-only handle.
+ * ARITHMETIC.  No transcendental function: + - x / and sqrt only, single correctly rounded fp64 operations in the order
+ * written, never contracted.  Linear stage: the entry's terms and weight are staged per chunk and pair product (i, j) is
+ * summed over the chunk's entries from the left as (omega c_i) c_j from +0.0; Gauss-Newton sums as the multilateration's;
+ * chunk sums as [sum][chunk]; one wavefront in which lane j adds chunks j, j + 64, .. of the stage from the left to +0.0,
+ * then the butterfly.  The same bits on every call.  No atomics on doubles.
+ * ERRORS.  CORA_ERR_NOT_READY: no measurement table, no chain tables, or no placement tables.  CORA_ERR_ARG: a partitioned
+ * handle; min_ranges below the linear stage's unknowns + 1; a mask that fixes no chain; gn_steps outside [0, 16]; a null
+ * X or out; two range measurements that name one range row.  CORA_ERR_SHAPE: a leading dimension below N.  CORA_ERR_NAN: a
+ * sum or a range row that is not finite (the device forms report it through the handle's flag word).  CORA_ERR_HIP: a
+ * device form on a plan-only handle.
+ * STATE.  Nothing the handle computes with changes. */
+int cora_set_chain_placement(cora_ctx *ctx, const unsigned char *chain_fixed /* [chains] or NULL */, int min_ranges);
+int cora_chain_placement_counts(const cora_ctx *ctx, int64_t out[4]);
+int cora_chain_placement_order(const cora_ctx *ctx, int32_t *stage_chain);
+int cora_place_chains_dev(cora_ctx *ctx, double *dX, int gn_steps, int64_t out[5], unsigned char *status, double *cost_start,
+                          double *cost_linear, double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate);
+int cora_place_chains(cora_ctx *ctx, double *X, int ldx, int gn_steps, int64_t out[5], unsigned char *status, double *cost_start,
+                      double *cost_linear, double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate);
+int cora_debug_place_chains_host(cora_ctx *ctx, double *X, int ldx, int gn_steps, int64_t out[5], unsigned char *status,
+                                 double *cost_start, double *cost_linear, double *cost_final, int32_t *chosen, double *transforms,
+                                 unsigned char *degenerate);
+
 /* Timing helpers: HIP events on the handle's stream. */
 int cora_timer_start(cora_ctx *ctx);
 int cora_timer_stop_ms(cora_ctx *ctx, float *ms); /* synchronises */

@@ -94,6 +94,8 @@ int cora_problem_variable_size(cora_problem *p, int64_t *rows);
  *                                                        seed 7: getOdomInitialization's start up to rounding)
  *  "rangeAidedInitialization" (none)             -> out   odometryInitialization with the landmarks placed from the ranges
  *                                                        (Problem::rangeAidedInitialization, seed 7, 5 Gauss-Newton steps)
+ *  "multiRobotInitialization" (none)             -> out   rangeAidedInitialization with the chains first placed from the ranges
+ *                                                        between them (Problem::multiRobotInitialization, seed 7, 5 steps, default min_ranges)
  *  "getTranslationExplicitSolution" A=Y (implicit) -> out (d+1)n + r + l rows (src/CORA_problem.cpp:1168)
  *  "alignEstimateToOrigin"    A=Y (rank d)       -> out (d+1)n + r + l rows (src/CORA_problem.cpp:1234)
  * Inputs are N x cols with leading dimension N = cora_problem_variable_size() (cols is checked
@@ -111,6 +113,14 @@ int cora_problem_odometry_chains(const cora_problem *p, int64_t counts[2], int64
  * formulation the result is passed through checkVariablesAreValid (an error off the manifold). */
 int cora_problem_range_aided_initialization(cora_problem *p, uint64_t seed, int gn_steps, double *out, int64_t counts[4],
                                             unsigned char *status, double *cost_linear, double *cost_final);
+/* Problem::multiRobotInitialization (an extension beyond the reference; include/cora_hip.h, "chain placement from
+ * inter-robot ranges").  min_ranges <= 0: the default.  out: data-matrix-size x rank.  counts = { chains placed, not placed,
+ * Gauss-Newton steps taken, stages }; status, cost_start, cost_linear, cost_final: one entry per chain of
+ * cora_problem_odometry_chains; transforms: d * d + d per chain.  landmark_counts and landmark_status as counts and status of
+ * cora_problem_range_aided_initialization.  Every array but out may be NULL. */
+int cora_problem_multi_robot_initialization(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, double *out, int64_t counts[4],
+                                            unsigned char *status, double *cost_start, double *cost_linear, double *cost_final,
+                                            double *transforms, int64_t landmark_counts[4], unsigned char *landmark_status);
 /* compute_Lambda_blocks(Y): stiefel d x dn (ld d), oblique r */
 int cora_problem_lambda_blocks(cora_problem *p, const double *Y, double *stiefel, double *oblique);
 /* Problem::measurementResiduals (an extension beyond the reference; formulas in include/cora_hip.h, "per-measurement
