@@ -1161,6 +1161,75 @@ class Context:
         """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
         return self._pl_call(lambda *a: self.L.cora_place_chains_dev(self.h, C.c_void_p(x_ptr), *a), gn_steps)
 
+    # ---- placement from pose-landmark sightings (include/cora_hip.h, cora_place_by_sightings_dev)
+    def set_sighting_placement(self, chain_fixed=None, landmark_fixed=None, min_sightings=None):
+        """Orders landmarks and odometry chains into stages from the pose-landmark sightings: chain_fixed a mask per chain
+        or None (chain 0); landmark_fixed a mask per landmark or None (none); min_sightings None: 4 d."""
+        if min_sightings is None:
+            min_sightings = 4 * self.d
+        def mask(a, m, what):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(np.asarray(a).reshape(-1) != 0, dtype=np.uint8)
+            if len(a) != m:
+                raise CoraError(5, "%s needs %d entries, not %d" % (what, m, len(a)))
+            a = np.concatenate([a, np.zeros(1, dtype=np.uint8)])  # (never an empty buffer)
+            return a, a.ctypes.data_as(C.c_void_p)
+        kc, pc = mask(chain_fixed, self.odometry_chains_count()[0], "chain_fixed")
+        kl, plm = mask(landmark_fixed, self.nt - self.n, "landmark_fixed")
+        self._chk(self.L.cora_set_sighting_placement(self.h, pc, plm, int(min_sightings)))
+
+    def sighting_placement_counts(self):
+        """(stages, sightings used, chunks, skipped edges) of the installed tables."""
+        out = (C.c_int64 * 4)()
+        self._chk(self.L.cora_sighting_placement_counts(self.h, out))
+        return tuple(int(v) for v in out)
+
+    def sighting_placement_order(self):
+        """The stages in order as a list of (kind, items): kind "L", "C" or "REFIT", items the landmarks or chains."""
+        ns, _, nc, _ = self.sighting_placement_counts()
+        kind, ptr = np.zeros(ns + 1, dtype=np.int32), np.zeros(ns + 2, dtype=np.int32)
+        items = np.zeros(nc + 1, dtype=np.int32)  # (a list has at least one chunk)
+        self._chk(self.L.cora_sighting_placement_order(self.h, kind.ctypes.data_as(_ip), ptr.ctypes.data_as(_ip), items.ctypes.data_as(_ip)))
+        return [(("L", "C", "REFIT")[kind[s]], items[ptr[s]:ptr[s + 1]].copy()) for s in range(ns)]
+
+    def _sg_call(self, fn):
+        nch, nr, g, nl = self.odometry_chains_count()[0], self.measurement_counts()[1], self.d * self.d + self.d, self.nt - self.n
+        out = (C.c_int64 * 6)()
+        status, chosen = np.zeros(nch + 1, dtype=np.uint8), np.zeros(nch + 1, dtype=np.int32)
+        cs, cf, tr = np.zeros(nch + 1), np.zeros(nch + 1), np.zeros((nch + 1) * g)
+        ls, lc = np.zeros(nl + 1, dtype=np.uint8), np.zeros(nl + 1)
+        deg = np.zeros(nr + 1, dtype=np.uint8)
+        self._chk(fn(out, status.ctypes.data_as(C.c_void_p), _d(cs), _d(cf), chosen.ctypes.data_as(_ip), _d(tr),
+                     ls.ctypes.data_as(C.c_void_p), _d(lc), deg.ctypes.data_as(C.c_void_p)))
+        return dict(placed=int(out[0]), not_placed=int(out[1]), landmarks_placed=int(out[2]), landmarks_not_placed=int(out[3]),
+                    n_degenerate=int(out[4]), stages=int(out[5]), status=status[:nch], cost_start=cs[:nch], cost_final=cf[:nch],
+                    chosen=chosen[:nch], transforms=tr[:nch * g].reshape(nch, g), landmark_status=ls[:nl], landmark_cost=lc[:nl],
+                    degenerate=deg[:nr].astype(bool))
+
+    def _sg_host(self, fn, X):
+        X = np.array(X, dtype=np.float64, order="F", copy=True)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise CoraError(1, "X must have d columns")
+        res = self._sg_call(lambda *a: fn(self.h, _d(X), X.shape[0], *a))
+        res["X"] = X
+        return res
+
+    def place_by_sightings(self, X):
+        """Landmarks and chains of the host matrix X (N x d) placed from the sightings, on the device.  Returns dict X (a
+        copy with the landmarks', the chains' and the range rows rewritten), placed, not_placed, landmarks_placed,
+        landmarks_not_placed, n_degenerate, stages, status, cost_start, cost_final, chosen (per chain), transforms (per
+        chain: R row-major, then t), landmark_status, landmark_cost (per landmark), degenerate (bool per range measurement)."""
+        return self._sg_host(self.L.cora_place_by_sightings, X)
+
+    def debug_place_by_sightings_host(self, X):
+        """The same on the host in the device's bracket order (no GPU needed): X has the device's bits."""
+        return self._sg_host(self.L.cora_debug_place_by_sightings_host, X)
+
+    def place_by_sightings_dev(self, x_ptr):
+        """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
+        return self._sg_call(lambda *a: self.L.cora_place_by_sightings_dev(self.h, C.c_void_p(x_ptr), *a))
+
     # ---- test hook
     def debug_format_spmm_host(self, X):
         X = _f(X)

@@ -22,6 +22,7 @@
 //   odom.inc            odometry initialisation: chain tables, device-pointer, host-pointer and host-mirror form
 //   multilat.inc        landmark initialisation from ranges: list tables, device-pointer, host-pointer and host-mirror form
 //   placement.inc       chain placement from inter-robot ranges: stage tables, device-pointer, host-pointer and host-mirror form
+//   sighting.inc        placement from pose-landmark sightings: stage and list tables, device-pointer, host-pointer and host-mirror form
 //   comm.inc            native communication: RCCL, in-process and device-side (p2p.h) transports
 #include <hip/hip_runtime.h>
 // RCCL's types and the few enumerators used, declared here (NCCL's public ABI: they have not changed since 2.0): the
@@ -161,6 +162,29 @@ struct PlTables {
   unsigned char *d_deg = nullptr;   // one byte per range measurement
   int32_t *d_range_rows = nullptr;  // [3][n_ranges] internal rows: range | b | a (as MlTables')
 };
+// The tables of cora_set_sighting_placement (capi/sighting.inc): the order of the stages, decided from structure alone; per
+// stage its kind and its lists; per list the landmark or chain and its chunks; the entries (first rotation row and
+// translation row of the pose, row of the landmark, edge) in table order, cut into chunks of kSgChunk entries, rows already
+// internal; the positions of every C-stage's chains (SgArgs, kernels.h); the device copies, the chunks' partial sums, the
+// lists' state, the range rows' bytes
+struct SgTables {
+  bool built = false;
+  int min_sightings = 0;
+  int64_t skipped = 0;
+  std::vector<int32_t> stage_kind, stage_list0, stage_apply0;  // [stages] 0 L | 1 C | 2 REFIT, [stages + 1], [stages + 1]
+  std::vector<int32_t> list_item, list_chunk0, list_row;       // [lists] landmark or chain, [lists + 1], [lists]
+  std::vector<int32_t> chunk_begin, chunk_len, chunk_list;     // [chunks]
+  std::vector<int32_t> ent_rot, ent_trn, ent_lm, ent_e;        // [entries]
+  std::vector<int32_t> apply_pos, apply_list;                  // [positions of all C-stages]
+  std::vector<unsigned char> chain_init, lm_init;  // [chains] 0 taken | 1 never taken | 3 no sighting | 4 fixed; [landmarks] 0 in the REFIT | 1 | 3 fixed
+  std::vector<int32_t> chain_list, lm_list;        // [chains], [landmarks]: the C-stage list of the chain, the REFIT list of the landmark (-1: none)
+  int32_t *d_idx = nullptr;      // chunk_begin | chunk_len | chunk_list | list_chunk0 | list_row | ent_rot | ent_trn | ent_lm | ent_e | apply_pos | apply_list
+  double *d_partial = nullptr;   // [kSgMaxSums(d)][chunks]
+  double *d_state = nullptr;     // [lists][kSgState(d)]
+  int32_t *d_istate = nullptr;   // [lists][kSgInts]
+  unsigned char *d_deg = nullptr;   // one byte per range measurement
+  int32_t *d_range_rows = nullptr;  // [3][n_ranges] internal rows: range | b | a (as MlTables')
+};
 struct cora_ctx {
   HostFormat F;
   LongImage LI;  // what the long rows' device arrays hold (long_image.h); derived from F at creation, device handles only
@@ -169,6 +193,7 @@ struct cora_ctx {
   OdomTables odom;
   MlTables ml;
   PlTables pl;
+  SgTables sg;
   cora_native_comm *native_comm = nullptr;  // owned: the library's own communication (cora_comm_create_*)
   cora::P2PState *p2p_pending = nullptr;    // a mailbox exported by cora_comm_p2p_handle, not yet connected
   int device = -1;
@@ -665,6 +690,14 @@ void free_pl(cora_ctx *c) {  // (the device must be current where there is one)
   T = PlTables();
 }
 
+void free_sg(cora_ctx *c) {  // (the device must be current where there is one)
+  SgTables &T = c->sg;
+  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state), static_cast<void *>(T.d_istate),
+                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows)})
+    if (p) (void)hipFree(p);
+  T = SgTables();
+}
+
 void free_ml(cora_ctx *c) {  // (the device must be current where there is one)
   MlTables &T = c->ml;
   for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_init), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state),
@@ -678,6 +711,7 @@ void free_measurements(cora_ctx *c) {  // (the device must be current)
   free_odom(c);      // (so do the chain tables: their positions name its edges)
   free_ml(c);        // (and the multilateration's lists: their entries name its ranges)
   free_pl(c);        // (and the chain placement's stages)
+  free_sg(c);        // (and the sighting placement's lists: their entries name its edges)
   MeasurementTable &M = c->meas;
   for (void *p : {static_cast<void *>(M.d_edge_rows), static_cast<void *>(M.d_range_rows), static_cast<void *>(M.d_edge_data),
                   static_cast<void *>(M.d_range_data), static_cast<void *>(M.d_out)})
@@ -715,6 +749,7 @@ extern "C" {
 #include "capi/odom.inc"
 #include "capi/multilat.inc"
 #include "capi/placement.inc"
+#include "capi/sighting.inc"
 
 }  // extern "C"
 

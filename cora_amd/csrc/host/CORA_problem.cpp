@@ -1181,10 +1181,17 @@ Matrix Problem::multiRobotInitialization(uint64_t seed, int gn_steps, int min_ra
   return odometryStart(seed, gn_steps, info, "Problem::multiRobotInitialization", true, min_ranges, chains_info);
 }
 
+Matrix Problem::sightingInitialization(uint64_t seed, int gn_steps, int min_ranges, int min_sightings, SightingPlacementInfo *sight_info,
+                                       ChainPlacementInfo *chains_info, LandmarkInitInfo *info) const {
+  if (gn_steps < 0) throw std::invalid_argument("Problem::sightingInitialization: gn_steps must be in [0, 16]");
+  return odometryStart(seed, gn_steps, info, "Problem::sightingInitialization", true, min_ranges, chains_info, true, min_sightings, sight_info);
+}
+
 // the odometry start; with gn_steps >= 0 the landmarks are then placed from the ranges (cora_multilaterate_dev), with
-// `place` after the chains were (cora_place_chains_dev)
+// `place` after the chains were (cora_place_chains_dev), with `sightings` after landmarks and chains were placed from the
+// pose-landmark sightings (cora_place_by_sightings_dev)
 Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where, bool place, int min_ranges,
-                              ChainPlacementInfo *chains_info) const {
+                              ChainPlacementInfo *chains_info, bool sightings, int min_sightings, SightingPlacementInfo *sight_info) const {
   checkUpToDate();
   if (part_world_ > 1) throw std::runtime_error(std::string(where) + ": not supported on a partitioned handle");
   ensureMeasurementTable();
@@ -1242,11 +1249,61 @@ Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *inf
   if (gn_steps < 0 && !idx.empty())
     CORA_CALL(cora_odometry_set_range_rows_dev(c, static_cast<int64_t>(idx.size()), idx.data(), dirs.data(), v.x), where);
   const Matrix Qm = odom_draws::drawRotation(g, U, p);
-  if (place && gn_steps >= 0 && !chains.empty()) {
+  // per chain: fixed or placed by the sighting step (the fixed chains of the range placement); per landmark: placed by it
+  std::vector<unsigned char> chain_done, lm_done(static_cast<size_t>(nl) + 1, 0);
+  if (sightings && gn_steps >= 0 && !chains.empty()) {
+    // (after every draw of odometryInitialization: the step draws nothing)
+    const size_t nch = chains.size(), G = static_cast<size_t>(d) * d + d;
+    CORA_CALL(cora_set_sighting_placement(c, nullptr, nullptr, min_sightings > 0 ? min_sightings : 4 * d), where);
+    int64_t out[6] = {0, 0, 0, 0, 0, 0};
+    std::vector<unsigned char> status(nch + 1, 0), ls(static_cast<size_t>(nl) + 1, 0);
+    std::vector<int32_t> chosen(nch + 1, 0);
+    std::vector<double> cs(nch + 1, 0.0), cf(nch + 1, 0.0), tr(nch * G + 1, 0.0), lc(static_cast<size_t>(nl) + 1, 0.0);
+    CORA_CALL(cora_place_by_sightings_dev(c, v.x, out, status.data(), cs.data(), cf.data(), chosen.data(), tr.data(), ls.data(), lc.data(), nullptr),
+              where);
+    chain_done.assign(nch + 1, 0);
+    long fixed = 0;
+    for (size_t ch = 0; ch < nch; ++ch) {
+      chain_done[ch] = status[ch] == 0 || status[ch] == 4 ? 1 : 0;
+      fixed += status[ch] == 4 ? 1 : 0;
+    }
+    for (int l = 0; l < nl; ++l) lm_done[static_cast<size_t>(l)] = ls[static_cast<size_t>(l)] == 0 ? 1 : 0;
+    if (sight_info) {
+      sight_info->chains_fixed = fixed;
+      sight_info->chains_placed = static_cast<long>(out[0]);
+      sight_info->chains_not_placed = static_cast<long>(out[1]);
+      sight_info->landmarks_placed = static_cast<long>(out[2]);
+      sight_info->landmarks_not_placed = static_cast<long>(out[3]);
+      sight_info->stages = static_cast<long>(out[5]);
+      sight_info->status.assign(status.begin(), status.begin() + static_cast<std::ptrdiff_t>(nch));
+      sight_info->cost_start.assign(cs.begin(), cs.begin() + static_cast<std::ptrdiff_t>(nch));
+      sight_info->cost_final.assign(cf.begin(), cf.begin() + static_cast<std::ptrdiff_t>(nch));
+      sight_info->chosen.assign(chosen.begin(), chosen.begin() + static_cast<std::ptrdiff_t>(nch));
+      sight_info->transforms.assign(tr.begin(), tr.begin() + static_cast<std::ptrdiff_t>(nch * G));
+      sight_info->landmark_status.assign(ls.begin(), ls.begin() + nl);
+      sight_info->landmark_cost.assign(lc.begin(), lc.begin() + nl);
+    }
+  }
+  bool chains_left = true;  // (the sighting step may have left no chain to the ranges)
+  if (!chain_done.empty()) {
+    chains_left = false;
+    for (size_t ch = 0; ch < chains.size(); ++ch) chains_left = chains_left || !chain_done[ch];
+    if (!chains_left && chains_info) {
+      *chains_info = ChainPlacementInfo();
+      chains_info->status.assign(chains.size(), 4);
+      chains_info->cost_start.assign(chains.size(), 0.0);
+      chains_info->cost_linear.assign(chains.size(), 0.0);
+      chains_info->cost_final.assign(chains.size(), 0.0);
+      chains_info->transforms.assign(chains.size() * (static_cast<size_t>(d) * d + d), 0.0);
+      for (size_t ch = 0; ch < chains.size(); ++ch)
+        for (int a = 0; a < d; ++a) chains_info->transforms[ch * (static_cast<size_t>(d) * d + d) + static_cast<size_t>(a) * d + a] = 1.0;
+    }
+  }
+  if (place && gn_steps >= 0 && !chains.empty() && chains_left) {
     // (after every draw of odometryInitialization: the placement draws nothing.  Its range rows are recomputed by the
     // multilateration below, which also decides the fallback directions.)
     const size_t nch = chains.size(), G = static_cast<size_t>(d) * d + d;
-    CORA_CALL(cora_set_chain_placement(c, nullptr, min_ranges > 0 ? min_ranges : 4 * (d == 2 ? 7 : 16)), where);
+    CORA_CALL(cora_set_chain_placement(c, chain_done.empty() ? nullptr : chain_done.data(), min_ranges > 0 ? min_ranges : 4 * (d == 2 ? 7 : 16)), where);
     int64_t out[5] = {0, 0, 0, 0, 0};
     std::vector<unsigned char> status(nch + 1, 0);
     std::vector<double> cs(nch + 1, 0.0), cl(nch + 1, 0.0), cf(nch + 1, 0.0), tr(nch * G + 1, 0.0);
@@ -1272,6 +1329,8 @@ Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *inf
         pose_ok[static_cast<size_t>(pose_symbol_idxs_.at(m.first_id))] = 1;
         pose_ok[static_cast<size_t>(pose_symbol_idxs_.at(m.second_id))] = 1;
       }
+    for (int l = 0; l < nl; ++l)
+      if (lm_done[static_cast<size_t>(l)]) on[static_cast<size_t>(l)] = 0;  // (the sightings placed it)
     CORA_CALL(cora_set_multilateration(c, pose_ok.data(), on.data()), where);
     int64_t out[4] = {0, 0, 0, 0};
     std::vector<unsigned char> status(static_cast<size_t>(nl) + 1, 0), after(nr + 1, 0);

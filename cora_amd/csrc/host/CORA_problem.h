@@ -173,6 +173,19 @@ struct ChainPlacementInfo {
   std::vector<Scalar> transforms;      // per chain d * d + d: R row-major, then t, as written
 };
 
+/** What Problem::sightingInitialization reports about the sighting step (cora_place_by_sightings_dev, include/cora_hip.h). */
+struct SightingPlacementInfo {
+  long chains_fixed = 0, chains_placed = 0, chains_not_placed = 0;  // status 4 | 0 | 1, 2, 3
+  long landmarks_placed = 0, landmarks_not_placed = 0;              // status 0 | 1, 2
+  long stages = 0;
+  std::vector<unsigned char> status;   // per chain (0 placed, 1 never taken, 2 refused by the device, 3 no sighting, 4 fixed)
+  std::vector<Scalar> cost_start, cost_final;  // per chain: sum tau |x_t(l) - p|^2 over its list, before and as applied
+  std::vector<int32_t> chosen;         // per chain: 1 moved, 0 left where it stood, -1 no list
+  std::vector<Scalar> transforms;      // per chain d * d + d: R row-major, then t, as applied
+  std::vector<unsigned char> landmark_status;  // per landmark (0 placed, 1 no sighting from a placed chain, 2 sum tau <= 0, 3 fixed)
+  std::vector<Scalar> landmark_cost;   // per landmark: the sighting cost of its REFIT list at the row written
+};
+
 class Problem {
  private:
   int dim_;
@@ -254,8 +267,10 @@ class Problem {
   void ensurePreconditioner() const;
   void ensureMeasurementTable() const;
   // gn_steps < 0: no multilateration; place: the chains are first placed from the ranges between them (min_ranges <= 0: the default)
+  // sightings: before that, landmarks and chains are placed from the pose-landmark sightings (min_sightings <= 0: the default)
   Matrix odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where, bool place = false, int min_ranges = 0,
-                       ChainPlacementInfo *chains_info = nullptr) const;
+                       ChainPlacementInfo *chains_info = nullptr, bool sightings = false, int min_sightings = 0,
+                       SightingPlacementInfo *sight_info = nullptr) const;
   void fillImplicitFormulationMatrices() const;
   [[noreturn]] void throwLast(int status, const char *where) const;
 
@@ -480,6 +495,16 @@ class Problem {
    * never raises the range cost over its own entries; nothing else is promised.  std::runtime_error on a partitioned handle. */
   Matrix multiRobotInitialization(uint64_t seed = 7, int gn_steps = 5, int min_ranges = 0, ChainPlacementInfo *chains_info = nullptr,
                                   LandmarkInitInfo *info = nullptr) const;
+  /** EXTENSION beyond the reference: multiRobotInitialization with landmarks and chains first placed from the
+   * pose-landmark sightings (cora_place_by_sightings_dev), chain 0 fixed: exactly the draws of odometryInitialization in
+   * the same order (the new step draws nothing), then the sighting placement, then cora_place_chains_dev for the chains
+   * the sightings left (its fixed chains: every chain the sighting step fixed or placed; skipped when none is left), then
+   * the multilateration for the landmarks the sightings did not place, the range rows and the lift.  On a problem without
+   * sightings the result has multiRobotInitialization's bits.  A landmark that only a range-placed chain sights is not
+   * revisited.  min_sightings <= 0: 4 d.  std::runtime_error on a partitioned handle. */
+  Matrix sightingInitialization(uint64_t seed = 7, int gn_steps = 5, int min_ranges = 0, int min_sightings = 0,
+                                SightingPlacementInfo *sight_info = nullptr, ChainPlacementInfo *chains_info = nullptr,
+                                LandmarkInitInfo *info = nullptr) const;
 
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;

@@ -253,6 +253,7 @@ int cora_problem_op(cora_problem *p, const char *op, int cols, const double *A, 
     else if (o == "odometryInitialization") res = q.odometryInitialization();
     else if (o == "rangeAidedInitialization") res = q.rangeAidedInitialization();
     else if (o == "multiRobotInitialization") res = q.multiRobotInitialization();
+    else if (o == "sightingInitialization") res = q.sightingInitialization();
     else if (o == "getTranslationExplicitSolution") res = q.getTranslationExplicitSolution(wrap(A, N, r));
     else if (o == "alignEstimateToOrigin") res = q.alignEstimateToOrigin(wrap(A, N, r));
     else throw std::invalid_argument("unknown operator " + o);
@@ -331,6 +332,49 @@ int cora_problem_multi_robot_initialization(cora_problem *p, uint64_t seed, int 
       landmark_counts[3] = info.gn_steps;
     }
     if (landmark_status) std::copy(info.status.begin(), info.status.end(), landmark_status);
+  });
+}
+
+int cora_problem_sighting_initialization(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, int min_sightings, double *out,
+                                         int64_t counts[6], unsigned char *status, double *cost_start, double *cost_final, int32_t *chosen,
+                                         double *transforms, unsigned char *landmark_status, double *landmark_cost, int64_t chain_counts[4],
+                                         unsigned char *chain_status, int64_t landmark_counts[4], unsigned char *range_landmark_status) {
+  return guarded([&] {
+    SightingPlacementInfo si;
+    ChainPlacementInfo ci;
+    LandmarkInitInfo info;
+    const Matrix res = p->problem.sightingInitialization(seed, gn_steps, min_ranges, min_sightings, &si, &ci, &info);
+    if (res.rows() == p->problem.getExpectedVariableSize()) p->problem.checkVariablesAreValid(res);  // (throws off the manifold)
+    std::memcpy(out, res.data(), sizeof(double) * static_cast<size_t>(res.size()));
+    if (counts) {
+      counts[0] = si.chains_fixed;
+      counts[1] = si.chains_placed;
+      counts[2] = si.chains_not_placed;
+      counts[3] = si.landmarks_placed;
+      counts[4] = si.landmarks_not_placed;
+      counts[5] = si.stages;
+    }
+    if (status) std::copy(si.status.begin(), si.status.end(), status);
+    if (cost_start) std::copy(si.cost_start.begin(), si.cost_start.end(), cost_start);
+    if (cost_final) std::copy(si.cost_final.begin(), si.cost_final.end(), cost_final);
+    if (chosen) std::copy(si.chosen.begin(), si.chosen.end(), chosen);
+    if (transforms) std::copy(si.transforms.begin(), si.transforms.end(), transforms);
+    if (landmark_status) std::copy(si.landmark_status.begin(), si.landmark_status.end(), landmark_status);
+    if (landmark_cost) std::copy(si.landmark_cost.begin(), si.landmark_cost.end(), landmark_cost);
+    if (chain_counts) {
+      chain_counts[0] = ci.placed;
+      chain_counts[1] = ci.not_placed;
+      chain_counts[2] = ci.gn_steps;
+      chain_counts[3] = ci.stages;
+    }
+    if (chain_status) std::copy(ci.status.begin(), ci.status.end(), chain_status);
+    if (landmark_counts) {
+      landmark_counts[0] = info.solved;
+      landmark_counts[1] = info.not_solved;
+      landmark_counts[2] = info.degenerate_range_rows;
+      landmark_counts[3] = info.gn_steps;
+    }
+    if (range_landmark_status) std::copy(info.status.begin(), info.status.end(), range_landmark_status);
   });
 }
 

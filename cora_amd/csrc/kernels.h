@@ -1470,6 +1470,242 @@ __host__ __device__ inline void pl_apply(const double *g, double *rot, double *t
   for (int c = 0; c < D; ++c) trn[c] = nt[c];
 }
 
+// Placement from pose-landmark sightings (kernels/sighting.inc; include/cora_hip.h, cora_place_by_sightings_dev).  A
+// sighting is an edge without a second rotation from a position of an odometry chain to a landmark: its prediction is
+// p = x_t(a) + sum_c t_c X_a[c, :].  The host orders the work into STAGES (capi/sighting.inc) of three kinds: an L-stage
+// sets landmarks to the weighted mean of their predictions, a C-stage moves chains by the weighted rigid alignment of their
+// predictions onto the landmarks, the REFIT sets the landmarks again.  A stage holds LISTS (one per landmark or chain) of
+// entries (first rotation row and translation row of the pose, row of the landmark, edge), cut into chunks of kSgChunk
+// entries, none across two lists; ALL lists of a stage share its launches:
+//   L-stage, REFIT : pass (mode 0: sum tau | tau (p - p_0)) and fold (one wavefront per list; writes the landmark's row)
+//   C-stage        : pass and fold of the alignment's sums (mode 1), pass and fold of the two costs (mode 2), apply
+//   after the REFIT: pass and fold of the landmarks' cost (mode 3)
+// Coordinates are relative to the list's first entry: p' = p - p_0, l' = x_t(l) - l_0.
+// BRACKET ORDER, a function of the list length and kSgChunk alone and the same in the host mirror (capi/sighting.inc):
+// as the multilateration's -- butterfly per wavefront, lanes without an entry hold +0.0, the four wavefronts of a chunk from
+// the left; fold: lane j takes 0.0 + chunk j + chunk (j + 64) + .. of the list from the left, then the butterfly.
+// Every term is made of single correctly rounded fp64 operations in the order written, never contracted.
+constexpr int kSgChunk = 256;
+constexpr double kSgMinSpread = 1e-6;  // the refusal rule of sg_chain_solve, in units of length
+constexpr int kSgLmSums(int d) { return 1 + d; }                   // sum tau | tau (p - p_0)
+constexpr int kSgChainSums(int d) { return 3 + 2 * d + d * d; }    // tau | tau p' | tau l' | tau l' p'^T (row-major) | tau |p'|^2 | tau |l'|^2
+constexpr int kSgCostSums = 2;                                     // at the identity | at g
+constexpr int kSgMaxSums(int d) { return kSgChainSums(d); }
+constexpr int kSgG(int d) { return d * d + d; }                    // R row-major | translation
+// a chain's list: R | t | t' = R p_0 + t - l_0 | cost_start | cost_final;  a landmark's: x | sum tau | cost
+constexpr int kSgState(int d) { return kSgG(d) + d + 2; }
+constexpr int kSgInts = 2;  // status | chosen
+struct SgArgs {
+  int d = 0, mode = 0;
+  int32_t chunk0 = 0, n_chunks = 0;   // the stage's chunks in the chunk table
+  int32_t list0 = 0, n_lists = 0;     // the stage's lists in the list table
+  int32_t apply0 = 0, n_apply = 0;    // the positions of the stage's chains in the apply table
+  int64_t n_edges = 0, pstride = 0;
+  const int32_t *chunk_begin = nullptr, *chunk_len = nullptr, *chunk_list = nullptr;  // [chunks of all stages]
+  const int32_t *list_chunk0 = nullptr, *list_row = nullptr;  // [lists + 1], [lists]: the landmark's INTERNAL row (a chain's list: -1)
+  const int32_t *ent_rot = nullptr, *ent_trn = nullptr, *ent_lm = nullptr, *ent_e = nullptr;  // [entries]: INTERNAL rows, edge
+  const int32_t *apply_pos = nullptr, *apply_list = nullptr;  // [positions of all C-stages]: chain-table position, its list
+  const int32_t *pos_rot = nullptr, *pos_trn = nullptr;       // the chain tables' (OdomArgs)
+  const double *edge_data = nullptr;   // the measurement table's, [d*d + d + 2][n_edges]
+  double *partial = nullptr;           // [kSgMaxSums(d)][pstride], pstride = the chunks of all stages
+  double *state = nullptr;             // [lists][kSgState(d)]
+  int32_t *istate = nullptr;           // [lists][kSgInts]
+  double *x = nullptr;                 // d columns at stride ld_for(d) = d
+  int *flag = nullptr;                 // |= 1 where a sum is not finite
+};
+hipError_t launch_sighting_pass_fold(const SgArgs &A, hipStream_t st);  // pass and fold of A.mode over the stage A describes
+hipError_t launch_sighting_apply(const SgArgs &A, hipStream_t st);
+// p = x_t(a) + sum_c t_c X_a[c, :]  (from x_t(a), c ascending, one fma per term)
+template <int D>
+__host__ __device__ inline void sg_predict(const double *rot, const double *trn, const double *t, double *p) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    double v = trn[k];
+#pragma unroll
+    for (int c = 0; c < D; ++c) v = fma(t[c], rot[c * D + k], v);
+    p[k] = v;
+  }
+}
+template <int D>
+__host__ __device__ inline void sg_lm_terms(const double *p0, const double *p, double tau, double *s) {
+#pragma clang fp contract(off)
+  s[0] = tau;
+#pragma unroll
+  for (int c = 0; c < D; ++c) s[1 + c] = tau * (p[c] - p0[c]);
+}
+// x = p_0 + (sum tau (p - p_0)) / sum tau; status 0, or 2 (x untouched) where sum tau <= 0 (or is not a number)
+template <int D>
+__host__ __device__ inline int sg_lm_solve(const double *S, const double *p0, double *x) {
+#pragma clang fp contract(off)
+  if (!(S[0] > 0.0)) return 2;
+#pragma unroll
+  for (int c = 0; c < D; ++c) x[c] = p0[c] + S[1 + c] / S[0];
+  return 0;
+}
+// tau |x_t(l) - p|^2, the table's own translation residual of the edge (from +0.0, c ascending)
+template <int D>
+__host__ __device__ inline double sg_lm_cost(const double *p, const double *l, double tau) {
+#pragma clang fp contract(off)
+  double q = 0.0;
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    const double r = l[c] - p[c];
+    q = fma(r, r, q);
+  }
+  return tau * q;
+}
+template <int D>
+__host__ __device__ inline void sg_chain_terms(const double *p0, const double *l0, const double *p, const double *l, double tau, double *s) {
+#pragma clang fp contract(off)
+  double pp[D], ll[D], np = 0.0, nl = 0.0;
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    pp[c] = p[c] - p0[c];
+    ll[c] = l[c] - l0[c];
+    np = fma(pp[c], pp[c], np);
+    nl = fma(ll[c], ll[c], nl);
+  }
+  s[0] = tau;
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    s[1 + c] = tau * pp[c];
+    s[1 + D + c] = tau * ll[c];
+  }
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+#pragma unroll
+    for (int b = 0; b < D; ++b) s[1 + 2 * D + a * D + b] = (tau * ll[a]) * pp[b];
+  s[1 + 2 * D + D * D] = tau * np;
+  s[2 + 2 * D + D * D] = tau * nl;
+}
+// The weighted rigid alignment from the sums: H = sum tau l' p'^T - (sum tau l')(sum tau p')^T / sum tau, R =
+// round_rotation(H), t' = lbar - R pbar with the relative centroids, t = t' + l_0 - R p_0.  g: R | t | t'.
+// REFUSED (status 2, g = the identity with t' = p_0 - l_0), a function of the sums alone, with W = sum tau,
+// s_p = sum tau |p'|^2 - |sum tau p'|^2 / W and s_l likewise (the two centred spreads), k = kSgMinSpread:
+//   W <= 0, s_p <= 0 or s_l <= 0 (no spread), or
+//   d = 2:  |H|_F^2 <= k^2 s_p s_l                   (H = 0: no direction at all)
+//   d = 3:  |cof(H)|_F^2 <= k^4 (s_p s_l)^2          (the sum of the squared 2 x 2 minors: rank below 2)
+// (every comparison written so that a NaN refuses).  With singular values s_1 >= s_2 >= s_3 of H these read
+// s_1^2 + s_2^2 <= k^2 s_p s_l and s_1^2 s_2^2 + s_1^2 s_3^2 + s_2^2 s_3^2 <= k^4 (s_p s_l)^2.
+template <int D>
+__host__ __device__ inline int sg_chain_solve(const double *S, const double *p0, const double *l0, double *g) {
+#pragma clang fp contract(off)
+  constexpr int G = kSgG(D);
+  const double *Sp = S + 1, *Sl = S + 1 + D, *Slp = S + 1 + 2 * D;
+  const double W = S[0];
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) g[i] = i / D == i % D ? 1.0 : 0.0;
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    g[D * D + c] = 0.0;
+    g[G + c] = p0[c] - l0[c];
+  }
+  if (!(W > 0.0)) return 2;
+  double H[D][D], np = 0.0, nl = 0.0;
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    np = fma(Sp[c], Sp[c], np);
+    nl = fma(Sl[c], Sl[c], nl);
+  }
+  const double sp = S[1 + 2 * D + D * D] - np / W, sl = S[2 + 2 * D + D * D] - nl / W;
+  if (!(sp > 0.0) || !(sl > 0.0)) return 2;
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+#pragma unroll
+    for (int b = 0; b < D; ++b) H[a][b] = Slp[a * D + b] - (Sl[a] * Sp[b]) / W;
+  const double scale = sp * sl, k2 = kSgMinSpread * kSgMinSpread;
+  if constexpr (D == 2) {
+    const double f = fma(H[1][1], H[1][1], fma(H[1][0], H[1][0], fma(H[0][1], H[0][1], H[0][0] * H[0][0])));
+    if (!(f > k2 * scale)) return 2;
+  } else {
+    double q = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        const int a1 = (a + 1) % 3, a2 = (a + 2) % 3, b1 = (b + 1) % 3, b2 = (b + 2) % 3;
+        const double m = fma(H[a1][b1], H[a2][b2], -(H[a1][b2] * H[a2][b1]));
+        q = fma(m, m, q);
+      }
+    if (!(q > (k2 * scale) * (k2 * scale))) return 2;
+  }
+  round_rotation<D>(H);
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+#pragma unroll
+    for (int b = 0; b < D; ++b) g[a * D + b] = H[a][b];
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    double rp = 0.0, r0 = 0.0;  // R pbar, R p_0 (from +0.0, k ascending)
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      rp = fma(H[a][k], Sp[k] / W, rp);
+      r0 = fma(H[a][k], p0[k], r0);
+    }
+    const double tr = Sl[a] / W - rp;
+    g[G + a] = tr;
+    g[D * D + a] = (tr + l0[a]) - r0;
+  }
+  return 0;
+}
+// the two costs of one entry: at the identity, tau |x_t(l) - p|^2 as the table has it; at g, tau |R p' + t' - l'|^2
+template <int D>
+__host__ __device__ inline void sg_cost_terms(const double *g, const double *p0, const double *l0, const double *p, const double *l, double tau,
+                                              double *s) {
+#pragma clang fp contract(off)
+  constexpr int G = kSgG(D);
+  s[0] = sg_lm_cost<D>(p, l, tau);
+  double pp[D], q = 0.0;
+#pragma unroll
+  for (int c = 0; c < D; ++c) pp[c] = p[c] - p0[c];
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    double v = g[G + a];
+#pragma unroll
+    for (int k = 0; k < D; ++k) v = fma(g[a * D + k], pp[k], v);
+    const double r = v - (l[a] - l0[a]);
+    q = fma(r, r, q);
+  }
+  s[1] = tau * q;
+}
+// what lane 0 of a list's fold does with the list's sums S in mode MODE; row: the landmark's row of x (modes 0 and 3);
+// p0, l0: the first entry's prediction and landmark.  False where a sum is not finite.
+template <int D, int MODE>
+__host__ __device__ inline bool sg_fold(const double *S, double *st, int32_t *ist, const double *p0, const double *l0, double *row) {
+  constexpr int G = kSgG(D);
+  constexpr int ns = MODE == 0 ? kSgLmSums(D) : (MODE == 1 ? kSgChainSums(D) : (MODE == 2 ? kSgCostSums : 1));
+  bool finite = odom_finite(S, ns);
+  if constexpr (MODE == 0) {
+    double x[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) x[c] = row[c];
+    ist[0] = finite ? sg_lm_solve<D>(S, p0, x) : 2;
+    ist[1] = ist[0] == 0 ? 1 : 0;
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+      st[c] = x[c];
+      if (ist[0] == 0) row[c] = x[c];
+    }
+    st[D] = S[0];
+    st[D + 1] = 0.0;
+  } else if constexpr (MODE == 1) {
+    double g[G + D];
+    ist[0] = sg_chain_solve<D>(S, p0, l0, g);  // (sums that are not finite: the call fails, whatever g is)
+    ist[1] = 0;
+#pragma unroll
+    for (int i = 0; i < G + D; ++i) st[i] = g[i];
+    finite = finite && odom_finite(g, G + D);
+  } else if constexpr (MODE == 2) {
+    ist[1] = ist[0] == 0 && S[1] < S[0] ? 1 : 0;
+    st[G + D] = S[0];
+    st[G + D + 1] = ist[1] ? S[1] : S[0];  // the cost of what is applied
+  } else {
+    st[D + 1] = S[0];
+  }
+  return finite;
+}
+
 // In-place update of Q's values (kernels/update_values.inc).  src: the sources of ValueMap (cora_internal.h), vals: the
 // new CSR values on the device.
 // check: flag |= 1 where a value is not finite, |= 2 where a mirror pair (mirror[2j], mirror[2j + 1]) differs.

@@ -607,6 +607,39 @@ hipError_t launch_place_apply(const PlArgs &A, hipStream_t st) {
   else hipLaunchKernelGGL(k_pl_apply<3>, grid, dim3(256), 0, st, A);
   return hipGetLastError();
 }
+// the placement from sightings (kernels/sighting.inc): every launch serves all lists of the one stage A describes
+static bool sighting_args_ok(const SgArgs &A) {
+  return (A.d == 2 || A.d == 3) && A.n_chunks > 0 && A.chunk0 >= 0 && A.n_lists > 0 && A.list0 >= 0 && A.n_edges > 0 &&
+         A.pstride >= static_cast<int64_t>(A.chunk0) + A.n_chunks && A.chunk_begin && A.chunk_len && A.chunk_list && A.list_chunk0 && A.list_row &&
+         A.ent_rot && A.ent_trn && A.ent_lm && A.ent_e && A.edge_data && A.partial && A.state && A.istate && A.x && A.flag;
+}
+template <int D, int MODE>
+static void sighting_pass_fold(const SgArgs &A, hipStream_t st) {
+  hipLaunchKernelGGL((k_sg_pass<D, MODE>), dim3(static_cast<unsigned>(A.n_chunks)), dim3(kSgChunk), 0, st, A);
+  hipLaunchKernelGGL((k_sg_fold<D, MODE>), dim3(static_cast<unsigned>(A.n_lists)), dim3(kWave), 0, st, A);
+}
+hipError_t launch_sighting_pass_fold(const SgArgs &A, hipStream_t st) {
+  if (!sighting_args_ok(A) || A.mode < 0 || A.mode > 3) return hipErrorInvalidValue;
+  if (A.d == 2) {
+    if (A.mode == 0) sighting_pass_fold<2, 0>(A, st);
+    else if (A.mode == 1) sighting_pass_fold<2, 1>(A, st);
+    else if (A.mode == 2) sighting_pass_fold<2, 2>(A, st);
+    else sighting_pass_fold<2, 3>(A, st);
+  } else {
+    if (A.mode == 0) sighting_pass_fold<3, 0>(A, st);
+    else if (A.mode == 1) sighting_pass_fold<3, 1>(A, st);
+    else if (A.mode == 2) sighting_pass_fold<3, 2>(A, st);
+    else sighting_pass_fold<3, 3>(A, st);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_sighting_apply(const SgArgs &A, hipStream_t st) {
+  if (!sighting_args_ok(A) || A.n_apply <= 0 || A.apply0 < 0 || !A.apply_pos || !A.apply_list || !A.pos_rot || !A.pos_trn) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<unsigned>((A.n_apply + 255) / 256));
+  if (A.d == 2) hipLaunchKernelGGL(k_sg_apply<2>, grid, dim3(256), 0, st, A);
+  else hipLaunchKernelGGL(k_sg_apply<3>, grid, dim3(256), 0, st, A);
+  return hipGetLastError();
+}
 hipError_t launch_round_amax(int64_t n, const double *y, double *partial, int nblocks, int *flag, hipStream_t st) {
   if (n < 1 || nblocks < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_round_amax, dim3(nblocks), dim3(256), 0, st, n, y, partial, flag);

@@ -27,7 +27,7 @@ int main(int argc, char **argv) {
   }
   int max_rank = 10, gn_steps = 5;
   std::string tum, save_dir, residuals, weights, robust, barc2, weights_out, aligned_tum, rpe_steps, rpe_dists;
-  bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false, landmark_init = false, place_chains = false;
+  bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false, landmark_init = false, place_chains = false, sightings = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--jacobi") jacobi = true;
@@ -64,12 +64,16 @@ int main(int argc, char **argv) {
     // with --odom-init --device-init: the chains after the first are first placed from the pose-pose ranges between chains
     // (Problem::multiRobotInitialization, which then places the landmarks as --landmark-init does)
     else if (a == "--place-chains") place_chains = true;
+    // with --odom-init --device-init: landmarks and chains are first placed from the pose-landmark sightings, then the chains
+    // that are left from the ranges and the landmarks that are left by multilateration (Problem::sightingInitialization)
+    else if (a == "--sightings") sightings = true;
   }
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
   try {
     if (device_init && !odom) throw std::runtime_error("--device-init composes the odometry start on the device: it needs --odom-init");
     if (place_chains && !device_init) throw std::runtime_error("--place-chains places the chains of the device's odometry start: it needs --odom-init --device-init");
+    if (sightings && !device_init) throw std::runtime_error("--sightings places landmarks and chains of the device's odometry start: it needs --odom-init --device-init");
     if (landmark_init && !device_init) throw std::runtime_error("--landmark-init places the landmarks of the device's odometry start: it needs --odom-init --device-init");
     const auto t_start = clk::now();
     CORA::Problem problem = CORA::parsePyfgTextToProblem(argv[1]);
@@ -138,6 +142,21 @@ int main(int argc, char **argv) {
       x0 = problem.multiRobotInitialization(7, gn_steps, 0, &ci);
       std::printf("chain placement: %ld chains placed, %ld not placed (%ld Gauss-Newton steps); range residual sum at the start %.6e with it, %.6e without\n",
                   ci.placed, ci.not_placed, ci.gn_steps, range_sum(x0), without);
+    }
+    if (sightings) {  // (an extension beyond the reference: Problem::sightingInitialization)
+      CORA::SightingPlacementInfo si;
+      auto sighting_sum = [&](const CORA::Matrix &x) {
+        const CORA::MeasurementResiduals res =
+            problem.measurementResiduals(implicit ? CORA::Matrix(x.block(0, 0, problem.rotAndRangeMatrixSize(), x.cols())) : x);
+        double sum = 0;
+        for (const double v : res.pose_landmark) sum += v;
+        return sum;
+      };
+      const double without = sighting_sum(x0);  // (the start as it stands)
+      x0 = problem.sightingInitialization(7, gn_steps, 0, 0, &si);
+      std::printf("sighting placement: %ld chains fixed or placed, %ld not placed; %ld landmarks placed, %ld not placed (%ld stages); sighting cost at the start %.6e with it, %.6e without\n",
+                  si.chains_fixed + si.chains_placed, si.chains_not_placed, si.landmarks_placed, si.landmarks_not_placed, si.stages,
+                  sighting_sum(x0), without);
     }
     if (odom && implicit)  // examples/paper_experiments.cpp:623-625
       x0 = x0.block(0, 0, problem.rotAndRangeMatrixSize(), x0.cols());

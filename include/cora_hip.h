@@ -924,6 +924,93 @@ int cora_debug_place_chains_host(cora_ctx *ctx, double *X, int ldx, int gn_steps
                                  double *cost_start, double *cost_linear, double *cost_final, int32_t *chosen, double *transforms,
                                  unsigned char *degenerate);
 
+/* ---- PLACEMENT FROM POSE-LANDMARK SIGHTINGS, on the device ----------------------------------------------------------------
+ * Places landmarks and whole odometry chains of a resident vector of d columns (the output of cora_odometry_init_dev)
+ * from the pose-landmark sightings of the measurement table, in place; both solves are closed-form.  Needs a measurement
+ * table (cora_set_measurements), chain tables (cora_set_odometry_chains) and the tables of cora_set_sighting_placement.
+ * DEFINITIONS.
+ *   sighting         an edge of the measurement table whose second rotation row is -1, whose first translation row is the
+ *                    translation row of a position of an odometry chain and whose second translation row is a landmark's
+ *                    row (past the n poses' translation rows).  Every other edge without a second rotation (a landmark
+ *                    prior, a sighting from a free pose) is skipped and counted.  Its data: pose a, landmark l, t and tau as
+ *                    the table holds them.
+ *   prediction       p = x_t(a) + sum_c t_c X_a[c, :] from the vector as it stands: the point at which the table's
+ *                    translation residual of the edge is zero.
+ *   sighting cost    of a set of sightings: sum tau |x_t(l) - p|^2, the table's own residual.
+ *   order            decided on the host from structure alone.  The placed chains start as chain_fixed (NULL: chain 0), the
+ *                    placed landmarks as landmark_fixed (NULL: none).  Then an L-stage and a C-stage alternate until
+ *                    neither takes anything; then one REFIT stage follows.  A stage that takes nothing is no stage.
+ *   L-stage          every unplaced landmark with at least one sighting from a position of a placed chain; its list is
+ *                    those sightings in table order; it counts as placed from then on.
+ *   C-stage          EVERY unplaced chain with at least min_sightings sightings of placed landmarks, among them at least d
+ *                    distinct landmarks: all of them in the same stage, solved side by side in the same launches.  A chain's
+ *                    list is those sightings in table order.  min_sightings >= d.
+ *   REFIT            every landmark outside landmark_fixed with a sighting from any placed chain is set again, from ALL its
+ *                    sightings by placed chains.
+ *   lists            cut into chunks of 256; no chunk spans two lists.  Coordinates are relative to the first entry of the
+ *                    list: p' = p - p_0, l' = x_t(l) - l_0.
+ *   landmark         x_t(l) = p_0 + (sum tau (p_i - p_0)) / sum tau.  landmark_status: 0 placed | 1 no sighting from a placed
+ *                    chain | 2 sum tau <= 0 (the row is not touched) | 3 fixed.  The status and landmark_cost (the sighting
+ *                    cost of the REFIT's list at the row written; 0 without a list) are the REFIT's.
+ *   chain            g = (R, t) that minimises sum tau |R p_i + t - x_t(l_i)|^2 over the list.  From the sums of tau, tau p',
+ *                    tau l', tau l' p'^T, tau |p'|^2, tau |l'|^2 (11 at d = 2, 18 at d = 3):  W = sum tau,
+ *                    H = sum tau l' p'^T - (sum tau l')(sum tau p')^T / W,  R = the rotation that maximises tr(R^T H)
+ *                    (one-sided Jacobi with the determinant correction on the smallest singular value),  t' = (sum tau l')
+ *                    / W - R (sum tau p') / W,  t = t' + l_0 - R p_0.  A second pass evaluates the sighting cost of the list
+ *                    at the identity (cost_start) and at g (as tau |R p' + t' - l'|^2).  g is applied only where its
+ *                    cost is below cost_start (chosen 1, cost_final = the cost at g); otherwise the chain's rows are not
+ *                    touched (chosen 0, cost_final = cost_start): cost_final <= cost_start as doubles, always.
+ *                    status: 0 placed | 1 never taken (too few sightings of placed landmarks or too few distinct ones) |
+ *                    2 taken but refused by the device | 3 no sighting at all | 4 fixed.
+ *   refusal          a function of the sums alone.  With the centred spreads s_p = sum tau |p'|^2 - |sum tau p'|^2 / W and
+ *                    s_l likewise, and k = 1e-6 (a length ratio): refused where W <= 0, s_p <= 0 or s_l <= 0 (no spread), or
+ *                    d = 2: |H|_F^2 <= k^2 s_p s_l;  d = 3: |cof(H)|_F^2 <= k^4 (s_p s_l)^2, the sum of the squared 2 x 2
+ *                    minors (rank below d - 1: all sighted landmarks at one point, at d = 3 all on one line).  A NaN refuses.
+ *                    A refused chain keeps its rows (cost_final = cost_start, chosen 0); by the structural order it STILL
+ *                    COUNTS AS PLACED for the stages after it: its sightings enter the later L-stages and the REFIT.
+ *   apply            t_i <- R t_i + t and the stored block R_i^T <- R_i^T R^T for every position of the stage's chains.
+ *   range rows       afterwards the unit range rows of ALL range measurements are recomputed in the direction of least
+ *                    residual, as cora_place_chains_dev does, with its degenerate bytes and count.
+ * cora_set_sighting_placement   validates, decides the order, translates the rows once and uploads.  The tables stay on the
+ *            handle until replaced, until the measurement table or the chain tables are replaced or until the handle is
+ *            destroyed.  Works on a plan-only handle, except for the upload.  A refused call leaves the tables as they were.
+ * cora_sighting_placement_counts   out = {stages, sightings used (entries of all lists), chunks, skipped edges}.
+ * cora_sighting_placement_order    stage_kind[stages]: 0 L | 1 C | 2 REFIT;  stage_ptr[stages + 1];  items[stage_ptr[stages]]:
+ *            the landmarks (L, REFIT) or chains (C) of stage s at items[stage_ptr[s] .. stage_ptr[s + 1]), ascending; one
+ *            item per list, and a list has at least one chunk: `chunks` entries always suffice.
+ * cora_place_by_sightings_dev   out (host) = {chains placed (status 0), chains not placed (1, 2, 3), landmarks placed (0),
+ *            landmarks not placed (1, 2), degenerate range rows, stages};  status, cost_start, cost_final, chosen: host
+ *            arrays with one entry per chain or NULL (costs 0 and chosen -1 where the chain has no list);  transforms:
+ *            [chains][d * d + d], R row-major then t as applied, the identity where nothing was applied;
+ *            landmark_status, landmark_cost: one entry per landmark or NULL;  degenerate: host bytes, one per range
+ *            measurement, or NULL.  Launches per stage: L-stage 2, C-stage 5, REFIT 2 + 2 for the landmarks' cost; then the
+ *            range rows.  Everything on the handle's stream; synchronises once, at the end.
+ * cora_place_by_sightings       the host-pointer form, in place: X is N x d column-major with leading dimension ldx.
+ * cora_debug_place_by_sightings_host   the same on the host in the device's bracket order and through the functions the
+ *            kernels call: X has the device's bits.  Works on a plan-only handle.
+ * ARITHMETIC.  No transcendental function: + - x / and sqrt only, single correctly rounded fp64 operations in the order
+ * written, never contracted.  Sums: the butterfly within a wavefront (lanes without an entry hold +0.0), the four
+ * wavefronts of a chunk from the left, chunk sums as [sum][chunk]; one wavefront per list in which lane j adds chunks
+ * j, j + 64, .. of the list from the left to +0.0, then the butterfly.  The same bits on every call.  No atomics on doubles.
+ * ERRORS.  CORA_ERR_NOT_READY: no measurement table, no chain tables, or no sighting tables.  CORA_ERR_ARG: a partitioned
+ * handle; min_sightings < d; a mask that fixes no chain; a null X or out; two range measurements that name one range row.
+ * CORA_ERR_SHAPE: a leading dimension below N.  CORA_ERR_NAN: a sum or a range row that is not finite (the device forms
+ * report it through the handle's flag word).  CORA_ERR_HIP: a device form on a plan-only handle.
+ * STATE.  Nothing the handle computes with changes. */
+int cora_set_sighting_placement(cora_ctx *ctx, const unsigned char *chain_fixed /* [chains] or NULL */,
+                                const unsigned char *landmark_fixed /* [landmarks] or NULL */, int min_sightings);
+int cora_sighting_placement_counts(const cora_ctx *ctx, int64_t out[4]);
+int cora_sighting_placement_order(const cora_ctx *ctx, int32_t *stage_kind, int32_t *stage_ptr, int32_t *items);
+int cora_place_by_sightings_dev(cora_ctx *ctx, double *dX, int64_t out[6], unsigned char *status, double *cost_start, double *cost_final,
+                                int32_t *chosen, double *transforms, unsigned char *landmark_status, double *landmark_cost,
+                                unsigned char *degenerate);
+int cora_place_by_sightings(cora_ctx *ctx, double *X, int ldx, int64_t out[6], unsigned char *status, double *cost_start,
+                            double *cost_final, int32_t *chosen, double *transforms, unsigned char *landmark_status,
+                            double *landmark_cost, unsigned char *degenerate);
+int cora_debug_place_by_sightings_host(cora_ctx *ctx, double *X, int ldx, int64_t out[6], unsigned char *status, double *cost_start,
+                                       double *cost_final, int32_t *chosen, double *transforms, unsigned char *landmark_status,
+                                       double *landmark_cost, unsigned char *degenerate);
+
 /* Timing helpers: HIP events on the handle's stream. */
 int cora_timer_start(cora_ctx *ctx);
 int cora_timer_stop_ms(cora_ctx *ctx, float *ms); /* synchronises */

@@ -96,6 +96,8 @@ int cora_problem_variable_size(cora_problem *p, int64_t *rows);
  *                                                        (Problem::rangeAidedInitialization, seed 7, 5 Gauss-Newton steps)
  *  "multiRobotInitialization" (none)             -> out   rangeAidedInitialization with the chains first placed from the ranges
  *                                                        between them (Problem::multiRobotInitialization, seed 7, 5 steps, default min_ranges)
+ *  "sightingInitialization"   (none)             -> out   multiRobotInitialization with landmarks and chains first placed from the
+ *                                                        pose-landmark sightings (Problem::sightingInitialization, seed 7, defaults)
  *  "getTranslationExplicitSolution" A=Y (implicit) -> out (d+1)n + r + l rows (src/CORA_problem.cpp:1168)
  *  "alignEstimateToOrigin"    A=Y (rank d)       -> out (d+1)n + r + l rows (src/CORA_problem.cpp:1234)
  * Inputs are N x cols with leading dimension N = cora_problem_variable_size() (cols is checked
@@ -121,6 +123,18 @@ int cora_problem_range_aided_initialization(cora_problem *p, uint64_t seed, int 
 int cora_problem_multi_robot_initialization(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, double *out, int64_t counts[4],
                                             unsigned char *status, double *cost_start, double *cost_linear, double *cost_final,
                                             double *transforms, int64_t landmark_counts[4], unsigned char *landmark_status);
+/* Problem::sightingInitialization (an extension beyond the reference; include/cora_hip.h, "placement from pose-landmark
+ * sightings").  min_ranges, min_sightings <= 0: the defaults.  out: data-matrix-size x rank.  counts = { chains fixed, placed,
+ * not placed, landmarks placed, not placed, stages } of the sighting step; status, cost_start, cost_final, chosen: one entry
+ * per chain of cora_problem_odometry_chains; transforms: d * d + d per chain; landmark_status, landmark_cost: one entry per
+ * landmark.  chain_counts and chain_status: counts and status of cora_problem_multi_robot_initialization for the range
+ * placement of the chains the sightings left (all fixed where it was skipped); landmark_counts and range_landmark_status: as
+ * counts and status of cora_problem_range_aided_initialization, for the landmarks the sightings did not place.  Every array
+ * but out may be NULL. */
+int cora_problem_sighting_initialization(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, int min_sightings, double *out,
+                                         int64_t counts[6], unsigned char *status, double *cost_start, double *cost_final, int32_t *chosen,
+                                         double *transforms, unsigned char *landmark_status, double *landmark_cost, int64_t chain_counts[4],
+                                         unsigned char *chain_status, int64_t landmark_counts[4], unsigned char *range_landmark_status);
 /* compute_Lambda_blocks(Y): stiefel d x dn (ld d), oblique r */
 int cora_problem_lambda_blocks(cora_problem *p, const double *Y, double *stiefel, double *oblique);
 /* Problem::measurementResiduals (an extension beyond the reference; formulas in include/cora_hip.h, "per-measurement
