@@ -1230,6 +1230,66 @@ class Context:
         """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
         return self._sg_call(lambda *a: self.L.cora_place_by_sightings_dev(self.h, C.c_void_p(x_ptr), *a))
 
+    # ---- placement from inter-chain relative-pose edges (include/cora_hip.h, cora_place_by_closures_dev)
+    def set_closure_placement(self, chain_fixed=None, min_closures=1):
+        """Orders the odometry chains into stages from the relative-pose edges between chains: chain_fixed a mask per chain
+        or None (chain 0); min_closures >= 1."""
+        pc = kc = None
+        if chain_fixed is not None:
+            kc = np.ascontiguousarray(np.asarray(chain_fixed).reshape(-1) != 0, dtype=np.uint8)
+            nch = self.odometry_chains_count()[0]
+            if len(kc) != nch:
+                raise CoraError(5, "chain_fixed needs %d entries, not %d" % (nch, len(kc)))
+            kc = np.concatenate([kc, np.zeros(1, dtype=np.uint8)])  # (never an empty buffer)
+            pc = kc.ctypes.data_as(C.c_void_p)
+        self._chk(self.L.cora_set_closure_placement(self.h, pc, int(min_closures)))
+
+    def closure_placement_counts(self):
+        """(stages, closures used, chunks, skipped + unused edges) of the installed tables."""
+        out = (C.c_int64 * 4)()
+        self._chk(self.L.cora_closure_placement_counts(self.h, out))
+        return tuple(int(v) for v in out)
+
+    def closure_placement_order(self):
+        """The stages in order: a list with the chains of each stage, ascending."""
+        ns, _, nc, _ = self.closure_placement_counts()
+        ptr, items = np.zeros(ns + 2, dtype=np.int32), np.zeros(nc + 1, dtype=np.int32)  # (a list has at least one chunk)
+        self._chk(self.L.cora_closure_placement_order(self.h, ptr.ctypes.data_as(_ip), items.ctypes.data_as(_ip)))
+        return [items[ptr[s]:ptr[s + 1]].copy() for s in range(ns)]
+
+    def _cl_call(self, fn):
+        nch, nr, g = self.odometry_chains_count()[0], self.measurement_counts()[1], self.d * self.d + self.d
+        out = (C.c_int64 * 5)()
+        status, chosen = np.zeros(nch + 1, dtype=np.uint8), np.zeros(nch + 1, dtype=np.int32)
+        cs, cf, tr = np.zeros(nch + 1), np.zeros(nch + 1), np.zeros((nch + 1) * g)
+        deg = np.zeros(nr + 1, dtype=np.uint8)
+        self._chk(fn(out, status.ctypes.data_as(C.c_void_p), _d(cs), _d(cf), chosen.ctypes.data_as(_ip), _d(tr), deg.ctypes.data_as(C.c_void_p)))
+        return dict(placed=int(out[0]), not_placed=int(out[1]), n_degenerate=int(out[2]), stages=int(out[3]), refused=int(out[4]),
+                    status=status[:nch], cost_start=cs[:nch], cost_final=cf[:nch], chosen=chosen[:nch],
+                    transforms=tr[:nch * g].reshape(nch, g), degenerate=deg[:nr].astype(bool))
+
+    def _cl_host(self, fn, X):
+        X = np.array(X, dtype=np.float64, order="F", copy=True)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise CoraError(1, "X must have d columns")
+        res = self._cl_call(lambda *a: fn(self.h, _d(X), X.shape[0], *a))
+        res["X"] = X
+        return res
+
+    def place_by_closures(self, X):
+        """The chains of the host matrix X (N x d) placed from the closures, on the device.  Returns dict X (a copy with the
+        chains' and the range rows rewritten), placed, not_placed, n_degenerate, stages, refused, status, cost_start,
+        cost_final, chosen (per chain), transforms (per chain: G row-major, then s), degenerate (bool per range measurement)."""
+        return self._cl_host(self.L.cora_place_by_closures, X)
+
+    def debug_place_by_closures_host(self, X):
+        """The same on the host in the device's bracket order (no GPU needed): X has the device's bits."""
+        return self._cl_host(self.L.cora_debug_place_by_closures_host, X)
+
+    def place_by_closures_dev(self, x_ptr):
+        """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
+        return self._cl_call(lambda *a: self.L.cora_place_by_closures_dev(self.h, C.c_void_p(x_ptr), *a))
+
     # ---- test hook
     def debug_format_spmm_host(self, X):
         X = _f(X)

@@ -23,6 +23,7 @@
 //   multilat.inc        landmark initialisation from ranges: list tables, device-pointer, host-pointer and host-mirror form
 //   placement.inc       chain placement from inter-robot ranges: stage tables, device-pointer, host-pointer and host-mirror form
 //   sighting.inc        placement from pose-landmark sightings: stage and list tables, device-pointer, host-pointer and host-mirror form
+//   closure.inc         placement from inter-chain relative-pose edges: stage and list tables, device-pointer, host-pointer and host-mirror form
 //   comm.inc            native communication: RCCL, in-process and device-side (p2p.h) transports
 #include <hip/hip_runtime.h>
 // RCCL's types and the few enumerators used, declared here (NCCL's public ABI: they have not changed since 2.0): the
@@ -185,6 +186,28 @@ struct SgTables {
   unsigned char *d_deg = nullptr;   // one byte per range measurement
   int32_t *d_range_rows = nullptr;  // [3][n_ranges] internal rows: range | b | a (as MlTables')
 };
+// The tables of cora_set_closure_placement (capi/closure.inc): the order of the stages, decided from structure alone; per
+// stage its lists; per list the chain and its chunks; the entries (edge, direction) in table order, cut into chunks of
+// kClChunk entries; the positions of every stage's chains (ClArgs, kernels.h); the device copies, the chunks' partial sums,
+// the lists' state, the range rows' bytes
+struct ClTables {
+  bool built = false;
+  int min_closures = 0;
+  int64_t skipped = 0, unused = 0;  // non-chain relative-pose edges that are no closure; closures in no list
+  std::vector<int32_t> stage_list0, stage_apply0;              // [stages + 1]
+  std::vector<int32_t> list_item, list_chunk0;                 // [lists] chain, [lists + 1]
+  std::vector<int32_t> chunk_begin, chunk_len, chunk_list;     // [chunks]
+  std::vector<int32_t> ent_e, ent_dir;                         // [entries]
+  std::vector<int32_t> apply_pos, apply_list;                  // [positions of all stages]
+  std::vector<unsigned char> chain_init;  // [chains] 0 taken | 1 never taken | 3 no inter-chain closure | 4 fixed
+  std::vector<int32_t> chain_list;        // [chains]: the list of the chain (-1: none)
+  int32_t *d_idx = nullptr;      // chunk_begin | chunk_len | chunk_list | list_chunk0 | ent_e | ent_dir | apply_pos | apply_list
+  double *d_partial = nullptr;   // [kClSums(d)][chunks]
+  double *d_state = nullptr;     // [lists][kSgState(d)]
+  int32_t *d_istate = nullptr;   // [lists][kSgInts]
+  unsigned char *d_deg = nullptr;   // one byte per range measurement
+  int32_t *d_range_rows = nullptr;  // [3][n_ranges] internal rows: range | b | a (as MlTables')
+};
 struct cora_ctx {
   HostFormat F;
   LongImage LI;  // what the long rows' device arrays hold (long_image.h); derived from F at creation, device handles only
@@ -194,6 +217,7 @@ struct cora_ctx {
   MlTables ml;
   PlTables pl;
   SgTables sg;
+  ClTables cl;
   cora_native_comm *native_comm = nullptr;  // owned: the library's own communication (cora_comm_create_*)
   cora::P2PState *p2p_pending = nullptr;    // a mailbox exported by cora_comm_p2p_handle, not yet connected
   int device = -1;
@@ -698,6 +722,14 @@ void free_sg(cora_ctx *c) {  // (the device must be current where there is one)
   T = SgTables();
 }
 
+void free_cl(cora_ctx *c) {  // (the device must be current where there is one)
+  ClTables &T = c->cl;
+  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state), static_cast<void *>(T.d_istate),
+                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows)})
+    if (p) (void)hipFree(p);
+  T = ClTables();
+}
+
 void free_ml(cora_ctx *c) {  // (the device must be current where there is one)
   MlTables &T = c->ml;
   for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_init), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state),
@@ -712,6 +744,7 @@ void free_measurements(cora_ctx *c) {  // (the device must be current)
   free_ml(c);        // (and the multilateration's lists: their entries name its ranges)
   free_pl(c);        // (and the chain placement's stages)
   free_sg(c);        // (and the sighting placement's lists: their entries name its edges)
+  free_cl(c);        // (and the closure placement's lists: their entries name its edges)
   MeasurementTable &M = c->meas;
   for (void *p : {static_cast<void *>(M.d_edge_rows), static_cast<void *>(M.d_range_rows), static_cast<void *>(M.d_edge_data),
                   static_cast<void *>(M.d_range_data), static_cast<void *>(M.d_out)})
@@ -750,6 +783,7 @@ extern "C" {
 #include "capi/multilat.inc"
 #include "capi/placement.inc"
 #include "capi/sighting.inc"
+#include "capi/closure.inc"
 
 }  // extern "C"
 

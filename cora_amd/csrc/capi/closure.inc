@@ -1,0 +1,443 @@
+// Part of capi.hip (one translation unit; included there, in this order).  placement of odometry chains from inter-chain relative-pose edges (closures; the weighted rigid alignment of a chain onto chains placed before it, rotation and translation residuals together): order of the stages and list tables, device-pointer form, host-pointer form, host mirror.  Reads the measurement table and the chain tables; writes nothing the handle computes with.
+
+namespace {
+
+int cl_check(cora_ctx *c) {
+  if (c->F.L.world > 1) return fail(c, CORA_ERR_ARG, "the closure placement is not supported on partitioned handles");
+  if (!c->meas.set) return fail(c, CORA_ERR_NOT_READY, "no measurement table (cora_set_measurements)");
+  if (!c->odom.built) return fail(c, CORA_ERR_NOT_READY, "no chain tables (cora_set_odometry_chains)");
+  return CORA_OK;
+}
+
+// the order of the stages and their lists, from structure alone (host part of T only)
+int cl_build(cora_ctx *c, const unsigned char *chain_fixed, int min_closures, ClTables &T) {
+  const Layout &L = c->F.L;
+  const MeasurementTable &M = c->meas;
+  const OdomTables &O = c->odom;
+  const int64_t ne = M.n_edges, nch = O.n_chains;
+  if (min_closures < 1) return fail(c, CORA_ERR_ARG, "min_closures must be at least 1");
+  if (ne >= (int64_t(1) << 31)) return fail(c, CORA_ERR_ARG, "the edge table has more entries than a 32-bit index holds");
+  std::vector<unsigned char> placed(static_cast<size_t>(nch), 0);
+  if (chain_fixed) {
+    bool any = false;
+    for (int64_t ch = 0; ch < nch; ++ch) any = (placed[static_cast<size_t>(ch)] = chain_fixed[ch] ? 1 : 0) || any;
+    if (!any) return fail(c, CORA_ERR_ARG, "chain_fixed fixes no chain");
+  } else if (nch > 0) {
+    placed[0] = 1;
+  } else {
+    return fail(c, CORA_ERR_ARG, "no chain to fix: the chain tables hold no chain");
+  }
+  const std::vector<unsigned char> fixed = placed;
+  std::vector<int32_t> chain_of(static_cast<size_t>(L.rows), -1);
+  std::vector<std::vector<int32_t>> chain_pos(static_cast<size_t>(nch));
+  std::vector<unsigned char> chain_edge(static_cast<size_t>(ne), 0);
+  for (int64_t pos = 0; pos < O.P; ++pos) {
+    const int32_t ch = O.pos_chain[static_cast<size_t>(pos)], e = O.pos_edge[static_cast<size_t>(pos)];
+    chain_of[static_cast<size_t>(O.pos_trn[static_cast<size_t>(pos)])] = ch;
+    chain_pos[static_cast<size_t>(ch)].push_back(static_cast<int32_t>(pos));
+    if (e >= 0) chain_edge[static_cast<size_t>(e)] = 1;
+  }
+  // the closures in table order: edge, chain of a, chain of b   (edge_rows: [ra | rb | ta | tb][edge])
+  std::vector<int32_t> c_e, c_a, c_b;
+  for (int64_t e = 0; e < ne; ++e) {
+    if (M.edge_rows[static_cast<size_t>(ne + e)] < 0 || chain_edge[static_cast<size_t>(e)]) continue;  // a sighting, an edge of a chain
+    const int32_t ca = chain_of[static_cast<size_t>(M.edge_rows[static_cast<size_t>(2 * ne + e)])];
+    const int32_t cb = chain_of[static_cast<size_t>(M.edge_rows[static_cast<size_t>(3 * ne + e)])];
+    if (ca < 0 || cb < 0 || ca == cb) {
+      ++T.skipped;
+      continue;
+    }
+    c_e.push_back(static_cast<int32_t>(e));
+    c_a.push_back(ca);
+    c_b.push_back(cb);
+  }
+  const size_t ncl = c_e.size();
+  T.min_closures = min_closures;
+  T.stage_list0.assign(1, 0);
+  T.stage_apply0.assign(1, 0);
+  T.list_chunk0.assign(1, 0);
+  T.chain_list.assign(static_cast<size_t>(nch), -1);
+  for (;;) {
+    // EVERY unplaced chain with min_closures closures against chains placed before this stage, in ONE stage
+    std::vector<std::vector<size_t>> members(static_cast<size_t>(nch));
+    for (size_t u = 0; u < ncl; ++u) {
+      const size_t a = static_cast<size_t>(c_a[u]), b = static_cast<size_t>(c_b[u]);
+      if (placed[a] && !placed[b]) members[b].push_back(u);
+      else if (placed[b] && !placed[a]) members[a].push_back(u);
+    }
+    std::vector<int32_t> chains;
+    for (int64_t ch = 0; ch < nch; ++ch) {
+      const std::vector<size_t> &mb = members[static_cast<size_t>(ch)];
+      if (mb.empty() || static_cast<int64_t>(mb.size()) < min_closures) continue;
+      const int32_t list = static_cast<int32_t>(T.list_item.size());
+      T.chain_list[static_cast<size_t>(ch)] = list;
+      for (const int32_t pos : chain_pos[static_cast<size_t>(ch)]) {
+        T.apply_pos.push_back(pos);
+        T.apply_list.push_back(list);
+      }
+      const size_t begin = T.ent_e.size();
+      for (const size_t u : mb) {
+        T.ent_e.push_back(c_e[u]);
+        T.ent_dir.push_back(c_a[u] == ch ? 1 : 0);
+      }
+      const int64_t len = static_cast<int64_t>(mb.size());
+      for (int64_t at = 0; at < len; at += kClChunk) {
+        T.chunk_begin.push_back(static_cast<int32_t>(static_cast<int64_t>(begin) + at));
+        T.chunk_len.push_back(static_cast<int32_t>(std::min<int64_t>(kClChunk, len - at)));
+        T.chunk_list.push_back(list);
+      }
+      T.list_item.push_back(static_cast<int32_t>(ch));
+      T.list_chunk0.push_back(static_cast<int32_t>(T.chunk_begin.size()));
+      chains.push_back(static_cast<int32_t>(ch));
+    }
+    if (chains.empty()) break;
+    T.stage_list0.push_back(static_cast<int32_t>(T.list_item.size()));
+    T.stage_apply0.push_back(static_cast<int32_t>(T.apply_pos.size()));
+    for (const int32_t ch : chains) placed[static_cast<size_t>(ch)] = 1;
+  }
+  T.unused = static_cast<int64_t>(ncl) - static_cast<int64_t>(T.ent_e.size());
+  std::vector<unsigned char> has(static_cast<size_t>(nch), 0);
+  for (size_t u = 0; u < ncl; ++u) has[static_cast<size_t>(c_a[u])] = has[static_cast<size_t>(c_b[u])] = 1;
+  T.chain_init.assign(static_cast<size_t>(nch), 0);
+  for (int64_t ch = 0; ch < nch; ++ch) {
+    const size_t i = static_cast<size_t>(ch);
+    T.chain_init[i] = fixed[i] ? 4 : (T.chain_list[i] >= 0 ? 0 : (has[i] ? 1 : 3));
+  }
+  if (T.ent_e.size() >= (size_t(1) << 31)) return fail(c, CORA_ERR_ARG, "the lists have more entries than a 32-bit index holds");
+  // (a range row two measurements name would be written by two threads of the range-row step)
+  const int64_t nr = M.n_ranges;
+  std::vector<unsigned char> written(static_cast<size_t>(L.rows), 0);
+  for (int64_t m = 0; m < nr; ++m) {
+    unsigned char &w = written[static_cast<size_t>(M.range_rows[static_cast<size_t>(m)])];
+    if (w) return fail(c, CORA_ERR_ARG, "range measurement " + std::to_string(m) + " names a range row an earlier one names");
+    w = 1;
+  }
+  T.built = true;
+  return CORA_OK;
+}
+
+// the device side of freshly built tables (T's device pointers are null); on failure T owns what was allocated
+int cl_upload(cora_ctx *c, ClTables &T) {
+  std::vector<int32_t> idx;
+  for (const std::vector<int32_t> *v : {&T.chunk_begin, &T.chunk_len, &T.chunk_list, &T.list_chunk0, &T.ent_e, &T.ent_dir, &T.apply_pos, &T.apply_list})
+    idx.insert(idx.end(), v->begin(), v->end());
+  idx.push_back(0);  // (never an empty buffer)
+  HIP_TRY(c, to_device(&T.d_idx, idx));
+  const int d = c->F.L.d;
+  const size_t nlist = std::max<size_t>(T.list_item.size(), 1), nc = std::max<size_t>(T.chunk_begin.size(), 1);
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_partial), static_cast<size_t>(kClSums(d)) * nc * sizeof(double)));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_state), static_cast<size_t>(kSgState(d)) * nlist * sizeof(double)));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_istate), static_cast<size_t>(kSgInts) * nlist * sizeof(int32_t)));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_deg), std::max<size_t>(static_cast<size_t>(c->meas.n_ranges), 1)));
+  // the range-row step over the table with a and b exchanged: the direction of least residual (ml_upload)
+  const size_t nr = static_cast<size_t>(c->meas.n_ranges);
+  std::vector<int32_t> rows(c->meas.range_rows);
+  std::swap_ranges(rows.begin() + static_cast<std::ptrdiff_t>(nr), rows.begin() + static_cast<std::ptrdiff_t>(2 * nr), rows.begin() + static_cast<std::ptrdiff_t>(2 * nr));
+  rows.push_back(0);
+  HIP_TRY(c, to_device(&T.d_range_rows, rows));
+  return CORA_OK;
+}
+
+void cl_release(ClTables &T) {  // a table that never reached the handle
+  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state), static_cast<void *>(T.d_istate),
+                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows)})
+    if (p) (void)hipFree(p);
+}
+
+int cl_args_check(cora_ctx *c, const double *X, const int64_t *out) {
+  if (!c->cl.built) return fail(c, CORA_ERR_NOT_READY, "no closure tables (cora_set_closure_placement)");
+  if (!X || !out) return fail(c, CORA_ERR_ARG, "null pointer");
+  return CORA_OK;
+}
+
+// what a call returns, from the lists' state ([lists][kSgState(d)], [lists][kSgInts])
+void cl_results(const cora_ctx *c, const std::vector<double> &state, const std::vector<int32_t> &ist, int64_t n_deg, int64_t out[5],
+                unsigned char *status, double *cost_start, double *cost_final, int32_t *chosen, double *transforms) {
+  const int d = c->F.L.d, G = kSgG(d), NS = kSgState(d);
+  const ClTables &T = c->cl;
+  const size_t nch = T.chain_init.size();
+  for (int i = 0; i < 5; ++i) out[i] = 0;
+  for (size_t ch = 0; ch < nch; ++ch) {
+    const int32_t list = T.chain_list[ch];
+    const int32_t *li = list >= 0 ? ist.data() + static_cast<size_t>(list) * kSgInts : nullptr;
+    const double *st = list >= 0 ? state.data() + static_cast<size_t>(list) * NS : nullptr;
+    const int s = li ? li[0] : T.chain_init[ch];
+    out[0] += s == 0 ? 1 : 0;
+    out[1] += s == 1 || s == 2 || s == 3 ? 1 : 0;
+    out[4] += s == 2 ? 1 : 0;
+    if (status) status[ch] = static_cast<unsigned char>(s);
+    if (cost_start) cost_start[ch] = st ? st[G + d] : 0.0;
+    if (cost_final) cost_final[ch] = st ? st[G + d + 1] : 0.0;
+    if (chosen) chosen[ch] = li ? li[1] : -1;
+    if (transforms)
+      for (int i = 0; i < G; ++i) transforms[ch * G + i] = li && li[1] > 0 ? st[i] : (i < d * d && i / d == i % d ? 1.0 : 0.0);
+  }
+  out[2] = n_deg;
+  out[3] = static_cast<int64_t>(T.stage_list0.size()) - 1;
+}
+
+extern "C++" {  // (templates: this file is included inside extern "C")
+template <int D>
+void cl_host_entry(const cora_ctx *c, const double *oi, size_t e, double *P, double *q, double *l, double *res, double *kt) {
+  constexpr int NF = D * D + D + 2;
+  const ClTables &T = c->cl;
+  const MeasurementTable &M = c->meas;
+  const size_t ne = static_cast<size_t>(M.n_edges), m = static_cast<size_t>(T.ent_e[e]);
+  double f[NF];
+  for (int i = 0; i < NF; ++i) f[i] = M.edge_data[static_cast<size_t>(i) * ne + m];
+  cl_entry<D>(oi + static_cast<size_t>(M.edge_rows[m]) * D, oi + static_cast<size_t>(M.edge_rows[2 * ne + m]) * D,
+              oi + static_cast<size_t>(M.edge_rows[ne + m]) * D, oi + static_cast<size_t>(M.edge_rows[3 * ne + m]) * D, f, T.ent_dir[e], P, q, l, res);
+  kt[0] = f[D * D + D];
+  kt[1] = f[D * D + D + 1];
+}
+// pass and fold of one mode over one stage, in the kernels' order
+template <int D, int MODE>
+bool cl_host_pass_fold(const cora_ctx *c, size_t s, const double *oi, std::vector<double> &partial, std::vector<double> &state, std::vector<int32_t> &ist) {
+  constexpr int NS = MODE == 0 ? kClSums(D) : kClCostSums;
+  const ClTables &T = c->cl;
+  const size_t nc = std::max<size_t>(T.chunk_begin.size(), 1);
+  const size_t l0 = static_cast<size_t>(T.stage_list0[s]), l1 = static_cast<size_t>(T.stage_list0[s + 1]);
+  bool finite = true;
+  double P0[D * D], q0[D], lm0[D], res0, kt0[2];
+  for (size_t ch = static_cast<size_t>(T.list_chunk0[l0]); ch < static_cast<size_t>(T.list_chunk0[l1]); ++ch) {
+    const size_t list = static_cast<size_t>(T.chunk_list[ch]);
+    cl_host_entry<D>(c, oi, static_cast<size_t>(T.chunk_begin[static_cast<size_t>(T.list_chunk0[list])]), P0, q0, lm0, &res0, kt0);
+    double wave[kClChunk / kWave][NS];
+    for (int w = 0; w < kClChunk / kWave; ++w) {
+      double term[kWave][NS];
+      for (int lane = 0; lane < kWave; ++lane) {
+        const int i = w * kWave + lane;
+        for (int k = 0; k < NS; ++k) term[lane][k] = 0.0;
+        if (i >= T.chunk_len[ch]) continue;
+        double P[D * D], q[D], l[D], res, kt[2];
+        cl_host_entry<D>(c, oi, static_cast<size_t>(T.chunk_begin[ch]) + i, P, q, l, &res, kt);
+        if constexpr (MODE == 0) {
+          cl_terms<D>(q0, lm0, P, q, l, kt[0], kt[1], term[lane]);
+        } else {
+          term[lane][0] = res;
+          term[lane][1] = cl_cost_at<D>(state.data() + list * kSgState(D), q0, lm0, P, q, l, kt[0], kt[1]);
+        }
+      }
+      for (int k = 0; k < NS; ++k) {
+        double v[kWave];
+        for (int lane = 0; lane < kWave; ++lane) v[lane] = term[lane][k];
+        wave[w][k] = ml_host_wave_sum(v);
+      }
+    }
+    for (int k = 0; k < NS; ++k) {
+      double v = wave[0][k];
+      for (int w = 1; w < kClChunk / kWave; ++w) v = v + wave[w][k];
+      partial[static_cast<size_t>(k) * nc + ch] = v;
+    }
+  }
+  for (size_t list = l0; list < l1; ++list) {
+    double S[NS];
+    for (int k = 0; k < NS; ++k) {
+      double v[kWave];
+      for (int lane = 0; lane < kWave; ++lane) {
+        v[lane] = 0.0;
+        for (int64_t ch = static_cast<int64_t>(T.list_chunk0[list]) + lane; ch < T.list_chunk0[list + 1]; ch += kWave)
+          v[lane] = v[lane] + partial[static_cast<size_t>(k) * nc + static_cast<size_t>(ch)];
+      }
+      S[k] = ml_host_wave_sum(v);
+    }
+    cl_host_entry<D>(c, oi, static_cast<size_t>(T.chunk_begin[static_cast<size_t>(T.list_chunk0[list])]), P0, q0, lm0, &res0, kt0);
+    finite = cl_fold<D, MODE>(S, state.data() + list * kSgState(D), ist.data() + list * kSgInts, q0, lm0) && finite;
+  }
+  return finite;
+}
+// the whole placement on the host, in the kernels' order: oi a d-column resident vector; state and ist as on the device
+template <int D>
+bool cl_host_run(const cora_ctx *c, double *oi, std::vector<double> &state, std::vector<int32_t> &ist, unsigned char *deg, int64_t *n_deg) {
+  const ClTables &T = c->cl;
+  const OdomTables &O = c->odom;
+  const MeasurementTable &M = c->meas;
+  const int64_t nr = M.n_ranges;
+  bool finite = true;
+  std::vector<double> partial(static_cast<size_t>(kClSums(D)) * std::max<size_t>(T.chunk_begin.size(), 1), 0.0);
+  for (size_t s = 0; s + 1 < T.stage_list0.size(); ++s) {
+    finite = cl_host_pass_fold<D, 0>(c, s, oi, partial, state, ist) && finite;
+    finite = cl_host_pass_fold<D, 1>(c, s, oi, partial, state, ist) && finite;
+    for (int32_t i = T.stage_apply0[s]; i < T.stage_apply0[s + 1]; ++i) {
+      const size_t list = static_cast<size_t>(T.apply_list[static_cast<size_t>(i)]), pos = static_cast<size_t>(T.apply_pos[static_cast<size_t>(i)]);
+      if (ist[list * kSgInts + 1] <= 0) continue;
+      pl_apply<D>(state.data() + list * kSgState(D), oi + static_cast<size_t>(O.pos_rot[pos]) * D, oi + static_cast<size_t>(O.pos_trn[pos]) * D);
+    }
+  }
+  int64_t count = 0;
+  for (int64_t m = 0; m < nr; ++m) {
+    const size_t rr = static_cast<size_t>(M.range_rows[static_cast<size_t>(m)]), ta = static_cast<size_t>(M.range_rows[static_cast<size_t>(nr + m)]),
+                 tb = static_cast<size_t>(M.range_rows[static_cast<size_t>(2 * nr + m)]);
+    double row[D];
+    const bool degenerate = odom_range_row<D>(oi + tb * D, oi + ta * D, row);  // (towards a: see ml_upload)
+    std::copy(row, row + D, oi + rr * D);
+    if (deg) deg[m] = degenerate ? 1 : 0;
+    count += degenerate ? 1 : 0;
+    finite = odom_finite(row, D) && finite;
+  }
+  *n_deg = count;
+  return finite;
+}
+}  // extern "C++"
+
+}  // namespace
+
+int cora_set_closure_placement(cora_ctx *c, const unsigned char *chain_fixed, int min_closures) {
+  if (!c) return CORA_ERR_ARG;
+  int rc = cl_check(c);
+  if (rc) return rc;
+  ClTables T;
+  if ((rc = cl_build(c, chain_fixed, min_closures, T))) return rc;
+  if (c->has_device) {
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, CORA_ERR_HIP, "hipSetDevice failed");
+    if ((rc = cl_upload(c, T))) {
+      cl_release(T);
+      return rc;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    free_cl(c);
+  }
+  c->cl = std::move(T);
+  return CORA_OK;
+}
+
+int cora_closure_placement_counts(const cora_ctx *c, int64_t out[4]) {
+  if (!c || !out) return CORA_ERR_ARG;
+  out[0] = c->cl.stage_list0.empty() ? 0 : static_cast<int64_t>(c->cl.stage_list0.size()) - 1;
+  out[1] = static_cast<int64_t>(c->cl.ent_e.size());
+  out[2] = static_cast<int64_t>(c->cl.chunk_begin.size());
+  out[3] = c->cl.skipped + c->cl.unused;
+  return CORA_OK;
+}
+
+int cora_closure_placement_order(const cora_ctx *c, int32_t *stage_ptr, int32_t *items) {
+  if (!c || !stage_ptr || !items) return CORA_ERR_ARG;
+  const ClTables &T = c->cl;
+  std::copy(T.stage_list0.begin(), T.stage_list0.end(), stage_ptr);
+  if (T.stage_list0.empty()) stage_ptr[0] = 0;
+  std::copy(T.list_item.begin(), T.list_item.end(), items);
+  return CORA_OK;
+}
+
+int cora_place_by_closures_dev(cora_ctx *c, double *dX, int64_t out[5], unsigned char *status, double *cost_start, double *cost_final,
+                               int32_t *chosen, double *transforms, unsigned char *degenerate) {
+  if (!c) return CORA_ERR_ARG;
+  int rc = cl_check(c);
+  if (rc) return rc;
+  NEED_DEVICE(c);
+  if ((rc = cl_args_check(c, dX, out))) return rc;
+  const Layout &L = c->F.L;
+  const MeasurementTable &M = c->meas;
+  ClTables &T = c->cl;
+  const OdomTables &O = c->odom;
+  const int d = L.d, nb = odom_range_blocks(M.n_ranges);
+  const size_t ns = T.stage_list0.size() - 1, nc = T.chunk_begin.size(), ne = T.ent_e.size(), nlist = T.list_item.size(), na = T.apply_pos.size();
+  if ((rc = ensure_red(c, static_cast<size_t>(nb) / 2 + 4))) return rc;
+  ClArgs A;
+  A.d = d;
+  A.n_edges = M.n_edges;
+  A.pstride = static_cast<int64_t>(std::max<size_t>(nc, 1));
+  A.chunk_begin = T.d_idx;
+  A.chunk_len = A.chunk_begin + nc;
+  A.chunk_list = A.chunk_len + nc;
+  A.list_chunk0 = A.chunk_list + nc;
+  A.ent_e = A.list_chunk0 + nlist + 1;
+  A.ent_dir = A.ent_e + ne;
+  A.apply_pos = A.ent_dir + ne;
+  A.apply_list = A.apply_pos + na;
+  A.pos_rot = O.d_idx + 2 * O.P;
+  A.pos_trn = O.d_idx + 3 * O.P;
+  A.edge_rows = M.d_edge_rows;
+  A.edge_data = M.d_edge_data;
+  A.partial = T.d_partial;
+  A.state = T.d_state;
+  A.istate = T.d_istate;
+  A.x = dX;
+  A.flag = c->d_flag;
+  OdomFillArgs Fl;  // the range-row step of the odometry initialisation, its rules unchanged, over the exchanged table
+  Fl.d = d;
+  Fl.n_ranges = M.n_ranges;
+  Fl.range_rows = T.d_range_rows;
+  Fl.deg = T.d_deg;
+  Fl.partial = reinterpret_cast<int *>(c->d_red);
+  Fl.words = Fl.partial + nb;
+  Fl.flag = c->d_flag;
+  Fl.out = dX;
+  wrote(c, dX);
+  HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
+  for (size_t s = 0; s < ns; ++s) {  // dependent: a stage reads the rows the stages before it wrote
+    A.list0 = T.stage_list0[s];
+    A.n_lists = T.stage_list0[s + 1] - A.list0;
+    A.chunk0 = T.list_chunk0[static_cast<size_t>(A.list0)];
+    A.n_chunks = T.list_chunk0[static_cast<size_t>(T.stage_list0[s + 1])] - A.chunk0;
+    A.apply0 = T.stage_apply0[s];
+    A.n_apply = T.stage_apply0[s + 1] - A.apply0;
+    A.mode = 0;
+    HIP_TRY(c, launch_closure_pass_fold(A, c->stream));
+    A.mode = 1;
+    HIP_TRY(c, launch_closure_pass_fold(A, c->stream));
+    HIP_TRY(c, launch_closure_apply(A, c->stream));
+  }
+  HIP_TRY(c, launch_odom_ranges(Fl, c->stream));  // (after the chains' rows)
+  int words[2] = {0, 0};
+  std::vector<double> state(nlist * kSgState(d));
+  std::vector<int32_t> ist(nlist * kSgInts);
+  HIP_TRY(c, hipMemcpyAsync(words, Fl.words, sizeof(words), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->h_flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (nlist > 0) {
+    HIP_TRY(c, hipMemcpyAsync(state.data(), T.d_state, state.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(ist.data(), T.d_istate, ist.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (degenerate && M.n_ranges > 0)
+    HIP_TRY(c, hipMemcpyAsync(degenerate, T.d_deg, static_cast<size_t>(M.n_ranges), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (*c->h_flag) return fail(c, CORA_ERR_NAN, "a sum of the closure placement is not finite");
+  cl_results(c, state, ist, words[0], out, status, cost_start, cost_final, chosen, transforms);
+  return CORA_OK;
+}
+
+int cora_place_by_closures(cora_ctx *c, double *X, int ldx, int64_t out[5], unsigned char *status, double *cost_start, double *cost_final,
+                           int32_t *chosen, double *transforms, unsigned char *degenerate) {
+  if (!c) return CORA_ERR_ARG;
+  int rc = cl_check(c);
+  if (rc) return rc;
+  NEED_DEVICE(c);
+  if ((rc = cl_args_check(c, X, out))) return rc;
+  if (ldx < c->F.L.N) return fail(c, CORA_ERR_SHAPE, "leading dimension smaller than N");
+  const int d = c->F.L.d;
+  double *dX;
+  if ((rc = compare_vec(c, 3, ld_for(d), &dX))) return rc;
+  rc = upload_impl(c, X, ldx, d, dX);
+  if (rc == CORA_OK) rc = cora_place_by_closures_dev(c, dX, out, status, cost_start, cost_final, chosen, transforms, degenerate);
+  if (rc == CORA_OK) rc = download_impl(c, dX, d, X, ldx);
+  // the vector of this form is not kept: a caller that stays resident uses cora_place_by_closures_dev
+  (void)hipStreamSynchronize(c->stream);
+  compare_release(c, 3, 4, 0);
+  return rc;
+}
+
+// The same on the host through the translated tables, every sum in the kernels' bracket order and every term and solve
+// through the functions of kernels.h the kernels call: the output has the device's bits.  Works on a plan-only handle.
+int cora_debug_place_by_closures_host(cora_ctx *c, double *X, int ldx, int64_t out[5], unsigned char *status, double *cost_start,
+                                      double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate) {
+  if (!c) return CORA_ERR_ARG;
+  int rc = cl_check(c);
+  if (rc) return rc;
+  if ((rc = cl_args_check(c, X, out))) return rc;
+  const HostFormat &F = c->F;
+  const Layout &L = F.L;
+  if (ldx < L.N) return fail(c, CORA_ERR_SHAPE, "leading dimension smaller than N");
+  const int d = L.d;
+  const size_t nlist = c->cl.list_item.size();
+  std::vector<double> oi(static_cast<size_t>(L.rows) * d, 0.0), state(nlist * kSgState(d), 0.0);
+  std::vector<int32_t> ist(nlist * kSgInts, 0);
+  for (int cc = 0; cc < d; ++cc)
+    for (int64_t i = 0; i < L.N; ++i) oi[static_cast<size_t>(F.api2int[i]) * d + cc] = X[static_cast<size_t>(cc) * ldx + i];
+  int64_t n_deg = 0;
+  const bool finite = d == 2 ? cl_host_run<2>(c, oi.data(), state, ist, degenerate, &n_deg) : cl_host_run<3>(c, oi.data(), state, ist, degenerate, &n_deg);
+  if (!finite) return fail(c, CORA_ERR_NAN, "a sum of the closure placement is not finite");
+  for (int cc = 0; cc < d; ++cc)
+    for (int64_t i = 0; i < L.N; ++i) X[static_cast<size_t>(cc) * ldx + i] = oi[static_cast<size_t>(F.api2int[i]) * d + cc];
+  cl_results(c, state, ist, n_deg, out, status, cost_start, cost_final, chosen, transforms);
+  return CORA_OK;
+}

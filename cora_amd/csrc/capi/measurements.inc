@@ -80,6 +80,7 @@ int cora_set_measurements(cora_ctx *c, int64_t n_edges, const int32_t *edge_rows
     c->ml = MlTables();      // (and the multilateration's lists)
     c->pl = PlTables();      // (and the chain placement's stages)
     c->sg = SgTables();      // (and the sighting placement's lists)
+    c->cl = ClTables();      // (and the closure placement's lists)
     c->meas = std::move(T);
     c->meas.set = true;
   }

@@ -111,6 +111,7 @@ int odom_install(cora_ctx *c, int64_t n_chains, const int64_t *chain_ptr, const 
   }
   free_pl(c);  // (the chain placement's stages name the positions of the chains they were built from)
   free_sg(c);  // (so do the sighting placement's lists)
+  free_cl(c);  // (and the closure placement's)
   c->odom = std::move(T);
   return CORA_OK;
 }

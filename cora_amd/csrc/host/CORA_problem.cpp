@@ -1187,11 +1187,21 @@ Matrix Problem::sightingInitialization(uint64_t seed, int gn_steps, int min_rang
   return odometryStart(seed, gn_steps, info, "Problem::sightingInitialization", true, min_ranges, chains_info, true, min_sightings, sight_info);
 }
 
+Matrix Problem::closureInitialization(uint64_t seed, int gn_steps, int min_ranges, int min_sightings, int min_closures,
+                                      ClosurePlacementInfo *closure_info, SightingPlacementInfo *sight_info, ChainPlacementInfo *chains_info,
+                                      LandmarkInitInfo *info) const {
+  if (gn_steps < 0) throw std::invalid_argument("Problem::closureInitialization: gn_steps must be in [0, 16]");
+  return odometryStart(seed, gn_steps, info, "Problem::closureInitialization", true, min_ranges, chains_info, true, min_sightings, sight_info, true,
+                       min_closures, closure_info);
+}
+
 // the odometry start; with gn_steps >= 0 the landmarks are then placed from the ranges (cora_multilaterate_dev), with
 // `place` after the chains were (cora_place_chains_dev), with `sightings` after landmarks and chains were placed from the
-// pose-landmark sightings (cora_place_by_sightings_dev)
+// pose-landmark sightings (cora_place_by_sightings_dev), with `closures` after the chains were placed from the relative-pose
+// edges between chains (cora_place_by_closures_dev)
 Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where, bool place, int min_ranges,
-                              ChainPlacementInfo *chains_info, bool sightings, int min_sightings, SightingPlacementInfo *sight_info) const {
+                              ChainPlacementInfo *chains_info, bool sightings, int min_sightings, SightingPlacementInfo *sight_info, bool closures,
+                              int min_closures, ClosurePlacementInfo *closure_info) const {
   checkUpToDate();
   if (part_world_ > 1) throw std::runtime_error(std::string(where) + ": not supported on a partitioned handle");
   ensureMeasurementTable();
@@ -1249,12 +1259,47 @@ Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *inf
   if (gn_steps < 0 && !idx.empty())
     CORA_CALL(cora_odometry_set_range_rows_dev(c, static_cast<int64_t>(idx.size()), idx.data(), dirs.data(), v.x), where);
   const Matrix Qm = odom_draws::drawRotation(g, U, p);
+  // per chain: fixed or placed by the closure step (the fixed chains of the sighting placement; empty: chain 0 alone)
+  std::vector<unsigned char> closure_done;
+  if (closures && gn_steps >= 0 && !chains.empty()) {
+    // (after every draw of odometryInitialization: the step draws nothing.  Without an inter-chain closure it has no stage,
+    // moves nothing and fixes chain 0 alone, the sighting placement's default; its range rows are written again below.)
+    const size_t nch = chains.size(), G = static_cast<size_t>(d) * d + d;
+    CORA_CALL(cora_set_closure_placement(c, nullptr, min_closures > 0 ? min_closures : 1), where);
+    int64_t out[5] = {0, 0, 0, 0, 0}, tc[4] = {0, 0, 0, 0};
+    std::vector<unsigned char> status(nch + 1, 0);
+    std::vector<int32_t> chosen(nch + 1, 0);
+    std::vector<double> cs(nch + 1, 0.0), cf(nch + 1, 0.0), tr(nch * G + 1, 0.0);
+    CORA_CALL(cora_closure_placement_counts(c, tc), where);
+    CORA_CALL(cora_place_by_closures_dev(c, v.x, out, status.data(), cs.data(), cf.data(), chosen.data(), tr.data(), nullptr), where);
+    closure_done.assign(nch + 1, 0);
+    long fixed = 0;
+    for (size_t ch = 0; ch < nch; ++ch) {
+      closure_done[ch] = status[ch] == 0 || status[ch] == 4 ? 1 : 0;
+      fixed += status[ch] == 4 ? 1 : 0;
+    }
+    if (closure_info) {
+      closure_info->chains_fixed = fixed;
+      closure_info->chains_placed = static_cast<long>(out[0]);
+      closure_info->chains_not_placed = static_cast<long>(out[1]);
+      closure_info->chains_refused = static_cast<long>(out[4]);
+      closure_info->stages = static_cast<long>(out[3]);
+      closure_info->closures_used = static_cast<long>(tc[1]);
+      closure_info->edges_skipped = static_cast<long>(tc[3]);
+      closure_info->status.assign(status.begin(), status.begin() + static_cast<std::ptrdiff_t>(nch));
+      closure_info->cost_start.assign(cs.begin(), cs.begin() + static_cast<std::ptrdiff_t>(nch));
+      closure_info->cost_final.assign(cf.begin(), cf.begin() + static_cast<std::ptrdiff_t>(nch));
+      closure_info->chosen.assign(chosen.begin(), chosen.begin() + static_cast<std::ptrdiff_t>(nch));
+      closure_info->transforms.assign(tr.begin(), tr.begin() + static_cast<std::ptrdiff_t>(nch * G));
+    }
+  }
   // per chain: fixed or placed by the sighting step (the fixed chains of the range placement); per landmark: placed by it
   std::vector<unsigned char> chain_done, lm_done(static_cast<size_t>(nl) + 1, 0);
   if (sightings && gn_steps >= 0 && !chains.empty()) {
     // (after every draw of odometryInitialization: the step draws nothing)
     const size_t nch = chains.size(), G = static_cast<size_t>(d) * d + d;
-    CORA_CALL(cora_set_sighting_placement(c, nullptr, nullptr, min_sightings > 0 ? min_sightings : 4 * d), where);
+    CORA_CALL(cora_set_sighting_placement(c, closure_done.empty() ? nullptr : closure_done.data(), nullptr, min_sightings > 0 ? min_sightings : 4 * d),
+              where);
     int64_t out[6] = {0, 0, 0, 0, 0, 0};
     std::vector<unsigned char> status(nch + 1, 0), ls(static_cast<size_t>(nl) + 1, 0);
     std::vector<int32_t> chosen(nch + 1, 0);

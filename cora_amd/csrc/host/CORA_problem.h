@@ -186,6 +186,16 @@ struct SightingPlacementInfo {
   std::vector<Scalar> landmark_cost;   // per landmark: the sighting cost of its REFIT list at the row written
 };
 
+/** What Problem::closureInitialization reports about the closure step (cora_place_by_closures_dev, include/cora_hip.h). */
+struct ClosurePlacementInfo {
+  long chains_fixed = 0, chains_placed = 0, chains_not_placed = 0, chains_refused = 0;  // status 4 | 0 | 1, 2, 3 | 2
+  long stages = 0, closures_used = 0, edges_skipped = 0;  // entries of all lists; skipped + unused edges
+  std::vector<unsigned char> status;   // per chain (0 placed, 1 never taken, 2 refused by the device, 3 no inter-chain closure, 4 fixed)
+  std::vector<Scalar> cost_start, cost_final;  // per chain: the closure cost of its list, before and as applied
+  std::vector<int32_t> chosen;         // per chain: 1 moved, 0 left where it stood, -1 no list
+  std::vector<Scalar> transforms;      // per chain d * d + d: G row-major, then s, as applied
+};
+
 class Problem {
  private:
   int dim_;
@@ -267,10 +277,12 @@ class Problem {
   void ensurePreconditioner() const;
   void ensureMeasurementTable() const;
   // gn_steps < 0: no multilateration; place: the chains are first placed from the ranges between them (min_ranges <= 0: the default)
+  // closures: first of all, the chains are placed from the relative-pose edges between chains (min_closures <= 0: 1)
   // sightings: before that, landmarks and chains are placed from the pose-landmark sightings (min_sightings <= 0: the default)
   Matrix odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where, bool place = false, int min_ranges = 0,
                        ChainPlacementInfo *chains_info = nullptr, bool sightings = false, int min_sightings = 0,
-                       SightingPlacementInfo *sight_info = nullptr) const;
+                       SightingPlacementInfo *sight_info = nullptr, bool closures = false, int min_closures = 0,
+                       ClosurePlacementInfo *closure_info = nullptr) const;
   void fillImplicitFormulationMatrices() const;
   [[noreturn]] void throwLast(int status, const char *where) const;
 
@@ -505,6 +517,15 @@ class Problem {
   Matrix sightingInitialization(uint64_t seed = 7, int gn_steps = 5, int min_ranges = 0, int min_sightings = 0,
                                 SightingPlacementInfo *sight_info = nullptr, ChainPlacementInfo *chains_info = nullptr,
                                 LandmarkInitInfo *info = nullptr) const;
+  /** EXTENSION beyond the reference: sightingInitialization with the chains first placed from the relative-pose edges
+   * BETWEEN chains (cora_place_by_closures_dev), chain 0 fixed: exactly the draws of odometryInitialization in the same
+   * order (the new step draws nothing), then the closure placement, then the sighting placement with every chain of
+   * closure status 0 or 4 as its fixed set, then cora_place_chains_dev for the chains still left, the multilateration, the
+   * range rows and the lift: one pipeline (odometryStart) with one more step.  On a problem without inter-chain closures
+   * the result has sightingInitialization's bits.  min_closures <= 0: 1.  std::runtime_error on a partitioned handle. */
+  Matrix closureInitialization(uint64_t seed = 7, int gn_steps = 5, int min_ranges = 0, int min_sightings = 0, int min_closures = 0,
+                               ClosurePlacementInfo *closure_info = nullptr, SightingPlacementInfo *sight_info = nullptr,
+                               ChainPlacementInfo *chains_info = nullptr, LandmarkInitInfo *info = nullptr) const;
 
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;

@@ -254,6 +254,7 @@ int cora_problem_op(cora_problem *p, const char *op, int cols, const double *A, 
     else if (o == "rangeAidedInitialization") res = q.rangeAidedInitialization();
     else if (o == "multiRobotInitialization") res = q.multiRobotInitialization();
     else if (o == "sightingInitialization") res = q.sightingInitialization();
+    else if (o == "closureInitialization") res = q.closureInitialization();
     else if (o == "getTranslationExplicitSolution") res = q.getTranslationExplicitSolution(wrap(A, N, r));
     else if (o == "alignEstimateToOrigin") res = q.alignEstimateToOrigin(wrap(A, N, r));
     else throw std::invalid_argument("unknown operator " + o);
@@ -361,6 +362,60 @@ int cora_problem_sighting_initialization(cora_problem *p, uint64_t seed, int gn_
     if (transforms) std::copy(si.transforms.begin(), si.transforms.end(), transforms);
     if (landmark_status) std::copy(si.landmark_status.begin(), si.landmark_status.end(), landmark_status);
     if (landmark_cost) std::copy(si.landmark_cost.begin(), si.landmark_cost.end(), landmark_cost);
+    if (chain_counts) {
+      chain_counts[0] = ci.placed;
+      chain_counts[1] = ci.not_placed;
+      chain_counts[2] = ci.gn_steps;
+      chain_counts[3] = ci.stages;
+    }
+    if (chain_status) std::copy(ci.status.begin(), ci.status.end(), chain_status);
+    if (landmark_counts) {
+      landmark_counts[0] = info.solved;
+      landmark_counts[1] = info.not_solved;
+      landmark_counts[2] = info.degenerate_range_rows;
+      landmark_counts[3] = info.gn_steps;
+    }
+    if (range_landmark_status) std::copy(info.status.begin(), info.status.end(), range_landmark_status);
+  });
+}
+
+int cora_problem_closure_initialization(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, int min_sightings, int min_closures,
+                                        double *out, int64_t counts[7], unsigned char *status, double *cost_start, double *cost_final,
+                                        int32_t *chosen, double *transforms, int64_t sighting_counts[6], unsigned char *sighting_status,
+                                        unsigned char *landmark_status, int64_t chain_counts[4], unsigned char *chain_status,
+                                        int64_t landmark_counts[4], unsigned char *range_landmark_status) {
+  return guarded([&] {
+    ClosurePlacementInfo li;
+    SightingPlacementInfo si;
+    ChainPlacementInfo ci;
+    LandmarkInitInfo info;
+    const Matrix res = p->problem.closureInitialization(seed, gn_steps, min_ranges, min_sightings, min_closures, &li, &si, &ci, &info);
+    if (res.rows() == p->problem.getExpectedVariableSize()) p->problem.checkVariablesAreValid(res);  // (throws off the manifold)
+    std::memcpy(out, res.data(), sizeof(double) * static_cast<size_t>(res.size()));
+    if (counts) {
+      counts[0] = li.chains_fixed;
+      counts[1] = li.chains_placed;
+      counts[2] = li.chains_not_placed;
+      counts[3] = li.chains_refused;
+      counts[4] = li.stages;
+      counts[5] = li.closures_used;
+      counts[6] = li.edges_skipped;
+    }
+    if (status) std::copy(li.status.begin(), li.status.end(), status);
+    if (cost_start) std::copy(li.cost_start.begin(), li.cost_start.end(), cost_start);
+    if (cost_final) std::copy(li.cost_final.begin(), li.cost_final.end(), cost_final);
+    if (chosen) std::copy(li.chosen.begin(), li.chosen.end(), chosen);
+    if (transforms) std::copy(li.transforms.begin(), li.transforms.end(), transforms);
+    if (sighting_counts) {
+      sighting_counts[0] = si.chains_fixed;
+      sighting_counts[1] = si.chains_placed;
+      sighting_counts[2] = si.chains_not_placed;
+      sighting_counts[3] = si.landmarks_placed;
+      sighting_counts[4] = si.landmarks_not_placed;
+      sighting_counts[5] = si.stages;
+    }
+    if (sighting_status) std::copy(si.status.begin(), si.status.end(), sighting_status);
+    if (landmark_status) std::copy(si.landmark_status.begin(), si.landmark_status.end(), landmark_status);
     if (chain_counts) {
       chain_counts[0] = ci.placed;
       chain_counts[1] = ci.not_placed;

@@ -1706,6 +1706,217 @@ __host__ __device__ inline bool sg_fold(const double *S, double *st, int32_t *is
   return finite;
 }
 
+// Placement from inter-chain relative-pose edges (kernels/closure.inc; include/cora_hip.h, cora_place_by_closures_dev).  A
+// CLOSURE is an edge with a second rotation that is no edge of an odometry chain and whose two poses are positions of two
+// different chains.  Against a placed chain its two residuals are functions of the motion g = (G, s) of the other chain:
+// kappa |G - P|_F^2 + tau |G q + s - l|^2, with (dir 0: a placed, b moves) P = X_a^T R X_b, q = x_t(b), l = x_t(a) + R_a t
+// and (dir 1: a moves, b placed) P = X_b^T R^T X_a, q = x_t(a) + R_a t, l = x_t(b): the two P are transposes of each other.
+// The host orders the chains into STAGES (capi/closure.inc); a stage holds one LIST per chain taken in it (its closures
+// against chains placed before the stage, in table order: edge and dir), cut into chunks of kClChunk entries, none across
+// two lists; ALL lists of a stage share its five launches:
+//   pass and fold of the sums (mode 0; the fold solves, cl_solve), pass and fold of the two costs (mode 1), apply.
+// The lists' state has the layout of the sighting placement's chain lists (kSgState, kSgInts), so the apply is k_sg_apply.
+// Coordinates are relative to the list's first entry: q' = q - q_0, l' = l - l_0.  BRACKET ORDER and arithmetic: as the
+// sighting placement's (above), the same in the host mirror (capi/closure.inc).
+constexpr int kClChunk = 256;
+constexpr double kClMinRank = 1e-6;  // the refusal rule of cl_solve, relative to the bound S of |H|_F
+// tau | tau q' | tau l' | tau l' q'^T (row-major) | tau |q'|^2 | tau |l'|^2 (sg_chain_terms' layout) | kappa | kappa P (row-major)
+constexpr int kClSums(int d) { return 4 + 2 * d + 2 * d * d; }
+constexpr int kClCostSums = 2;  // at the identity (the table's own rot + trans residuals) | at g
+struct ClArgs {
+  int d = 0, mode = 0;
+  int32_t chunk0 = 0, n_chunks = 0;   // the stage's chunks in the chunk table
+  int32_t list0 = 0, n_lists = 0;     // the stage's lists in the list table
+  int32_t apply0 = 0, n_apply = 0;    // the positions of the stage's chains in the apply table
+  int64_t n_edges = 0, pstride = 0;
+  const int32_t *chunk_begin = nullptr, *chunk_len = nullptr, *chunk_list = nullptr;  // [chunks of all stages]
+  const int32_t *list_chunk0 = nullptr;                      // [lists + 1]
+  const int32_t *ent_e = nullptr, *ent_dir = nullptr;        // [entries]: edge, 0 a placed and b moves | 1 a moves and b placed
+  const int32_t *apply_pos = nullptr, *apply_list = nullptr;  // [positions of all stages]: chain-table position, its list
+  const int32_t *pos_rot = nullptr, *pos_trn = nullptr;       // the chain tables' (OdomArgs)
+  const int32_t *edge_rows = nullptr;  // the measurement table's, [ra | rb | ta | tb][n_edges], INTERNAL rows
+  const double *edge_data = nullptr;   // the measurement table's, [d*d + d + 2][n_edges]
+  double *partial = nullptr;           // [kClSums(d)][pstride], pstride = the chunks of all stages
+  double *state = nullptr;             // [lists][kSgState(d)]: G | s | s' | cost_start | cost_final
+  int32_t *istate = nullptr;           // [lists][kSgInts]: status | chosen
+  double *x = nullptr;                 // d columns at stride ld_for(d) = d
+  int *flag = nullptr;                 // |= 1 where a sum is not finite
+};
+hipError_t launch_closure_pass_fold(const ClArgs &A, hipStream_t st);  // pass and fold of A.mode over the stage A describes
+hipError_t launch_closure_apply(const ClArgs &A, hipStream_t st);     // k_sg_apply over the stage's positions
+// One entry from the rows as they stand: Y = R^T X_a (Y[b][k] from +0.0, a ascending), P (dir 0: P[i][j] = sum_b Y[b][i]
+// X_b[b][j] from +0.0, b ascending; dir 1: its transpose), q and l, the table's own residuals res = kappa |X_b - Y|_F^2 +
+// tau |x_t(b) - (x_t(a) + R_a t)|^2 (each from +0.0, row-major resp. c ascending).  f: the edge's fields R | t | kappa | tau.
+template <int D>
+__host__ __device__ inline void cl_entry(const double *xa, const double *ta, const double *xb, const double *tb, const double *f, int dir,
+                                         double *P, double *q, double *l, double *res) {
+#pragma clang fp contract(off)
+  double Y[D * D], pa[D];
+#pragma unroll
+  for (int b = 0; b < D; ++b)
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      double v = 0.0;
+#pragma unroll
+      for (int a = 0; a < D; ++a) v = fma(f[a * D + b], xa[a * D + k], v);
+      Y[b * D + k] = v;
+    }
+  double rot = 0.0;
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) {
+    const double r = xb[i] - Y[i];
+    rot = fma(r, r, rot);
+  }
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      double v = 0.0;
+#pragma unroll
+      for (int b = 0; b < D; ++b) v = fma(Y[b * D + i], xb[b * D + j], v);
+      P[dir ? j * D + i : i * D + j] = v;
+    }
+  sg_predict<D>(xa, ta, f + D * D, pa);
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    q[c] = dir ? pa[c] : tb[c];
+    l[c] = dir ? tb[c] : pa[c];
+  }
+  res[0] = f[D * D + D] * rot + sg_lm_cost<D>(pa, tb, f[D * D + D + 1]);
+}
+// the entry's terms of the sums (kClSums): sg_chain_terms' with p = q, then kappa and kappa P
+template <int D>
+__host__ __device__ inline void cl_terms(const double *q0, const double *l0, const double *P, const double *q, const double *l, double kappa,
+                                         double tau, double *s) {
+#pragma clang fp contract(off)
+  sg_chain_terms<D>(q0, l0, q, l, tau, s);
+  s[3 + 2 * D + D * D] = kappa;
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) s[4 + 2 * D + D * D + i] = kappa * P[i];
+}
+// The minimiser of the list's closure cost from its sums, with W = sum tau, K = sum kappa: H = sum kappa P + [W > 0: sum tau
+// l' q'^T - (sum tau l')(sum tau q')^T / W], G = round_rotation(H), s' = [W > 0: (sum tau l') / W - G (sum tau q') / W, else
+// 0], s = s' + l_0 - G q_0.  g: G | s | s'.
+// REFUSED (status 2, g = the identity with s' = q_0 - l_0), a function of the sums alone, with the centred spreads s_q = sum
+// tau |q'|^2 - |sum tau q'|^2 / W and s_l likewise (0 where W <= 0), S = K sqrt(d) + sqrt(max(s_q, 0) max(s_l, 0)) (an upper
+// bound of |H|_F) and k = kClMinRank:
+//   K <= 0 and W <= 0;  K <= 0 and (s_q <= 0 or s_l <= 0);
+//   d = 2:  |H|_F^2 <= k^2 S^2;      d = 3:  |cof(H)|_F^2 <= k^4 S^4
+// (every comparison written so that a NaN refuses).
+template <int D>
+__host__ __device__ inline int cl_solve(const double *S, const double *q0, const double *l0, double *g) {
+#pragma clang fp contract(off)
+  constexpr int G = kSgG(D);
+  const double *Sq = S + 1, *Sl = S + 1 + D, *Slq = S + 1 + 2 * D, *SP = S + 4 + 2 * D + D * D;
+  const double W = S[0], K = S[3 + 2 * D + D * D];
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) g[i] = i / D == i % D ? 1.0 : 0.0;
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    g[D * D + c] = 0.0;
+    g[G + c] = q0[c] - l0[c];
+  }
+  const bool hasW = W > 0.0, hasK = K > 0.0;
+  if (!hasW && !hasK) return 2;
+  double sq = 0.0, sl = 0.0;
+  if (hasW) {
+    double nq = 0.0, nl = 0.0;
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+      nq = fma(Sq[c], Sq[c], nq);
+      nl = fma(Sl[c], Sl[c], nl);
+    }
+    sq = S[1 + 2 * D + D * D] - nq / W;
+    sl = S[2 + 2 * D + D * D] - nl / W;
+  }
+  if (!hasK && (!(sq > 0.0) || !(sl > 0.0))) return 2;
+  double H[D][D];
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+#pragma unroll
+    for (int b = 0; b < D; ++b) H[a][b] = hasW ? SP[a * D + b] + (Slq[a * D + b] - (Sl[a] * Sq[b]) / W) : SP[a * D + b];
+  const double root_d = D == 2 ? 1.4142135623730951 : 1.7320508075688772;  // sqrt(d), correctly rounded
+  const double bound = (hasK ? K * root_d : 0.0) + sqrt((sq > 0.0 ? sq : 0.0) * (sl > 0.0 ? sl : 0.0));
+  const double k2 = kClMinRank * kClMinRank, b2 = bound * bound;
+  if constexpr (D == 2) {
+    const double f = fma(H[1][1], H[1][1], fma(H[1][0], H[1][0], fma(H[0][1], H[0][1], H[0][0] * H[0][0])));
+    if (!(f > k2 * b2)) return 2;
+  } else {
+    double m2 = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        const int a1 = (a + 1) % 3, a2 = (a + 2) % 3, b1 = (b + 1) % 3, b2i = (b + 2) % 3;
+        const double m = fma(H[a1][b1], H[a2][b2i], -(H[a1][b2i] * H[a2][b1]));
+        m2 = fma(m, m, m2);
+      }
+    if (!(m2 > (k2 * b2) * (k2 * b2))) return 2;
+  }
+  round_rotation<D>(H);
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+#pragma unroll
+    for (int b = 0; b < D; ++b) g[a * D + b] = H[a][b];
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    double rq = 0.0, r0 = 0.0;  // G qbar, G q_0 (from +0.0, k ascending)
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      if (hasW) rq = fma(H[a][k], Sq[k] / W, rq);
+      r0 = fma(H[a][k], q0[k], r0);
+    }
+    const double tr = hasW ? Sl[a] / W - rq : 0.0;
+    g[G + a] = tr;
+    g[D * D + a] = (tr + l0[a]) - r0;
+  }
+  return 0;
+}
+// the cost of one entry at g: kappa |G - P|_F^2 (from +0.0, row-major) + tau |G q' + s' - l'|^2
+template <int D>
+__host__ __device__ inline double cl_cost_at(const double *g, const double *q0, const double *l0, const double *P, const double *q, const double *l,
+                                             double kappa, double tau) {
+#pragma clang fp contract(off)
+  constexpr int G = kSgG(D);
+  double rot = 0.0, trn = 0.0, qq[D];
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) {
+    const double r = g[i] - P[i];
+    rot = fma(r, r, rot);
+  }
+#pragma unroll
+  for (int c = 0; c < D; ++c) qq[c] = q[c] - q0[c];
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    double v = g[G + a];
+#pragma unroll
+    for (int k = 0; k < D; ++k) v = fma(g[a * D + k], qq[k], v);
+    const double r = v - (l[a] - l0[a]);
+    trn = fma(r, r, trn);
+  }
+  return kappa * rot + tau * trn;
+}
+// what lane 0 of a list's fold does with the list's sums S in mode MODE (0 solve, 1 costs); q0, l0: the first entry's.
+// False where a sum is not finite.
+template <int D, int MODE>
+__host__ __device__ inline bool cl_fold(const double *S, double *st, int32_t *ist, const double *q0, const double *l0) {
+  constexpr int G = kSgG(D);
+  bool finite = odom_finite(S, MODE == 0 ? kClSums(D) : kClCostSums);
+  if constexpr (MODE == 0) {
+    double g[G + D];
+    ist[0] = cl_solve<D>(S, q0, l0, g);  // (sums that are not finite: the call fails, whatever g is)
+    ist[1] = 0;
+#pragma unroll
+    for (int i = 0; i < G + D; ++i) st[i] = g[i];
+    finite = finite && odom_finite(g, G + D);
+  } else {
+    ist[1] = ist[0] == 0 && S[1] < S[0] ? 1 : 0;
+    st[G + D] = S[0];
+    st[G + D + 1] = ist[1] ? S[1] : S[0];  // the cost of what is applied
+  }
+  return finite;
+}
+
 // In-place update of Q's values (kernels/update_values.inc).  src: the sources of ValueMap (cora_internal.h), vals: the
 // new CSR values on the device.
 // check: flag |= 1 where a value is not finite, |= 2 where a mirror pair (mirror[2j], mirror[2j + 1]) differs.

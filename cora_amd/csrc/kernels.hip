@@ -26,7 +26,7 @@
 #define CORA_LDG 63
 #endif
 
-// ONE source in fifteen pieces (round 6: the file had grown to 3 700 lines); this file holds the switches of the translation units
+// ONE source in sixteen pieces (round 6: the file had grown to 3 700 lines); this file holds the switches of the translation units
 // and, at the end, the measurement builds' read-back hooks.  Inside namespace cora, in this order:
 //   kernels/common.inc   row loads / stores, wave reductions, the STPCG state's scalar steps
 //   kernels/spmm.inc     the sliced SpMM with fused epilogues (chain slices, row slices, long-row chunks)        CORA_TU & 1
@@ -40,6 +40,7 @@
 //   kernels/multilat.inc  landmark initialisation from ranges: pass over the chunks of the range lists, fold and solve per landmark  CORA_TU & 2
 //   kernels/placement.inc  chain placement from inter-robot ranges: linear and Gauss-Newton pass and fold per stage, the rigid motion of a chain  CORA_TU & 2
 //   kernels/sighting.inc  placement from pose-landmark sightings: pass and fold over all lists of a stage, the rigid motion of a stage's chains  CORA_TU & 2
+//   kernels/closure.inc  placement from inter-chain relative-pose edges: pass and fold over all lists of a stage (sums and solve, costs)  CORA_TU & 2
 //   kernels/update_values.inc  in-place update of Q's values: check of the new values, gather passes                CORA_TU & 2
 //   kernels/assemble.inc  Q(w) from per-measurement weights through the term map: check, short and long entries     CORA_TU & 2
 //   kernels/tri.inc      the staged Cholesky solve: k_rowop, k_blockop, k_subblock                                 CORA_TU & 4
@@ -57,6 +58,7 @@ namespace cora {
 #include "kernels/multilat.inc"
 #include "kernels/placement.inc"
 #include "kernels/sighting.inc"
+#include "kernels/closure.inc"
 #include "kernels/update_values.inc"
 #include "kernels/assemble.inc"
 #include "kernels/tri.inc"

@@ -640,6 +640,47 @@ hipError_t launch_sighting_apply(const SgArgs &A, hipStream_t st) {
   else hipLaunchKernelGGL(k_sg_apply<3>, grid, dim3(256), 0, st, A);
   return hipGetLastError();
 }
+// the placement from closures (kernels/closure.inc): every launch serves all lists of the one stage A describes
+static bool closure_args_ok(const ClArgs &A) {
+  return (A.d == 2 || A.d == 3) && A.n_chunks > 0 && A.chunk0 >= 0 && A.n_lists > 0 && A.list0 >= 0 && A.n_edges > 0 &&
+         A.pstride >= static_cast<int64_t>(A.chunk0) + A.n_chunks && A.chunk_begin && A.chunk_len && A.chunk_list && A.list_chunk0 && A.ent_e &&
+         A.ent_dir && A.edge_rows && A.edge_data && A.partial && A.state && A.istate && A.x && A.flag;
+}
+template <int D, int MODE>
+static void closure_pass_fold(const ClArgs &A, hipStream_t st) {
+  hipLaunchKernelGGL((k_cl_pass<D, MODE>), dim3(static_cast<unsigned>(A.n_chunks)), dim3(kClChunk), 0, st, A);
+  hipLaunchKernelGGL((k_cl_fold<D, MODE>), dim3(static_cast<unsigned>(A.n_lists)), dim3(kWave), 0, st, A);
+}
+hipError_t launch_closure_pass_fold(const ClArgs &A, hipStream_t st) {
+  if (!closure_args_ok(A) || A.mode < 0 || A.mode > 1) return hipErrorInvalidValue;
+  if (A.d == 2) {
+    if (A.mode == 0) closure_pass_fold<2, 0>(A, st);
+    else closure_pass_fold<2, 1>(A, st);
+  } else {
+    if (A.mode == 0) closure_pass_fold<3, 0>(A, st);
+    else closure_pass_fold<3, 1>(A, st);
+  }
+  return hipGetLastError();
+}
+// the lists' state has the sighting placement's layout: its apply kernel serves, reading only these fields
+hipError_t launch_closure_apply(const ClArgs &A, hipStream_t st) {
+  if (!closure_args_ok(A) || A.n_apply <= 0 || A.apply0 < 0 || !A.apply_pos || !A.apply_list || !A.pos_rot || !A.pos_trn) return hipErrorInvalidValue;
+  SgArgs G;
+  G.d = A.d;
+  G.apply0 = A.apply0;
+  G.n_apply = A.n_apply;
+  G.apply_pos = A.apply_pos;
+  G.apply_list = A.apply_list;
+  G.pos_rot = A.pos_rot;
+  G.pos_trn = A.pos_trn;
+  G.state = A.state;
+  G.istate = A.istate;
+  G.x = A.x;
+  const dim3 grid(static_cast<unsigned>((A.n_apply + 255) / 256));
+  if (A.d == 2) hipLaunchKernelGGL(k_sg_apply<2>, grid, dim3(256), 0, st, G);
+  else hipLaunchKernelGGL(k_sg_apply<3>, grid, dim3(256), 0, st, G);
+  return hipGetLastError();
+}
 hipError_t launch_round_amax(int64_t n, const double *y, double *partial, int nblocks, int *flag, hipStream_t st) {
   if (n < 1 || nblocks < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_round_amax, dim3(nblocks), dim3(256), 0, st, n, y, partial, flag);

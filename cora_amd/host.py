@@ -200,7 +200,7 @@ class Problem:
             out = np.zeros(1)
         pa, pb, pc = ptr(A), ptr(B), ptr(C_)
         if name != "evaluateObjective":
-            full = name in ("getOdomInitialization", "odometryInitialization", "rangeAidedInitialization", "multiRobotInitialization", "sightingInitialization",
+            full = name in ("getOdomInitialization", "odometryInitialization", "rangeAidedInitialization", "multiRobotInitialization", "sightingInitialization", "closureInitialization",
                             "getTranslationExplicitSolution", "alignEstimateToOrigin")
             out = np.zeros((dm["N"] if full else N, cols[0] if cols else p), order="F")
         if len(set(cols)) > 1:
@@ -278,6 +278,36 @@ class Problem:
         return out, dict(fixed=int(cnt[0]), placed=int(cnt[1]), not_placed=int(cnt[2]), landmarks_placed=int(cnt[3]),
                          landmarks_not_placed=int(cnt[4]), stages=int(cnt[5]), status=status[:nch], cost_start=cs[:nch], cost_final=cf[:nch],
                          chosen=chosen[:nch], transforms=tr[:-1].reshape(nch, d * d + d), landmark_status=ls[:nl], landmark_cost=lc[:nl],
+                         chains=dict(placed=int(ccnt[0]), not_placed=int(ccnt[1]), steps=int(ccnt[2]), stages=int(ccnt[3]), status=cstatus[:nch]),
+                         landmarks=dict(solved=int(lcnt[0]), not_solved=int(lcnt[1]), n_degenerate=int(lcnt[2]), steps=int(lcnt[3]),
+                                        status=rls[:nl]))
+
+    def closure_initialization(self, seed=7, gn_steps=5, min_ranges=0, min_sightings=0, min_closures=0):
+        """Problem::closureInitialization: (x0, info) with info a dict fixed, placed, not_placed, refused, stages,
+        closures_used, edges_skipped, status, cost_start, cost_final, chosen, transforms (per chain of odometry_chains()) of
+        the closure step; sightings (fixed, placed, not_placed, landmarks_placed, landmarks_not_placed, stages, status,
+        landmark_status of the sighting step that followed), chains and landmarks as sighting_initialization has them.
+        0: the defaults.  The start has passed checkVariablesAreValid."""
+        dm = self.dims()
+        d = dm["d"]
+        nl = dm["N"] - (d + 1) * dm["n"] - dm["r"]
+        nch = len(self.odometry_chains())
+        out = np.zeros((dm["N"], dm["rank"]), order="F")
+        cnt, scnt, ccnt, lcnt = (C.c_int64 * 7)(), (C.c_int64 * 6)(), (C.c_int64 * 4)(), (C.c_int64 * 4)()
+        status, sstatus, cstatus = (np.zeros(nch + 1, dtype=np.uint8) for _ in range(3))
+        chosen = np.zeros(nch + 1, dtype=np.int32)
+        ls, rls = np.zeros(nl + 1, dtype=np.uint8), np.zeros(nl + 1, dtype=np.uint8)
+        cs, cf, tr = np.zeros(nch + 1), np.zeros(nch + 1), np.zeros(nch * (d * d + d) + 1)
+        self._chk(self.L.cora_problem_closure_initialization(
+            self.h, C.c_uint64(seed), int(gn_steps), int(min_ranges), int(min_sightings), int(min_closures), out.ctypes.data_as(_dp), cnt,
+            status.ctypes.data_as(C.c_void_p), cs.ctypes.data_as(_dp), cf.ctypes.data_as(_dp), chosen.ctypes.data_as(C.POINTER(C.c_int32)),
+            tr.ctypes.data_as(_dp), scnt, sstatus.ctypes.data_as(C.c_void_p), ls.ctypes.data_as(C.c_void_p), ccnt,
+            cstatus.ctypes.data_as(C.c_void_p), lcnt, rls.ctypes.data_as(C.c_void_p)))
+        return out, dict(fixed=int(cnt[0]), placed=int(cnt[1]), not_placed=int(cnt[2]), refused=int(cnt[3]), stages=int(cnt[4]),
+                         closures_used=int(cnt[5]), edges_skipped=int(cnt[6]), status=status[:nch], cost_start=cs[:nch], cost_final=cf[:nch],
+                         chosen=chosen[:nch], transforms=tr[:-1].reshape(nch, d * d + d),
+                         sightings=dict(fixed=int(scnt[0]), placed=int(scnt[1]), not_placed=int(scnt[2]), landmarks_placed=int(scnt[3]),
+                                        landmarks_not_placed=int(scnt[4]), stages=int(scnt[5]), status=sstatus[:nch], landmark_status=ls[:nl]),
                          chains=dict(placed=int(ccnt[0]), not_placed=int(ccnt[1]), steps=int(ccnt[2]), stages=int(ccnt[3]), status=cstatus[:nch]),
                          landmarks=dict(solved=int(lcnt[0]), not_solved=int(lcnt[1]), n_degenerate=int(lcnt[2]), steps=int(lcnt[3]),
                                         status=rls[:nl]))

@@ -27,7 +27,7 @@ int main(int argc, char **argv) {
   }
   int max_rank = 10, gn_steps = 5;
   std::string tum, save_dir, residuals, weights, robust, barc2, weights_out, aligned_tum, rpe_steps, rpe_dists;
-  bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false, landmark_init = false, place_chains = false, sightings = false;
+  bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false, landmark_init = false, place_chains = false, sightings = false, closures = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--jacobi") jacobi = true;
@@ -67,6 +67,9 @@ int main(int argc, char **argv) {
     // with --odom-init --device-init: landmarks and chains are first placed from the pose-landmark sightings, then the chains
     // that are left from the ranges and the landmarks that are left by multilateration (Problem::sightingInitialization)
     else if (a == "--sightings") sightings = true;
+    // with --odom-init --device-init: the chains are first placed from the relative-pose edges between chains, then everything
+    // --sightings does (Problem::closureInitialization)
+    else if (a == "--closures") closures = true;
   }
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
@@ -74,6 +77,7 @@ int main(int argc, char **argv) {
     if (device_init && !odom) throw std::runtime_error("--device-init composes the odometry start on the device: it needs --odom-init");
     if (place_chains && !device_init) throw std::runtime_error("--place-chains places the chains of the device's odometry start: it needs --odom-init --device-init");
     if (sightings && !device_init) throw std::runtime_error("--sightings places landmarks and chains of the device's odometry start: it needs --odom-init --device-init");
+    if (closures && !device_init) throw std::runtime_error("--closures places the chains of the device's odometry start: it needs --odom-init --device-init");
     if (landmark_init && !device_init) throw std::runtime_error("--landmark-init places the landmarks of the device's odometry start: it needs --odom-init --device-init");
     const auto t_start = clk::now();
     CORA::Problem problem = CORA::parsePyfgTextToProblem(argv[1]);
@@ -157,6 +161,26 @@ int main(int argc, char **argv) {
       std::printf("sighting placement: %ld chains fixed or placed, %ld not placed; %ld landmarks placed, %ld not placed (%ld stages); sighting cost at the start %.6e with it, %.6e without\n",
                   si.chains_fixed + si.chains_placed, si.chains_not_placed, si.landmarks_placed, si.landmarks_not_placed, si.stages,
                   sighting_sum(x0), without);
+    }
+    if (closures) {  // (an extension beyond the reference: Problem::closureInitialization)
+      CORA::ClosurePlacementInfo li;
+      const CORA::Matrix without = problem.sightingInitialization(7, gn_steps);  // (the same pipeline without the step)
+      x0 = problem.closureInitialization(7, gn_steps, 0, 0, 0, &li);
+      // the closure cost: the table's own rot + trans residuals of the relative-pose edges that are no edge of a chain
+      std::vector<char> in_chain(static_cast<size_t>(problem.numPosePoseMeasurements()), 0);
+      for (const auto &ch : problem.odometryChains())
+        for (const int32_t e : ch) in_chain[static_cast<size_t>(e)] = 1;
+      auto closure_sum = [&](const CORA::Matrix &x) {
+        const CORA::MeasurementResiduals res =
+            problem.measurementResiduals(implicit ? CORA::Matrix(x.block(0, 0, problem.rotAndRangeMatrixSize(), x.cols())) : x);
+        double sum = 0;
+        for (size_t e = 0; e < in_chain.size(); ++e)
+          if (!in_chain[e]) sum += res.rel_pose_rot[e] + res.rel_pose_trans[e];
+        return sum;
+      };
+      std::printf("closure placement: %ld chains fixed or placed, %ld not placed, %ld refused (%ld stages, %ld closures used, %ld edges skipped or unused); closure cost at the start %.6e with it, %.6e without\n",
+                  li.chains_fixed + li.chains_placed, li.chains_not_placed, li.chains_refused, li.stages, li.closures_used, li.edges_skipped,
+                  closure_sum(x0), closure_sum(without));
     }
     if (odom && implicit)  // examples/paper_experiments.cpp:623-625
       x0 = x0.block(0, 0, problem.rotAndRangeMatrixSize(), x0.cols());

@@ -1011,6 +1011,75 @@ int cora_debug_place_by_sightings_host(cora_ctx *ctx, double *X, int ldx, int64_
                                        double *cost_final, int32_t *chosen, double *transforms, unsigned char *landmark_status,
                                        double *landmark_cost, unsigned char *degenerate);
 
+/* ---- PLACEMENT FROM INTER-CHAIN RELATIVE-POSE EDGES (closures), on the device ------------------------------------------------
+ * Moves whole odometry chains by one rigid motion each so that the relative-pose edges BETWEEN chains (inter-robot loop
+ * closures, rendezvous, closures across a gap in one robot's odometry) are met, in place; the solve is closed-form and
+ * the global minimiser of the list's cost.  Needs a measurement table (cora_set_measurements), chain tables
+ * (cora_set_odometry_chains) and the tables of cora_set_closure_placement.
+ * DEFINITIONS.
+ *   closure          an edge of the measurement table with a rotation part (second rotation row >= 0) that is no edge of an
+ *                    odometry chain and whose two poses are positions of two DIFFERENT chains.  Every other non-chain edge
+ *                    with a rotation part (both ends in one chain, an end in a free pose) is skipped and counted; edges
+ *                    without a rotation part (sightings, priors on a position) are no relative-pose edges and are not counted.
+ *   motion           g = (G, s) of a chain: t_i <- G t_i + s, R_i <- G R_i, the stored block X_i <- X_i G^T.
+ *   P, q, l          of a closure between a placed and the moving chain, from the vector as it stands:
+ *                      a placed, b moving:  P = X_a^T R X_b,      q = x_t(b),            l = x_t(a) + R_a t
+ *                      a moving, b placed:  P = X_b^T R^T X_a,    q = x_t(a) + R_a t,    l = x_t(b)
+ *                    so that the edge's residuals after the motion are kappa |G - P|_F^2 and tau |G q + s - l|^2.
+ *   closure cost     of a list: J(G, s) = sum kappa |G - P|_F^2 + sum tau |G q + s - l|^2.
+ *   order            decided once on the host from structure alone.  Placed: chain_fixed, NULL: chain 0.  Stage k takes
+ *                    EVERY unplaced chain with at least min_closures closures against chains placed BEFORE stage k; its list
+ *                    is those closures in table order, cut into chunks of 256, none across two lists; all lists of a stage
+ *                    share its launches; repeated until a stage takes nothing.  Closures between two chains taken in the
+ *                    same stage, or to a chain never placed, are unused and counted.  min_closures >= 1.
+ *   solve            relative to the list's first entry, q' = q - q_0, l' = l - l_0, W = sum tau, K = sum kappa:
+ *                    H = sum kappa P + sum tau l' q'^T - (sum tau l')(sum tau q')^T / W (the last two dropped where W <= 0),
+ *                    G = round_rotation(H) (maximises tr(G^T H)), s' = (sum tau l') / W - G (sum tau q') / W (0 where
+ *                    W <= 0), s = s' + l_0 - G q_0.  A second pass evaluates the cost at the identity (cost_start: the sum
+ *                    of the table's own rot + trans residuals of the list's edges) and at g (kappa |G - P|^2 + tau |G q' +
+ *                    s' - l'|^2); g is applied only where its cost is below cost_start (chosen 1, cost_final the cost at g);
+ *                    otherwise the rows are not touched (chosen 0, cost_final = cost_start).  cost_final <= cost_start.
+ *   status           0 placed | 1 never taken (inter-chain closures, but too few against placed chains) | 2 taken, refused
+ *                    by the device | 3 no inter-chain closure at all | 4 fixed.
+ *   refusal          a function of the sums alone; a NaN refuses.  With the centred spreads s_q = sum tau |q'|^2 - |sum tau
+ *                    q'|^2 / W and s_l likewise (0 where W <= 0), S = K sqrt(d) + sqrt(max(s_q, 0) max(s_l, 0)) (an upper
+ *                    bound of |H|_F) and k = 1e-6: refused where K <= 0 and W <= 0; where K <= 0 and s_q <= 0 or s_l <= 0;
+ *                    d = 2: |H|_F^2 <= k^2 S^2;  d = 3: |cof(H)|_F^2 <= k^4 S^4.  A refused chain keeps its rows; by the
+ *                    structural order it STILL COUNTS AS PLACED for the stages after it.
+ *   range rows       afterwards the unit range rows of ALL range measurements are recomputed in the direction of least
+ *                    residual, as cora_place_by_sightings_dev does, with its degenerate bytes and count.
+ * cora_set_closure_placement   validates, decides the order and uploads.  The tables stay on the handle until replaced, until
+ *            the measurement table or the chain tables are replaced or until the handle is destroyed.  Works on a plan-only
+ *            handle, except for the upload.  A refused call leaves the tables as they were.
+ * cora_closure_placement_counts   out = {stages, closures used (entries of all lists), chunks, skipped + unused edges}.
+ * cora_closure_placement_order    stage_ptr[stages + 1];  items[stage_ptr[stages]]: the chains of stage s at
+ *            items[stage_ptr[s] .. stage_ptr[s + 1]), ascending; `chunks` entries always suffice.
+ * cora_place_by_closures_dev   out (host) = {chains placed (status 0), chains not placed (1, 2, 3), degenerate range rows,
+ *            stages, chains refused (2)};  status, cost_start, cost_final, chosen: host arrays with one entry per chain or
+ *            NULL (costs 0 and chosen -1 where the chain has no list);  transforms: [chains][d * d + d], G row-major then s
+ *            as applied, the identity where nothing was applied;  degenerate: host bytes, one per range measurement, or
+ *            NULL.  5 launches per stage whatever the number of chains in it, then 2 for the range rows.  Everything on the
+ *            handle's stream; synchronises once, at the end.
+ * cora_place_by_closures       the host-pointer form, in place: X is N x d column-major with leading dimension ldx.
+ * cora_debug_place_by_closures_host   the same on the host in the device's bracket order and through the functions the
+ *            kernels call: X has the device's bits.  Works on a plan-only handle.
+ * ARITHMETIC.  As the sighting placement's: + - x / and sqrt only, single correctly rounded fp64 operations in the order
+ * written, never contracted; the same order of the sums; the same bits on every call; no atomics on doubles.
+ * ERRORS.  CORA_ERR_NOT_READY: no measurement table, no chain tables, or no closure tables.  CORA_ERR_ARG: a partitioned
+ * handle; min_closures < 1; a mask that fixes no chain; a null X or out; two range measurements that name one range row.
+ * CORA_ERR_SHAPE: a leading dimension below N.  CORA_ERR_NAN: a sum or a range row that is not finite (the device forms
+ * report it through the handle's flag word).  CORA_ERR_HIP: a device form on a plan-only handle.
+ * STATE.  Nothing the handle computes with changes. */
+int cora_set_closure_placement(cora_ctx *ctx, const unsigned char *chain_fixed /* [chains] or NULL */, int min_closures);
+int cora_closure_placement_counts(const cora_ctx *ctx, int64_t out[4]);
+int cora_closure_placement_order(const cora_ctx *ctx, int32_t *stage_ptr, int32_t *items);
+int cora_place_by_closures_dev(cora_ctx *ctx, double *dX, int64_t out[5], unsigned char *status, double *cost_start, double *cost_final,
+                               int32_t *chosen, double *transforms, unsigned char *degenerate);
+int cora_place_by_closures(cora_ctx *ctx, double *X, int ldx, int64_t out[5], unsigned char *status, double *cost_start,
+                           double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate);
+int cora_debug_place_by_closures_host(cora_ctx *ctx, double *X, int ldx, int64_t out[5], unsigned char *status, double *cost_start,
+                                      double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate);
+
 /* Timing helpers: HIP events on the handle's stream. */
 int cora_timer_start(cora_ctx *ctx);
 int cora_timer_stop_ms(cora_ctx *ctx, float *ms); /* synchronises */

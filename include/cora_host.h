@@ -98,6 +98,8 @@ int cora_problem_variable_size(cora_problem *p, int64_t *rows);
  *                                                        between them (Problem::multiRobotInitialization, seed 7, 5 steps, default min_ranges)
  *  "sightingInitialization"   (none)             -> out   multiRobotInitialization with landmarks and chains first placed from the
  *                                                        pose-landmark sightings (Problem::sightingInitialization, seed 7, defaults)
+ *  "closureInitialization"    (none)             -> out   sightingInitialization with the chains first placed from the relative-pose
+ *                                                        edges between chains (Problem::closureInitialization, seed 7, defaults)
  *  "getTranslationExplicitSolution" A=Y (implicit) -> out (d+1)n + r + l rows (src/CORA_problem.cpp:1168)
  *  "alignEstimateToOrigin"    A=Y (rank d)       -> out (d+1)n + r + l rows (src/CORA_problem.cpp:1234)
  * Inputs are N x cols with leading dimension N = cora_problem_variable_size() (cols is checked
@@ -135,6 +137,18 @@ int cora_problem_sighting_initialization(cora_problem *p, uint64_t seed, int gn_
                                          int64_t counts[6], unsigned char *status, double *cost_start, double *cost_final, int32_t *chosen,
                                          double *transforms, unsigned char *landmark_status, double *landmark_cost, int64_t chain_counts[4],
                                          unsigned char *chain_status, int64_t landmark_counts[4], unsigned char *range_landmark_status);
+/* Problem::closureInitialization (an extension beyond the reference; include/cora_hip.h, "placement from inter-chain
+ * relative-pose edges").  min_ranges, min_sightings, min_closures <= 0: the defaults.  out: data-matrix-size x rank.
+ * counts = { chains fixed, placed, not placed, refused, stages, closures used, skipped + unused edges } of the closure step;
+ * status, cost_start, cost_final, chosen: one entry per chain of cora_problem_odometry_chains; transforms: d * d + d per
+ * chain.  sighting_counts, sighting_status, landmark_status: counts, status and landmark_status of
+ * cora_problem_sighting_initialization for the sighting step that followed (its fixed chains: closure status 0 or 4); the
+ * last four as there.  Every array but out may be NULL. */
+int cora_problem_closure_initialization(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, int min_sightings, int min_closures,
+                                        double *out, int64_t counts[7], unsigned char *status, double *cost_start, double *cost_final,
+                                        int32_t *chosen, double *transforms, int64_t sighting_counts[6], unsigned char *sighting_status,
+                                        unsigned char *landmark_status, int64_t chain_counts[4], unsigned char *chain_status,
+                                        int64_t landmark_counts[4], unsigned char *range_landmark_status);
 /* compute_Lambda_blocks(Y): stiefel d x dn (ld d), oblique r */
 int cora_problem_lambda_blocks(cora_problem *p, const double *Y, double *stiefel, double *oblique);
 /* Problem::measurementResiduals (an extension beyond the reference; formulas in include/cora_hip.h, "per-measurement
