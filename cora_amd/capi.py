@@ -1290,6 +1290,43 @@ class Context:
         """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
         return self._cl_call(lambda *a: self.L.cora_place_by_closures_dev(self.h, C.c_void_p(x_ptr), *a))
 
+    # ---- outlier-robust placement from closures (include/cora_hip.h, cora_place_by_closures_robust_dev)
+    def _clr_call(self, fn, barc2, min_consensus):
+        nch, ne, g = self.odometry_chains_count()[0], self.measurement_counts()[0], self.d * self.d + self.d
+        out = (C.c_int64 * 7)()
+        status, chosen = np.zeros(nch + 1, dtype=np.uint8), np.zeros(nch + 1, dtype=np.int32)
+        cs, cf, tr = np.zeros(nch + 1), np.zeros(nch + 1), np.zeros((nch + 1) * g)
+        cons, ll = np.zeros(nch + 1, dtype=np.int32), np.zeros(nch + 1, dtype=np.int32)
+        inl = np.zeros(ne + 1, dtype=np.uint8)
+        self._chk(fn(C.c_double(barc2), int(min_consensus), out, status.ctypes.data_as(C.c_void_p), _d(cs), _d(cf), chosen.ctypes.data_as(_ip),
+                     _d(tr), cons.ctypes.data_as(_ip), ll.ctypes.data_as(_ip), inl.ctypes.data_as(C.c_void_p)))
+        return dict(placed=int(out[0]), not_placed=int(out[1]), n_degenerate=int(out[2]), stages=int(out[3]), refused=int(out[4]),
+                    no_consensus=int(out[5]), excluded=int(out[6]), status=status[:nch], cost_start=cs[:nch], cost_final=cf[:nch],
+                    chosen=chosen[:nch], transforms=tr[:nch * g].reshape(nch, g), consensus=cons[:nch], list_len=ll[:nch], inlier=inl[:ne])
+
+    def _clr_host(self, fn, X, barc2, min_consensus):
+        X = np.array(X, dtype=np.float64, order="F", copy=True)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise CoraError(1, "X must have d columns")
+        res = self._clr_call(lambda *a: fn(self.h, _d(X), X.shape[0], *a), barc2, min_consensus)
+        res["X"] = X
+        return res
+
+    def place_by_closures_robust(self, X, barc2, min_consensus=2):
+        """place_by_closures with a consensus vote in front of the fit: every closure of a list proposes a motion, the proposal
+        most closures agree with (coupled residual <= barc2) is elected and the fit runs over the agreeing closures only.
+        Returns place_by_closures' dict without degenerate, plus consensus and list_len (per chain), inlier (per edge of the
+        measurement table: 1 | 0 | 2 in no list), no_consensus (chains of status 5) and excluded (entries outside the inliers)."""
+        return self._clr_host(self.L.cora_place_by_closures_robust, X, barc2, min_consensus)
+
+    def debug_place_by_closures_robust_host(self, X, barc2, min_consensus=2):
+        """The same on the host in the device's bracket order (no GPU needed): the device's bits."""
+        return self._clr_host(self.L.cora_debug_place_by_closures_robust_host, X, barc2, min_consensus)
+
+    def place_by_closures_robust_dev(self, x_ptr, barc2, min_consensus=2):
+        """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
+        return self._clr_call(lambda *a: self.L.cora_place_by_closures_robust_dev(self.h, C.c_void_p(x_ptr), *a), barc2, min_consensus)
+
     # ---- test hook
     def debug_format_spmm_host(self, X):
         X = _f(X)

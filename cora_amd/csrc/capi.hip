@@ -23,7 +23,7 @@
 //   multilat.inc        landmark initialisation from ranges: list tables, device-pointer, host-pointer and host-mirror form
 //   placement.inc       chain placement from inter-robot ranges: stage tables, device-pointer, host-pointer and host-mirror form
 //   sighting.inc        placement from pose-landmark sightings: stage and list tables, device-pointer, host-pointer and host-mirror form
-//   closure.inc         placement from inter-chain relative-pose edges: stage and list tables, device-pointer, host-pointer and host-mirror form
+//   closure.inc         placement from inter-chain relative-pose edges: stage and list tables, device-pointer, host-pointer and host-mirror form, plain and with the consensus vote
 //   comm.inc            native communication: RCCL, in-process and device-side (p2p.h) transports
 #include <hip/hip_runtime.h>
 // RCCL's types and the few enumerators used, declared here (NCCL's public ABI: they have not changed since 2.0): the
@@ -207,6 +207,11 @@ struct ClTables {
   int32_t *d_istate = nullptr;   // [lists][kSgInts]
   unsigned char *d_deg = nullptr;   // one byte per range measurement
   int32_t *d_range_rows = nullptr;  // [3][n_ranges] internal rows: range | b | a (as MlTables')
+  // the consensus vote's (cora_place_by_closures_robust_dev): scratch of a call, like d_partial
+  int32_t *d_votes = nullptr;       // [entries]
+  double *d_cstate = nullptr;       // [lists][kClCState(d)]
+  int32_t *d_cint = nullptr;        // [lists][kClCInts]
+  unsigned char *d_inlier = nullptr;  // [n_edges]
 };
 struct cora_ctx {
   HostFormat F;
@@ -725,7 +730,8 @@ void free_sg(cora_ctx *c) {  // (the device must be current where there is one)
 void free_cl(cora_ctx *c) {  // (the device must be current where there is one)
   ClTables &T = c->cl;
   for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state), static_cast<void *>(T.d_istate),
-                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows)})
+                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows), static_cast<void *>(T.d_votes), static_cast<void *>(T.d_cstate),
+                  static_cast<void *>(T.d_cint), static_cast<void *>(T.d_inlier)})
     if (p) (void)hipFree(p);
   T = ClTables();
 }

@@ -1,4 +1,4 @@
-// Part of capi.hip (one translation unit; included there, in this order).  placement of odometry chains from inter-chain relative-pose edges (closures; the weighted rigid alignment of a chain onto chains placed before it, rotation and translation residuals together): order of the stages and list tables, device-pointer form, host-pointer form, host mirror.  Reads the measurement table and the chain tables; writes nothing the handle computes with.
+// Part of capi.hip (one translation unit; included there, in this order).  placement of odometry chains from inter-chain relative-pose edges (closures; the weighted rigid alignment of a chain onto chains placed before it, rotation and translation residuals together): order of the stages and list tables, device-pointer form, host-pointer form, host mirror, each plain and with the consensus vote in front of the fit (cora_place_by_closures_robust_dev).  Reads the measurement table and the chain tables; writes nothing the handle computes with.
 
 namespace {
 
@@ -135,12 +135,18 @@ int cl_upload(cora_ctx *c, ClTables &T) {
   std::swap_ranges(rows.begin() + static_cast<std::ptrdiff_t>(nr), rows.begin() + static_cast<std::ptrdiff_t>(2 * nr), rows.begin() + static_cast<std::ptrdiff_t>(2 * nr));
   rows.push_back(0);
   HIP_TRY(c, to_device(&T.d_range_rows, rows));
+  // the consensus vote's scratch
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_votes), std::max<size_t>(T.ent_e.size(), 1) * sizeof(int32_t)));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_cstate), static_cast<size_t>(kClCState(d)) * nlist * sizeof(double)));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_cint), static_cast<size_t>(kClCInts) * nlist * sizeof(int32_t)));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_inlier), std::max<size_t>(static_cast<size_t>(c->meas.n_edges), 1)));
   return CORA_OK;
 }
 
 void cl_release(ClTables &T) {  // a table that never reached the handle
   for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state), static_cast<void *>(T.d_istate),
-                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows)})
+                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows), static_cast<void *>(T.d_votes), static_cast<void *>(T.d_cstate),
+                  static_cast<void *>(T.d_cint), static_cast<void *>(T.d_inlier)})
     if (p) (void)hipFree(p);
 }
 
@@ -148,6 +154,55 @@ int cl_args_check(cora_ctx *c, const double *X, const int64_t *out) {
   if (!c->cl.built) return fail(c, CORA_ERR_NOT_READY, "no closure tables (cora_set_closure_placement)");
   if (!X || !out) return fail(c, CORA_ERR_ARG, "null pointer");
   return CORA_OK;
+}
+
+// the kernels' arguments of a call on the resident vector dX: the tables' device side and, for the range-row step of the
+// odometry initialisation (its rules unchanged, over the exchanged table), Fl
+void cl_fill_args(cora_ctx *c, double *dX, ClArgs &A, OdomFillArgs &Fl) {
+  const Layout &L = c->F.L;
+  const MeasurementTable &M = c->meas;
+  ClTables &T = c->cl;
+  const OdomTables &O = c->odom;
+  const int d = L.d, nb = odom_range_blocks(M.n_ranges);
+  const size_t nc = T.chunk_begin.size(), ne = T.ent_e.size(), nlist = T.list_item.size(), na = T.apply_pos.size();
+  A.d = d;
+  A.n_edges = M.n_edges;
+  A.pstride = static_cast<int64_t>(std::max<size_t>(nc, 1));
+  A.chunk_begin = T.d_idx;
+  A.chunk_len = A.chunk_begin + nc;
+  A.chunk_list = A.chunk_len + nc;
+  A.list_chunk0 = A.chunk_list + nc;
+  A.ent_e = A.list_chunk0 + nlist + 1;
+  A.ent_dir = A.ent_e + ne;
+  A.apply_pos = A.ent_dir + ne;
+  A.apply_list = A.apply_pos + na;
+  A.pos_rot = O.d_idx + 2 * O.P;
+  A.pos_trn = O.d_idx + 3 * O.P;
+  A.edge_rows = M.d_edge_rows;
+  A.edge_data = M.d_edge_data;
+  A.partial = T.d_partial;
+  A.state = T.d_state;
+  A.istate = T.d_istate;
+  A.x = dX;
+  A.flag = c->d_flag;
+  // the range-row step of the odometry initialisation, its rules unchanged, over the exchanged table
+  Fl.d = d;
+  Fl.n_ranges = M.n_ranges;
+  Fl.range_rows = T.d_range_rows;
+  Fl.deg = T.d_deg;
+  Fl.partial = reinterpret_cast<int *>(c->d_red);
+  Fl.words = Fl.partial + nb;
+  Fl.flag = c->d_flag;
+  Fl.out = dX;
+}
+// the stage s of the tables in A
+void cl_stage_args(const ClTables &T, size_t s, ClArgs &A) {
+  A.list0 = T.stage_list0[s];
+  A.n_lists = T.stage_list0[s + 1] - A.list0;
+  A.chunk0 = T.list_chunk0[static_cast<size_t>(A.list0)];
+  A.n_chunks = T.list_chunk0[static_cast<size_t>(T.stage_list0[s + 1])] - A.chunk0;
+  A.apply0 = T.stage_apply0[s];
+  A.n_apply = T.stage_apply0[s + 1] - A.apply0;
 }
 
 // what a call returns, from the lists' state ([lists][kSgState(d)], [lists][kSgInts])
@@ -190,9 +245,63 @@ void cl_host_entry(const cora_ctx *c, const double *oi, size_t e, double *P, dou
   kt[0] = f[D * D + D];
   kt[1] = f[D * D + D + 1];
 }
-// pass and fold of one mode over one stage, in the kernels' order
+// the consensus vote of a robust call on the host: the setting and the lists' elected hypotheses, as on the device
+struct ClHostVote {
+  double barc2;
+  int min_consensus;
+  std::vector<double> cstate;      // [lists][kClCState(d)]
+  std::vector<int32_t> cint;       // [lists][kClCInts]
+  std::vector<unsigned char> inl;  // [n_edges]
+};
+// vote and election over one stage (k_cl_vote, k_cl_elect): the votes are integers, so the order of the scoring is free
+template <int D>
+bool cl_host_vote_elect(const cora_ctx *c, size_t s, const double *oi, ClHostVote &hv, std::vector<int32_t> &ist) {
+  constexpr int GS = kClCState(D), NE = D * D + 2 * D + 2;
+  const ClTables &T = c->cl;
+  bool finite = true;
+  for (size_t list = static_cast<size_t>(T.stage_list0[s]); list < static_cast<size_t>(T.stage_list0[s + 1]); ++list) {
+    const size_t last = static_cast<size_t>(T.list_chunk0[list + 1]) - 1, begin = static_cast<size_t>(T.chunk_begin[static_cast<size_t>(T.list_chunk0[list])]);
+    const size_t len = static_cast<size_t>(T.chunk_begin[last] + T.chunk_len[last]) - begin;
+    std::vector<double> ent(len * NE);  // P | q | l | kappa | tau
+    for (size_t j = 0; j < len; ++j) {
+      double *f = ent.data() + j * NE, res;
+      cl_host_entry<D>(c, oi, begin + j, f, f + D * D, f + D * D + D, &res, f + D * D + 2 * D);
+    }
+    const double *q0 = ent.data() + D * D, *l0 = q0 + D;
+    int32_t bv = -1, be = static_cast<int32_t>(len);
+    for (size_t h = 0; h < len; ++h) {
+      const double *fh = ent.data() + h * NE;
+      double g[GS];
+      cl_hypothesis<D>(q0, l0, fh, fh + D * D, fh + D * D + D, g);
+      int32_t vote = 0;
+      if (fh[D * D + 2 * D] > 0.0) {
+        finite = odom_finite(g, GS) && finite;
+        for (size_t j = 0; j < len; ++j) {
+          const double *f = ent.data() + j * NE;
+          vote += cl_agrees(cl_cost_at<D>(g, q0, l0, f, f + D * D, f + D * D + D, f[D * D + 2 * D], f[D * D + 2 * D + 1]), hv.barc2) ? 1 : 0;
+        }
+      }
+      if (cl_better(vote, static_cast<int32_t>(h), bv, be)) {
+        bv = vote;
+        be = static_cast<int32_t>(h);
+      }
+    }
+    const double *fh = ent.data() + static_cast<size_t>(be) * NE;
+    double *g = hv.cstate.data() + list * GS;
+    cl_hypothesis<D>(q0, l0, fh, fh + D * D, fh + D * D + D, g);
+    hv.cint[list * kClCInts] = be;
+    hv.cint[list * kClCInts + 1] = bv;
+    ist[list * kSgInts] = bv < hv.min_consensus ? 5 : 0;
+    ist[list * kSgInts + 1] = 0;
+    finite = odom_finite(g, GS) && finite;
+  }
+  return finite;
+}
+// pass and fold of one mode over one stage, in the kernels' order; hv: over the inliers of the elected hypotheses only (an
+// entry outside adds +0.0 terms), the folds with status 5 passed through
 template <int D, int MODE>
-bool cl_host_pass_fold(const cora_ctx *c, size_t s, const double *oi, std::vector<double> &partial, std::vector<double> &state, std::vector<int32_t> &ist) {
+bool cl_host_pass_fold(const cora_ctx *c, size_t s, const double *oi, std::vector<double> &partial, std::vector<double> &state, std::vector<int32_t> &ist,
+                       ClHostVote *hv = nullptr) {
   constexpr int NS = MODE == 0 ? kClSums(D) : kClCostSums;
   const ClTables &T = c->cl;
   const size_t nc = std::max<size_t>(T.chunk_begin.size(), 1);
@@ -211,6 +320,11 @@ bool cl_host_pass_fold(const cora_ctx *c, size_t s, const double *oi, std::vecto
         if (i >= T.chunk_len[ch]) continue;
         double P[D * D], q[D], l[D], res, kt[2];
         cl_host_entry<D>(c, oi, static_cast<size_t>(T.chunk_begin[ch]) + i, P, q, l, &res, kt);
+        if (hv) {
+          const bool in = cl_agrees(cl_cost_at<D>(hv->cstate.data() + list * kClCState(D), q0, lm0, P, q, l, kt[0], kt[1]), hv->barc2);
+          if constexpr (MODE == 0) hv->inl[static_cast<size_t>(T.ent_e[static_cast<size_t>(T.chunk_begin[ch]) + i])] = in ? 1 : 0;
+          if (!in) continue;
+        }
         if constexpr (MODE == 0) {
           cl_terms<D>(q0, lm0, P, q, l, kt[0], kt[1], term[lane]);
         } else {
@@ -242,13 +356,16 @@ bool cl_host_pass_fold(const cora_ctx *c, size_t s, const double *oi, std::vecto
       S[k] = ml_host_wave_sum(v);
     }
     cl_host_entry<D>(c, oi, static_cast<size_t>(T.chunk_begin[static_cast<size_t>(T.list_chunk0[list])]), P0, q0, lm0, &res0, kt0);
-    finite = cl_fold<D, MODE>(S, state.data() + list * kSgState(D), ist.data() + list * kSgInts, q0, lm0) && finite;
+    finite = (hv ? cl_fold_robust<D, MODE>(S, state.data() + list * kSgState(D), ist.data() + list * kSgInts, q0, lm0)
+                 : cl_fold<D, MODE>(S, state.data() + list * kSgState(D), ist.data() + list * kSgInts, q0, lm0)) &&
+             finite;
   }
   return finite;
 }
 // the whole placement on the host, in the kernels' order: oi a d-column resident vector; state and ist as on the device
 template <int D>
-bool cl_host_run(const cora_ctx *c, double *oi, std::vector<double> &state, std::vector<int32_t> &ist, unsigned char *deg, int64_t *n_deg) {
+bool cl_host_run(const cora_ctx *c, double *oi, std::vector<double> &state, std::vector<int32_t> &ist, unsigned char *deg, int64_t *n_deg,
+                 ClHostVote *hv = nullptr) {
   const ClTables &T = c->cl;
   const OdomTables &O = c->odom;
   const MeasurementTable &M = c->meas;
@@ -256,8 +373,9 @@ bool cl_host_run(const cora_ctx *c, double *oi, std::vector<double> &state, std:
   bool finite = true;
   std::vector<double> partial(static_cast<size_t>(kClSums(D)) * std::max<size_t>(T.chunk_begin.size(), 1), 0.0);
   for (size_t s = 0; s + 1 < T.stage_list0.size(); ++s) {
-    finite = cl_host_pass_fold<D, 0>(c, s, oi, partial, state, ist) && finite;
-    finite = cl_host_pass_fold<D, 1>(c, s, oi, partial, state, ist) && finite;
+    if (hv) finite = cl_host_vote_elect<D>(c, s, oi, *hv, ist) && finite;
+    finite = cl_host_pass_fold<D, 0>(c, s, oi, partial, state, ist, hv) && finite;
+    finite = cl_host_pass_fold<D, 1>(c, s, oi, partial, state, ist, hv) && finite;
     for (int32_t i = T.stage_apply0[s]; i < T.stage_apply0[s + 1]; ++i) {
       const size_t list = static_cast<size_t>(T.apply_list[static_cast<size_t>(i)]), pos = static_cast<size_t>(T.apply_pos[static_cast<size_t>(i)]);
       if (ist[list * kSgInts + 1] <= 0) continue;
@@ -319,6 +437,95 @@ int cora_closure_placement_order(const cora_ctx *c, int32_t *stage_ptr, int32_t 
   return CORA_OK;
 }
 
+namespace {
+// the consensus setting and the outputs of a robust call (cora_place_by_closures_robust_dev)
+struct ClConsensus {
+  double barc2;
+  int min_consensus;
+  int32_t *consensus, *list_len;
+  unsigned char *inlier;
+};
+int cl_consensus_check(cora_ctx *c, double barc2, int min_consensus) {
+  if (!(barc2 > 0.0) || !std::isfinite(barc2)) return fail(c, CORA_ERR_ARG, "barc2 must be finite and positive");
+  if (min_consensus < 1) return fail(c, CORA_ERR_ARG, "min_consensus must be at least 1");
+  return CORA_OK;
+}
+// what a robust call returns beyond the plain call's: cint [lists][kClCInts], inl [n_edges] (2 where an edge is in no list)
+void cl_robust_results(const cora_ctx *c, const std::vector<int32_t> &ist, const std::vector<int32_t> &cint, const std::vector<unsigned char> &inl,
+                       const ClConsensus &rb, int64_t out[7]) {
+  const ClTables &T = c->cl;
+  const size_t nch = T.chain_init.size(), ne = static_cast<size_t>(c->meas.n_edges);
+  out[5] = out[6] = 0;
+  for (size_t ch = 0; ch < nch; ++ch) {
+    const int32_t list = T.chain_list[ch];
+    if (list >= 0 && ist[static_cast<size_t>(list) * kSgInts] == 5) ++out[5];
+    if (rb.consensus) rb.consensus[ch] = list >= 0 ? cint[static_cast<size_t>(list) * kClCInts + 1] : 0;
+    if (rb.list_len) {
+      const size_t first = list >= 0 ? static_cast<size_t>(T.list_chunk0[static_cast<size_t>(list)]) : 0;
+      const size_t last = list >= 0 ? static_cast<size_t>(T.list_chunk0[static_cast<size_t>(list) + 1]) - 1 : 0;
+      rb.list_len[ch] = list >= 0 ? T.chunk_begin[last] + T.chunk_len[last] - T.chunk_begin[first] : 0;
+    }
+  }
+  for (size_t e = 0; e < ne; ++e) out[6] += inl[e] == 0 ? 1 : 0;
+  if (rb.inlier) std::copy(inl.begin(), inl.begin() + static_cast<std::ptrdiff_t>(ne), rb.inlier);
+}
+// the device-pointer forms: rb null, the plain placement (5 launches per stage); else the consensus vote in front of the
+// masked passes (7 launches per stage)
+int cl_place_dev(cora_ctx *c, double *dX, const ClConsensus *rb, int64_t *out, unsigned char *status, double *cost_start, double *cost_final,
+                 int32_t *chosen, double *transforms, unsigned char *degenerate) {
+  const MeasurementTable &M = c->meas;
+  ClTables &T = c->cl;
+  const int d = c->F.L.d, nb = odom_range_blocks(M.n_ranges);
+  const size_t ns = T.stage_list0.size() - 1, nlist = T.list_item.size(), ne = static_cast<size_t>(M.n_edges);
+  int rc;
+  if ((rc = ensure_red(c, static_cast<size_t>(nb) / 2 + 4))) return rc;
+  ClRobustArgs R;
+  ClArgs &A = R.A;
+  OdomFillArgs Fl;
+  cl_fill_args(c, dX, A, Fl);
+  if (rb) {
+    R.barc2 = rb->barc2;
+    R.min_consensus = rb->min_consensus;
+    R.votes = T.d_votes;
+    R.cstate = T.d_cstate;
+    R.cint = T.d_cint;
+    R.inlier = T.d_inlier;
+  }
+  wrote(c, dX);
+  HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
+  if (rb && ne > 0) HIP_TRY(c, hipMemsetAsync(T.d_inlier, 2, ne, c->stream));  // (an edge of no list)
+  for (size_t s = 0; s < ns; ++s) {  // dependent: a stage reads the rows the stages before it wrote
+    cl_stage_args(T, s, A);
+    if (rb) HIP_TRY(c, launch_closure_vote_elect(R, c->stream));
+    A.mode = 0;
+    HIP_TRY(c, rb ? launch_closure_robust_pass_fold(R, c->stream) : launch_closure_pass_fold(A, c->stream));
+    A.mode = 1;
+    HIP_TRY(c, rb ? launch_closure_robust_pass_fold(R, c->stream) : launch_closure_pass_fold(A, c->stream));
+    HIP_TRY(c, launch_closure_apply(A, c->stream));
+  }
+  HIP_TRY(c, launch_odom_ranges(Fl, c->stream));  // (after the chains' rows)
+  int words[2] = {0, 0};
+  std::vector<double> state(nlist * kSgState(d));
+  std::vector<int32_t> ist(nlist * kSgInts), cint(rb ? nlist * kClCInts : 0);
+  std::vector<unsigned char> inl(rb ? ne : 0);
+  HIP_TRY(c, hipMemcpyAsync(words, Fl.words, sizeof(words), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->h_flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (nlist > 0) {
+    HIP_TRY(c, hipMemcpyAsync(state.data(), T.d_state, state.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(ist.data(), T.d_istate, ist.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (rb) HIP_TRY(c, hipMemcpyAsync(cint.data(), T.d_cint, cint.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (rb && ne > 0) HIP_TRY(c, hipMemcpyAsync(inl.data(), T.d_inlier, ne, hipMemcpyDeviceToHost, c->stream));
+  if (degenerate && M.n_ranges > 0)
+    HIP_TRY(c, hipMemcpyAsync(degenerate, T.d_deg, static_cast<size_t>(M.n_ranges), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (*c->h_flag) return fail(c, CORA_ERR_NAN, rb ? "a sum or a hypothesis of the closure placement is not finite" : "a sum of the closure placement is not finite");
+  cl_results(c, state, ist, words[0], out, status, cost_start, cost_final, chosen, transforms);
+  if (rb) cl_robust_results(c, ist, cint, inl, *rb, out);
+  return CORA_OK;
+}
+}  // namespace
+
 int cora_place_by_closures_dev(cora_ctx *c, double *dX, int64_t out[5], unsigned char *status, double *cost_start, double *cost_final,
                                int32_t *chosen, double *transforms, unsigned char *degenerate) {
   if (!c) return CORA_ERR_ARG;
@@ -326,75 +533,70 @@ int cora_place_by_closures_dev(cora_ctx *c, double *dX, int64_t out[5], unsigned
   if (rc) return rc;
   NEED_DEVICE(c);
   if ((rc = cl_args_check(c, dX, out))) return rc;
-  const Layout &L = c->F.L;
-  const MeasurementTable &M = c->meas;
-  ClTables &T = c->cl;
-  const OdomTables &O = c->odom;
-  const int d = L.d, nb = odom_range_blocks(M.n_ranges);
-  const size_t ns = T.stage_list0.size() - 1, nc = T.chunk_begin.size(), ne = T.ent_e.size(), nlist = T.list_item.size(), na = T.apply_pos.size();
-  if ((rc = ensure_red(c, static_cast<size_t>(nb) / 2 + 4))) return rc;
-  ClArgs A;
-  A.d = d;
-  A.n_edges = M.n_edges;
-  A.pstride = static_cast<int64_t>(std::max<size_t>(nc, 1));
-  A.chunk_begin = T.d_idx;
-  A.chunk_len = A.chunk_begin + nc;
-  A.chunk_list = A.chunk_len + nc;
-  A.list_chunk0 = A.chunk_list + nc;
-  A.ent_e = A.list_chunk0 + nlist + 1;
-  A.ent_dir = A.ent_e + ne;
-  A.apply_pos = A.ent_dir + ne;
-  A.apply_list = A.apply_pos + na;
-  A.pos_rot = O.d_idx + 2 * O.P;
-  A.pos_trn = O.d_idx + 3 * O.P;
-  A.edge_rows = M.d_edge_rows;
-  A.edge_data = M.d_edge_data;
-  A.partial = T.d_partial;
-  A.state = T.d_state;
-  A.istate = T.d_istate;
-  A.x = dX;
-  A.flag = c->d_flag;
-  OdomFillArgs Fl;  // the range-row step of the odometry initialisation, its rules unchanged, over the exchanged table
-  Fl.d = d;
-  Fl.n_ranges = M.n_ranges;
-  Fl.range_rows = T.d_range_rows;
-  Fl.deg = T.d_deg;
-  Fl.partial = reinterpret_cast<int *>(c->d_red);
-  Fl.words = Fl.partial + nb;
-  Fl.flag = c->d_flag;
-  Fl.out = dX;
-  wrote(c, dX);
-  HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
-  for (size_t s = 0; s < ns; ++s) {  // dependent: a stage reads the rows the stages before it wrote
-    A.list0 = T.stage_list0[s];
-    A.n_lists = T.stage_list0[s + 1] - A.list0;
-    A.chunk0 = T.list_chunk0[static_cast<size_t>(A.list0)];
-    A.n_chunks = T.list_chunk0[static_cast<size_t>(T.stage_list0[s + 1])] - A.chunk0;
-    A.apply0 = T.stage_apply0[s];
-    A.n_apply = T.stage_apply0[s + 1] - A.apply0;
-    A.mode = 0;
-    HIP_TRY(c, launch_closure_pass_fold(A, c->stream));
-    A.mode = 1;
-    HIP_TRY(c, launch_closure_pass_fold(A, c->stream));
-    HIP_TRY(c, launch_closure_apply(A, c->stream));
+  return cl_place_dev(c, dX, nullptr, out, status, cost_start, cost_final, chosen, transforms, degenerate);
+}
+
+int cora_place_by_closures_robust_dev(cora_ctx *c, double *dX, double barc2, int min_consensus, int64_t out[7], unsigned char *status,
+                                      double *cost_start, double *cost_final, int32_t *chosen, double *transforms, int32_t *consensus,
+                                      int32_t *list_len, unsigned char *inlier) {
+  if (!c) return CORA_ERR_ARG;
+  int rc = cl_check(c);
+  if (rc) return rc;
+  NEED_DEVICE(c);
+  if ((rc = cl_args_check(c, dX, out)) || (rc = cl_consensus_check(c, barc2, min_consensus))) return rc;
+  const ClConsensus rb{barc2, min_consensus, consensus, list_len, inlier};
+  return cl_place_dev(c, dX, &rb, out, status, cost_start, cost_final, chosen, transforms, nullptr);
+}
+
+namespace {
+// the host-pointer forms: upload, the device-pointer form, download
+int cl_place_host_ptr(cora_ctx *c, double *X, int ldx, const ClConsensus *rb, int64_t *out, unsigned char *status, double *cost_start,
+                      double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate) {
+  if (ldx < c->F.L.N) return fail(c, CORA_ERR_SHAPE, "leading dimension smaller than N");
+  const int d = c->F.L.d;
+  double *dX;
+  int rc;
+  if ((rc = compare_vec(c, 3, ld_for(d), &dX))) return rc;
+  rc = upload_impl(c, X, ldx, d, dX);
+  if (rc == CORA_OK) rc = cl_place_dev(c, dX, rb, out, status, cost_start, cost_final, chosen, transforms, degenerate);
+  if (rc == CORA_OK) rc = download_impl(c, dX, d, X, ldx);
+  // the vector of this form is not kept: a caller that stays resident uses the device-pointer form
+  (void)hipStreamSynchronize(c->stream);
+  compare_release(c, 3, 4, 0);
+  return rc;
+}
+// The same on the host through the translated tables, every sum in the kernels' bracket order and every term, hypothesis and
+// solve through the functions of kernels.h the kernels call: the output has the device's bits.  Works on a plan-only handle.
+int cl_place_mirror(cora_ctx *c, double *X, int ldx, const ClConsensus *rb, int64_t *out, unsigned char *status, double *cost_start,
+                    double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate) {
+  const HostFormat &F = c->F;
+  const Layout &L = F.L;
+  if (ldx < L.N) return fail(c, CORA_ERR_SHAPE, "leading dimension smaller than N");
+  const int d = L.d;
+  const size_t nlist = c->cl.list_item.size();
+  std::vector<double> oi(static_cast<size_t>(L.rows) * d, 0.0), state(nlist * kSgState(d), 0.0);
+  std::vector<int32_t> ist(nlist * kSgInts, 0);
+  ClHostVote hv;
+  if (rb) {
+    hv.barc2 = rb->barc2;
+    hv.min_consensus = rb->min_consensus;
+    hv.cstate.assign(nlist * kClCState(d), 0.0);
+    hv.cint.assign(nlist * kClCInts, 0);
+    hv.inl.assign(static_cast<size_t>(c->meas.n_edges), 2);
   }
-  HIP_TRY(c, launch_odom_ranges(Fl, c->stream));  // (after the chains' rows)
-  int words[2] = {0, 0};
-  std::vector<double> state(nlist * kSgState(d));
-  std::vector<int32_t> ist(nlist * kSgInts);
-  HIP_TRY(c, hipMemcpyAsync(words, Fl.words, sizeof(words), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->h_flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (nlist > 0) {
-    HIP_TRY(c, hipMemcpyAsync(state.data(), T.d_state, state.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(ist.data(), T.d_istate, ist.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  }
-  if (degenerate && M.n_ranges > 0)
-    HIP_TRY(c, hipMemcpyAsync(degenerate, T.d_deg, static_cast<size_t>(M.n_ranges), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (*c->h_flag) return fail(c, CORA_ERR_NAN, "a sum of the closure placement is not finite");
-  cl_results(c, state, ist, words[0], out, status, cost_start, cost_final, chosen, transforms);
+  for (int cc = 0; cc < d; ++cc)
+    for (int64_t i = 0; i < L.N; ++i) oi[static_cast<size_t>(F.api2int[i]) * d + cc] = X[static_cast<size_t>(cc) * ldx + i];
+  int64_t n_deg = 0;
+  const bool finite = d == 2 ? cl_host_run<2>(c, oi.data(), state, ist, degenerate, &n_deg, rb ? &hv : nullptr)
+                             : cl_host_run<3>(c, oi.data(), state, ist, degenerate, &n_deg, rb ? &hv : nullptr);
+  if (!finite) return fail(c, CORA_ERR_NAN, rb ? "a sum or a hypothesis of the closure placement is not finite" : "a sum of the closure placement is not finite");
+  for (int cc = 0; cc < d; ++cc)
+    for (int64_t i = 0; i < L.N; ++i) X[static_cast<size_t>(cc) * ldx + i] = oi[static_cast<size_t>(F.api2int[i]) * d + cc];
+  cl_results(c, state, ist, n_deg, out, status, cost_start, cost_final, chosen, transforms);
+  if (rb) cl_robust_results(c, ist, hv.cint, hv.inl, *rb, out);
   return CORA_OK;
 }
+}  // namespace
 
 int cora_place_by_closures(cora_ctx *c, double *X, int ldx, int64_t out[5], unsigned char *status, double *cost_start, double *cost_final,
                            int32_t *chosen, double *transforms, unsigned char *degenerate) {
@@ -403,41 +605,37 @@ int cora_place_by_closures(cora_ctx *c, double *X, int ldx, int64_t out[5], unsi
   if (rc) return rc;
   NEED_DEVICE(c);
   if ((rc = cl_args_check(c, X, out))) return rc;
-  if (ldx < c->F.L.N) return fail(c, CORA_ERR_SHAPE, "leading dimension smaller than N");
-  const int d = c->F.L.d;
-  double *dX;
-  if ((rc = compare_vec(c, 3, ld_for(d), &dX))) return rc;
-  rc = upload_impl(c, X, ldx, d, dX);
-  if (rc == CORA_OK) rc = cora_place_by_closures_dev(c, dX, out, status, cost_start, cost_final, chosen, transforms, degenerate);
-  if (rc == CORA_OK) rc = download_impl(c, dX, d, X, ldx);
-  // the vector of this form is not kept: a caller that stays resident uses cora_place_by_closures_dev
-  (void)hipStreamSynchronize(c->stream);
-  compare_release(c, 3, 4, 0);
-  return rc;
+  return cl_place_host_ptr(c, X, ldx, nullptr, out, status, cost_start, cost_final, chosen, transforms, degenerate);
 }
 
-// The same on the host through the translated tables, every sum in the kernels' bracket order and every term and solve
-// through the functions of kernels.h the kernels call: the output has the device's bits.  Works on a plan-only handle.
+int cora_place_by_closures_robust(cora_ctx *c, double *X, int ldx, double barc2, int min_consensus, int64_t out[7], unsigned char *status,
+                                  double *cost_start, double *cost_final, int32_t *chosen, double *transforms, int32_t *consensus,
+                                  int32_t *list_len, unsigned char *inlier) {
+  if (!c) return CORA_ERR_ARG;
+  int rc = cl_check(c);
+  if (rc) return rc;
+  NEED_DEVICE(c);
+  if ((rc = cl_args_check(c, X, out)) || (rc = cl_consensus_check(c, barc2, min_consensus))) return rc;
+  const ClConsensus rb{barc2, min_consensus, consensus, list_len, inlier};
+  return cl_place_host_ptr(c, X, ldx, &rb, out, status, cost_start, cost_final, chosen, transforms, nullptr);
+}
+
 int cora_debug_place_by_closures_host(cora_ctx *c, double *X, int ldx, int64_t out[5], unsigned char *status, double *cost_start,
                                       double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate) {
   if (!c) return CORA_ERR_ARG;
   int rc = cl_check(c);
   if (rc) return rc;
   if ((rc = cl_args_check(c, X, out))) return rc;
-  const HostFormat &F = c->F;
-  const Layout &L = F.L;
-  if (ldx < L.N) return fail(c, CORA_ERR_SHAPE, "leading dimension smaller than N");
-  const int d = L.d;
-  const size_t nlist = c->cl.list_item.size();
-  std::vector<double> oi(static_cast<size_t>(L.rows) * d, 0.0), state(nlist * kSgState(d), 0.0);
-  std::vector<int32_t> ist(nlist * kSgInts, 0);
-  for (int cc = 0; cc < d; ++cc)
-    for (int64_t i = 0; i < L.N; ++i) oi[static_cast<size_t>(F.api2int[i]) * d + cc] = X[static_cast<size_t>(cc) * ldx + i];
-  int64_t n_deg = 0;
-  const bool finite = d == 2 ? cl_host_run<2>(c, oi.data(), state, ist, degenerate, &n_deg) : cl_host_run<3>(c, oi.data(), state, ist, degenerate, &n_deg);
-  if (!finite) return fail(c, CORA_ERR_NAN, "a sum of the closure placement is not finite");
-  for (int cc = 0; cc < d; ++cc)
-    for (int64_t i = 0; i < L.N; ++i) X[static_cast<size_t>(cc) * ldx + i] = oi[static_cast<size_t>(F.api2int[i]) * d + cc];
-  cl_results(c, state, ist, n_deg, out, status, cost_start, cost_final, chosen, transforms);
-  return CORA_OK;
+  return cl_place_mirror(c, X, ldx, nullptr, out, status, cost_start, cost_final, chosen, transforms, degenerate);
+}
+
+int cora_debug_place_by_closures_robust_host(cora_ctx *c, double *X, int ldx, double barc2, int min_consensus, int64_t out[7],
+                                             unsigned char *status, double *cost_start, double *cost_final, int32_t *chosen, double *transforms,
+                                             int32_t *consensus, int32_t *list_len, unsigned char *inlier) {
+  if (!c) return CORA_ERR_ARG;
+  int rc = cl_check(c);
+  if (rc) return rc;
+  if ((rc = cl_args_check(c, X, out)) || (rc = cl_consensus_check(c, barc2, min_consensus))) return rc;
+  const ClConsensus rb{barc2, min_consensus, consensus, list_len, inlier};
+  return cl_place_mirror(c, X, ldx, &rb, out, status, cost_start, cost_final, chosen, transforms, nullptr);
 }

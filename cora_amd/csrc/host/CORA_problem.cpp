@@ -1189,10 +1189,13 @@ Matrix Problem::sightingInitialization(uint64_t seed, int gn_steps, int min_rang
 
 Matrix Problem::closureInitialization(uint64_t seed, int gn_steps, int min_ranges, int min_sightings, int min_closures,
                                       ClosurePlacementInfo *closure_info, SightingPlacementInfo *sight_info, ChainPlacementInfo *chains_info,
-                                      LandmarkInitInfo *info) const {
+                                      LandmarkInitInfo *info, ClosureConsensus consensus) const {
   if (gn_steps < 0) throw std::invalid_argument("Problem::closureInitialization: gn_steps must be in [0, 16]");
+  if (!std::isfinite(consensus.barc2)) throw std::invalid_argument("Problem::closureInitialization: the consensus threshold must be finite");
+  if (consensus.barc2 > 0 && consensus.min_consensus < 1)
+    throw std::invalid_argument("Problem::closureInitialization: min_consensus must be at least 1");
   return odometryStart(seed, gn_steps, info, "Problem::closureInitialization", true, min_ranges, chains_info, true, min_sightings, sight_info, true,
-                       min_closures, closure_info);
+                       min_closures, closure_info, consensus);
 }
 
 // the odometry start; with gn_steps >= 0 the landmarks are then placed from the ranges (cora_multilaterate_dev), with
@@ -1201,7 +1204,7 @@ Matrix Problem::closureInitialization(uint64_t seed, int gn_steps, int min_range
 // edges between chains (cora_place_by_closures_dev)
 Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where, bool place, int min_ranges,
                               ChainPlacementInfo *chains_info, bool sightings, int min_sightings, SightingPlacementInfo *sight_info, bool closures,
-                              int min_closures, ClosurePlacementInfo *closure_info) const {
+                              int min_closures, ClosurePlacementInfo *closure_info, ClosureConsensus consensus) const {
   checkUpToDate();
   if (part_world_ > 1) throw std::runtime_error(std::string(where) + ": not supported on a partitioned handle");
   ensureMeasurementTable();
@@ -1266,12 +1269,21 @@ Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *inf
     // moves nothing and fixes chain 0 alone, the sighting placement's default; its range rows are written again below.)
     const size_t nch = chains.size(), G = static_cast<size_t>(d) * d + d;
     CORA_CALL(cora_set_closure_placement(c, nullptr, min_closures > 0 ? min_closures : 1), where);
-    int64_t out[5] = {0, 0, 0, 0, 0}, tc[4] = {0, 0, 0, 0};
+    int64_t out[7] = {0, 0, 0, 0, 0, 0, 0}, tc[4] = {0, 0, 0, 0}, mc[2] = {0, 0};
+    const bool robust = consensus.barc2 > 0;
     std::vector<unsigned char> status(nch + 1, 0);
     std::vector<int32_t> chosen(nch + 1, 0);
     std::vector<double> cs(nch + 1, 0.0), cf(nch + 1, 0.0), tr(nch * G + 1, 0.0);
     CORA_CALL(cora_closure_placement_counts(c, tc), where);
-    CORA_CALL(cora_place_by_closures_dev(c, v.x, out, status.data(), cs.data(), cf.data(), chosen.data(), tr.data(), nullptr), where);
+    CORA_CALL(cora_measurement_counts(c, mc), where);
+    std::vector<int32_t> votes(robust ? nch + 1 : 0, 0), lens(robust ? nch + 1 : 0, 0);
+    std::vector<unsigned char> inlier(robust ? static_cast<size_t>(mc[0]) + 1 : 0, 0);
+    if (robust)  // (a chain without consensus, status 5, is handed on like a refused one)
+      CORA_CALL(cora_place_by_closures_robust_dev(c, v.x, consensus.barc2, consensus.min_consensus, out, status.data(), cs.data(), cf.data(),
+                                                  chosen.data(), tr.data(), votes.data(), lens.data(), inlier.data()),
+                where);
+    else
+      CORA_CALL(cora_place_by_closures_dev(c, v.x, out, status.data(), cs.data(), cf.data(), chosen.data(), tr.data(), nullptr), where);
     closure_done.assign(nch + 1, 0);
     long fixed = 0;
     for (size_t ch = 0; ch < nch; ++ch) {
@@ -1291,6 +1303,11 @@ Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *inf
       closure_info->cost_final.assign(cf.begin(), cf.begin() + static_cast<std::ptrdiff_t>(nch));
       closure_info->chosen.assign(chosen.begin(), chosen.begin() + static_cast<std::ptrdiff_t>(nch));
       closure_info->transforms.assign(tr.begin(), tr.begin() + static_cast<std::ptrdiff_t>(nch * G));
+      closure_info->chains_no_consensus = static_cast<long>(out[5]);
+      closure_info->closures_excluded = static_cast<long>(out[6]);
+      closure_info->consensus.assign(votes.begin(), votes.begin() + static_cast<std::ptrdiff_t>(robust ? nch : 0));
+      closure_info->list_len.assign(lens.begin(), lens.begin() + static_cast<std::ptrdiff_t>(robust ? nch : 0));
+      closure_info->inlier.assign(inlier.begin(), inlier.begin() + static_cast<std::ptrdiff_t>(robust ? mc[0] : 0));
     }
   }
   // per chain: fixed or placed by the sighting step (the fixed chains of the range placement); per landmark: placed by it

@@ -194,6 +194,20 @@ struct ClosurePlacementInfo {
   std::vector<Scalar> cost_start, cost_final;  // per chain: the closure cost of its list, before and as applied
   std::vector<int32_t> chosen;         // per chain: 1 moved, 0 left where it stood, -1 no list
   std::vector<Scalar> transforms;      // per chain d * d + d: G row-major, then s, as applied
+  // with a consensus vote (ClosureConsensus; status 5: taken, no consensus); empty / 0 without one
+  long chains_no_consensus = 0, closures_excluded = 0;  // status 5; entries outside the inliers of their lists
+  std::vector<int32_t> consensus, list_len;  // per chain: the vote of the elected closure, the closures of the chain's list
+  std::vector<unsigned char> inlier;   // per edge of the measurement table: 1 inlier | 0 in a list, not an inlier | 2 in no list
+};
+
+/** The consensus vote of the closure step (cora_place_by_closures_robust_dev, include/cora_hip.h).  barc2 <= 0: off, the
+ * plain least-squares placement and its bits.  barc2 > 0: every closure of a list proposes a motion, the one most closures
+ * agree with (coupled rot + trans residual <= barc2, the quantity the GNC weights threshold) is elected and the fit runs over
+ * the agreeing closures only; a chain whose elected closure has fewer than min_consensus votes keeps its rows (status 5) and
+ * is handed to the later steps like a refused one. */
+struct ClosureConsensus {
+  Scalar barc2 = 0;
+  int min_consensus = 2;
 };
 
 class Problem {
@@ -282,7 +296,7 @@ class Problem {
   Matrix odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where, bool place = false, int min_ranges = 0,
                        ChainPlacementInfo *chains_info = nullptr, bool sightings = false, int min_sightings = 0,
                        SightingPlacementInfo *sight_info = nullptr, bool closures = false, int min_closures = 0,
-                       ClosurePlacementInfo *closure_info = nullptr) const;
+                       ClosurePlacementInfo *closure_info = nullptr, ClosureConsensus consensus = ClosureConsensus()) const;
   void fillImplicitFormulationMatrices() const;
   [[noreturn]] void throwLast(int status, const char *where) const;
 
@@ -522,10 +536,13 @@ class Problem {
    * order (the new step draws nothing), then the closure placement, then the sighting placement with every chain of
    * closure status 0 or 4 as its fixed set, then cora_place_chains_dev for the chains still left, the multilateration, the
    * range rows and the lift: one pipeline (odometryStart) with one more step.  On a problem without inter-chain closures
-   * the result has sightingInitialization's bits.  min_closures <= 0: 1.  std::runtime_error on a partitioned handle. */
+   * the result has sightingInitialization's bits.  min_closures <= 0: 1.  consensus: the outlier-robust closure step
+   * (ClosureConsensus; the default is off: the same bits as without the argument); std::invalid_argument for a barc2 that is
+   * not finite or a min_consensus below 1.  std::runtime_error on a partitioned handle. */
   Matrix closureInitialization(uint64_t seed = 7, int gn_steps = 5, int min_ranges = 0, int min_sightings = 0, int min_closures = 0,
                                ClosurePlacementInfo *closure_info = nullptr, SightingPlacementInfo *sight_info = nullptr,
-                               ChainPlacementInfo *chains_info = nullptr, LandmarkInitInfo *info = nullptr) const;
+                               ChainPlacementInfo *chains_info = nullptr, LandmarkInitInfo *info = nullptr,
+                               ClosureConsensus consensus = ClosureConsensus()) const;
 
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;

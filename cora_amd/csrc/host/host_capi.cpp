@@ -255,6 +255,8 @@ int cora_problem_op(cora_problem *p, const char *op, int cols, const double *A, 
     else if (o == "multiRobotInitialization") res = q.multiRobotInitialization();
     else if (o == "sightingInitialization") res = q.sightingInitialization();
     else if (o == "closureInitialization") res = q.closureInitialization();
+    else if (o == "closureInitializationConsensus")  // (the operator form takes no arguments: barc2 = 200, min_consensus = 2)
+      res = q.closureInitialization(7, 5, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, ClosureConsensus{200.0, 2});
     else if (o == "getTranslationExplicitSolution") res = q.getTranslationExplicitSolution(wrap(A, N, r));
     else if (o == "alignEstimateToOrigin") res = q.alignEstimateToOrigin(wrap(A, N, r));
     else throw std::invalid_argument("unknown operator " + o);
@@ -384,12 +386,35 @@ int cora_problem_closure_initialization(cora_problem *p, uint64_t seed, int gn_s
                                         int32_t *chosen, double *transforms, int64_t sighting_counts[6], unsigned char *sighting_status,
                                         unsigned char *landmark_status, int64_t chain_counts[4], unsigned char *chain_status,
                                         int64_t landmark_counts[4], unsigned char *range_landmark_status) {
+  return cora_problem_closure_initialization_consensus(p, seed, gn_steps, min_ranges, min_sightings, min_closures, 0.0, 2, out, counts, status,
+                                                       cost_start, cost_final, chosen, transforms, nullptr, nullptr, nullptr, nullptr,
+                                                       sighting_counts, sighting_status, landmark_status, chain_counts, chain_status,
+                                                       landmark_counts, range_landmark_status);
+}
+
+int cora_problem_closure_initialization_consensus(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, int min_sightings, int min_closures,
+                                                  double consensus_barc2, int min_consensus, double *out, int64_t counts[7],
+                                                  unsigned char *status, double *cost_start, double *cost_final, int32_t *chosen,
+                                                  double *transforms, int64_t consensus_counts[2], int32_t *consensus, int32_t *list_len,
+                                                  unsigned char *inlier, int64_t sighting_counts[6], unsigned char *sighting_status,
+                                                  unsigned char *landmark_status, int64_t chain_counts[4], unsigned char *chain_status,
+                                                  int64_t landmark_counts[4], unsigned char *range_landmark_status) {
   return guarded([&] {
     ClosurePlacementInfo li;
     SightingPlacementInfo si;
     ChainPlacementInfo ci;
     LandmarkInitInfo info;
-    const Matrix res = p->problem.closureInitialization(seed, gn_steps, min_ranges, min_sightings, min_closures, &li, &si, &ci, &info);
+    ClosureConsensus vote;
+    vote.barc2 = consensus_barc2;
+    vote.min_consensus = min_consensus;
+    const Matrix res = p->problem.closureInitialization(seed, gn_steps, min_ranges, min_sightings, min_closures, &li, &si, &ci, &info, vote);
+    if (consensus_counts) {
+      consensus_counts[0] = li.chains_no_consensus;
+      consensus_counts[1] = li.closures_excluded;
+    }
+    if (consensus) std::copy(li.consensus.begin(), li.consensus.end(), consensus);
+    if (list_len) std::copy(li.list_len.begin(), li.list_len.end(), list_len);
+    if (inlier) std::copy(li.inlier.begin(), li.inlier.end(), inlier);
     if (res.rows() == p->problem.getExpectedVariableSize()) p->problem.checkVariablesAreValid(res);  // (throws off the manifold)
     std::memcpy(out, res.data(), sizeof(double) * static_cast<size_t>(res.size()));
     if (counts) {

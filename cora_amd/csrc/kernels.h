@@ -1872,29 +1872,40 @@ __host__ __device__ inline int cl_solve(const double *S, const double *q0, const
   }
   return 0;
 }
-// the cost of one entry at g: kappa |G - P|_F^2 (from +0.0, row-major) + tau |G q' + s' - l'|^2
+// the cost of one entry at g from its relative coordinates q' = q - q_0, l' = l - l_0: kappa |G - P|_F^2 (from +0.0,
+// row-major) + tau |G q' + s' - l'|^2
 template <int D>
-__host__ __device__ inline double cl_cost_at(const double *g, const double *q0, const double *l0, const double *P, const double *q, const double *l,
-                                             double kappa, double tau) {
+__host__ __device__ inline double cl_cost_rel(const double *g, const double *P, const double *qq, const double *ll, double kappa, double tau) {
 #pragma clang fp contract(off)
   constexpr int G = kSgG(D);
-  double rot = 0.0, trn = 0.0, qq[D];
+  double rot = 0.0, trn = 0.0;
 #pragma unroll
   for (int i = 0; i < D * D; ++i) {
     const double r = g[i] - P[i];
     rot = fma(r, r, rot);
   }
 #pragma unroll
-  for (int c = 0; c < D; ++c) qq[c] = q[c] - q0[c];
-#pragma unroll
   for (int a = 0; a < D; ++a) {
     double v = g[G + a];
 #pragma unroll
     for (int k = 0; k < D; ++k) v = fma(g[a * D + k], qq[k], v);
-    const double r = v - (l[a] - l0[a]);
+    const double r = v - ll[a];
     trn = fma(r, r, trn);
   }
   return kappa * rot + tau * trn;
+}
+// the cost of one entry at g: cl_cost_rel at q' = q - q_0, l' = l - l_0 (the same operations in the same order)
+template <int D>
+__host__ __device__ inline double cl_cost_at(const double *g, const double *q0, const double *l0, const double *P, const double *q, const double *l,
+                                             double kappa, double tau) {
+#pragma clang fp contract(off)
+  double qq[D], ll[D];
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    qq[c] = q[c] - q0[c];
+    ll[c] = l[c] - l0[c];
+  }
+  return cl_cost_rel<D>(g, P, qq, ll, kappa, tau);
 }
 // what lane 0 of a list's fold does with the list's sums S in mode MODE (0 solve, 1 costs); q0, l0: the first entry's.
 // False where a sum is not finite.
@@ -1913,6 +1924,78 @@ __host__ __device__ inline bool cl_fold(const double *S, double *st, int32_t *is
     ist[1] = ist[0] == 0 && S[1] < S[0] ? 1 : 0;
     st[G + D] = S[0];
     st[G + D + 1] = ist[1] ? S[1] : S[0];  // the cost of what is applied
+  }
+  return finite;
+}
+
+// Outlier-robust placement from closures: a consensus vote over minimal hypotheses (kernels/closure.inc; include/cora_hip.h,
+// cora_place_by_closures_robust_dev).  Tables, stages, lists and chunks are the plain placement's.  Every entry h
+// of a list with kappa_h > 0 proposes the motion g_h its one edge determines (cl_hypothesis); every entry j is scored under
+// every proposal, r(h, j) = cl_cost_at(g_h, .., entry j); vote(h) = #{j : r(h, j) <= barc2} (cl_agrees: a NaN is no vote; an
+// invalid h has vote 0).  Elected: the largest vote, among equal votes the lowest entry (cl_better); consensus = its vote;
+// consensus < min_consensus: status 5, the chain keeps its rows.  I = {j : r(h*, j) <= barc2}; the sums and the two costs of
+// the plain placement run over I alone: AN ENTRY OUTSIDE I ADDS +0.0 FOR EACH OF ITS TERMS, exactly as a lane beyond the
+// chunk's end does, so the bracket order of a sum is the plain placement's.  Seven launches per stage:
+//   vote, elect, pass and fold of the sums over I, pass and fold of the two costs over I, apply.
+constexpr int kClCState(int d) { return kSgG(d) + d; }  // of the elected hypothesis: G | s | s'
+constexpr int kClCInts = 2;                             // elected entry (index in its list) | consensus
+struct ClRobustArgs {
+  ClArgs A;
+  double barc2 = 0.0;
+  int min_consensus = 0;
+  int32_t *votes = nullptr;         // [entries]
+  double *cstate = nullptr;         // [lists][kClCState(d)]
+  int32_t *cint = nullptr;          // [lists][kClCInts]
+  unsigned char *inlier = nullptr;  // [n_edges]: written where an edge is an entry, 1 in I | 0 outside
+};
+hipError_t launch_closure_vote_elect(const ClRobustArgs &R, hipStream_t st);      // k_cl_vote and k_cl_elect over the stage
+hipError_t launch_closure_robust_pass_fold(const ClRobustArgs &R, hipStream_t st);  // masked pass and fold of R.A.mode
+// The motion entry h proposes: G = P as cl_entry produced it, s'[a] = (l[a] - l_0[a]) - sum_k G[a][k] (q[k] - q_0[k]) (the sum
+// from +0.0, k ascending), s = (s' + l_0) - G q_0 as cl_solve writes it.  g: G | s | s'.
+template <int D>
+__host__ __device__ inline void cl_hypothesis(const double *q0, const double *l0, const double *P, const double *q, const double *l, double *g) {
+#pragma clang fp contract(off)
+  constexpr int G = kSgG(D);
+  double qq[D];
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) g[i] = P[i];
+#pragma unroll
+  for (int c = 0; c < D; ++c) qq[c] = q[c] - q0[c];
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    double rq = 0.0, r0 = 0.0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      rq = fma(P[a * D + k], qq[k], rq);
+      r0 = fma(P[a * D + k], q0[k], r0);
+    }
+    const double tr = (l[a] - l0[a]) - rq;
+    g[G + a] = tr;
+    g[D * D + a] = (tr + l0[a]) - r0;
+  }
+}
+__host__ __device__ inline bool cl_agrees(double r, double barc2) { return r <= barc2; }  // (a NaN is no vote)
+// the election's order: (vote, entry) beats (v, e)
+__host__ __device__ inline bool cl_better(int32_t vote, int32_t entry, int32_t v, int32_t e) { return vote > v || (vote == v && entry < e); }
+// cl_fold with status 5 passed through: a list without consensus has the identity (as a refused one) and is never chosen
+template <int D, int MODE>
+__host__ __device__ inline bool cl_fold_robust(const double *S, double *st, int32_t *ist, const double *q0, const double *l0) {
+  constexpr int G = kSgG(D);
+  if (ist[0] != 5) return cl_fold<D, MODE>(S, st, ist, q0, l0);
+  const bool finite = odom_finite(S, MODE == 0 ? kClSums(D) : kClCostSums);
+  if constexpr (MODE == 0) {
+#pragma unroll
+    for (int i = 0; i < D * D; ++i) st[i] = i / D == i % D ? 1.0 : 0.0;
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+      st[D * D + c] = 0.0;
+      st[G + c] = q0[c] - l0[c];
+    }
+    ist[1] = 0;
+  } else {
+    ist[1] = 0;
+    st[G + D] = S[0];
+    st[G + D + 1] = S[0];
   }
   return finite;
 }

@@ -662,6 +662,38 @@ hipError_t launch_closure_pass_fold(const ClArgs &A, hipStream_t st) {
   }
   return hipGetLastError();
 }
+// the consensus vote of the robust placement: one workgroup per chunk, then one wavefront per list
+static bool closure_robust_args_ok(const ClRobustArgs &R) {
+  return closure_args_ok(R.A) && R.barc2 > 0.0 && R.min_consensus >= 1 && R.votes && R.cstate && R.cint && R.inlier;
+}
+hipError_t launch_closure_vote_elect(const ClRobustArgs &R, hipStream_t st) {
+  if (!closure_robust_args_ok(R)) return hipErrorInvalidValue;
+  const dim3 chunks(static_cast<unsigned>(R.A.n_chunks)), lists(static_cast<unsigned>(R.A.n_lists));
+  if (R.A.d == 2) {
+    hipLaunchKernelGGL(k_cl_vote<2>, chunks, dim3(kClChunk), 0, st, R);
+    hipLaunchKernelGGL(k_cl_elect<2>, lists, dim3(kWave), 0, st, R);
+  } else {
+    hipLaunchKernelGGL(k_cl_vote<3>, chunks, dim3(kClChunk), 0, st, R);
+    hipLaunchKernelGGL(k_cl_elect<3>, lists, dim3(kWave), 0, st, R);
+  }
+  return hipGetLastError();
+}
+template <int D, int MODE>
+static void closure_robust_pass_fold(const ClRobustArgs &R, hipStream_t st) {
+  hipLaunchKernelGGL((k_cl_pass_robust<D, MODE>), dim3(static_cast<unsigned>(R.A.n_chunks)), dim3(kClChunk), 0, st, R);
+  hipLaunchKernelGGL((k_cl_fold_robust<D, MODE>), dim3(static_cast<unsigned>(R.A.n_lists)), dim3(kWave), 0, st, R);
+}
+hipError_t launch_closure_robust_pass_fold(const ClRobustArgs &R, hipStream_t st) {
+  if (!closure_robust_args_ok(R) || R.A.mode < 0 || R.A.mode > 1) return hipErrorInvalidValue;
+  if (R.A.d == 2) {
+    if (R.A.mode == 0) closure_robust_pass_fold<2, 0>(R, st);
+    else closure_robust_pass_fold<2, 1>(R, st);
+  } else {
+    if (R.A.mode == 0) closure_robust_pass_fold<3, 0>(R, st);
+    else closure_robust_pass_fold<3, 1>(R, st);
+  }
+  return hipGetLastError();
+}
 // the lists' state has the sighting placement's layout: its apply kernel serves, reading only these fields
 hipError_t launch_closure_apply(const ClArgs &A, hipStream_t st) {
   if (!closure_args_ok(A) || A.n_apply <= 0 || A.apply0 < 0 || !A.apply_pos || !A.apply_list || !A.pos_rot || !A.pos_trn) return hipErrorInvalidValue;

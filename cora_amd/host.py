@@ -201,6 +201,7 @@ class Problem:
         pa, pb, pc = ptr(A), ptr(B), ptr(C_)
         if name != "evaluateObjective":
             full = name in ("getOdomInitialization", "odometryInitialization", "rangeAidedInitialization", "multiRobotInitialization", "sightingInitialization", "closureInitialization",
+                            "closureInitializationConsensus",
                             "getTranslationExplicitSolution", "alignEstimateToOrigin")
             out = np.zeros((dm["N"] if full else N, cols[0] if cols else p), order="F")
         if len(set(cols)) > 1:
@@ -282,28 +283,43 @@ class Problem:
                          landmarks=dict(solved=int(lcnt[0]), not_solved=int(lcnt[1]), n_degenerate=int(lcnt[2]), steps=int(lcnt[3]),
                                         status=rls[:nl]))
 
-    def closure_initialization(self, seed=7, gn_steps=5, min_ranges=0, min_sightings=0, min_closures=0):
+    def closure_initialization(self, seed=7, gn_steps=5, min_ranges=0, min_sightings=0, min_closures=0, consensus_barc2=None, min_consensus=2):
         """Problem::closureInitialization: (x0, info) with info a dict fixed, placed, not_placed, refused, stages,
         closures_used, edges_skipped, status, cost_start, cost_final, chosen, transforms (per chain of odometry_chains()) of
         the closure step; sightings (fixed, placed, not_placed, landmarks_placed, landmarks_not_placed, stages, status,
         landmark_status of the sighting step that followed), chains and landmarks as sighting_initialization has them.
-        0: the defaults.  The start has passed checkVariablesAreValid."""
+        0: the defaults.  The start has passed checkVariablesAreValid.
+        consensus_barc2: None, the plain closure step; a threshold > 0, the closure step with a consensus vote
+        (ClosureConsensus, CORA_problem.h): the fit of a chain runs over the closures that agree with the elected one, a chain
+        whose elected closure has fewer than min_consensus votes has status 5, and info gains no_consensus, excluded, consensus
+        and list_len (per chain) and inlier (per edge of the measurement table, relative poses first: 1 | 0 | 2 in no list)."""
         dm = self.dims()
         d = dm["d"]
         nl = dm["N"] - (d + 1) * dm["n"] - dm["r"]
         nch = len(self.odometry_chains())
+        robust = consensus_barc2 is not None
+        if robust and not consensus_barc2 > 0:
+            raise HostError("consensus_barc2 must be positive (None: no consensus vote)")
+        mcnt, vcnt = (C.c_int64 * 5)(), (C.c_int64 * 2)()
+        self._chk(self.L.cora_problem_measurement_counts(self.h, mcnt))
+        ne = int(sum(mcnt[:4]))
+        cons, ll, inl = np.zeros(nch + 1, dtype=np.int32), np.zeros(nch + 1, dtype=np.int32), np.zeros(ne + 1, dtype=np.uint8)
+        i32 = C.POINTER(C.c_int32)
         out = np.zeros((dm["N"], dm["rank"]), order="F")
         cnt, scnt, ccnt, lcnt = (C.c_int64 * 7)(), (C.c_int64 * 6)(), (C.c_int64 * 4)(), (C.c_int64 * 4)()
         status, sstatus, cstatus = (np.zeros(nch + 1, dtype=np.uint8) for _ in range(3))
         chosen = np.zeros(nch + 1, dtype=np.int32)
         ls, rls = np.zeros(nl + 1, dtype=np.uint8), np.zeros(nl + 1, dtype=np.uint8)
         cs, cf, tr = np.zeros(nch + 1), np.zeros(nch + 1), np.zeros(nch * (d * d + d) + 1)
-        self._chk(self.L.cora_problem_closure_initialization(
-            self.h, C.c_uint64(seed), int(gn_steps), int(min_ranges), int(min_sightings), int(min_closures), out.ctypes.data_as(_dp), cnt,
-            status.ctypes.data_as(C.c_void_p), cs.ctypes.data_as(_dp), cf.ctypes.data_as(_dp), chosen.ctypes.data_as(C.POINTER(C.c_int32)),
-            tr.ctypes.data_as(_dp), scnt, sstatus.ctypes.data_as(C.c_void_p), ls.ctypes.data_as(C.c_void_p), ccnt,
-            cstatus.ctypes.data_as(C.c_void_p), lcnt, rls.ctypes.data_as(C.c_void_p)))
-        return out, dict(fixed=int(cnt[0]), placed=int(cnt[1]), not_placed=int(cnt[2]), refused=int(cnt[3]), stages=int(cnt[4]),
+        self._chk(self.L.cora_problem_closure_initialization_consensus(
+            self.h, C.c_uint64(seed), int(gn_steps), int(min_ranges), int(min_sightings), int(min_closures),
+            C.c_double(consensus_barc2 if robust else 0.0), int(min_consensus), out.ctypes.data_as(_dp), cnt,
+            status.ctypes.data_as(C.c_void_p), cs.ctypes.data_as(_dp), cf.ctypes.data_as(_dp), chosen.ctypes.data_as(i32),
+            tr.ctypes.data_as(_dp), vcnt, cons.ctypes.data_as(i32), ll.ctypes.data_as(i32), inl.ctypes.data_as(C.c_void_p), scnt,
+            sstatus.ctypes.data_as(C.c_void_p), ls.ctypes.data_as(C.c_void_p), ccnt, cstatus.ctypes.data_as(C.c_void_p), lcnt,
+            rls.ctypes.data_as(C.c_void_p)))
+        extra = dict(no_consensus=int(vcnt[0]), excluded=int(vcnt[1]), consensus=cons[:nch], list_len=ll[:nch], inlier=inl[:ne]) if robust else {}
+        return out, dict(**extra, fixed=int(cnt[0]), placed=int(cnt[1]), not_placed=int(cnt[2]), refused=int(cnt[3]), stages=int(cnt[4]),
                          closures_used=int(cnt[5]), edges_skipped=int(cnt[6]), status=status[:nch], cost_start=cs[:nch], cost_final=cf[:nch],
                          chosen=chosen[:nch], transforms=tr[:-1].reshape(nch, d * d + d),
                          sightings=dict(fixed=int(scnt[0]), placed=int(scnt[1]), not_placed=int(scnt[2]), landmarks_placed=int(scnt[3]),

@@ -22,11 +22,13 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding] [--device-init [--landmark-init] [--place-chains] [--gn-steps k]]" << std::endl;
+    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding] [--device-init [--landmark-init] [--place-chains] [--sightings] [--closures [--closure-consensus barc2 [--closure-min-consensus k]]] [--gn-steps k]]" << std::endl;
     return 1;
   }
   int max_rank = 10, gn_steps = 5;
   std::string tum, save_dir, residuals, weights, robust, barc2, weights_out, aligned_tum, rpe_steps, rpe_dists;
+  CORA::ClosureConsensus closure_consensus;
+  bool consensus_given = false;
   bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false, landmark_init = false, place_chains = false, sightings = false, closures = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
@@ -70,6 +72,10 @@ int main(int argc, char **argv) {
     // with --odom-init --device-init: the chains are first placed from the relative-pose edges between chains, then everything
     // --sightings does (Problem::closureInitialization)
     else if (a == "--closures") closures = true;
+    // with --closures: a consensus vote in front of each chain's fit (ClosureConsensus): the threshold on a closure's coupled
+    // rot + trans residual, and the votes the elected closure needs
+    else if (a == "--closure-consensus" && i + 1 < argc) closure_consensus.barc2 = std::atof(argv[++i]), consensus_given = true;
+    else if (a == "--closure-min-consensus" && i + 1 < argc) closure_consensus.min_consensus = std::atoi(argv[++i]), consensus_given = true;
   }
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
@@ -78,6 +84,8 @@ int main(int argc, char **argv) {
     if (place_chains && !device_init) throw std::runtime_error("--place-chains places the chains of the device's odometry start: it needs --odom-init --device-init");
     if (sightings && !device_init) throw std::runtime_error("--sightings places landmarks and chains of the device's odometry start: it needs --odom-init --device-init");
     if (closures && !device_init) throw std::runtime_error("--closures places the chains of the device's odometry start: it needs --odom-init --device-init");
+    if (consensus_given && !closures) throw std::runtime_error("--closure-consensus and --closure-min-consensus set the vote of the closure step: they need --closures");
+    if (consensus_given && !(closure_consensus.barc2 > 0)) throw std::runtime_error("--closure-consensus: expected a threshold > 0");
     if (landmark_init && !device_init) throw std::runtime_error("--landmark-init places the landmarks of the device's odometry start: it needs --odom-init --device-init");
     const auto t_start = clk::now();
     CORA::Problem problem = CORA::parsePyfgTextToProblem(argv[1]);
@@ -165,7 +173,7 @@ int main(int argc, char **argv) {
     if (closures) {  // (an extension beyond the reference: Problem::closureInitialization)
       CORA::ClosurePlacementInfo li;
       const CORA::Matrix without = problem.sightingInitialization(7, gn_steps);  // (the same pipeline without the step)
-      x0 = problem.closureInitialization(7, gn_steps, 0, 0, 0, &li);
+      x0 = problem.closureInitialization(7, gn_steps, 0, 0, 0, &li, nullptr, nullptr, nullptr, closure_consensus);
       // the closure cost: the table's own rot + trans residuals of the relative-pose edges that are no edge of a chain
       std::vector<char> in_chain(static_cast<size_t>(problem.numPosePoseMeasurements()), 0);
       for (const auto &ch : problem.odometryChains())
@@ -181,6 +189,13 @@ int main(int argc, char **argv) {
       std::printf("closure placement: %ld chains fixed or placed, %ld not placed, %ld refused (%ld stages, %ld closures used, %ld edges skipped or unused); closure cost at the start %.6e with it, %.6e without\n",
                   li.chains_fixed + li.chains_placed, li.chains_not_placed, li.chains_refused, li.stages, li.closures_used, li.edges_skipped,
                   closure_sum(x0), closure_sum(without));
+      if (consensus_given) {
+        double least = 1.0;  // the smallest consensus / list length over the taken chains
+        for (size_t ch = 0; ch < li.list_len.size(); ++ch)
+          if (li.list_len[ch] > 0) least = std::min(least, static_cast<double>(li.consensus[ch]) / li.list_len[ch]);
+        std::printf("closure consensus: %ld chains without consensus, %ld closures excluded; smallest consensus / list length %.4f\n",
+                    li.chains_no_consensus, li.closures_excluded, least);
+      }
     }
     if (odom && implicit)  // examples/paper_experiments.cpp:623-625
       x0 = x0.block(0, 0, problem.rotAndRangeMatrixSize(), x0.cols());

@@ -1080,6 +1080,49 @@ int cora_place_by_closures(cora_ctx *ctx, double *X, int ldx, int64_t out[5], un
 int cora_debug_place_by_closures_host(cora_ctx *ctx, double *X, int ldx, int64_t out[5], unsigned char *status, double *cost_start,
                                       double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate);
 
+/* Outlier-robust placement from closures: a consensus vote over minimal hypotheses in front of the closed-form fit (DESIGN
+ * 7o).  Closures are the measurement kind most likely to be grossly wrong (perceptual aliasing), and one wrong closure among
+ * ten drags the least-squares fit of cora_place_by_closures_dev away from all ten.  The tables, the stages, the lists and the
+ * 256-entry chunks are exactly those of cora_set_closure_placement: there is no new set call, and the order still depends on
+ * structure alone.  Per list of a stage, with (q_0, l_0) the list's first entry's (an origin only, whether or not that entry
+ * turns out to be an inlier):
+ *   hypothesis       entry h is VALID where kappa_h > 0 and then proposes g_h = (G_h, s_h): G_h = P_h as computed from the rows
+ *                    (not rounded: a product of three orthogonal blocks), s'_h[a] = (l_h[a] - l_0[a]) - sum_k G_h[a][k]
+ *                    (q_h[k] - q_0[k]) (k ascending from +0.0), s_h = (s'_h + l_0) - G_h q_0.
+ *   residual         r(h, j) = kappa_j |G_h - P_j|_F^2 + tau_j |G_h q'_j + s'_h - l'_j|^2: the coupled rot + trans residual of
+ *                    edge j after the motion g_h, the quantity cora_gnc_weights thresholds for a coupled edge (no 1/2); the
+ *                    function and the bits of the plain placement's cost at g.
+ *   vote             vote(h) = #{ j in the list : r(h, j) <= barc2 }; a NaN is no vote; an invalid h has vote 0; an entry
+ *                    with kappa = 0 still votes for others where its translation part agrees.  barc2: one finite scalar > 0.
+ *   election         h* = the entry of largest vote, among equal votes the lowest entry of the list; consensus = vote(h*).
+ *                    consensus < min_consensus (min_consensus >= 1): status 5, "taken, no consensus"; the chain keeps its
+ *                    rows (chosen 0, the identity) and, like a refused chain, STILL COUNTS AS PLACED for later stages.
+ *   inliers          I = { j : r(h*, j) <= barc2 }, the same function and bits as the vote.
+ *   refit            the plain placement's sums, solve (its refusal rule unchanged: status 2 is still possible), and two costs
+ *                    over the entries of I only.  AN ENTRY OUTSIDE I ADDS +0.0 FOR EACH OF ITS TERMS (it is not skipped: the
+ *                    bracket order of every sum is the plain placement's, a lane beyond a chunk's end adds the same +0.0).
+ *                    The chain moves only where the cost over I falls; cost_start and cost_final are over I.  One refit, no
+ *                    re-election.
+ *   cost             L^2 residual evaluations per list of L entries, by design: every entry is a hypothesis.
+ * out = the plain call's five fields, then {chains without consensus (status 5; they are not among out[1]), entries outside I
+ * summed over all lists}.  status, cost_start, cost_final, chosen, transforms: as the plain call's, NULL allowed.  consensus
+ * [chains]: the vote of the elected entry, 0 where the chain was not taken;  list_len [chains]: the entries of the chain's
+ * list, 0 without one;  inlier [n_edges]: 1 in I of its list | 0 in a list, outside I | 2 in no list;  each NULL allowed.  7
+ * launches per stage (vote, elect, pass, fold, pass, fold, apply), then 2 for the range rows (their degenerate count is
+ * out[2]).  cora_place_by_closures_robust: the host-pointer form.  cora_debug_place_by_closures_robust_host: the mirror, the
+ * same functions in the same bracket order: the device's bits; works on a plan-only handle.
+ * ERRORS.  The plain call's; CORA_ERR_ARG also for barc2 not finite or <= 0 and for min_consensus < 1; CORA_ERR_NAN also for a
+ * valid or elected hypothesis that is not finite.  STATE.  Nothing the handle computes with changes, nor its tables. */
+int cora_place_by_closures_robust_dev(cora_ctx *ctx, double *dX, double barc2, int min_consensus, int64_t out[7], unsigned char *status,
+                                      double *cost_start, double *cost_final, int32_t *chosen, double *transforms, int32_t *consensus,
+                                      int32_t *list_len, unsigned char *inlier);
+int cora_place_by_closures_robust(cora_ctx *ctx, double *X, int ldx, double barc2, int min_consensus, int64_t out[7], unsigned char *status,
+                                  double *cost_start, double *cost_final, int32_t *chosen, double *transforms, int32_t *consensus,
+                                  int32_t *list_len, unsigned char *inlier);
+int cora_debug_place_by_closures_robust_host(cora_ctx *ctx, double *X, int ldx, double barc2, int min_consensus, int64_t out[7],
+                                             unsigned char *status, double *cost_start, double *cost_final, int32_t *chosen, double *transforms,
+                                             int32_t *consensus, int32_t *list_len, unsigned char *inlier);
+
 /* Timing helpers: HIP events on the handle's stream. */
 int cora_timer_start(cora_ctx *ctx);
 int cora_timer_stop_ms(cora_ctx *ctx, float *ms); /* synchronises */

@@ -149,6 +149,21 @@ int cora_problem_closure_initialization(cora_problem *p, uint64_t seed, int gn_s
                                         int32_t *chosen, double *transforms, int64_t sighting_counts[6], unsigned char *sighting_status,
                                         unsigned char *landmark_status, int64_t chain_counts[4], unsigned char *chain_status,
                                         int64_t landmark_counts[4], unsigned char *range_landmark_status);
+/* The same with the closure step's consensus vote (ClosureConsensus, CORA_problem.h; cora_place_by_closures_robust_dev,
+ * include/cora_hip.h): consensus_barc2 <= 0 is off and has cora_problem_closure_initialization's bits; > 0: every closure of
+ * a list proposes a motion, the fit runs over the closures that agree with the elected one, and a chain whose elected closure
+ * has fewer than min_consensus (>= 1) votes has status 5 and is handed on like a refused one.  consensus_counts = { chains
+ * without consensus, closures excluded };  consensus, list_len: one entry per chain;  inlier: one byte per edge of the
+ * measurement table, the relative poses, pose priors, pose-landmark measurements and landmark priors in this order, each as
+ * added (cora_problem_measurement_counts [0] + .. + [3] bytes: 1 inlier | 0 in a list, not an inlier | 2 in no list).  With the vote off the
+ * three arrays are not written.  Every array but out may be NULL. */
+int cora_problem_closure_initialization_consensus(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, int min_sightings, int min_closures,
+                                                  double consensus_barc2, int min_consensus, double *out, int64_t counts[7],
+                                                  unsigned char *status, double *cost_start, double *cost_final, int32_t *chosen,
+                                                  double *transforms, int64_t consensus_counts[2], int32_t *consensus, int32_t *list_len,
+                                                  unsigned char *inlier, int64_t sighting_counts[6], unsigned char *sighting_status,
+                                                  unsigned char *landmark_status, int64_t chain_counts[4], unsigned char *chain_status,
+                                                  int64_t landmark_counts[4], unsigned char *range_landmark_status);
 /* compute_Lambda_blocks(Y): stiefel d x dn (ld d), oblique r */
 int cora_problem_lambda_blocks(cora_problem *p, const double *Y, double *stiefel, double *oblique);
 /* Problem::measurementResiduals (an extension beyond the reference; formulas in include/cora_hip.h, "per-measurement
