@@ -1044,20 +1044,32 @@ class Context:
             self._chk(self.L.cora_odometry_set_range_rows_dev(self.h, C.c_int64(len(idx)), idx.ctypes.data_as(_ip), _d(dirs),
                                                               C.c_void_p(out_ptr)))
 
+    # ---- shared by the initialisers below
+    def _mask(self, a, m, what):
+        """(array, pointer) of a mask of m entries as bytes, (None, None) for None; the array owns the pointer's memory."""
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(np.asarray(a).reshape(-1) != 0, dtype=np.uint8)
+        if len(a) != m:
+            raise CoraError(5, "%s needs %d entries, not %d" % (what, m, len(a)))
+        a = np.concatenate([a, np.zeros(1, dtype=np.uint8)])  # (never an empty buffer)
+        return a, a.ctypes.data_as(C.c_void_p)
+
+    def _with_host_X(self, call, fn, X, *args):
+        """call's dict of a host-matrix form fn (handle, X, ldx, ..) on a copy of X (N x d), the copy attached as X."""
+        X = np.array(X, dtype=np.float64, order="F", copy=True)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise CoraError(1, "X must have d columns")
+        res = call(lambda *a: fn(self.h, _d(X), X.shape[0], *a), *args)
+        res["X"] = X
+        return res
+
     # ---- landmark initialisation from ranges: multilateration (include/cora_hip.h, cora_multilaterate_dev)
     def set_multilateration(self, pose_ok=None, landmark_on=None):
         """Groups the usable ranges of the measurement table per landmark: pose_ok [n] / landmark_on [nt - n] masks or
         None (all)."""
-        def mask(a, m, what):
-            if a is None:
-                return None, None
-            a = np.ascontiguousarray(np.asarray(a).reshape(-1) != 0, dtype=np.uint8)
-            if len(a) != m:
-                raise CoraError(5, "%s needs %d entries, not %d" % (what, m, len(a)))
-            a = np.concatenate([a, np.zeros(1, dtype=np.uint8)])  # (never an empty buffer)
-            return a, a.ctypes.data_as(C.c_void_p)
-        po, ppo = mask(pose_ok, self.n, "pose_ok")
-        lo, plo = mask(landmark_on, self.nt - self.n, "landmark_on")
+        po, ppo = self._mask(pose_ok, self.n, "pose_ok")
+        lo, plo = self._mask(landmark_on, self.nt - self.n, "landmark_on")
         self._chk(self.L.cora_set_multilateration(self.h, ppo, plo))
 
     def multilateration_counts(self):
@@ -1076,23 +1088,15 @@ class Context:
         return dict(solved=int(out[0]), not_solved=int(out[1]), n_degenerate=int(out[2]), steps=int(out[3]), status=status[:nl],
                     cost_linear=cl[:nl], cost_final=cf[:nl], chosen=chosen[:nl], degenerate=deg[:nr].astype(bool))
 
-    def _ml_host(self, fn, X, gn_steps):
-        X = np.array(X, dtype=np.float64, order="F", copy=True)
-        if X.ndim != 2 or X.shape[1] != self.d:
-            raise CoraError(1, "X must have d columns")
-        res = self._ml_call(lambda *a: fn(self.h, _d(X), X.shape[0], *a), gn_steps)
-        res["X"] = X
-        return res
-
     def multilaterate(self, X, gn_steps=5):
         """The landmarks of the host matrix X (N x d) from the ranges, on the device.  Returns dict X (a copy with the
         landmark and range rows rewritten), solved, not_solved, n_degenerate, steps, status, cost_linear, cost_final,
         chosen (per landmark), degenerate (bool per range measurement)."""
-        return self._ml_host(self.L.cora_multilaterate, X, gn_steps)
+        return self._with_host_X(self._ml_call, self.L.cora_multilaterate, X, gn_steps)
 
     def debug_multilaterate_host(self, X, gn_steps=5):
         """The same on the host in the device's bracket order (no GPU needed): X has the device's bits."""
-        return self._ml_host(self.L.cora_debug_multilaterate_host, X, gn_steps)
+        return self._with_host_X(self._ml_call, self.L.cora_debug_multilaterate_host, X, gn_steps)
 
     def multilaterate_dev(self, x_ptr, gn_steps=5):
         """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
@@ -1104,14 +1108,7 @@ class Context:
         None (chain 0); min_ranges None: 4 x the unknowns of the linear stage (28 at d = 2, 64 at d = 3)."""
         if min_ranges is None:
             min_ranges = 4 * (7 if self.d == 2 else 16)
-        keep, ptr = None, None
-        if chain_fixed is not None:
-            nch = self.odometry_chains_count()[0]
-            a = np.ascontiguousarray(np.asarray(chain_fixed).reshape(-1) != 0, dtype=np.uint8)
-            if len(a) != nch:
-                raise CoraError(5, "chain_fixed needs %d entries, not %d" % (nch, len(a)))
-            keep = np.concatenate([a, np.zeros(1, dtype=np.uint8)])  # (never an empty buffer)
-            ptr = keep.ctypes.data_as(C.c_void_p)
+        keep, ptr = self._mask(chain_fixed, self.odometry_chains_count()[0], "chain_fixed")
         self._chk(self.L.cora_set_chain_placement(self.h, ptr, int(min_ranges)))
 
     def chain_placement_counts(self):
@@ -1138,24 +1135,16 @@ class Context:
                     status=status[:nch], cost_start=cs[:nch], cost_linear=cl[:nch], cost_final=cf[:nch], chosen=chosen[:nch],
                     transforms=tr[:nch * g].reshape(nch, g), degenerate=deg[:nr].astype(bool))
 
-    def _pl_host(self, fn, X, gn_steps):
-        X = np.array(X, dtype=np.float64, order="F", copy=True)
-        if X.ndim != 2 or X.shape[1] != self.d:
-            raise CoraError(1, "X must have d columns")
-        res = self._pl_call(lambda *a: fn(self.h, _d(X), X.shape[0], *a), gn_steps)
-        res["X"] = X
-        return res
-
     def place_chains(self, X, gn_steps=5):
         """The chains of the host matrix X (N x d) moved rigidly onto the fixed chains from the ranges between chains, on
         the device.  Returns dict X (a copy with the chains' rows and the range rows rewritten), placed, not_placed, steps,
         n_degenerate, stages, status, cost_start, cost_linear, cost_final, chosen (per chain), transforms (per chain: R
         row-major, then t), degenerate (bool per range measurement)."""
-        return self._pl_host(self.L.cora_place_chains, X, gn_steps)
+        return self._with_host_X(self._pl_call, self.L.cora_place_chains, X, gn_steps)
 
     def debug_place_chains_host(self, X, gn_steps=5):
         """The same on the host in the device's bracket order (no GPU needed): X has the device's bits."""
-        return self._pl_host(self.L.cora_debug_place_chains_host, X, gn_steps)
+        return self._with_host_X(self._pl_call, self.L.cora_debug_place_chains_host, X, gn_steps)
 
     def place_chains_dev(self, x_ptr, gn_steps=5):
         """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
@@ -1167,16 +1156,8 @@ class Context:
         or None (chain 0); landmark_fixed a mask per landmark or None (none); min_sightings None: 4 d."""
         if min_sightings is None:
             min_sightings = 4 * self.d
-        def mask(a, m, what):
-            if a is None:
-                return None, None
-            a = np.ascontiguousarray(np.asarray(a).reshape(-1) != 0, dtype=np.uint8)
-            if len(a) != m:
-                raise CoraError(5, "%s needs %d entries, not %d" % (what, m, len(a)))
-            a = np.concatenate([a, np.zeros(1, dtype=np.uint8)])  # (never an empty buffer)
-            return a, a.ctypes.data_as(C.c_void_p)
-        kc, pc = mask(chain_fixed, self.odometry_chains_count()[0], "chain_fixed")
-        kl, plm = mask(landmark_fixed, self.nt - self.n, "landmark_fixed")
+        kc, pc = self._mask(chain_fixed, self.odometry_chains_count()[0], "chain_fixed")
+        kl, plm = self._mask(landmark_fixed, self.nt - self.n, "landmark_fixed")
         self._chk(self.L.cora_set_sighting_placement(self.h, pc, plm, int(min_sightings)))
 
     def sighting_placement_counts(self):
@@ -1207,24 +1188,16 @@ class Context:
                     chosen=chosen[:nch], transforms=tr[:nch * g].reshape(nch, g), landmark_status=ls[:nl], landmark_cost=lc[:nl],
                     degenerate=deg[:nr].astype(bool))
 
-    def _sg_host(self, fn, X):
-        X = np.array(X, dtype=np.float64, order="F", copy=True)
-        if X.ndim != 2 or X.shape[1] != self.d:
-            raise CoraError(1, "X must have d columns")
-        res = self._sg_call(lambda *a: fn(self.h, _d(X), X.shape[0], *a))
-        res["X"] = X
-        return res
-
     def place_by_sightings(self, X):
         """Landmarks and chains of the host matrix X (N x d) placed from the sightings, on the device.  Returns dict X (a
         copy with the landmarks', the chains' and the range rows rewritten), placed, not_placed, landmarks_placed,
         landmarks_not_placed, n_degenerate, stages, status, cost_start, cost_final, chosen (per chain), transforms (per
         chain: R row-major, then t), landmark_status, landmark_cost (per landmark), degenerate (bool per range measurement)."""
-        return self._sg_host(self.L.cora_place_by_sightings, X)
+        return self._with_host_X(self._sg_call, self.L.cora_place_by_sightings, X)
 
     def debug_place_by_sightings_host(self, X):
         """The same on the host in the device's bracket order (no GPU needed): X has the device's bits."""
-        return self._sg_host(self.L.cora_debug_place_by_sightings_host, X)
+        return self._with_host_X(self._sg_call, self.L.cora_debug_place_by_sightings_host, X)
 
     def place_by_sightings_dev(self, x_ptr):
         """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
@@ -1234,14 +1207,7 @@ class Context:
     def set_closure_placement(self, chain_fixed=None, min_closures=1):
         """Orders the odometry chains into stages from the relative-pose edges between chains: chain_fixed a mask per chain
         or None (chain 0); min_closures >= 1."""
-        pc = kc = None
-        if chain_fixed is not None:
-            kc = np.ascontiguousarray(np.asarray(chain_fixed).reshape(-1) != 0, dtype=np.uint8)
-            nch = self.odometry_chains_count()[0]
-            if len(kc) != nch:
-                raise CoraError(5, "chain_fixed needs %d entries, not %d" % (nch, len(kc)))
-            kc = np.concatenate([kc, np.zeros(1, dtype=np.uint8)])  # (never an empty buffer)
-            pc = kc.ctypes.data_as(C.c_void_p)
+        kc, pc = self._mask(chain_fixed, self.odometry_chains_count()[0], "chain_fixed")
         self._chk(self.L.cora_set_closure_placement(self.h, pc, int(min_closures)))
 
     def closure_placement_counts(self):
@@ -1268,23 +1234,15 @@ class Context:
                     status=status[:nch], cost_start=cs[:nch], cost_final=cf[:nch], chosen=chosen[:nch],
                     transforms=tr[:nch * g].reshape(nch, g), degenerate=deg[:nr].astype(bool))
 
-    def _cl_host(self, fn, X):
-        X = np.array(X, dtype=np.float64, order="F", copy=True)
-        if X.ndim != 2 or X.shape[1] != self.d:
-            raise CoraError(1, "X must have d columns")
-        res = self._cl_call(lambda *a: fn(self.h, _d(X), X.shape[0], *a))
-        res["X"] = X
-        return res
-
     def place_by_closures(self, X):
         """The chains of the host matrix X (N x d) placed from the closures, on the device.  Returns dict X (a copy with the
         chains' and the range rows rewritten), placed, not_placed, n_degenerate, stages, refused, status, cost_start,
         cost_final, chosen (per chain), transforms (per chain: G row-major, then s), degenerate (bool per range measurement)."""
-        return self._cl_host(self.L.cora_place_by_closures, X)
+        return self._with_host_X(self._cl_call, self.L.cora_place_by_closures, X)
 
     def debug_place_by_closures_host(self, X):
         """The same on the host in the device's bracket order (no GPU needed): X has the device's bits."""
-        return self._cl_host(self.L.cora_debug_place_by_closures_host, X)
+        return self._with_host_X(self._cl_call, self.L.cora_debug_place_by_closures_host, X)
 
     def place_by_closures_dev(self, x_ptr):
         """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
@@ -1304,24 +1262,16 @@ class Context:
                     no_consensus=int(out[5]), excluded=int(out[6]), status=status[:nch], cost_start=cs[:nch], cost_final=cf[:nch],
                     chosen=chosen[:nch], transforms=tr[:nch * g].reshape(nch, g), consensus=cons[:nch], list_len=ll[:nch], inlier=inl[:ne])
 
-    def _clr_host(self, fn, X, barc2, min_consensus):
-        X = np.array(X, dtype=np.float64, order="F", copy=True)
-        if X.ndim != 2 or X.shape[1] != self.d:
-            raise CoraError(1, "X must have d columns")
-        res = self._clr_call(lambda *a: fn(self.h, _d(X), X.shape[0], *a), barc2, min_consensus)
-        res["X"] = X
-        return res
-
     def place_by_closures_robust(self, X, barc2, min_consensus=2):
         """place_by_closures with a consensus vote in front of the fit: every closure of a list proposes a motion, the proposal
         most closures agree with (coupled residual <= barc2) is elected and the fit runs over the agreeing closures only.
         Returns place_by_closures' dict without degenerate, plus consensus and list_len (per chain), inlier (per edge of the
         measurement table: 1 | 0 | 2 in no list), no_consensus (chains of status 5) and excluded (entries outside the inliers)."""
-        return self._clr_host(self.L.cora_place_by_closures_robust, X, barc2, min_consensus)
+        return self._with_host_X(self._clr_call, self.L.cora_place_by_closures_robust, X, barc2, min_consensus)
 
     def debug_place_by_closures_robust_host(self, X, barc2, min_consensus=2):
         """The same on the host in the device's bracket order (no GPU needed): the device's bits."""
-        return self._clr_host(self.L.cora_debug_place_by_closures_robust_host, X, barc2, min_consensus)
+        return self._with_host_X(self._clr_call, self.L.cora_debug_place_by_closures_robust_host, X, barc2, min_consensus)
 
     def place_by_closures_robust_dev(self, x_ptr, barc2, min_consensus=2):
         """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""

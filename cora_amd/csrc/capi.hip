@@ -2,7 +2,7 @@
 // device memory and stream; every compute entry point ends in a HIP kernel of
 // kernels.hip -- there is no CPU fallback.
 //
-// ONE translation unit in seventeen pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
+// ONE translation unit in eighteen pieces (round 6: the file had grown to 3 400 lines).  This file holds the handle (cora_ctx), the
 // error / device macros and the helpers every part uses; the entry points live in capi/*.inc, included at the end in this order:
 //   handle.inc          creation of (partitioned) handles, destruction, rank state, row maps, statistics
 //   resident.inc        device vectors, the current point, the trust-region trial / accept pair, products, projections
@@ -19,6 +19,7 @@
 //   compare.inc         trajectory comparison after an orthogonal alignment: device-pointer, host-pointer and host form
 //   rpe.inc             relative pose error over a pair table of the handle: table, device-pointer, host-pointer and host-mirror form
 //   round.inc           rounding of a relaxed point to SE(d): device-pointer, host-pointer and host-mirror form
+//   init_common.inc     what the five initialisers below share: the range-row step, the three forms of a call, installing and building tables, the mirror's sums
 //   odom.inc            odometry initialisation: chain tables, device-pointer, host-pointer and host-mirror form
 //   multilat.inc        landmark initialisation from ranges: list tables, device-pointer, host-pointer and host-mirror form
 //   placement.inc       chain placement from inter-robot ranges: stage tables, device-pointer, host-pointer and host-mirror form
@@ -87,6 +88,12 @@ static int native_product_gather(cora_native_comm *nc, double *dX, int ld, hipSt
                                  hipEvent_t after_collective = nullptr);
 static const std::string &native_error(const cora_native_comm *nc);
 static int native_allgather_rows(cora_native_comm *nc, double *dX, int ld, int64_t row0, int64_t nrows);  // one piece of every shard, packed
+// frees the device arrays named and nulls the pointers (the device must be current): the ONE list of a table's device pointers is
+// the argument list of its release()
+template <class... P>
+static void free_device(P *&...p) {
+  ((p ? (void)hipFree(p) : void(), p = nullptr), ...);
+}
 // The measurement table of cora_set_measurements (capi/measurements.inc), rows already translated to the internal order,
 // structure-of-arrays [field][measurement] on the host and on the device (ResidualArgs, kernels.h)
 struct MeasurementTable {
@@ -113,7 +120,7 @@ struct PosePairTable {
 };
 // The chain tables of cora_set_odometry_chains (capi/odom.inc): one entry per chain position (a chain's head, then its
 // edges), rows already internal (OdomArgs, kernels.h); the poses in no chain and the landmarks' rows (OdomFillArgs); the
-// device copies, the scan's tile totals and carries, the staging of the starts and the landmarks, the flag bytes
+// device copies, the scan's tile totals and carries, the staging of the starts and the landmarks
 struct OdomTables {
   bool built = false;  // (false: built at the next initialisation as "no chains", every pose free)
   int64_t n_chains = 0, P = 0;
@@ -123,11 +130,24 @@ struct OdomTables {
   double *d_work = nullptr;      // totals | carry, kOdomFields(d) x tiles each
   double *d_stage = nullptr;     // starts [n_chains][d] | landmarks [nt - n][d]
   double *h_stage = nullptr;     // the same, pinned
+  void release() {
+    free_device(d_idx, d_work, d_stage);
+    if (h_stage) (void)hipHostFree(h_stage);
+    h_stage = nullptr;
+  }
+};
+// What the initialisers below share.  Every call of theirs ends in the range-row step (range_rows_step, capi/init_common.inc),
+// which owns its device arrays on the handle (RangeRowStep below), built at first need and freed with the measurement table.
+// Each table struct names its device pointers once, in release(): a table that never reached the handle is released, the
+// handle's is freed (free_tables: release, then back to the default state).
+struct RangeRowStep {
+  int32_t *d_exchanged = nullptr;  // [3][n_ranges] internal rows: range | b | a (the measurement table's with a and b exchanged)
   unsigned char *d_deg = nullptr;  // one byte per range measurement
+  void release() { free_device(d_exchanged, d_deg); }
 };
 // The tables of cora_set_multilateration (capi/multilat.inc): the usable ranges of the measurement table grouped per
 // landmark in table order (after the masks), cut into chunks of kMlChunk entries, rows already internal (MlArgs,
-// kernels.h); the device copies, the chunks' partial sums, the landmarks' state, the flag bytes of the range rows
+// kernels.h); the device copies, the chunks' partial sums, the landmarks' state
 struct MlTables {
   bool built = false;
   int64_t n_with_list = 0, usable = 0, skipped = 0;
@@ -140,13 +160,12 @@ struct MlTables {
   double *d_partial = nullptr;   // [kMlSums(d)][chunks]
   double *d_state = nullptr;     // [nl][kMlState(d)]
   int32_t *d_istate = nullptr;   // [nl][kMlInts]
-  unsigned char *d_deg = nullptr;  // one byte per range measurement
-  int32_t *d_range_rows = nullptr;  // [3][n_ranges] internal rows: range | b | a (the measurement table's with a and b exchanged)
+  void release() { free_device(d_idx, d_init, d_partial, d_state, d_istate); }
 };
 // The tables of cora_set_chain_placement (capi/placement.inc): the order of the stages, decided from structure alone; per
 // stage the chain, its positions in the chain tables, the first entry's rows and the stage's chunks; the entry lists (row
 // of the chain's position, row of the anchor, range measurement) in table order, cut into chunks of kPlChunk entries, rows
-// already internal (PlArgs, kernels.h); the device copies, the chunks' partial sums, the stages' state, the range rows' bytes
+// already internal (PlArgs, kernels.h); the device copies, the chunks' partial sums, the stages' state
 struct PlTables {
   bool built = false;
   int min_ranges = 0;
@@ -160,14 +179,13 @@ struct PlTables {
   double *d_partial = nullptr;   // [kPlSums(d)][max_chunks]
   double *d_state = nullptr;     // [stages][kPlState(d)]
   int32_t *d_istate = nullptr;   // [stages][kPlInts]
-  unsigned char *d_deg = nullptr;   // one byte per range measurement
-  int32_t *d_range_rows = nullptr;  // [3][n_ranges] internal rows: range | b | a (as MlTables')
+  void release() { free_device(d_idx, d_partial, d_state, d_istate); }
 };
 // The tables of cora_set_sighting_placement (capi/sighting.inc): the order of the stages, decided from structure alone; per
 // stage its kind and its lists; per list the landmark or chain and its chunks; the entries (first rotation row and
 // translation row of the pose, row of the landmark, edge) in table order, cut into chunks of kSgChunk entries, rows already
 // internal; the positions of every C-stage's chains (SgArgs, kernels.h); the device copies, the chunks' partial sums, the
-// lists' state, the range rows' bytes
+// lists' state
 struct SgTables {
   bool built = false;
   int min_sightings = 0;
@@ -183,13 +201,12 @@ struct SgTables {
   double *d_partial = nullptr;   // [kSgMaxSums(d)][chunks]
   double *d_state = nullptr;     // [lists][kSgState(d)]
   int32_t *d_istate = nullptr;   // [lists][kSgInts]
-  unsigned char *d_deg = nullptr;   // one byte per range measurement
-  int32_t *d_range_rows = nullptr;  // [3][n_ranges] internal rows: range | b | a (as MlTables')
+  void release() { free_device(d_idx, d_partial, d_state, d_istate); }
 };
 // The tables of cora_set_closure_placement (capi/closure.inc): the order of the stages, decided from structure alone; per
 // stage its lists; per list the chain and its chunks; the entries (edge, direction) in table order, cut into chunks of
 // kClChunk entries; the positions of every stage's chains (ClArgs, kernels.h); the device copies, the chunks' partial sums,
-// the lists' state, the range rows' bytes
+// the lists' state, the consensus vote's scratch
 struct ClTables {
   bool built = false;
   int min_closures = 0;
@@ -205,13 +222,12 @@ struct ClTables {
   double *d_partial = nullptr;   // [kClSums(d)][chunks]
   double *d_state = nullptr;     // [lists][kSgState(d)]
   int32_t *d_istate = nullptr;   // [lists][kSgInts]
-  unsigned char *d_deg = nullptr;   // one byte per range measurement
-  int32_t *d_range_rows = nullptr;  // [3][n_ranges] internal rows: range | b | a (as MlTables')
   // the consensus vote's (cora_place_by_closures_robust_dev): scratch of a call, like d_partial
   int32_t *d_votes = nullptr;       // [entries]
   double *d_cstate = nullptr;       // [lists][kClCState(d)]
   int32_t *d_cint = nullptr;        // [lists][kClCInts]
   unsigned char *d_inlier = nullptr;  // [n_edges]
+  void release() { free_device(d_idx, d_partial, d_state, d_istate, d_votes, d_cstate, d_cint, d_inlier); }
 };
 struct cora_ctx {
   HostFormat F;
@@ -219,6 +235,7 @@ struct cora_ctx {
   MeasurementTable meas;
   PosePairTable pairs;
   OdomTables odom;
+  RangeRowStep range_step;
   MlTables ml;
   PlTables pl;
   SgTables sg;
@@ -703,58 +720,22 @@ void free_assembly(cora_ctx *c) {  // (the device must be current where there is
   c->tmap = TermMap();
 }
 
-void free_odom(cora_ctx *c) {  // (the device must be current where there is one)
-  OdomTables &T = c->odom;
-  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_work), static_cast<void *>(T.d_stage), static_cast<void *>(T.d_deg)})
-    if (p) (void)hipFree(p);
-  if (T.h_stage) (void)hipHostFree(T.h_stage);
-  T = OdomTables();
-}
-
-void free_pl(cora_ctx *c) {  // (the device must be current where there is one)
-  PlTables &T = c->pl;
-  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state), static_cast<void *>(T.d_istate),
-                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows)})
-    if (p) (void)hipFree(p);
-  T = PlTables();
-}
-
-void free_sg(cora_ctx *c) {  // (the device must be current where there is one)
-  SgTables &T = c->sg;
-  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state), static_cast<void *>(T.d_istate),
-                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows)})
-    if (p) (void)hipFree(p);
-  T = SgTables();
-}
-
-void free_cl(cora_ctx *c) {  // (the device must be current where there is one)
-  ClTables &T = c->cl;
-  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state), static_cast<void *>(T.d_istate),
-                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows), static_cast<void *>(T.d_votes), static_cast<void *>(T.d_cstate),
-                  static_cast<void *>(T.d_cint), static_cast<void *>(T.d_inlier)})
-    if (p) (void)hipFree(p);
-  T = ClTables();
-}
-
-void free_ml(cora_ctx *c) {  // (the device must be current where there is one)
-  MlTables &T = c->ml;
-  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_init), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state),
-                  static_cast<void *>(T.d_istate), static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows)})
-    if (p) (void)hipFree(p);
-  T = MlTables();
+template <class T>
+void free_tables(T &t) {  // (the device must be current where there is one)
+  t.release();
+  t = T();
 }
 
 void free_measurements(cora_ctx *c) {  // (the device must be current)
-  free_assembly(c);  // (the term map belongs to the table)
-  free_odom(c);      // (so do the chain tables: their positions name its edges)
-  free_ml(c);        // (and the multilateration's lists: their entries name its ranges)
-  free_pl(c);        // (and the chain placement's stages)
-  free_sg(c);        // (and the sighting placement's lists: their entries name its edges)
-  free_cl(c);        // (and the closure placement's lists: their entries name its edges)
+  free_assembly(c);            // (the term map belongs to the table)
+  free_tables(c->odom);        // (so do the chain tables: their positions name its edges)
+  free_tables(c->range_step);  // (and the exchanged range rows)
+  free_tables(c->ml);          // (and the multilateration's lists: their entries name its ranges)
+  free_tables(c->pl);          // (and the chain placement's stages)
+  free_tables(c->sg);          // (and the sighting placement's lists: their entries name its edges)
+  free_tables(c->cl);          // (and the closure placement's lists: their entries name its edges)
   MeasurementTable &M = c->meas;
-  for (void *p : {static_cast<void *>(M.d_edge_rows), static_cast<void *>(M.d_range_rows), static_cast<void *>(M.d_edge_data),
-                  static_cast<void *>(M.d_range_data), static_cast<void *>(M.d_out)})
-    if (p) (void)hipFree(p);
+  free_device(M.d_edge_rows, M.d_range_rows, M.d_edge_data, M.d_range_data, M.d_out);
   M = MeasurementTable();
 }
 
@@ -785,6 +766,7 @@ extern "C" {
 #include "capi/compare.inc"
 #include "capi/rpe.inc"
 #include "capi/round.inc"
+#include "capi/init_common.inc"
 #include "capi/odom.inc"
 #include "capi/multilat.inc"
 #include "capi/placement.inc"

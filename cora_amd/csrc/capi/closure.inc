@@ -1,4 +1,4 @@
-// Part of capi.hip (one translation unit; included there, in this order).  placement of odometry chains from inter-chain relative-pose edges (closures; the weighted rigid alignment of a chain onto chains placed before it, rotation and translation residuals together): order of the stages and list tables, device-pointer form, host-pointer form, host mirror, each plain and with the consensus vote in front of the fit (cora_place_by_closures_robust_dev).  Reads the measurement table and the chain tables; writes nothing the handle computes with.
+// Part of capi.hip (one translation unit; included there, in this order).  placement of odometry chains from inter-chain relative-pose edges (closures; the weighted rigid alignment of a chain onto chains placed before it, rotation and translation residuals together): order of the stages and list tables, device-pointer form, host-pointer form, host mirror, each plain and with the consensus vote in front of the fit (cora_place_by_closures_robust_dev).  Reads the measurement table and the chain tables; writes nothing the handle computes with.  What it shares with the other initialisers -- the range-row step, the host-pointer and host-mirror wrappers, installing tables, chunk cutting, the mirror's sums -- is in capi/init_common.inc.
 
 namespace {
 
@@ -11,32 +11,20 @@ int cl_check(cora_ctx *c) {
 
 // the order of the stages and their lists, from structure alone (host part of T only)
 int cl_build(cora_ctx *c, const unsigned char *chain_fixed, int min_closures, ClTables &T) {
-  const Layout &L = c->F.L;
   const MeasurementTable &M = c->meas;
   const OdomTables &O = c->odom;
   const int64_t ne = M.n_edges, nch = O.n_chains;
   if (min_closures < 1) return fail(c, CORA_ERR_ARG, "min_closures must be at least 1");
   if (ne >= (int64_t(1) << 31)) return fail(c, CORA_ERR_ARG, "the edge table has more entries than a 32-bit index holds");
-  std::vector<unsigned char> placed(static_cast<size_t>(nch), 0);
-  if (chain_fixed) {
-    bool any = false;
-    for (int64_t ch = 0; ch < nch; ++ch) any = (placed[static_cast<size_t>(ch)] = chain_fixed[ch] ? 1 : 0) || any;
-    if (!any) return fail(c, CORA_ERR_ARG, "chain_fixed fixes no chain");
-  } else if (nch > 0) {
-    placed[0] = 1;
-  } else {
-    return fail(c, CORA_ERR_ARG, "no chain to fix: the chain tables hold no chain");
-  }
+  std::vector<unsigned char> placed;
+  if (const int rc = seed_fixed_chains(c, chain_fixed, placed)) return rc;
   const std::vector<unsigned char> fixed = placed;
-  std::vector<int32_t> chain_of(static_cast<size_t>(L.rows), -1);
-  std::vector<std::vector<int32_t>> chain_pos(static_cast<size_t>(nch));
+  const ChainMaps maps = chain_maps(c);
+  const std::vector<int32_t> &chain_of = maps.chain_of;
+  const std::vector<std::vector<int32_t>> &chain_pos = maps.chain_pos;
   std::vector<unsigned char> chain_edge(static_cast<size_t>(ne), 0);
-  for (int64_t pos = 0; pos < O.P; ++pos) {
-    const int32_t ch = O.pos_chain[static_cast<size_t>(pos)], e = O.pos_edge[static_cast<size_t>(pos)];
-    chain_of[static_cast<size_t>(O.pos_trn[static_cast<size_t>(pos)])] = ch;
-    chain_pos[static_cast<size_t>(ch)].push_back(static_cast<int32_t>(pos));
+  for (const int32_t e : O.pos_edge)
     if (e >= 0) chain_edge[static_cast<size_t>(e)] = 1;
-  }
   // the closures in table order: edge, chain of a, chain of b   (edge_rows: [ra | rb | ta | tb][edge])
   std::vector<int32_t> c_e, c_a, c_b;
   for (int64_t e = 0; e < ne; ++e) {
@@ -80,12 +68,7 @@ int cl_build(cora_ctx *c, const unsigned char *chain_fixed, int min_closures, Cl
         T.ent_e.push_back(c_e[u]);
         T.ent_dir.push_back(c_a[u] == ch ? 1 : 0);
       }
-      const int64_t len = static_cast<int64_t>(mb.size());
-      for (int64_t at = 0; at < len; at += kClChunk) {
-        T.chunk_begin.push_back(static_cast<int32_t>(static_cast<int64_t>(begin) + at));
-        T.chunk_len.push_back(static_cast<int32_t>(std::min<int64_t>(kClChunk, len - at)));
-        T.chunk_list.push_back(list);
-      }
+      cut_chunks(static_cast<int64_t>(begin), static_cast<int64_t>(mb.size()), T.chunk_begin, T.chunk_len, &T.chunk_list, list);
       T.list_item.push_back(static_cast<int32_t>(ch));
       T.list_chunk0.push_back(static_cast<int32_t>(T.chunk_begin.size()));
       chains.push_back(static_cast<int32_t>(ch));
@@ -104,37 +87,19 @@ int cl_build(cora_ctx *c, const unsigned char *chain_fixed, int min_closures, Cl
     T.chain_init[i] = fixed[i] ? 4 : (T.chain_list[i] >= 0 ? 0 : (has[i] ? 1 : 3));
   }
   if (T.ent_e.size() >= (size_t(1) << 31)) return fail(c, CORA_ERR_ARG, "the lists have more entries than a 32-bit index holds");
-  // (a range row two measurements name would be written by two threads of the range-row step)
-  const int64_t nr = M.n_ranges;
-  std::vector<unsigned char> written(static_cast<size_t>(L.rows), 0);
-  for (int64_t m = 0; m < nr; ++m) {
-    unsigned char &w = written[static_cast<size_t>(M.range_rows[static_cast<size_t>(m)])];
-    if (w) return fail(c, CORA_ERR_ARG, "range measurement " + std::to_string(m) + " names a range row an earlier one names");
-    w = 1;
-  }
+  if (const int rc = range_rows_unique(c)) return rc;
   T.built = true;
   return CORA_OK;
 }
 
 // the device side of freshly built tables (T's device pointers are null); on failure T owns what was allocated
 int cl_upload(cora_ctx *c, ClTables &T) {
-  std::vector<int32_t> idx;
-  for (const std::vector<int32_t> *v : {&T.chunk_begin, &T.chunk_len, &T.chunk_list, &T.list_chunk0, &T.ent_e, &T.ent_dir, &T.apply_pos, &T.apply_list})
-    idx.insert(idx.end(), v->begin(), v->end());
-  idx.push_back(0);  // (never an empty buffer)
-  HIP_TRY(c, to_device(&T.d_idx, idx));
+  HIP_TRY(c, upload_joined(&T.d_idx, {&T.chunk_begin, &T.chunk_len, &T.chunk_list, &T.list_chunk0, &T.ent_e, &T.ent_dir, &T.apply_pos, &T.apply_list}));
   const int d = c->F.L.d;
   const size_t nlist = std::max<size_t>(T.list_item.size(), 1), nc = std::max<size_t>(T.chunk_begin.size(), 1);
   HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_partial), static_cast<size_t>(kClSums(d)) * nc * sizeof(double)));
   HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_state), static_cast<size_t>(kSgState(d)) * nlist * sizeof(double)));
   HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_istate), static_cast<size_t>(kSgInts) * nlist * sizeof(int32_t)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_deg), std::max<size_t>(static_cast<size_t>(c->meas.n_ranges), 1)));
-  // the range-row step over the table with a and b exchanged: the direction of least residual (ml_upload)
-  const size_t nr = static_cast<size_t>(c->meas.n_ranges);
-  std::vector<int32_t> rows(c->meas.range_rows);
-  std::swap_ranges(rows.begin() + static_cast<std::ptrdiff_t>(nr), rows.begin() + static_cast<std::ptrdiff_t>(2 * nr), rows.begin() + static_cast<std::ptrdiff_t>(2 * nr));
-  rows.push_back(0);
-  HIP_TRY(c, to_device(&T.d_range_rows, rows));
   // the consensus vote's scratch
   HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_votes), std::max<size_t>(T.ent_e.size(), 1) * sizeof(int32_t)));
   HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_cstate), static_cast<size_t>(kClCState(d)) * nlist * sizeof(double)));
@@ -143,29 +108,19 @@ int cl_upload(cora_ctx *c, ClTables &T) {
   return CORA_OK;
 }
 
-void cl_release(ClTables &T) {  // a table that never reached the handle
-  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state), static_cast<void *>(T.d_istate),
-                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows), static_cast<void *>(T.d_votes), static_cast<void *>(T.d_cstate),
-                  static_cast<void *>(T.d_cint), static_cast<void *>(T.d_inlier)})
-    if (p) (void)hipFree(p);
-}
-
 int cl_args_check(cora_ctx *c, const double *X, const int64_t *out) {
   if (!c->cl.built) return fail(c, CORA_ERR_NOT_READY, "no closure tables (cora_set_closure_placement)");
   if (!X || !out) return fail(c, CORA_ERR_ARG, "null pointer");
   return CORA_OK;
 }
 
-// the kernels' arguments of a call on the resident vector dX: the tables' device side and, for the range-row step of the
-// odometry initialisation (its rules unchanged, over the exchanged table), Fl
-void cl_fill_args(cora_ctx *c, double *dX, ClArgs &A, OdomFillArgs &Fl) {
-  const Layout &L = c->F.L;
+// the kernels' arguments of a call on the resident vector dX: the tables' device side
+void cl_fill_args(cora_ctx *c, double *dX, ClArgs &A) {
   const MeasurementTable &M = c->meas;
   ClTables &T = c->cl;
   const OdomTables &O = c->odom;
-  const int d = L.d, nb = odom_range_blocks(M.n_ranges);
   const size_t nc = T.chunk_begin.size(), ne = T.ent_e.size(), nlist = T.list_item.size(), na = T.apply_pos.size();
-  A.d = d;
+  A.d = c->F.L.d;
   A.n_edges = M.n_edges;
   A.pstride = static_cast<int64_t>(std::max<size_t>(nc, 1));
   A.chunk_begin = T.d_idx;
@@ -185,24 +140,6 @@ void cl_fill_args(cora_ctx *c, double *dX, ClArgs &A, OdomFillArgs &Fl) {
   A.istate = T.d_istate;
   A.x = dX;
   A.flag = c->d_flag;
-  // the range-row step of the odometry initialisation, its rules unchanged, over the exchanged table
-  Fl.d = d;
-  Fl.n_ranges = M.n_ranges;
-  Fl.range_rows = T.d_range_rows;
-  Fl.deg = T.d_deg;
-  Fl.partial = reinterpret_cast<int *>(c->d_red);
-  Fl.words = Fl.partial + nb;
-  Fl.flag = c->d_flag;
-  Fl.out = dX;
-}
-// the stage s of the tables in A
-void cl_stage_args(const ClTables &T, size_t s, ClArgs &A) {
-  A.list0 = T.stage_list0[s];
-  A.n_lists = T.stage_list0[s + 1] - A.list0;
-  A.chunk0 = T.list_chunk0[static_cast<size_t>(A.list0)];
-  A.n_chunks = T.list_chunk0[static_cast<size_t>(T.stage_list0[s + 1])] - A.chunk0;
-  A.apply0 = T.stage_apply0[s];
-  A.n_apply = T.stage_apply0[s + 1] - A.apply0;
 }
 
 // what a call returns, from the lists' state ([lists][kSgState(d)], [lists][kSgInts])
@@ -224,8 +161,8 @@ void cl_results(const cora_ctx *c, const std::vector<double> &state, const std::
     if (cost_start) cost_start[ch] = st ? st[G + d] : 0.0;
     if (cost_final) cost_final[ch] = st ? st[G + d + 1] : 0.0;
     if (chosen) chosen[ch] = li ? li[1] : -1;
-    if (transforms)
-      for (int i = 0; i < G; ++i) transforms[ch * G + i] = li && li[1] > 0 ? st[i] : (i < d * d && i / d == i % d ? 1.0 : 0.0);
+    if (transforms && li && li[1] > 0) std::copy(st, st + G, transforms + ch * G);
+    else if (transforms) identity_transform(d, transforms + ch * G);
   }
   out[2] = n_deg;
   out[3] = static_cast<int64_t>(T.stage_list0.size()) - 1;
@@ -311,50 +248,25 @@ bool cl_host_pass_fold(const cora_ctx *c, size_t s, const double *oi, std::vecto
   for (size_t ch = static_cast<size_t>(T.list_chunk0[l0]); ch < static_cast<size_t>(T.list_chunk0[l1]); ++ch) {
     const size_t list = static_cast<size_t>(T.chunk_list[ch]);
     cl_host_entry<D>(c, oi, static_cast<size_t>(T.chunk_begin[static_cast<size_t>(T.list_chunk0[list])]), P0, q0, lm0, &res0, kt0);
-    double wave[kClChunk / kWave][NS];
-    for (int w = 0; w < kClChunk / kWave; ++w) {
-      double term[kWave][NS];
-      for (int lane = 0; lane < kWave; ++lane) {
-        const int i = w * kWave + lane;
-        for (int k = 0; k < NS; ++k) term[lane][k] = 0.0;
-        if (i >= T.chunk_len[ch]) continue;
-        double P[D * D], q[D], l[D], res, kt[2];
-        cl_host_entry<D>(c, oi, static_cast<size_t>(T.chunk_begin[ch]) + i, P, q, l, &res, kt);
-        if (hv) {
-          const bool in = cl_agrees(cl_cost_at<D>(hv->cstate.data() + list * kClCState(D), q0, lm0, P, q, l, kt[0], kt[1]), hv->barc2);
-          if constexpr (MODE == 0) hv->inl[static_cast<size_t>(T.ent_e[static_cast<size_t>(T.chunk_begin[ch]) + i])] = in ? 1 : 0;
-          if (!in) continue;
-        }
-        if constexpr (MODE == 0) {
-          cl_terms<D>(q0, lm0, P, q, l, kt[0], kt[1], term[lane]);
-        } else {
-          term[lane][0] = res;
-          term[lane][1] = cl_cost_at<D>(state.data() + list * kSgState(D), q0, lm0, P, q, l, kt[0], kt[1]);
-        }
+    host_chunk_sums<NS>(T.chunk_len[ch], [&](int i, double *t) {
+      double P[D * D], q[D], l[D], res, kt[2];
+      cl_host_entry<D>(c, oi, static_cast<size_t>(T.chunk_begin[ch]) + i, P, q, l, &res, kt);
+      if (hv) {
+        const bool in = cl_agrees(cl_cost_at<D>(hv->cstate.data() + list * kClCState(D), q0, lm0, P, q, l, kt[0], kt[1]), hv->barc2);
+        if constexpr (MODE == 0) hv->inl[static_cast<size_t>(T.ent_e[static_cast<size_t>(T.chunk_begin[ch]) + i])] = in ? 1 : 0;
+        if (!in) return;
       }
-      for (int k = 0; k < NS; ++k) {
-        double v[kWave];
-        for (int lane = 0; lane < kWave; ++lane) v[lane] = term[lane][k];
-        wave[w][k] = ml_host_wave_sum(v);
+      if constexpr (MODE == 0) {
+        cl_terms<D>(q0, lm0, P, q, l, kt[0], kt[1], t);
+      } else {
+        t[0] = res;
+        t[1] = cl_cost_at<D>(state.data() + list * kSgState(D), q0, lm0, P, q, l, kt[0], kt[1]);
       }
-    }
-    for (int k = 0; k < NS; ++k) {
-      double v = wave[0][k];
-      for (int w = 1; w < kClChunk / kWave; ++w) v = v + wave[w][k];
-      partial[static_cast<size_t>(k) * nc + ch] = v;
-    }
+    }, partial.data(), nc, ch);
   }
   for (size_t list = l0; list < l1; ++list) {
     double S[NS];
-    for (int k = 0; k < NS; ++k) {
-      double v[kWave];
-      for (int lane = 0; lane < kWave; ++lane) {
-        v[lane] = 0.0;
-        for (int64_t ch = static_cast<int64_t>(T.list_chunk0[list]) + lane; ch < T.list_chunk0[list + 1]; ch += kWave)
-          v[lane] = v[lane] + partial[static_cast<size_t>(k) * nc + static_cast<size_t>(ch)];
-      }
-      S[k] = ml_host_wave_sum(v);
-    }
+    host_list_sums<NS>(partial.data(), nc, static_cast<size_t>(T.list_chunk0[list]), static_cast<size_t>(T.list_chunk0[list + 1]), S);
     cl_host_entry<D>(c, oi, static_cast<size_t>(T.chunk_begin[static_cast<size_t>(T.list_chunk0[list])]), P0, q0, lm0, &res0, kt0);
     finite = (hv ? cl_fold_robust<D, MODE>(S, state.data() + list * kSgState(D), ist.data() + list * kSgInts, q0, lm0)
                  : cl_fold<D, MODE>(S, state.data() + list * kSgState(D), ist.data() + list * kSgInts, q0, lm0)) &&
@@ -367,34 +279,16 @@ template <int D>
 bool cl_host_run(const cora_ctx *c, double *oi, std::vector<double> &state, std::vector<int32_t> &ist, unsigned char *deg, int64_t *n_deg,
                  ClHostVote *hv = nullptr) {
   const ClTables &T = c->cl;
-  const OdomTables &O = c->odom;
   const MeasurementTable &M = c->meas;
-  const int64_t nr = M.n_ranges;
   bool finite = true;
   std::vector<double> partial(static_cast<size_t>(kClSums(D)) * std::max<size_t>(T.chunk_begin.size(), 1), 0.0);
   for (size_t s = 0; s + 1 < T.stage_list0.size(); ++s) {
     if (hv) finite = cl_host_vote_elect<D>(c, s, oi, *hv, ist) && finite;
     finite = cl_host_pass_fold<D, 0>(c, s, oi, partial, state, ist, hv) && finite;
     finite = cl_host_pass_fold<D, 1>(c, s, oi, partial, state, ist, hv) && finite;
-    for (int32_t i = T.stage_apply0[s]; i < T.stage_apply0[s + 1]; ++i) {
-      const size_t list = static_cast<size_t>(T.apply_list[static_cast<size_t>(i)]), pos = static_cast<size_t>(T.apply_pos[static_cast<size_t>(i)]);
-      if (ist[list * kSgInts + 1] <= 0) continue;
-      pl_apply<D>(state.data() + list * kSgState(D), oi + static_cast<size_t>(O.pos_rot[pos]) * D, oi + static_cast<size_t>(O.pos_trn[pos]) * D);
-    }
+    host_apply_stage<D>(c->odom, T, s, state, ist, oi);
   }
-  int64_t count = 0;
-  for (int64_t m = 0; m < nr; ++m) {
-    const size_t rr = static_cast<size_t>(M.range_rows[static_cast<size_t>(m)]), ta = static_cast<size_t>(M.range_rows[static_cast<size_t>(nr + m)]),
-                 tb = static_cast<size_t>(M.range_rows[static_cast<size_t>(2 * nr + m)]);
-    double row[D];
-    const bool degenerate = odom_range_row<D>(oi + tb * D, oi + ta * D, row);  // (towards a: see ml_upload)
-    std::copy(row, row + D, oi + rr * D);
-    if (deg) deg[m] = degenerate ? 1 : 0;
-    count += degenerate ? 1 : 0;
-    finite = odom_finite(row, D) && finite;
-  }
-  *n_deg = count;
-  return finite;
+  return host_range_rows<D>(M, true, oi, deg, n_deg) && finite;
 }
 }  // extern "C++"
 
@@ -404,19 +298,7 @@ int cora_set_closure_placement(cora_ctx *c, const unsigned char *chain_fixed, in
   if (!c) return CORA_ERR_ARG;
   int rc = cl_check(c);
   if (rc) return rc;
-  ClTables T;
-  if ((rc = cl_build(c, chain_fixed, min_closures, T))) return rc;
-  if (c->has_device) {
-    if (hipSetDevice(c->device) != hipSuccess) return fail(c, CORA_ERR_HIP, "hipSetDevice failed");
-    if ((rc = cl_upload(c, T))) {
-      cl_release(T);
-      return rc;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    free_cl(c);
-  }
-  c->cl = std::move(T);
-  return CORA_OK;
+  return install_tables(c, c->cl, [&](ClTables &T) { return cl_build(c, chain_fixed, min_closures, T); }, [&](ClTables &T) { return cl_upload(c, T); });
 }
 
 int cora_closure_placement_counts(const cora_ctx *c, int64_t out[4]) {
@@ -445,6 +327,9 @@ struct ClConsensus {
   int32_t *consensus, *list_len;
   unsigned char *inlier;
 };
+const char *cl_not_finite(const ClConsensus *rb) {  // the refusal of a call whose flag word is set
+  return rb ? "a sum or a hypothesis of the closure placement is not finite" : "a sum of the closure placement is not finite";
+}
 int cl_consensus_check(cora_ctx *c, double barc2, int min_consensus) {
   if (!(barc2 > 0.0) || !std::isfinite(barc2)) return fail(c, CORA_ERR_ARG, "barc2 must be finite and positive");
   if (min_consensus < 1) return fail(c, CORA_ERR_ARG, "min_consensus must be at least 1");
@@ -475,14 +360,11 @@ int cl_place_dev(cora_ctx *c, double *dX, const ClConsensus *rb, int64_t *out, u
                  int32_t *chosen, double *transforms, unsigned char *degenerate) {
   const MeasurementTable &M = c->meas;
   ClTables &T = c->cl;
-  const int d = c->F.L.d, nb = odom_range_blocks(M.n_ranges);
+  const int d = c->F.L.d;
   const size_t ns = T.stage_list0.size() - 1, nlist = T.list_item.size(), ne = static_cast<size_t>(M.n_edges);
-  int rc;
-  if ((rc = ensure_red(c, static_cast<size_t>(nb) / 2 + 4))) return rc;
   ClRobustArgs R;
   ClArgs &A = R.A;
-  OdomFillArgs Fl;
-  cl_fill_args(c, dX, A, Fl);
+  cl_fill_args(c, dX, A);
   if (rb) {
     R.barc2 = rb->barc2;
     R.min_consensus = rb->min_consensus;
@@ -495,7 +377,7 @@ int cl_place_dev(cora_ctx *c, double *dX, const ClConsensus *rb, int64_t *out, u
   HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
   if (rb && ne > 0) HIP_TRY(c, hipMemsetAsync(T.d_inlier, 2, ne, c->stream));  // (an edge of no list)
   for (size_t s = 0; s < ns; ++s) {  // dependent: a stage reads the rows the stages before it wrote
-    cl_stage_args(T, s, A);
+    stage_args(T, s, A);
     if (rb) HIP_TRY(c, launch_closure_vote_elect(R, c->stream));
     A.mode = 0;
     HIP_TRY(c, rb ? launch_closure_robust_pass_fold(R, c->stream) : launch_closure_pass_fold(A, c->stream));
@@ -503,24 +385,18 @@ int cl_place_dev(cora_ctx *c, double *dX, const ClConsensus *rb, int64_t *out, u
     HIP_TRY(c, rb ? launch_closure_robust_pass_fold(R, c->stream) : launch_closure_pass_fold(A, c->stream));
     HIP_TRY(c, launch_closure_apply(A, c->stream));
   }
-  HIP_TRY(c, launch_odom_ranges(Fl, c->stream));  // (after the chains' rows)
-  int words[2] = {0, 0};
   std::vector<double> state(nlist * kSgState(d));
   std::vector<int32_t> ist(nlist * kSgInts), cint(rb ? nlist * kClCInts : 0);
   std::vector<unsigned char> inl(rb ? ne : 0);
-  HIP_TRY(c, hipMemcpyAsync(words, Fl.words, sizeof(words), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->h_flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (nlist > 0) {
-    HIP_TRY(c, hipMemcpyAsync(state.data(), T.d_state, state.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(ist.data(), T.d_istate, ist.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (rb) HIP_TRY(c, hipMemcpyAsync(cint.data(), T.d_cint, cint.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  }
-  if (rb && ne > 0) HIP_TRY(c, hipMemcpyAsync(inl.data(), T.d_inlier, ne, hipMemcpyDeviceToHost, c->stream));
-  if (degenerate && M.n_ranges > 0)
-    HIP_TRY(c, hipMemcpyAsync(degenerate, T.d_deg, static_cast<size_t>(M.n_ranges), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (*c->h_flag) return fail(c, CORA_ERR_NAN, rb ? "a sum or a hypothesis of the closure placement is not finite" : "a sum of the closure placement is not finite");
-  cl_results(c, state, ist, words[0], out, status, cost_start, cost_final, chosen, transforms);
+  int64_t n_deg = 0;
+  const int rc = range_rows_step(c, dX, true, degenerate, cl_not_finite(rb), &n_deg, [&]() -> int {  // (after the chains' rows)
+    if (const int e = read_back_state(c, state, T.d_state, ist, T.d_istate)) return e;
+    if (rb && nlist > 0) HIP_TRY(c, hipMemcpyAsync(cint.data(), T.d_cint, cint.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (rb && ne > 0) HIP_TRY(c, hipMemcpyAsync(inl.data(), T.d_inlier, ne, hipMemcpyDeviceToHost, c->stream));
+    return CORA_OK;
+  });
+  if (rc) return rc;
+  cl_results(c, state, ist, n_deg, out, status, cost_start, cost_final, chosen, transforms);
   if (rb) cl_robust_results(c, ist, cint, inl, *rb, out);
   return CORA_OK;
 }
@@ -549,32 +425,19 @@ int cora_place_by_closures_robust_dev(cora_ctx *c, double *dX, double barc2, int
 }
 
 namespace {
-// the host-pointer forms: upload, the device-pointer form, download
+// the host-pointer forms (with_uploaded_x)
 int cl_place_host_ptr(cora_ctx *c, double *X, int ldx, const ClConsensus *rb, int64_t *out, unsigned char *status, double *cost_start,
                       double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate) {
-  if (ldx < c->F.L.N) return fail(c, CORA_ERR_SHAPE, "leading dimension smaller than N");
-  const int d = c->F.L.d;
-  double *dX;
-  int rc;
-  if ((rc = compare_vec(c, 3, ld_for(d), &dX))) return rc;
-  rc = upload_impl(c, X, ldx, d, dX);
-  if (rc == CORA_OK) rc = cl_place_dev(c, dX, rb, out, status, cost_start, cost_final, chosen, transforms, degenerate);
-  if (rc == CORA_OK) rc = download_impl(c, dX, d, X, ldx);
-  // the vector of this form is not kept: a caller that stays resident uses the device-pointer form
-  (void)hipStreamSynchronize(c->stream);
-  compare_release(c, 3, 4, 0);
-  return rc;
+  return with_uploaded_x(c, X, ldx, [&](double *dX) {
+    return cl_place_dev(c, dX, rb, out, status, cost_start, cost_final, chosen, transforms, degenerate);
+  });
 }
-// The same on the host through the translated tables, every sum in the kernels' bracket order and every term, hypothesis and
-// solve through the functions of kernels.h the kernels call: the output has the device's bits.  Works on a plan-only handle.
+// the host mirrors (with_host_x), every hypothesis too through the function of kernels.h the kernels call
 int cl_place_mirror(cora_ctx *c, double *X, int ldx, const ClConsensus *rb, int64_t *out, unsigned char *status, double *cost_start,
                     double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate) {
-  const HostFormat &F = c->F;
-  const Layout &L = F.L;
-  if (ldx < L.N) return fail(c, CORA_ERR_SHAPE, "leading dimension smaller than N");
-  const int d = L.d;
+  const int d = c->F.L.d;
   const size_t nlist = c->cl.list_item.size();
-  std::vector<double> oi(static_cast<size_t>(L.rows) * d, 0.0), state(nlist * kSgState(d), 0.0);
+  std::vector<double> state(nlist * kSgState(d), 0.0);
   std::vector<int32_t> ist(nlist * kSgInts, 0);
   ClHostVote hv;
   if (rb) {
@@ -584,14 +447,11 @@ int cl_place_mirror(cora_ctx *c, double *X, int ldx, const ClConsensus *rb, int6
     hv.cint.assign(nlist * kClCInts, 0);
     hv.inl.assign(static_cast<size_t>(c->meas.n_edges), 2);
   }
-  for (int cc = 0; cc < d; ++cc)
-    for (int64_t i = 0; i < L.N; ++i) oi[static_cast<size_t>(F.api2int[i]) * d + cc] = X[static_cast<size_t>(cc) * ldx + i];
   int64_t n_deg = 0;
-  const bool finite = d == 2 ? cl_host_run<2>(c, oi.data(), state, ist, degenerate, &n_deg, rb ? &hv : nullptr)
-                             : cl_host_run<3>(c, oi.data(), state, ist, degenerate, &n_deg, rb ? &hv : nullptr);
-  if (!finite) return fail(c, CORA_ERR_NAN, rb ? "a sum or a hypothesis of the closure placement is not finite" : "a sum of the closure placement is not finite");
-  for (int cc = 0; cc < d; ++cc)
-    for (int64_t i = 0; i < L.N; ++i) X[static_cast<size_t>(cc) * ldx + i] = oi[static_cast<size_t>(F.api2int[i]) * d + cc];
+  const int rc = with_host_x(c, X, ldx, cl_not_finite(rb), [&](auto D, double *oi) {
+    return cl_host_run<D()>(c, oi, state, ist, degenerate, &n_deg, rb ? &hv : nullptr);
+  });
+  if (rc) return rc;
   cl_results(c, state, ist, n_deg, out, status, cost_start, cost_final, chosen, transforms);
   if (rb) cl_robust_results(c, ist, hv.cint, hv.inl, *rb, out);
   return CORA_OK;

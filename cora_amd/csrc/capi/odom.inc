@@ -1,4 +1,4 @@
-// Part of capi.hip (one translation unit; included there, in this order).  odometry initialisation (a segmented scan of SE(d) over the chains of the measurement table): chain tables, device-pointer form, host-pointer form, host mirror.  Reads the measurement table and the row maps; writes nothing the handle computes with.
+// Part of capi.hip (one translation unit; included there, in this order).  odometry initialisation (a segmented scan of SE(d) over the chains of the measurement table): chain tables, device-pointer form, host-pointer form, host mirror.  Reads the measurement table and the row maps; writes nothing the handle computes with.  What it shares with the other initialisers -- the range-row step, the host-pointer and host-mirror wrappers, installing tables, chunk cutting, the mirror's sums -- is in capi/init_common.inc.
 
 namespace {
 
@@ -59,13 +59,7 @@ int odom_build(cora_ctx *c, int64_t n_chains, const int64_t *chain_ptr, const in
     T.free_trn.push_back(trn_of[i]);
   }
   T.lm_row.assign(trn_of + L.n, trn_of + L.nt);
-  // (a range row two measurements name would be written by two threads)
-  std::fill(written.begin(), written.end(), 0);
-  for (int64_t m = 0; m < M.n_ranges; ++m) {
-    unsigned char &w = written[static_cast<size_t>(M.range_rows[static_cast<size_t>(m)])];
-    if (w) return fail(c, CORA_ERR_ARG, "range measurement " + std::to_string(m) + " names a range row an earlier one names");
-    w = 1;
-  }
+  if (const int rc = range_rows_unique(c)) return rc;
   T.built = true;
   return CORA_OK;
 }
@@ -76,43 +70,23 @@ size_t odom_stage_doubles(const cora_ctx *c, const OdomTables &T) {
 
 // the device side of freshly built tables (T's device pointers are null); on failure T owns what was allocated
 int odom_upload(cora_ctx *c, OdomTables &T) {
-  std::vector<int32_t> idx;
-  for (const std::vector<int32_t> *v : {&T.pos_edge, &T.pos_chain, &T.pos_rot, &T.pos_trn, &T.free_rot, &T.free_trn, &T.lm_row})
-    idx.insert(idx.end(), v->begin(), v->end());
-  HIP_TRY(c, to_device(&T.d_idx, idx));
+  HIP_TRY(c, upload_joined(&T.d_idx, {&T.pos_edge, &T.pos_chain, &T.pos_rot, &T.pos_trn, &T.free_rot, &T.free_trn, &T.lm_row}));
   const size_t work = 2 * static_cast<size_t>(kOdomFields(c->F.L.d)) * std::max(odom_tiles(T.P), 1);
   HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_work), work * sizeof(double)));
   const size_t stage = std::max<size_t>(odom_stage_doubles(c, T), 1) * sizeof(double);
   HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_stage), stage));
   HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&T.h_stage), stage));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_deg), std::max<size_t>(static_cast<size_t>(c->meas.n_ranges), 1)));
   return CORA_OK;
-}
-
-void odom_release(OdomTables &T) {  // a table that never reached the handle
-  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_work), static_cast<void *>(T.d_stage), static_cast<void *>(T.d_deg)})
-    if (p) (void)hipFree(p);
-  if (T.h_stage) (void)hipHostFree(T.h_stage);
 }
 
 // builds, uploads and installs; a failure leaves the handle's tables as they were
 int odom_install(cora_ctx *c, int64_t n_chains, const int64_t *chain_ptr, const int32_t *chain_edges) {
-  OdomTables T;
-  int rc = odom_build(c, n_chains, chain_ptr, chain_edges, T);
+  const int rc = install_tables(c, c->odom, [&](OdomTables &T) { return odom_build(c, n_chains, chain_ptr, chain_edges, T); },
+                                [&](OdomTables &T) { return odom_upload(c, T); });
   if (rc) return rc;
-  if (c->has_device) {
-    if (hipSetDevice(c->device) != hipSuccess) return fail(c, CORA_ERR_HIP, "hipSetDevice failed");
-    if ((rc = odom_upload(c, T))) {
-      odom_release(T);
-      return rc;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    free_odom(c);
-  }
-  free_pl(c);  // (the chain placement's stages name the positions of the chains they were built from)
-  free_sg(c);  // (so do the sighting placement's lists)
-  free_cl(c);  // (and the closure placement's)
-  c->odom = std::move(T);
+  free_tables(c->pl);  // (the chain placement's stages name the positions of the chains they were built from)
+  free_tables(c->sg);  // (so do the sighting placement's lists)
+  free_tables(c->cl);  // (and the closure placement's)
   return CORA_OK;
 }
 
@@ -154,7 +128,7 @@ template <int D>
 bool odom_host_run(const cora_ctx *c, const double *starts, const double *landmarks, double *oi, unsigned char *deg, int64_t *n_deg) {
   const OdomTables &T = c->odom;
   const MeasurementTable &M = c->meas;
-  const int64_t P = T.P, ne = M.n_edges, nr = M.n_ranges;
+  const int64_t P = T.P, ne = M.n_edges;
   const int ntiles = odom_tiles(P);
   bool finite = true;
   std::vector<OdomEl<D>> el(static_cast<size_t>(ntiles) * kOdomTile), carry(static_cast<size_t>(ntiles));
@@ -203,19 +177,7 @@ bool odom_host_run(const cora_ctx *c, const double *starts, const double *landma
   }
   for (size_t l = 0; l < T.lm_row.size(); ++l)
     for (int cc = 0; cc < D; ++cc) oi[static_cast<size_t>(T.lm_row[l]) * D + cc] = landmarks ? landmarks[l * D + cc] : 0.0;
-  int64_t count = 0;
-  for (int64_t m = 0; m < nr; ++m) {
-    const size_t rr = static_cast<size_t>(M.range_rows[static_cast<size_t>(m)]), ta = static_cast<size_t>(M.range_rows[static_cast<size_t>(nr + m)]),
-                 tb = static_cast<size_t>(M.range_rows[static_cast<size_t>(2 * nr + m)]);
-    double row[D];
-    const bool degenerate = odom_range_row<D>(oi + ta * D, oi + tb * D, row);
-    std::copy(row, row + D, oi + rr * D);
-    if (deg) deg[m] = degenerate ? 1 : 0;
-    count += degenerate ? 1 : 0;
-    finite = odom_finite(row, D) && finite;
-  }
-  *n_deg = count;
-  return finite;
+  return host_range_rows<D>(M, false, oi, deg, n_deg) && finite;
 }
 }  // extern "C++"
 
@@ -255,9 +217,8 @@ int cora_odometry_init_dev(cora_ctx *c, const double *starts, const double *land
   const Layout &L = c->F.L;
   const MeasurementTable &M = c->meas;
   OdomTables &T = c->odom;
-  const int d = L.d, nb = odom_range_blocks(M.n_ranges);
+  const int d = L.d;
   const size_t ns = static_cast<size_t>(T.n_chains) * d, nl = static_cast<size_t>(L.nt - L.n) * d;
-  if ((rc = ensure_red(c, static_cast<size_t>(nb) / 2 + 4))) return rc;
   if (ns) std::copy(starts, starts + ns, T.h_stage);
   if (landmarks && nl) std::copy(landmarks, landmarks + nl, T.h_stage + ns);
   if (ns + (landmarks ? nl : 0) > 0)
@@ -281,32 +242,20 @@ int cora_odometry_init_dev(cora_ctx *c, const double *starts, const double *land
   Fl.d = d;
   Fl.n_free = static_cast<int64_t>(T.free_rot.size());
   Fl.n_lm = static_cast<int64_t>(T.lm_row.size());
-  Fl.n_ranges = M.n_ranges;
   Fl.free_rot = A.pos_trn + T.P;
   Fl.free_trn = Fl.free_rot + Fl.n_free;
   Fl.lm_row = Fl.free_trn + Fl.n_free;
-  Fl.range_rows = M.d_range_rows;
   Fl.lm = landmarks ? T.d_stage + ns : nullptr;
-  Fl.deg = T.d_deg;
-  Fl.partial = reinterpret_cast<int *>(c->d_red);
-  Fl.words = Fl.partial + nb;
-  Fl.flag = c->d_flag;
   Fl.out = dOut;
   wrote(c, dOut);
   HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
   HIP_TRY(c, hipMemsetAsync(dOut, 0, vec_bytes(c, ld_for(d)), c->stream));
   HIP_TRY(c, launch_odom_fill(Fl, c->stream));
   HIP_TRY(c, launch_odom_scan(A, c->stream));
-  HIP_TRY(c, launch_odom_ranges(Fl, c->stream));  // (after both: it reads the translation rows they wrote)
-  int words[2] = {0, 0};
-  HIP_TRY(c, hipMemcpyAsync(words, Fl.words, sizeof(words), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->h_flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (degenerate && M.n_ranges > 0)
-    HIP_TRY(c, hipMemcpyAsync(degenerate, T.d_deg, static_cast<size_t>(M.n_ranges), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (*c->h_flag) return fail(c, CORA_ERR_NAN, "a product of the odometry initialisation is not finite");
+  // (after both: it reads the translation rows they wrote)
+  if ((rc = range_rows_step(c, dOut, false, degenerate, "a product of the odometry initialisation is not finite", &out[1], []() -> int { return CORA_OK; })))
+    return rc;
   out[0] = T.P;
-  out[1] = words[0];
   return CORA_OK;
 }
 

@@ -1,4 +1,4 @@
-// Part of capi.hip (one translation unit; included there, in this order).  chain placement from inter-robot ranges (a rigid motion per odometry chain from the pose-pose ranges between chains): order of the stages and entry tables, device-pointer form, host-pointer form, host mirror.  Reads the measurement table, the chain tables and the row maps; writes nothing the handle computes with.
+// Part of capi.hip (one translation unit; included there, in this order).  chain placement from inter-robot ranges (a rigid motion per odometry chain from the pose-pose ranges between chains): order of the stages and entry tables, device-pointer form, host-pointer form, host mirror.  Reads the measurement table, the chain tables and the row maps; writes nothing the handle computes with.  What it shares with the other initialisers -- the range-row step, the host-pointer and host-mirror wrappers, installing tables, chunk cutting, the mirror's sums -- is in capi/init_common.inc.
 
 namespace {
 
@@ -17,23 +17,10 @@ int pl_build(cora_ctx *c, const unsigned char *chain_fixed, int min_ranges, PlTa
   const int64_t nr = M.n_ranges, nch = O.n_chains;
   if (min_ranges < kPlUnknowns(L.d) + 1)
     return fail(c, CORA_ERR_ARG, "min_ranges must be at least " + std::to_string(kPlUnknowns(L.d) + 1) + ", the unknowns of the linear stage + 1");
-  std::vector<unsigned char> placed(static_cast<size_t>(nch), 0);
-  if (chain_fixed) {
-    bool any = false;
-    for (int64_t ch = 0; ch < nch; ++ch) any = (placed[static_cast<size_t>(ch)] = chain_fixed[ch] ? 1 : 0) || any;
-    if (!any) return fail(c, CORA_ERR_ARG, "chain_fixed fixes no chain");
-  } else if (nch > 0) {
-    placed[0] = 1;
-  } else {
-    return fail(c, CORA_ERR_ARG, "no chain to fix: the chain tables hold no chain");
-  }
-  std::vector<int32_t> chain_of(static_cast<size_t>(L.rows), -1), first(static_cast<size_t>(nch), -1), count(static_cast<size_t>(nch), 0);
-  for (int64_t pos = 0; pos < O.P; ++pos) {
-    const int32_t ch = O.pos_chain[static_cast<size_t>(pos)];
-    chain_of[static_cast<size_t>(O.pos_trn[static_cast<size_t>(pos)])] = ch;
-    if (first[static_cast<size_t>(ch)] < 0) first[static_cast<size_t>(ch)] = static_cast<int32_t>(pos);
-    ++count[static_cast<size_t>(ch)];
-  }
+  std::vector<unsigned char> placed;
+  if (const int rc = seed_fixed_chains(c, chain_fixed, placed)) return rc;
+  const ChainMaps maps = chain_maps(c);
+  const std::vector<int32_t> &chain_of = maps.chain_of;
   // the ranges between two chains; cnt[c][c'] entries of c against c'
   std::vector<int32_t> use_m, use_ca, use_cb;
   std::vector<int64_t> cnt(static_cast<size_t>(nch * nch), 0);
@@ -78,15 +65,12 @@ int pl_build(cora_ctx *c, const unsigned char *chain_fixed, int min_ranges, PlTa
       T.ent_m.push_back(m);
     }
     const int64_t len = static_cast<int64_t>(T.ent_m.size() - begin);
-    for (int64_t at = 0; at < len; at += kPlChunk) {
-      T.chunk_begin.push_back(static_cast<int32_t>(static_cast<int64_t>(begin) + at));
-      T.chunk_len.push_back(static_cast<int32_t>(std::min<int64_t>(kPlChunk, len - at)));
-    }
+    cut_chunks(static_cast<int64_t>(begin), len, T.chunk_begin, T.chunk_len, nullptr, 0);
     T.stage_chain.push_back(static_cast<int32_t>(take));
     T.stage_origin_q.push_back(T.ent_q[begin]);
     T.stage_origin_a.push_back(T.ent_a[begin]);
-    T.stage_pos0.push_back(first[static_cast<size_t>(take)]);
-    T.stage_npos.push_back(count[static_cast<size_t>(take)]);
+    T.stage_pos0.push_back(maps.chain_pos[static_cast<size_t>(take)].front());
+    T.stage_npos.push_back(static_cast<int32_t>(maps.chain_pos[static_cast<size_t>(take)].size()));
     T.stage_chunk0.push_back(static_cast<int32_t>(T.chunk_begin.size()));
     T.max_chunks = std::max<int64_t>(T.max_chunks, (len + kPlChunk - 1) / kPlChunk);
     placed[static_cast<size_t>(take)] = 1;
@@ -98,42 +82,20 @@ int pl_build(cora_ctx *c, const unsigned char *chain_fixed, int min_ranges, PlTa
     for (int64_t o = 0; o < nch; ++o) n += cnt[static_cast<size_t>(ch * nch + o)];
     T.chain_init[static_cast<size_t>(ch)] = n > 0 ? 1 : 3;
   }
-  // (a range row two measurements name would be written by two threads of the range-row step)
-  std::vector<unsigned char> written(static_cast<size_t>(L.rows), 0);
-  for (int64_t m = 0; m < nr; ++m) {
-    unsigned char &w = written[static_cast<size_t>(M.range_rows[static_cast<size_t>(m)])];
-    if (w) return fail(c, CORA_ERR_ARG, "range measurement " + std::to_string(m) + " names a range row an earlier one names");
-    w = 1;
-  }
+  if (const int rc = range_rows_unique(c)) return rc;
   T.built = true;
   return CORA_OK;
 }
 
 // the device side of freshly built tables (T's device pointers are null); on failure T owns what was allocated
 int pl_upload(cora_ctx *c, PlTables &T) {
-  std::vector<int32_t> idx;
-  for (const std::vector<int32_t> *v : {&T.chunk_begin, &T.chunk_len, &T.ent_q, &T.ent_a, &T.ent_m}) idx.insert(idx.end(), v->begin(), v->end());
-  idx.push_back(0);  // (never an empty buffer)
-  HIP_TRY(c, to_device(&T.d_idx, idx));
+  HIP_TRY(c, upload_joined(&T.d_idx, {&T.chunk_begin, &T.chunk_len, &T.ent_q, &T.ent_a, &T.ent_m}));
   const int d = c->F.L.d;
   const size_t ns = std::max<size_t>(T.stage_chain.size(), 1), nc = static_cast<size_t>(std::max<int64_t>(T.max_chunks, 1));
   HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_partial), static_cast<size_t>(kPlSums(d)) * nc * sizeof(double)));
   HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_state), static_cast<size_t>(kPlState(d)) * ns * sizeof(double)));
   HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_istate), static_cast<size_t>(kPlInts) * ns * sizeof(int32_t)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_deg), std::max<size_t>(static_cast<size_t>(c->meas.n_ranges), 1)));
-  // the range-row step over the table with a and b exchanged: the direction of least residual (ml_upload)
-  const size_t nr = static_cast<size_t>(c->meas.n_ranges);
-  std::vector<int32_t> rows(c->meas.range_rows);
-  std::swap_ranges(rows.begin() + static_cast<std::ptrdiff_t>(nr), rows.begin() + static_cast<std::ptrdiff_t>(2 * nr), rows.begin() + static_cast<std::ptrdiff_t>(2 * nr));
-  rows.push_back(0);
-  HIP_TRY(c, to_device(&T.d_range_rows, rows));
   return CORA_OK;
-}
-
-void pl_release(PlTables &T) {  // a table that never reached the handle
-  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state), static_cast<void *>(T.d_istate),
-                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows)})
-    if (p) (void)hipFree(p);
 }
 
 int pl_args_check(cora_ctx *c, const double *X, int gn_steps, const int64_t *out) {
@@ -157,8 +119,7 @@ void pl_results(const cora_ctx *c, const std::vector<double> &state, const std::
     if (cost_linear) cost_linear[ch] = 0.0;
     if (cost_final) cost_final[ch] = 0.0;
     if (chosen) chosen[ch] = -1;
-    if (transforms)
-      for (int i = 0; i < G; ++i) transforms[ch * G + i] = i < d * d && i / d == i % d ? 1.0 : 0.0;
+    if (transforms) identity_transform(d, transforms + ch * G);
   }
   for (size_t s = 0; s < ns; ++s) {
     const size_t ch = static_cast<size_t>(T.stage_chain[s]);
@@ -197,15 +158,6 @@ bool pl_host_run(const cora_ctx *c, int gn_steps, double *oi, std::vector<double
     const double *q0 = oi + static_cast<size_t>(T.stage_origin_q[s]) * D, *a0 = oi + static_cast<size_t>(T.stage_origin_a[s]) * D;
     double *st = state.data() + s * kPlState(D);
     int32_t *li = ist.data() + s * kPlInts;
-    // lane j: 0.0 + chunk j + chunk (j + 64) + .., then the butterfly
-    auto fold_sum = [&](int p) {
-      double v[kWave];
-      for (int lane = 0; lane < kWave; ++lane) {
-        v[lane] = 0.0;
-        for (size_t ch = static_cast<size_t>(lane); ch < nc; ch += kWave) v[lane] = v[lane] + partial[static_cast<size_t>(p) * stride + ch];
-      }
-      return ml_host_wave_sum(v);
-    };
     for (size_t ch = 0; ch < nc; ++ch) {
       const int len = T.chunk_len[c0 + ch];
       for (int i = 0; i < len; ++i) {
@@ -221,36 +173,18 @@ bool pl_host_run(const cora_ctx *c, int gn_steps, double *oi, std::vector<double
       }
     }
     double S[NP];
-    for (int p = 0; p < NP; ++p) S[p] = fold_sum(p);
+    host_list_sums<NP>(partial.data(), stride, 0, nc, S);
     finite = pl_fold_linear<D>(S, work.data(), st, li, q0, a0) && finite;
     for (int step = 0; step <= gn_steps + 1; ++step) {
       const double *g = st + (step == 0 ? G : 0);
-      for (size_t ch = 0; ch < nc; ++ch) {
-        double wave[kPlChunk / kWave][NS];
-        for (int w = 0; w < kPlChunk / kWave; ++w) {
-          double tm[kWave][NS];
-          for (int lane = 0; lane < kWave; ++lane) {
-            const int i = w * kWave + lane;
-            for (int k = 0; k < NS; ++k) tm[lane][k] = 0.0;
-            if (i >= T.chunk_len[c0 + ch]) continue;
-            const size_t e = static_cast<size_t>(T.chunk_begin[c0 + ch]) + i, m = static_cast<size_t>(T.ent_m[e]);
-            pl_gn_terms<D>(g, st[3 * G + 4], q0, a0, oi + static_cast<size_t>(T.ent_q[e]) * D, oi + static_cast<size_t>(T.ent_a[e]) * D,
-                           M.range_data[m], M.range_data[static_cast<size_t>(nr) + m], tm[lane]);
-          }
-          for (int k = 0; k < NS; ++k) {
-            double v[kWave];
-            for (int lane = 0; lane < kWave; ++lane) v[lane] = tm[lane][k];
-            wave[w][k] = ml_host_wave_sum(v);
-          }
-        }
-        for (int k = 0; k < NS; ++k) {
-          double v = wave[0][k];
-          for (int w = 1; w < kPlChunk / kWave; ++w) v = v + wave[w][k];
-          partial[static_cast<size_t>(k) * stride + ch] = v;
-        }
-      }
+      for (size_t ch = 0; ch < nc; ++ch)
+        host_chunk_sums<NS>(T.chunk_len[c0 + ch], [&](int i, double *t) {
+          const size_t e = static_cast<size_t>(T.chunk_begin[c0 + ch]) + i, m = static_cast<size_t>(T.ent_m[e]);
+          pl_gn_terms<D>(g, st[3 * G + 4], q0, a0, oi + static_cast<size_t>(T.ent_q[e]) * D, oi + static_cast<size_t>(T.ent_a[e]) * D,
+                         M.range_data[m], M.range_data[static_cast<size_t>(nr) + m], t);
+        }, partial.data(), stride, ch);
       double Sg[NS];
-      for (int k = 0; k < NS; ++k) Sg[k] = fold_sum(k);
+      host_list_sums<NS>(partial.data(), stride, 0, nc, Sg);
       finite = pl_fold_gn<D>(step, step == gn_steps + 1 ? 1 : 0, Sg, st, li, q0, a0) && finite;
     }
     if (li[1] > 0)
@@ -259,19 +193,7 @@ bool pl_host_run(const cora_ctx *c, int gn_steps, double *oi, std::vector<double
         pl_apply<D>(st + 2 * G, oi + static_cast<size_t>(O.pos_rot[pos]) * D, oi + static_cast<size_t>(O.pos_trn[pos]) * D);
       }
   }
-  int64_t count = 0;
-  for (int64_t m = 0; m < nr; ++m) {
-    const size_t rr = static_cast<size_t>(M.range_rows[static_cast<size_t>(m)]), ta = static_cast<size_t>(M.range_rows[static_cast<size_t>(nr + m)]),
-                 tb = static_cast<size_t>(M.range_rows[static_cast<size_t>(2 * nr + m)]);
-    double row[D];
-    const bool degenerate = odom_range_row<D>(oi + tb * D, oi + ta * D, row);  // (towards a: see ml_upload)
-    std::copy(row, row + D, oi + rr * D);
-    if (deg) deg[m] = degenerate ? 1 : 0;
-    count += degenerate ? 1 : 0;
-    finite = odom_finite(row, D) && finite;
-  }
-  *n_deg = count;
-  return finite;
+  return host_range_rows<D>(M, true, oi, deg, n_deg) && finite;
 }
 }  // extern "C++"
 
@@ -281,19 +203,7 @@ int cora_set_chain_placement(cora_ctx *c, const unsigned char *chain_fixed, int 
   if (!c) return CORA_ERR_ARG;
   int rc = pl_check(c);
   if (rc) return rc;
-  PlTables T;
-  if ((rc = pl_build(c, chain_fixed, min_ranges, T))) return rc;
-  if (c->has_device) {
-    if (hipSetDevice(c->device) != hipSuccess) return fail(c, CORA_ERR_HIP, "hipSetDevice failed");
-    if ((rc = pl_upload(c, T))) {
-      pl_release(T);
-      return rc;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    free_pl(c);
-  }
-  c->pl = std::move(T);
-  return CORA_OK;
+  return install_tables(c, c->pl, [&](PlTables &T) { return pl_build(c, chain_fixed, min_ranges, T); }, [&](PlTables &T) { return pl_upload(c, T); });
 }
 
 int cora_chain_placement_counts(const cora_ctx *c, int64_t out[4]) {
@@ -322,9 +232,8 @@ int cora_place_chains_dev(cora_ctx *c, double *dX, int gn_steps, int64_t out[5],
   const MeasurementTable &M = c->meas;
   PlTables &T = c->pl;
   const OdomTables &O = c->odom;
-  const int d = L.d, nb = odom_range_blocks(M.n_ranges);
+  const int d = L.d;
   const size_t ns = T.stage_chain.size(), nc = T.chunk_begin.size(), ne = T.ent_m.size();
-  if ((rc = ensure_red(c, static_cast<size_t>(nb) / 2 + 4))) return rc;
   PlArgs A;
   A.d = d;
   A.n_ranges = M.n_ranges;
@@ -340,15 +249,6 @@ int cora_place_chains_dev(cora_ctx *c, double *dX, int gn_steps, int64_t out[5],
   A.partial = T.d_partial;
   A.x = dX;
   A.flag = c->d_flag;
-  OdomFillArgs Fl;  // the range-row step of the odometry initialisation, its rules unchanged, over the exchanged table
-  Fl.d = d;
-  Fl.n_ranges = M.n_ranges;
-  Fl.range_rows = T.d_range_rows;
-  Fl.deg = T.d_deg;
-  Fl.partial = reinterpret_cast<int *>(c->d_red);
-  Fl.words = Fl.partial + nb;
-  Fl.flag = c->d_flag;
-  Fl.out = dX;
   wrote(c, dX);
   HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
   for (size_t s = 0; s < ns; ++s) {  // dependent: a stage reads the rows the stages before it wrote
@@ -370,21 +270,13 @@ int cora_place_chains_dev(cora_ctx *c, double *dX, int gn_steps, int64_t out[5],
     }
     HIP_TRY(c, launch_place_apply(A, c->stream));
   }
-  HIP_TRY(c, launch_odom_ranges(Fl, c->stream));  // (after the chains' rows)
-  int words[2] = {0, 0};
   std::vector<double> state(ns * kPlState(d));
   std::vector<int32_t> ist(ns * kPlInts);
-  HIP_TRY(c, hipMemcpyAsync(words, Fl.words, sizeof(words), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->h_flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (ns > 0) {
-    HIP_TRY(c, hipMemcpyAsync(state.data(), T.d_state, state.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(ist.data(), T.d_istate, ist.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  }
-  if (degenerate && M.n_ranges > 0)
-    HIP_TRY(c, hipMemcpyAsync(degenerate, T.d_deg, static_cast<size_t>(M.n_ranges), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (*c->h_flag) return fail(c, CORA_ERR_NAN, "a sum of the chain placement is not finite");
-  pl_results(c, state, ist, words[0], out, status, cost_start, cost_linear, cost_final, chosen, transforms);
+  int64_t n_deg = 0;
+  if ((rc = range_rows_step(c, dX, true, degenerate, "a sum of the chain placement is not finite", &n_deg,  // (after the chains' rows)
+                            [&] { return read_back_state(c, state, T.d_state, ist, T.d_istate); })))
+    return rc;
+  pl_results(c, state, ist, n_deg, out, status, cost_start, cost_linear, cost_final, chosen, transforms);
   return CORA_OK;
 }
 
@@ -395,43 +287,25 @@ int cora_place_chains(cora_ctx *c, double *X, int ldx, int gn_steps, int64_t out
   if (rc) return rc;
   NEED_DEVICE(c);
   if ((rc = pl_args_check(c, X, gn_steps, out))) return rc;
-  if (ldx < c->F.L.N) return fail(c, CORA_ERR_SHAPE, "leading dimension smaller than N");
-  const int d = c->F.L.d;
-  double *dX;
-  if ((rc = compare_vec(c, 3, ld_for(d), &dX))) return rc;
-  rc = upload_impl(c, X, ldx, d, dX);
-  if (rc == CORA_OK)
-    rc = cora_place_chains_dev(c, dX, gn_steps, out, status, cost_start, cost_linear, cost_final, chosen, transforms, degenerate);
-  if (rc == CORA_OK) rc = download_impl(c, dX, d, X, ldx);
-  // the vector of this form is not kept: a caller that stays resident uses cora_place_chains_dev
-  (void)hipStreamSynchronize(c->stream);
-  compare_release(c, 3, 4, 0);
-  return rc;
+  return with_uploaded_x(c, X, ldx, [&](double *dX) {
+    return cora_place_chains_dev(c, dX, gn_steps, out, status, cost_start, cost_linear, cost_final, chosen, transforms, degenerate);
+  });
 }
 
-// The same on the host through the translated tables, every sum in the kernels' bracket order and every term and solve
-// through the functions of kernels.h the kernels call: the output has the device's bits.  Works on a plan-only handle.
+// the host mirror (with_host_x)
 int cora_debug_place_chains_host(cora_ctx *c, double *X, int ldx, int gn_steps, int64_t out[5], unsigned char *status, double *cost_start,
                                  double *cost_linear, double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate) {
   if (!c) return CORA_ERR_ARG;
   int rc = pl_check(c);
   if (rc) return rc;
   if ((rc = pl_args_check(c, X, gn_steps, out))) return rc;
-  const HostFormat &F = c->F;
-  const Layout &L = F.L;
-  if (ldx < L.N) return fail(c, CORA_ERR_SHAPE, "leading dimension smaller than N");
-  const int d = L.d;
   const size_t ns = c->pl.stage_chain.size();
-  std::vector<double> oi(static_cast<size_t>(L.rows) * d, 0.0), state(ns * kPlState(d), 0.0);
+  std::vector<double> state(ns * kPlState(c->F.L.d), 0.0);
   std::vector<int32_t> ist(ns * kPlInts, 0);
-  for (int cc = 0; cc < d; ++cc)
-    for (int64_t i = 0; i < L.N; ++i) oi[static_cast<size_t>(F.api2int[i]) * d + cc] = X[static_cast<size_t>(cc) * ldx + i];
   int64_t n_deg = 0;
-  const bool finite = d == 2 ? pl_host_run<2>(c, gn_steps, oi.data(), state, ist, degenerate, &n_deg)
-                             : pl_host_run<3>(c, gn_steps, oi.data(), state, ist, degenerate, &n_deg);
-  if (!finite) return fail(c, CORA_ERR_NAN, "a sum of the chain placement is not finite");
-  for (int cc = 0; cc < d; ++cc)
-    for (int64_t i = 0; i < L.N; ++i) X[static_cast<size_t>(cc) * ldx + i] = oi[static_cast<size_t>(F.api2int[i]) * d + cc];
+  if ((rc = with_host_x(c, X, ldx, "a sum of the chain placement is not finite",
+                        [&](auto D, double *oi) { return pl_host_run<D()>(c, gn_steps, oi, state, ist, degenerate, &n_deg); })))
+    return rc;
   pl_results(c, state, ist, n_deg, out, status, cost_start, cost_linear, cost_final, chosen, transforms);
   return CORA_OK;
 }

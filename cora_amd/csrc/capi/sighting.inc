@@ -1,4 +1,4 @@
-// Part of capi.hip (one translation unit; included there, in this order).  placement from pose-landmark sightings (landmarks by the weighted mean of what placed poses predict, chains by the weighted rigid alignment onto placed landmarks): order of the stages and list tables, device-pointer form, host-pointer form, host mirror.  Reads the measurement table, the chain tables and the row maps; writes nothing the handle computes with.
+// Part of capi.hip (one translation unit; included there, in this order).  placement from pose-landmark sightings (landmarks by the weighted mean of what placed poses predict, chains by the weighted rigid alignment onto placed landmarks): order of the stages and list tables, device-pointer form, host-pointer form, host mirror.  Reads the measurement table, the chain tables and the row maps; writes nothing the handle computes with.  What it shares with the other initialisers -- the range-row step, the host-pointer and host-mirror wrappers, installing tables, chunk cutting, the mirror's sums -- is in capi/init_common.inc.
 
 namespace {
 
@@ -18,26 +18,15 @@ int sg_build(cora_ctx *c, const unsigned char *chain_fixed, const unsigned char 
   const int64_t ne = M.n_edges, nch = O.n_chains, nl = static_cast<int64_t>(O.lm_row.size());
   if (min_sightings < d) return fail(c, CORA_ERR_ARG, "min_sightings must be at least d");
   if (ne >= (int64_t(1) << 31)) return fail(c, CORA_ERR_ARG, "the edge table has more entries than a 32-bit index holds");
-  std::vector<unsigned char> placed(static_cast<size_t>(nch), 0), lm_placed(static_cast<size_t>(nl), 0);
-  if (chain_fixed) {
-    bool any = false;
-    for (int64_t ch = 0; ch < nch; ++ch) any = (placed[static_cast<size_t>(ch)] = chain_fixed[ch] ? 1 : 0) || any;
-    if (!any) return fail(c, CORA_ERR_ARG, "chain_fixed fixes no chain");
-  } else if (nch > 0) {
-    placed[0] = 1;
-  } else {
-    return fail(c, CORA_ERR_ARG, "no chain to fix: the chain tables hold no chain");
-  }
+  std::vector<unsigned char> placed, lm_placed(static_cast<size_t>(nl), 0);
+  if (const int rc = seed_fixed_chains(c, chain_fixed, placed)) return rc;
   if (landmark_fixed)
     for (int64_t l = 0; l < nl; ++l) lm_placed[static_cast<size_t>(l)] = landmark_fixed[l] ? 1 : 0;
   const std::vector<unsigned char> lm_fixed = lm_placed;
-  std::vector<int32_t> chain_of(static_cast<size_t>(L.rows), -1), lm_of(static_cast<size_t>(L.rows), -1);
-  std::vector<std::vector<int32_t>> chain_pos(static_cast<size_t>(nch));
-  for (int64_t pos = 0; pos < O.P; ++pos) {
-    const int32_t ch = O.pos_chain[static_cast<size_t>(pos)];
-    chain_of[static_cast<size_t>(O.pos_trn[static_cast<size_t>(pos)])] = ch;
-    chain_pos[static_cast<size_t>(ch)].push_back(static_cast<int32_t>(pos));
-  }
+  const ChainMaps maps = chain_maps(c);
+  const std::vector<int32_t> &chain_of = maps.chain_of;
+  const std::vector<std::vector<int32_t>> &chain_pos = maps.chain_pos;
+  std::vector<int32_t> lm_of(static_cast<size_t>(L.rows), -1);
   for (int64_t l = 0; l < nl; ++l) lm_of[static_cast<size_t>(O.lm_row[static_cast<size_t>(l)])] = static_cast<int32_t>(l);
   // the sightings in table order: edge, chain, landmark   (edge_rows: [ra | rb | ta | tb][edge])
   std::vector<int32_t> s_e, s_ch, s_lm;
@@ -67,12 +56,8 @@ int sg_build(cora_ctx *c, const unsigned char *chain_fixed, const unsigned char 
       T.ent_lm.push_back(M.edge_rows[static_cast<size_t>(3 * ne + e)]);
       T.ent_e.push_back(e);
     }
-    const int64_t len = static_cast<int64_t>(members.size());
-    for (int64_t at = 0; at < len; at += kSgChunk) {
-      T.chunk_begin.push_back(static_cast<int32_t>(static_cast<int64_t>(begin) + at));
-      T.chunk_len.push_back(static_cast<int32_t>(std::min<int64_t>(kSgChunk, len - at)));
-      T.chunk_list.push_back(static_cast<int32_t>(T.list_item.size()));
-    }
+    cut_chunks(static_cast<int64_t>(begin), static_cast<int64_t>(members.size()), T.chunk_begin, T.chunk_len, &T.chunk_list,
+               static_cast<int32_t>(T.list_item.size()));
     T.list_item.push_back(item);
     T.list_row.push_back(row);
     T.list_chunk0.push_back(static_cast<int32_t>(T.chunk_begin.size()));
@@ -147,45 +132,21 @@ int sg_build(cora_ctx *c, const unsigned char *chain_fixed, const unsigned char 
     T.lm_init[i] = lm_fixed[i] ? 3 : (T.lm_list[i] >= 0 ? 0 : 1);
   }
   if (T.ent_e.size() >= (size_t(1) << 31)) return fail(c, CORA_ERR_ARG, "the lists have more entries than a 32-bit index holds");
-  // (a range row two measurements name would be written by two threads of the range-row step)
-  const int64_t nr = M.n_ranges;
-  std::vector<unsigned char> written(static_cast<size_t>(L.rows), 0);
-  for (int64_t m = 0; m < nr; ++m) {
-    unsigned char &w = written[static_cast<size_t>(M.range_rows[static_cast<size_t>(m)])];
-    if (w) return fail(c, CORA_ERR_ARG, "range measurement " + std::to_string(m) + " names a range row an earlier one names");
-    w = 1;
-  }
+  if (const int rc = range_rows_unique(c)) return rc;
   T.built = true;
   return CORA_OK;
 }
 
 // the device side of freshly built tables (T's device pointers are null); on failure T owns what was allocated
 int sg_upload(cora_ctx *c, SgTables &T) {
-  std::vector<int32_t> idx;
-  for (const std::vector<int32_t> *v : {&T.chunk_begin, &T.chunk_len, &T.chunk_list, &T.list_chunk0, &T.list_row, &T.ent_rot, &T.ent_trn, &T.ent_lm,
-                                        &T.ent_e, &T.apply_pos, &T.apply_list})
-    idx.insert(idx.end(), v->begin(), v->end());
-  idx.push_back(0);  // (never an empty buffer)
-  HIP_TRY(c, to_device(&T.d_idx, idx));
+  HIP_TRY(c, upload_joined(&T.d_idx, {&T.chunk_begin, &T.chunk_len, &T.chunk_list, &T.list_chunk0, &T.list_row, &T.ent_rot, &T.ent_trn, &T.ent_lm,
+                                      &T.ent_e, &T.apply_pos, &T.apply_list}));
   const int d = c->F.L.d;
   const size_t nlist = std::max<size_t>(T.list_item.size(), 1), nc = std::max<size_t>(T.chunk_begin.size(), 1);
   HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_partial), static_cast<size_t>(kSgMaxSums(d)) * nc * sizeof(double)));
   HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_state), static_cast<size_t>(kSgState(d)) * nlist * sizeof(double)));
   HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_istate), static_cast<size_t>(kSgInts) * nlist * sizeof(int32_t)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_deg), std::max<size_t>(static_cast<size_t>(c->meas.n_ranges), 1)));
-  // the range-row step over the table with a and b exchanged: the direction of least residual (ml_upload)
-  const size_t nr = static_cast<size_t>(c->meas.n_ranges);
-  std::vector<int32_t> rows(c->meas.range_rows);
-  std::swap_ranges(rows.begin() + static_cast<std::ptrdiff_t>(nr), rows.begin() + static_cast<std::ptrdiff_t>(2 * nr), rows.begin() + static_cast<std::ptrdiff_t>(2 * nr));
-  rows.push_back(0);
-  HIP_TRY(c, to_device(&T.d_range_rows, rows));
   return CORA_OK;
-}
-
-void sg_release(SgTables &T) {  // a table that never reached the handle
-  for (void *p : {static_cast<void *>(T.d_idx), static_cast<void *>(T.d_partial), static_cast<void *>(T.d_state), static_cast<void *>(T.d_istate),
-                  static_cast<void *>(T.d_deg), static_cast<void *>(T.d_range_rows)})
-    if (p) (void)hipFree(p);
 }
 
 int sg_args_check(cora_ctx *c, const double *X, const int64_t *out) {
@@ -213,8 +174,8 @@ void sg_results(const cora_ctx *c, const std::vector<double> &state, const std::
     if (cost_start) cost_start[ch] = st ? st[G + d] : 0.0;
     if (cost_final) cost_final[ch] = st ? st[G + d + 1] : 0.0;
     if (chosen) chosen[ch] = li ? li[1] : -1;
-    if (transforms)
-      for (int i = 0; i < G; ++i) transforms[ch * G + i] = li && li[1] > 0 ? st[i] : (i < d * d && i / d == i % d ? 1.0 : 0.0);
+    if (transforms && li && li[1] > 0) std::copy(st, st + G, transforms + ch * G);
+    else if (transforms) identity_transform(d, transforms + ch * G);
   }
   for (size_t l = 0; l < nl; ++l) {
     const int32_t list = T.lm_list[l];
@@ -253,44 +214,19 @@ bool sg_host_pass_fold(const cora_ctx *c, size_t s, double *oi, std::vector<doub
     double p0[D];
     const double *lm0;
     (void)sg_host_entry<D>(c, oi, static_cast<size_t>(T.chunk_begin[static_cast<size_t>(T.list_chunk0[list])]), p0, &lm0);
-    double wave[kSgChunk / kWave][NS];
-    for (int w = 0; w < kSgChunk / kWave; ++w) {
-      double term[kWave][NS];
-      for (int lane = 0; lane < kWave; ++lane) {
-        const int i = w * kWave + lane;
-        for (int k = 0; k < NS; ++k) term[lane][k] = 0.0;
-        if (i >= T.chunk_len[ch]) continue;
-        double p[D];
-        const double *lm;
-        const double tau = sg_host_entry<D>(c, oi, static_cast<size_t>(T.chunk_begin[ch]) + i, p, &lm);
-        if constexpr (MODE == 0) sg_lm_terms<D>(p0, p, tau, term[lane]);
-        else if constexpr (MODE == 1) sg_chain_terms<D>(p0, lm0, p, lm, tau, term[lane]);
-        else if constexpr (MODE == 2) sg_cost_terms<D>(state.data() + list * kSgState(D), p0, lm0, p, lm, tau, term[lane]);
-        else term[lane][0] = sg_lm_cost<D>(p, lm, tau);
-      }
-      for (int k = 0; k < NS; ++k) {
-        double v[kWave];
-        for (int lane = 0; lane < kWave; ++lane) v[lane] = term[lane][k];
-        wave[w][k] = ml_host_wave_sum(v);
-      }
-    }
-    for (int k = 0; k < NS; ++k) {
-      double v = wave[0][k];
-      for (int w = 1; w < kSgChunk / kWave; ++w) v = v + wave[w][k];
-      partial[static_cast<size_t>(k) * nc + ch] = v;
-    }
+    host_chunk_sums<NS>(T.chunk_len[ch], [&](int i, double *t) {
+      double p[D];
+      const double *lm;
+      const double tau = sg_host_entry<D>(c, oi, static_cast<size_t>(T.chunk_begin[ch]) + i, p, &lm);
+      if constexpr (MODE == 0) sg_lm_terms<D>(p0, p, tau, t);
+      else if constexpr (MODE == 1) sg_chain_terms<D>(p0, lm0, p, lm, tau, t);
+      else if constexpr (MODE == 2) sg_cost_terms<D>(state.data() + list * kSgState(D), p0, lm0, p, lm, tau, t);
+      else t[0] = sg_lm_cost<D>(p, lm, tau);
+    }, partial.data(), nc, ch);
   }
   for (size_t list = l0; list < l1; ++list) {
     double S[NS];
-    for (int k = 0; k < NS; ++k) {
-      double v[kWave];
-      for (int lane = 0; lane < kWave; ++lane) {
-        v[lane] = 0.0;
-        for (int64_t ch = static_cast<int64_t>(T.list_chunk0[list]) + lane; ch < T.list_chunk0[list + 1]; ch += kWave)
-          v[lane] = v[lane] + partial[static_cast<size_t>(k) * nc + static_cast<size_t>(ch)];
-      }
-      S[k] = ml_host_wave_sum(v);
-    }
+    host_list_sums<NS>(partial.data(), nc, static_cast<size_t>(T.list_chunk0[list]), static_cast<size_t>(T.list_chunk0[list + 1]), S);
     double p0[D];
     const double *lm0;
     (void)sg_host_entry<D>(c, oi, static_cast<size_t>(T.chunk_begin[static_cast<size_t>(T.list_chunk0[list])]), p0, &lm0);
@@ -304,9 +240,7 @@ bool sg_host_pass_fold(const cora_ctx *c, size_t s, double *oi, std::vector<doub
 template <int D>
 bool sg_host_run(const cora_ctx *c, double *oi, std::vector<double> &state, std::vector<int32_t> &ist, unsigned char *deg, int64_t *n_deg) {
   const SgTables &T = c->sg;
-  const OdomTables &O = c->odom;
   const MeasurementTable &M = c->meas;
-  const int64_t nr = M.n_ranges;
   bool finite = true;
   std::vector<double> partial(static_cast<size_t>(kSgMaxSums(D)) * std::max<size_t>(T.chunk_begin.size(), 1), 0.0);
   for (size_t s = 0; s < T.stage_kind.size(); ++s) {
@@ -317,25 +251,9 @@ bool sg_host_run(const cora_ctx *c, double *oi, std::vector<double> &state, std:
     }
     finite = sg_host_pass_fold<D, 1>(c, s, oi, partial, state, ist) && finite;
     finite = sg_host_pass_fold<D, 2>(c, s, oi, partial, state, ist) && finite;
-    for (int32_t i = T.stage_apply0[s]; i < T.stage_apply0[s + 1]; ++i) {
-      const size_t list = static_cast<size_t>(T.apply_list[static_cast<size_t>(i)]), pos = static_cast<size_t>(T.apply_pos[static_cast<size_t>(i)]);
-      if (ist[list * kSgInts + 1] <= 0) continue;
-      pl_apply<D>(state.data() + list * kSgState(D), oi + static_cast<size_t>(O.pos_rot[pos]) * D, oi + static_cast<size_t>(O.pos_trn[pos]) * D);
-    }
+    host_apply_stage<D>(c->odom, T, s, state, ist, oi);
   }
-  int64_t count = 0;
-  for (int64_t m = 0; m < nr; ++m) {
-    const size_t rr = static_cast<size_t>(M.range_rows[static_cast<size_t>(m)]), ta = static_cast<size_t>(M.range_rows[static_cast<size_t>(nr + m)]),
-                 tb = static_cast<size_t>(M.range_rows[static_cast<size_t>(2 * nr + m)]);
-    double row[D];
-    const bool degenerate = odom_range_row<D>(oi + tb * D, oi + ta * D, row);  // (towards a: see ml_upload)
-    std::copy(row, row + D, oi + rr * D);
-    if (deg) deg[m] = degenerate ? 1 : 0;
-    count += degenerate ? 1 : 0;
-    finite = odom_finite(row, D) && finite;
-  }
-  *n_deg = count;
-  return finite;
+  return host_range_rows<D>(M, true, oi, deg, n_deg) && finite;
 }
 }  // extern "C++"
 
@@ -345,19 +263,8 @@ int cora_set_sighting_placement(cora_ctx *c, const unsigned char *chain_fixed, c
   if (!c) return CORA_ERR_ARG;
   int rc = sg_check(c);
   if (rc) return rc;
-  SgTables T;
-  if ((rc = sg_build(c, chain_fixed, landmark_fixed, min_sightings, T))) return rc;
-  if (c->has_device) {
-    if (hipSetDevice(c->device) != hipSuccess) return fail(c, CORA_ERR_HIP, "hipSetDevice failed");
-    if ((rc = sg_upload(c, T))) {
-      sg_release(T);
-      return rc;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    free_sg(c);
-  }
-  c->sg = std::move(T);
-  return CORA_OK;
+  return install_tables(c, c->sg, [&](SgTables &T) { return sg_build(c, chain_fixed, landmark_fixed, min_sightings, T); },
+                        [&](SgTables &T) { return sg_upload(c, T); });
 }
 
 int cora_sighting_placement_counts(const cora_ctx *c, int64_t out[4]) {
@@ -391,9 +298,8 @@ int cora_place_by_sightings_dev(cora_ctx *c, double *dX, int64_t out[6], unsigne
   const MeasurementTable &M = c->meas;
   SgTables &T = c->sg;
   const OdomTables &O = c->odom;
-  const int d = L.d, nb = odom_range_blocks(M.n_ranges);
+  const int d = L.d;
   const size_t ns = T.stage_kind.size(), nc = T.chunk_begin.size(), ne = T.ent_e.size(), nlist = T.list_item.size(), na = T.apply_pos.size();
-  if ((rc = ensure_red(c, static_cast<size_t>(nb) / 2 + 4))) return rc;
   SgArgs A;
   A.d = d;
   A.n_edges = M.n_edges;
@@ -417,24 +323,10 @@ int cora_place_by_sightings_dev(cora_ctx *c, double *dX, int64_t out[6], unsigne
   A.istate = T.d_istate;
   A.x = dX;
   A.flag = c->d_flag;
-  OdomFillArgs Fl;  // the range-row step of the odometry initialisation, its rules unchanged, over the exchanged table
-  Fl.d = d;
-  Fl.n_ranges = M.n_ranges;
-  Fl.range_rows = T.d_range_rows;
-  Fl.deg = T.d_deg;
-  Fl.partial = reinterpret_cast<int *>(c->d_red);
-  Fl.words = Fl.partial + nb;
-  Fl.flag = c->d_flag;
-  Fl.out = dX;
   wrote(c, dX);
   HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
   for (size_t s = 0; s < ns; ++s) {  // dependent: a stage reads the rows the stages before it wrote
-    A.list0 = T.stage_list0[s];
-    A.n_lists = T.stage_list0[s + 1] - A.list0;
-    A.chunk0 = T.list_chunk0[static_cast<size_t>(A.list0)];
-    A.n_chunks = T.list_chunk0[static_cast<size_t>(T.stage_list0[s + 1])] - A.chunk0;
-    A.apply0 = T.stage_apply0[s];
-    A.n_apply = T.stage_apply0[s + 1] - A.apply0;
+    stage_args(T, s, A);
     if (T.stage_kind[s] != 1) {
       A.mode = 0;
       HIP_TRY(c, launch_sighting_pass_fold(A, c->stream));
@@ -450,21 +342,13 @@ int cora_place_by_sightings_dev(cora_ctx *c, double *dX, int64_t out[6], unsigne
     HIP_TRY(c, launch_sighting_pass_fold(A, c->stream));
     HIP_TRY(c, launch_sighting_apply(A, c->stream));
   }
-  HIP_TRY(c, launch_odom_ranges(Fl, c->stream));  // (after the chains' and the landmarks' rows)
-  int words[2] = {0, 0};
   std::vector<double> state(nlist * kSgState(d));
   std::vector<int32_t> ist(nlist * kSgInts);
-  HIP_TRY(c, hipMemcpyAsync(words, Fl.words, sizeof(words), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->h_flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (nlist > 0) {
-    HIP_TRY(c, hipMemcpyAsync(state.data(), T.d_state, state.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(ist.data(), T.d_istate, ist.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  }
-  if (degenerate && M.n_ranges > 0)
-    HIP_TRY(c, hipMemcpyAsync(degenerate, T.d_deg, static_cast<size_t>(M.n_ranges), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (*c->h_flag) return fail(c, CORA_ERR_NAN, "a sum of the sighting placement is not finite");
-  sg_results(c, state, ist, words[0], out, status, cost_start, cost_final, chosen, transforms, landmark_status, landmark_cost);
+  int64_t n_deg = 0;
+  if ((rc = range_rows_step(c, dX, true, degenerate, "a sum of the sighting placement is not finite", &n_deg,  // (after the chains' and the landmarks' rows)
+                            [&] { return read_back_state(c, state, T.d_state, ist, T.d_istate); })))
+    return rc;
+  sg_results(c, state, ist, n_deg, out, status, cost_start, cost_final, chosen, transforms, landmark_status, landmark_cost);
   return CORA_OK;
 }
 
@@ -476,22 +360,12 @@ int cora_place_by_sightings(cora_ctx *c, double *X, int ldx, int64_t out[6], uns
   if (rc) return rc;
   NEED_DEVICE(c);
   if ((rc = sg_args_check(c, X, out))) return rc;
-  if (ldx < c->F.L.N) return fail(c, CORA_ERR_SHAPE, "leading dimension smaller than N");
-  const int d = c->F.L.d;
-  double *dX;
-  if ((rc = compare_vec(c, 3, ld_for(d), &dX))) return rc;
-  rc = upload_impl(c, X, ldx, d, dX);
-  if (rc == CORA_OK)
-    rc = cora_place_by_sightings_dev(c, dX, out, status, cost_start, cost_final, chosen, transforms, landmark_status, landmark_cost, degenerate);
-  if (rc == CORA_OK) rc = download_impl(c, dX, d, X, ldx);
-  // the vector of this form is not kept: a caller that stays resident uses cora_place_by_sightings_dev
-  (void)hipStreamSynchronize(c->stream);
-  compare_release(c, 3, 4, 0);
-  return rc;
+  return with_uploaded_x(c, X, ldx, [&](double *dX) {
+    return cora_place_by_sightings_dev(c, dX, out, status, cost_start, cost_final, chosen, transforms, landmark_status, landmark_cost, degenerate);
+  });
 }
 
-// The same on the host through the translated tables, every sum in the kernels' bracket order and every term and solve
-// through the functions of kernels.h the kernels call: the output has the device's bits.  Works on a plan-only handle.
+// the host mirror (with_host_x)
 int cora_debug_place_by_sightings_host(cora_ctx *c, double *X, int ldx, int64_t out[6], unsigned char *status, double *cost_start,
                                        double *cost_final, int32_t *chosen, double *transforms, unsigned char *landmark_status,
                                        double *landmark_cost, unsigned char *degenerate) {
@@ -499,20 +373,13 @@ int cora_debug_place_by_sightings_host(cora_ctx *c, double *X, int ldx, int64_t 
   int rc = sg_check(c);
   if (rc) return rc;
   if ((rc = sg_args_check(c, X, out))) return rc;
-  const HostFormat &F = c->F;
-  const Layout &L = F.L;
-  if (ldx < L.N) return fail(c, CORA_ERR_SHAPE, "leading dimension smaller than N");
-  const int d = L.d;
   const size_t nlist = c->sg.list_item.size();
-  std::vector<double> oi(static_cast<size_t>(L.rows) * d, 0.0), state(nlist * kSgState(d), 0.0);
+  std::vector<double> state(nlist * kSgState(c->F.L.d), 0.0);
   std::vector<int32_t> ist(nlist * kSgInts, 0);
-  for (int cc = 0; cc < d; ++cc)
-    for (int64_t i = 0; i < L.N; ++i) oi[static_cast<size_t>(F.api2int[i]) * d + cc] = X[static_cast<size_t>(cc) * ldx + i];
   int64_t n_deg = 0;
-  const bool finite = d == 2 ? sg_host_run<2>(c, oi.data(), state, ist, degenerate, &n_deg) : sg_host_run<3>(c, oi.data(), state, ist, degenerate, &n_deg);
-  if (!finite) return fail(c, CORA_ERR_NAN, "a sum of the sighting placement is not finite");
-  for (int cc = 0; cc < d; ++cc)
-    for (int64_t i = 0; i < L.N; ++i) X[static_cast<size_t>(cc) * ldx + i] = oi[static_cast<size_t>(F.api2int[i]) * d + cc];
+  if ((rc = with_host_x(c, X, ldx, "a sum of the sighting placement is not finite",
+                        [&](auto D, double *oi) { return sg_host_run<D()>(c, oi, state, ist, degenerate, &n_deg); })))
+    return rc;
   sg_results(c, state, ist, n_deg, out, status, cost_start, cost_final, chosen, transforms, landmark_status, landmark_cost);
   return CORA_OK;
 }

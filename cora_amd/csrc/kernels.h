@@ -1719,6 +1719,10 @@ __host__ __device__ inline bool sg_fold(const double *S, double *st, int32_t *is
 // Coordinates are relative to the list's first entry: q' = q - q_0, l' = l - l_0.  BRACKET ORDER and arithmetic: as the
 // sighting placement's (above), the same in the host mirror (capi/closure.inc).
 constexpr int kClChunk = 256;
+// the chunk of the four placement initialisers: their passes end in one chunk sum (kernels/common.inc), their table builders cut
+// lists with one function and their mirrors sum with one (capi/init_common.inc)
+constexpr int kSumChunk = 256;
+static_assert(kMlChunk == kSumChunk && kPlChunk == kSumChunk && kSgChunk == kSumChunk && kClChunk == kSumChunk, "one chunk size");
 constexpr double kClMinRank = 1e-6;  // the refusal rule of cl_solve, relative to the bound S of |H|_F
 // tau | tau q' | tau l' | tau l' q'^T (row-major) | tau |q'|^2 | tau |l'|^2 (sg_chain_terms' layout) | kappa | kappa P (row-major)
 constexpr int kClSums(int d) { return 4 + 2 * d + 2 * d * d; }

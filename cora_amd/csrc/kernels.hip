@@ -28,7 +28,7 @@
 
 // ONE source in sixteen pieces (round 6: the file had grown to 3 700 lines); this file holds the switches of the translation units
 // and, at the end, the measurement builds' read-back hooks.  Inside namespace cora, in this order:
-//   kernels/common.inc   row loads / stores, wave reductions, the STPCG state's scalar steps
+//   kernels/common.inc   row loads / stores, wave reductions, the chunk and list sums of the placement initialisers, the STPCG state's scalar steps
 //   kernels/spmm.inc     the sliced SpMM with fused epilogues (chain slices, row slices, long-row chunks)        CORA_TU & 1
 //   kernels/rows.inc     row-unit, vector, reduction, exchange and LOBPCG block kernels                           CORA_TU & 2
 //   kernels/residuals.inc  per-measurement residuals: one gather pass over the measurement table                   CORA_TU & 2

@@ -1,11 +1,12 @@
-// Part of kernels.hip (included there, in this order, inside namespace cora).  placement from inter-chain relative-pose edges: per stage one pass over the chunks of ALL the stage's lists and one fold per list (the sums with the closed-form solve, then the two costs); the rigid motion of the stage's chains is k_sg_apply (ClArgs, kernels.h); the outlier-robust form: the consensus vote (one workgroup per chunk, the list's entries through an LDS tile), the election, and the pass and fold over the inliers (ClRobustArgs) -- CORA_TU & 2
+// Part of kernels.hip (included there, in this order, inside namespace cora).  placement from inter-chain relative-pose edges: per stage one pass over the chunks of ALL the stage's lists and one fold per list (the sums with the closed-form solve, then the two costs); the rigid motion of the stage's chains is k_sg_apply (ClArgs, kernels.h); the outlier-robust form: the consensus vote (one workgroup per chunk, the list's entries through an LDS tile), the election, and the same pass and fold over the inliers (ClRobustArgs) -- CORA_TU & 2
 #if CORA_TU & 2
 // ---------------------------------------------------------------------------
 // placement from closures
 // ---------------------------------------------------------------------------
 // One thread per entry of a chunk, the entry's terms in registers (28 doubles at D = 3 for the sums).  The terms and
 // everything the fold computes are functions of kernels.h the host mirror calls; the sums are taken in the order
-// kernels.h writes down.  No atomics on doubles; the launches are the only synchronisation between workgroups.
+// kernels.h writes down (chunk_sums and list_sums, common.inc).  No atomics on doubles; the launches are the only
+// synchronisation between workgroups.
 template <int D, int MODE>
 struct ClSums {
   static constexpr int value = MODE == 0 ? kClSums(D) : kClCostSums;
@@ -26,10 +27,21 @@ __device__ __forceinline__ void cl_load(const ClArgs &A, int64_t e, double *P, d
   kt[1] = f[D * D + D + 1];
 }
 
-template <int D, int MODE>
-__global__ __launch_bounds__(kClChunk) void k_cl_pass(const ClArgs A) {
-  constexpr int NS = ClSums<D, MODE>::value;
+// the kernels' argument of the plain (ClArgs) and of the robust form (ClRobustArgs), and the plain part of either
+template <bool ROBUST>
+using ClKernelArgs = std::conditional_t<ROBUST, ClRobustArgs, ClArgs>;
+__host__ __device__ inline const ClArgs &cl_plain(const ClArgs &A) { return A; }
+__host__ __device__ inline const ClArgs &cl_plain(const ClRobustArgs &R) { return R.A; }
+
+// ROBUST: over the inliers of the elected hypothesis (k_cl_vote, k_cl_elect below): each entry re-evaluates r(h*, j) <= barc2
+// from cstate (the vote's function, the vote's bits); an entry outside I leaves its terms at +0.0.  Mode 0 also writes the
+// edge's flag byte.  The plain form loads none of that.
+template <int D, int MODE, bool ROBUST>
+__global__ __launch_bounds__(kClChunk) void k_cl_pass(const ClKernelArgs<ROBUST> K) {
+  constexpr int NS = ClSums<D, MODE>::value, GS = kClCState(D);
+  static_assert(GS == kSgG(D) + D, "the hypothesis has the layout of the state's G | s | s'");
   __shared__ double sm[kClChunk / kWave][NS];
+  const ClArgs &A = cl_plain(K);
   const int64_t chunk = static_cast<int64_t>(A.chunk0) + blockIdx.x;
   const int32_t list = A.chunk_list[chunk];
   double s[NS];
@@ -37,56 +49,46 @@ __global__ __launch_bounds__(kClChunk) void k_cl_pass(const ClArgs A) {
   for (int i = 0; i < NS; ++i) s[i] = 0.0;
   if (static_cast<int>(threadIdx.x) < A.chunk_len[chunk]) {
     const int64_t e = static_cast<int64_t>(A.chunk_begin[chunk]) + threadIdx.x;
-    double P[D * D], q[D], l[D], q0[D], l0[D], res, kt[2];
+    double P[D * D], q[D], l[D], q0[D], l0[D], res, kt[2], g[GS];
     {
       double P0[D * D], res0, kt0[2];
       cl_load<D>(A, A.chunk_begin[A.list_chunk0[list]], P0, q0, l0, &res0, kt0);  // the list's first entry
     }
     cl_load<D>(A, e, P, q, l, &res, kt);
+    bool in = true;
+    if constexpr (ROBUST) {
+#pragma unroll
+      for (int i = 0; i < GS; ++i) g[i] = K.cstate[static_cast<size_t>(list) * GS + i];
+      in = cl_agrees(cl_cost_at<D>(g, q0, l0, P, q, l, kt[0], kt[1]), K.barc2);
+      if constexpr (MODE == 0) K.inlier[A.ent_e[e]] = in ? 1 : 0;
+    }
     if constexpr (MODE == 0) {
-      cl_terms<D>(q0, l0, P, q, l, kt[0], kt[1], s);
-    } else {
-      constexpr int GS = kSgG(D) + D;
-      double g[GS];
+      if (in) cl_terms<D>(q0, l0, P, q, l, kt[0], kt[1], s);
+    } else if (in) {
 #pragma unroll
       for (int i = 0; i < GS; ++i) g[i] = A.state[static_cast<size_t>(list) * kSgState(D) + i];
       s[0] = res;
       s[1] = cl_cost_at<D>(g, q0, l0, P, q, l, kt[0], kt[1]);
     }
   }
-  ml_wave_sum<NS>(s);
-  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i) sm[w][i] = s[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    double v = sm[0][threadIdx.x];
-#pragma unroll
-    for (int j = 1; j < kClChunk / kWave; ++j) v = v + sm[j][threadIdx.x];
-    A.partial[static_cast<size_t>(threadIdx.x) * A.pstride + chunk] = v;
-  }
+  chunk_sums<NS>(s, sm, A.partial, A.pstride, chunk);
 }
 
-// one wavefront per list of the stage: the sums of its chunks, then lane 0 solves or compares (cl_fold)
-template <int D, int MODE>
-__global__ __launch_bounds__(kWave) void k_cl_fold(const ClArgs A) {
+// one wavefront per list of the stage: the sums of its chunks, then lane 0 solves or compares (cl_fold; ROBUST: cl_fold_robust,
+// status 5 passed through)
+template <int D, int MODE, bool ROBUST>
+__global__ __launch_bounds__(kWave) void k_cl_fold(const ClKernelArgs<ROBUST> K) {
   constexpr int NS = ClSums<D, MODE>::value;
+  const ClArgs &A = cl_plain(K);
   const int64_t list = static_cast<int64_t>(A.list0) + blockIdx.x;
-  const int lane = threadIdx.x;
   double s[NS];
-#pragma unroll
-  for (int i = 0; i < NS; ++i) s[i] = 0.0;
-  for (int64_t c = static_cast<int64_t>(A.list_chunk0[list]) + lane; c < A.list_chunk0[list + 1]; c += kWave)
-#pragma unroll
-    for (int i = 0; i < NS; ++i) s[i] = s[i] + A.partial[static_cast<size_t>(i) * A.pstride + c];
-  ml_wave_sum<NS>(s);
-  if (lane != 0) return;
+  list_sums<NS, int64_t>(s, A.partial, A.pstride, A.list_chunk0[list], A.list_chunk0[list + 1]);
+  if (threadIdx.x != 0) return;
   double P0[D * D], q0[D], l0[D], res0, kt0[2];
   cl_load<D>(A, A.chunk_begin[A.list_chunk0[list]], P0, q0, l0, &res0, kt0);
-  if (!cl_fold<D, MODE>(s, A.state + static_cast<size_t>(list) * kSgState(D), A.istate + static_cast<size_t>(list) * kSgInts, q0, l0))
-    atomicOr(A.flag, 1);
+  double *st = A.state + static_cast<size_t>(list) * kSgState(D);
+  int32_t *ist = A.istate + static_cast<size_t>(list) * kSgInts;
+  if (!(ROBUST ? cl_fold_robust<D, MODE>(s, st, ist, q0, l0) : cl_fold<D, MODE>(s, st, ist, q0, l0))) atomicOr(A.flag, 1);
 }
 
 // ---------------------------------------------------------------------------
@@ -195,74 +197,5 @@ __global__ __launch_bounds__(kWave) void k_cl_elect(const ClRobustArgs R) {
   A.istate[static_cast<size_t>(list) * kSgInts] = bv < R.min_consensus ? 5 : 0;
   A.istate[static_cast<size_t>(list) * kSgInts + 1] = 0;
   if (!odom_finite(g, GS)) atomicOr(A.flag, 1);
-}
-
-// k_cl_pass over the inliers of the elected hypothesis: each entry re-evaluates r(h*, j) <= barc2 from cstate (the vote's
-// function, the vote's bits); an entry outside I leaves its terms at +0.0.  Mode 0 also writes the edge's flag byte.
-template <int D, int MODE>
-__global__ __launch_bounds__(kClChunk) void k_cl_pass_robust(const ClRobustArgs R) {
-  constexpr int NS = ClSums<D, MODE>::value, GS = kClCState(D);
-  __shared__ double sm[kClChunk / kWave][NS];
-  const ClArgs &A = R.A;
-  const int64_t chunk = static_cast<int64_t>(A.chunk0) + blockIdx.x;
-  const int32_t list = A.chunk_list[chunk];
-  double s[NS];
-#pragma unroll
-  for (int i = 0; i < NS; ++i) s[i] = 0.0;
-  if (static_cast<int>(threadIdx.x) < A.chunk_len[chunk]) {
-    const int64_t e = static_cast<int64_t>(A.chunk_begin[chunk]) + threadIdx.x;
-    double P[D * D], q[D], l[D], q0[D], l0[D], res, kt[2], g[GS];
-    {
-      double P0[D * D], res0, kt0[2];
-      cl_load<D>(A, A.chunk_begin[A.list_chunk0[list]], P0, q0, l0, &res0, kt0);  // the list's first entry
-    }
-    cl_load<D>(A, e, P, q, l, &res, kt);
-#pragma unroll
-    for (int i = 0; i < GS; ++i) g[i] = R.cstate[static_cast<size_t>(list) * GS + i];
-    const bool in = cl_agrees(cl_cost_at<D>(g, q0, l0, P, q, l, kt[0], kt[1]), R.barc2);
-    if constexpr (MODE == 0) {
-      R.inlier[A.ent_e[e]] = in ? 1 : 0;
-      if (in) cl_terms<D>(q0, l0, P, q, l, kt[0], kt[1], s);
-    } else if (in) {
-#pragma unroll
-      for (int i = 0; i < GS; ++i) g[i] = A.state[static_cast<size_t>(list) * kSgState(D) + i];
-      s[0] = res;
-      s[1] = cl_cost_at<D>(g, q0, l0, P, q, l, kt[0], kt[1]);
-    }
-  }
-  ml_wave_sum<NS>(s);
-  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i) sm[w][i] = s[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    double v = sm[0][threadIdx.x];
-#pragma unroll
-    for (int j = 1; j < kClChunk / kWave; ++j) v = v + sm[j][threadIdx.x];
-    A.partial[static_cast<size_t>(threadIdx.x) * A.pstride + chunk] = v;
-  }
-}
-
-// k_cl_fold with status 5 passed through (cl_fold_robust)
-template <int D, int MODE>
-__global__ __launch_bounds__(kWave) void k_cl_fold_robust(const ClRobustArgs R) {
-  constexpr int NS = ClSums<D, MODE>::value;
-  const ClArgs &A = R.A;
-  const int64_t list = static_cast<int64_t>(A.list0) + blockIdx.x;
-  const int lane = threadIdx.x;
-  double s[NS];
-#pragma unroll
-  for (int i = 0; i < NS; ++i) s[i] = 0.0;
-  for (int64_t c = static_cast<int64_t>(A.list_chunk0[list]) + lane; c < A.list_chunk0[list + 1]; c += kWave)
-#pragma unroll
-    for (int i = 0; i < NS; ++i) s[i] = s[i] + A.partial[static_cast<size_t>(i) * A.pstride + c];
-  ml_wave_sum<NS>(s);
-  if (lane != 0) return;
-  double P0[D * D], q0[D], l0[D], res0, kt0[2];
-  cl_load<D>(A, A.chunk_begin[A.list_chunk0[list]], P0, q0, l0, &res0, kt0);
-  if (!cl_fold_robust<D, MODE>(s, A.state + static_cast<size_t>(list) * kSgState(D), A.istate + static_cast<size_t>(list) * kSgInts, q0, l0))
-    atomicOr(A.flag, 1);
 }
 #endif  // CORA_TU & 2

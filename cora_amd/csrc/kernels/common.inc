@@ -1,4 +1,4 @@
-// Part of kernels.hip (included there, in this order, inside namespace cora).  helpers every kernel family shares: row loads / stores, wave reductions, the STPCG state's scalar steps.
+// Part of kernels.hip (included there, in this order, inside namespace cora).  helpers every kernel family shares: row loads / stores, wave reductions, the chunk and list sums of the placement initialisers, the STPCG state's scalar steps.
 
 // ---------------------------------------------------------------------------
 // small helpers
@@ -111,6 +111,50 @@ __device__ __forceinline__ double kappa_sum_256(const double *__restrict__ parti
   }
   for (; b < n; b += 256) s0 += partial[b];
   return block_sum_256((s0 + s1) + (s2 + s3), sm);
+}
+
+// ---------------------------------------------------------------------------
+// the sums of the placement initialisers (multilat, placement, sighting, closure .inc), in the bracket order kernels.h
+// writes down: every pass ends in chunk_sums, every fold begins with list_sums
+// ---------------------------------------------------------------------------
+// the butterfly: afterwards every lane holds the wavefront's sum
+template <int NS>
+__device__ __forceinline__ void ml_wave_sum(double *s) {
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1)
+#pragma unroll
+    for (int i = 0; i < NS; ++i) s[i] = s[i] + __shfl_xor(s[i], off, kWave);
+}
+
+// The end of a pass: every thread's NS terms (+0.0 without an entry) summed over the workgroup's chunk -- the butterfly per
+// wavefront, the wavefronts' rows sm[w] from the left -- into partial[i * pstride + chunk].  The whole workgroup calls.
+template <int NS>
+__device__ __forceinline__ void chunk_sums(double (&s)[NS], double (*sm)[NS], double *partial, int64_t pstride, int64_t chunk) {
+  ml_wave_sum<NS>(s);
+  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < NS; ++i) sm[w][i] = s[i];
+  }
+  __syncthreads();
+  if (threadIdx.x < NS) {
+    double v = sm[0][threadIdx.x];
+#pragma unroll
+    for (int j = 1; j < kSumChunk / kWave; ++j) v = v + sm[j][threadIdx.x];
+    partial[static_cast<size_t>(threadIdx.x) * pstride + chunk] = v;
+  }
+}
+
+// The start of a fold by ONE wavefront: lane j takes 0.0 + chunk (c0 + j) + chunk (c0 + j + 64) + .. below c1 from the left,
+// then the butterfly; afterwards every lane holds the NS sums of the list in s.  (Index: the width the caller counts chunks in.)
+template <int NS, class Index>
+__device__ __forceinline__ void list_sums(double (&s)[NS], const double *partial, int64_t pstride, Index c0, Index c1) {
+#pragma unroll
+  for (int i = 0; i < NS; ++i) s[i] = 0.0;
+  for (Index c = c0 + static_cast<Index>(threadIdx.x); c < c1; c += kWave)
+#pragma unroll
+    for (int i = 0; i < NS; ++i) s[i] = s[i] + partial[static_cast<size_t>(i) * pstride + c];
+  ml_wave_sum<NS>(s);
 }
 
 // Scalar recurrences of the device-resident Steihaug-Toint PCG (StpcgState, kernels.h), run by ONE thread of the

@@ -607,67 +607,72 @@ hipError_t launch_place_apply(const PlArgs &A, hipStream_t st) {
   else hipLaunchKernelGGL(k_pl_apply<3>, grid, dim3(256), 0, st, A);
   return hipGetLastError();
 }
+// f(integral_constant D, integral_constant MODE) for the d (2 | 3) and the mode (0 .. MODES - 1, MODES 2 | 4; both checked by the
+// caller) of a call
+template <int MODES, class F>
+static void for_d_and_mode(int d, int mode, F f) {
+  auto with_d = [&](auto D) {
+    if (mode == 0) f(D, std::integral_constant<int, 0>());
+    else if (mode == 1) f(D, std::integral_constant<int, 1>());
+    else if constexpr (MODES == 4) {
+      if (mode == 2) f(D, std::integral_constant<int, 2>());
+      else f(D, std::integral_constant<int, 3>());
+    }
+  };
+  if (d == 2) with_d(std::integral_constant<int, 2>());
+  else with_d(std::integral_constant<int, 3>());
+}
 // the placement from sightings (kernels/sighting.inc): every launch serves all lists of the one stage A describes
 static bool sighting_args_ok(const SgArgs &A) {
   return (A.d == 2 || A.d == 3) && A.n_chunks > 0 && A.chunk0 >= 0 && A.n_lists > 0 && A.list0 >= 0 && A.n_edges > 0 &&
          A.pstride >= static_cast<int64_t>(A.chunk0) + A.n_chunks && A.chunk_begin && A.chunk_len && A.chunk_list && A.list_chunk0 && A.list_row &&
          A.ent_rot && A.ent_trn && A.ent_lm && A.ent_e && A.edge_data && A.partial && A.state && A.istate && A.x && A.flag;
 }
-template <int D, int MODE>
-static void sighting_pass_fold(const SgArgs &A, hipStream_t st) {
-  hipLaunchKernelGGL((k_sg_pass<D, MODE>), dim3(static_cast<unsigned>(A.n_chunks)), dim3(kSgChunk), 0, st, A);
-  hipLaunchKernelGGL((k_sg_fold<D, MODE>), dim3(static_cast<unsigned>(A.n_lists)), dim3(kWave), 0, st, A);
-}
 hipError_t launch_sighting_pass_fold(const SgArgs &A, hipStream_t st) {
   if (!sighting_args_ok(A) || A.mode < 0 || A.mode > 3) return hipErrorInvalidValue;
-  if (A.d == 2) {
-    if (A.mode == 0) sighting_pass_fold<2, 0>(A, st);
-    else if (A.mode == 1) sighting_pass_fold<2, 1>(A, st);
-    else if (A.mode == 2) sighting_pass_fold<2, 2>(A, st);
-    else sighting_pass_fold<2, 3>(A, st);
-  } else {
-    if (A.mode == 0) sighting_pass_fold<3, 0>(A, st);
-    else if (A.mode == 1) sighting_pass_fold<3, 1>(A, st);
-    else if (A.mode == 2) sighting_pass_fold<3, 2>(A, st);
-    else sighting_pass_fold<3, 3>(A, st);
-  }
+  for_d_and_mode<4>(A.d, A.mode, [&](auto D, auto MODE) {
+    hipLaunchKernelGGL((k_sg_pass<D(), MODE()>), dim3(static_cast<unsigned>(A.n_chunks)), dim3(kSgChunk), 0, st, A);
+    hipLaunchKernelGGL((k_sg_fold<D(), MODE()>), dim3(static_cast<unsigned>(A.n_lists)), dim3(kWave), 0, st, A);
+  });
   return hipGetLastError();
 }
-hipError_t launch_sighting_apply(const SgArgs &A, hipStream_t st) {
-  if (!sighting_args_ok(A) || A.n_apply <= 0 || A.apply0 < 0 || !A.apply_pos || !A.apply_list || !A.pos_rot || !A.pos_trn) return hipErrorInvalidValue;
+// the rigid motion of the stage's chains: k_sg_apply reads only these fields, of SgArgs or of ClArgs (whose lists' state has
+// the sighting placement's layout)
+template <class Args>
+static hipError_t chain_apply(const Args &A, hipStream_t st) {
+  if (A.n_apply <= 0 || A.apply0 < 0 || !A.apply_pos || !A.apply_list || !A.pos_rot || !A.pos_trn) return hipErrorInvalidValue;
+  const SgApplyArgs G{A.d, A.apply0, A.n_apply, A.apply_pos, A.apply_list, A.pos_rot, A.pos_trn, A.state, A.istate, A.x};
   const dim3 grid(static_cast<unsigned>((A.n_apply + 255) / 256));
-  if (A.d == 2) hipLaunchKernelGGL(k_sg_apply<2>, grid, dim3(256), 0, st, A);
-  else hipLaunchKernelGGL(k_sg_apply<3>, grid, dim3(256), 0, st, A);
+  if (A.d == 2) hipLaunchKernelGGL(k_sg_apply<2>, grid, dim3(256), 0, st, G);
+  else hipLaunchKernelGGL(k_sg_apply<3>, grid, dim3(256), 0, st, G);
   return hipGetLastError();
 }
+hipError_t launch_sighting_apply(const SgArgs &A, hipStream_t st) { return sighting_args_ok(A) ? chain_apply(A, st) : hipErrorInvalidValue; }
 // the placement from closures (kernels/closure.inc): every launch serves all lists of the one stage A describes
 static bool closure_args_ok(const ClArgs &A) {
   return (A.d == 2 || A.d == 3) && A.n_chunks > 0 && A.chunk0 >= 0 && A.n_lists > 0 && A.list0 >= 0 && A.n_edges > 0 &&
          A.pstride >= static_cast<int64_t>(A.chunk0) + A.n_chunks && A.chunk_begin && A.chunk_len && A.chunk_list && A.list_chunk0 && A.ent_e &&
          A.ent_dir && A.edge_rows && A.edge_data && A.partial && A.state && A.istate && A.x && A.flag;
 }
-template <int D, int MODE>
-static void closure_pass_fold(const ClArgs &A, hipStream_t st) {
-  hipLaunchKernelGGL((k_cl_pass<D, MODE>), dim3(static_cast<unsigned>(A.n_chunks)), dim3(kClChunk), 0, st, A);
-  hipLaunchKernelGGL((k_cl_fold<D, MODE>), dim3(static_cast<unsigned>(A.n_lists)), dim3(kWave), 0, st, A);
-}
-hipError_t launch_closure_pass_fold(const ClArgs &A, hipStream_t st) {
-  if (!closure_args_ok(A) || A.mode < 0 || A.mode > 1) return hipErrorInvalidValue;
-  if (A.d == 2) {
-    if (A.mode == 0) closure_pass_fold<2, 0>(A, st);
-    else closure_pass_fold<2, 1>(A, st);
-  } else {
-    if (A.mode == 0) closure_pass_fold<3, 0>(A, st);
-    else closure_pass_fold<3, 1>(A, st);
-  }
-  return hipGetLastError();
-}
-// the consensus vote of the robust placement: one workgroup per chunk, then one wavefront per list
-static bool closure_robust_args_ok(const ClRobustArgs &R) {
+static bool closure_args_ok(const ClRobustArgs &R) {
   return closure_args_ok(R.A) && R.barc2 > 0.0 && R.min_consensus >= 1 && R.votes && R.cstate && R.cint && R.inlier;
 }
+template <bool ROBUST>
+static hipError_t closure_pass_fold(const ClKernelArgs<ROBUST> &K, hipStream_t st) {
+  const ClArgs &A = cl_plain(K);
+  if (!closure_args_ok(K) || A.mode < 0 || A.mode > 1) return hipErrorInvalidValue;
+  for_d_and_mode<2>(A.d, A.mode, [&](auto D, auto MODE) {
+    hipLaunchKernelGGL((k_cl_pass<D(), MODE(), ROBUST>), dim3(static_cast<unsigned>(A.n_chunks)), dim3(kClChunk), 0, st, K);
+    hipLaunchKernelGGL((k_cl_fold<D(), MODE(), ROBUST>), dim3(static_cast<unsigned>(A.n_lists)), dim3(kWave), 0, st, K);
+  });
+  return hipGetLastError();
+}
+hipError_t launch_closure_pass_fold(const ClArgs &A, hipStream_t st) { return closure_pass_fold<false>(A, st); }
+hipError_t launch_closure_robust_pass_fold(const ClRobustArgs &R, hipStream_t st) { return closure_pass_fold<true>(R, st); }
+hipError_t launch_closure_apply(const ClArgs &A, hipStream_t st) { return closure_args_ok(A) ? chain_apply(A, st) : hipErrorInvalidValue; }
+// the consensus vote of the robust placement: one workgroup per chunk, then one wavefront per list
 hipError_t launch_closure_vote_elect(const ClRobustArgs &R, hipStream_t st) {
-  if (!closure_robust_args_ok(R)) return hipErrorInvalidValue;
+  if (!closure_args_ok(R)) return hipErrorInvalidValue;
   const dim3 chunks(static_cast<unsigned>(R.A.n_chunks)), lists(static_cast<unsigned>(R.A.n_lists));
   if (R.A.d == 2) {
     hipLaunchKernelGGL(k_cl_vote<2>, chunks, dim3(kClChunk), 0, st, R);
@@ -676,41 +681,6 @@ hipError_t launch_closure_vote_elect(const ClRobustArgs &R, hipStream_t st) {
     hipLaunchKernelGGL(k_cl_vote<3>, chunks, dim3(kClChunk), 0, st, R);
     hipLaunchKernelGGL(k_cl_elect<3>, lists, dim3(kWave), 0, st, R);
   }
-  return hipGetLastError();
-}
-template <int D, int MODE>
-static void closure_robust_pass_fold(const ClRobustArgs &R, hipStream_t st) {
-  hipLaunchKernelGGL((k_cl_pass_robust<D, MODE>), dim3(static_cast<unsigned>(R.A.n_chunks)), dim3(kClChunk), 0, st, R);
-  hipLaunchKernelGGL((k_cl_fold_robust<D, MODE>), dim3(static_cast<unsigned>(R.A.n_lists)), dim3(kWave), 0, st, R);
-}
-hipError_t launch_closure_robust_pass_fold(const ClRobustArgs &R, hipStream_t st) {
-  if (!closure_robust_args_ok(R) || R.A.mode < 0 || R.A.mode > 1) return hipErrorInvalidValue;
-  if (R.A.d == 2) {
-    if (R.A.mode == 0) closure_robust_pass_fold<2, 0>(R, st);
-    else closure_robust_pass_fold<2, 1>(R, st);
-  } else {
-    if (R.A.mode == 0) closure_robust_pass_fold<3, 0>(R, st);
-    else closure_robust_pass_fold<3, 1>(R, st);
-  }
-  return hipGetLastError();
-}
-// the lists' state has the sighting placement's layout: its apply kernel serves, reading only these fields
-hipError_t launch_closure_apply(const ClArgs &A, hipStream_t st) {
-  if (!closure_args_ok(A) || A.n_apply <= 0 || A.apply0 < 0 || !A.apply_pos || !A.apply_list || !A.pos_rot || !A.pos_trn) return hipErrorInvalidValue;
-  SgArgs G;
-  G.d = A.d;
-  G.apply0 = A.apply0;
-  G.n_apply = A.n_apply;
-  G.apply_pos = A.apply_pos;
-  G.apply_list = A.apply_list;
-  G.pos_rot = A.pos_rot;
-  G.pos_trn = A.pos_trn;
-  G.state = A.state;
-  G.istate = A.istate;
-  G.x = A.x;
-  const dim3 grid(static_cast<unsigned>((A.n_apply + 255) / 256));
-  if (A.d == 2) hipLaunchKernelGGL(k_sg_apply<2>, grid, dim3(256), 0, st, G);
-  else hipLaunchKernelGGL(k_sg_apply<3>, grid, dim3(256), 0, st, G);
   return hipGetLastError();
 }
 hipError_t launch_round_amax(int64_t n, const double *y, double *partial, int nblocks, int *flag, hipStream_t st) {

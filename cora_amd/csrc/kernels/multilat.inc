@@ -5,17 +5,8 @@
 // ---------------------------------------------------------------------------
 // One thread per entry of a chunk, the entry's NS terms in registers (14 doubles at D = 3 in the linear stage, 10 in a
 // Gauss-Newton stage).  The terms and everything the fold computes are functions of kernels.h the host mirror calls; the
-// sums are taken in the order kernels.h writes down.  No atomics on doubles; the launches are the only synchronisation
-// between workgroups.
-
-// the butterfly: afterwards every lane holds the wavefront's sum
-template <int NS>
-__device__ __forceinline__ void ml_wave_sum(double *s) {
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1)
-#pragma unroll
-    for (int i = 0; i < NS; ++i) s[i] = s[i] + __shfl_xor(s[i], off, kWave);
-}
+// sums are taken in the order kernels.h writes down (chunk_sums and list_sums, common.inc).  No atomics on doubles; the
+// launches are the only synchronisation between workgroups.
 
 template <int D, int NS, bool LINEAR>
 __device__ __forceinline__ void ml_pass(const MlArgs &A, double (*sm)[NS]) {
@@ -39,19 +30,7 @@ __device__ __forceinline__ void ml_pass(const MlArgs &A, double (*sm)[NS]) {
       ml_gn_terms<D>(y, t0, ti, r, w, s);
     }
   }
-  ml_wave_sum<NS>(s);
-  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i) sm[w][i] = s[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    double v = sm[0][threadIdx.x];
-#pragma unroll
-    for (int j = 1; j < kMlChunk / kWave; ++j) v = v + sm[j][threadIdx.x];
-    A.partial[static_cast<size_t>(threadIdx.x) * A.n_chunks + chunk] = v;
-  }
+  chunk_sums<NS>(s, sm, A.partial, A.n_chunks, chunk);
 }
 
 template <int D>
@@ -81,12 +60,7 @@ __device__ __forceinline__ void ml_fold_lm(const MlArgs &A) {
     return;
   }
   double s[NS];
-#pragma unroll
-  for (int i = 0; i < NS; ++i) s[i] = 0.0;
-  for (int64_t c = static_cast<int64_t>(A.lm_chunk0[l]) + lane; c < A.lm_chunk0[l + 1]; c += kWave)
-#pragma unroll
-    for (int i = 0; i < NS; ++i) s[i] = s[i] + A.partial[static_cast<size_t>(i) * A.n_chunks + c];
-  ml_wave_sum<NS>(s);
+  list_sums<NS, int64_t>(s, A.partial, A.n_chunks, A.lm_chunk0[l], A.lm_chunk0[l + 1]);
   if (lane != 0) return;
   double lst[kMlState(D)];
   int32_t li[kMlInts];

@@ -4,7 +4,8 @@
 // chain placement
 // ---------------------------------------------------------------------------
 // The terms and everything the folds compute are functions of kernels.h the host mirror calls; the sums are taken in the
-// order kernels.h writes down.  No atomics on doubles; the launches are the only synchronisation between workgroups.
+// order kernels.h writes down (chunk_sums and list_sums, common.inc).  No atomics on doubles; the launches are the only
+// synchronisation between workgroups.
 
 // The linear stage has kPlSums(D) sums per chunk (153 at D = 3), more than a thread holds as accumulators: every entry's
 // kPlTerms(D) terms and its weight are staged in LDS ((17 + 1) x 256 doubles = 36 KB at D = 3; the row stride of 17
@@ -36,20 +37,14 @@ __global__ __launch_bounds__(kPlChunk) void k_pl_pass_linear(const PlArgs A) {
   }
 }
 
-// B of a stage's sums at a time, from sum p0: lane j takes 0.0 + chunk j + chunk (j + 64) + .. from the left, then the
-// butterfly; lane 0 leaves them in S.  (B sums share a loop only to have their loads and exchanges in flight together:
-// each sum's additions are its own, in the order kernels.h writes down.)
+// B of a stage's sums at a time, from sum p0 (list_sums over the stage's chunks); lane 0 leaves them in S.  (B sums share a
+// loop only to have their loads and exchanges in flight together: each sum's additions are its own, in the order kernels.h
+// writes down.)
 template <int B>
 __device__ __forceinline__ void pl_fold_sums(const PlArgs &A, int p0, double *S) {
-  const int lane = threadIdx.x;
   double v[B];
-#pragma unroll
-  for (int k = 0; k < B; ++k) v[k] = 0.0;
-  for (int c = lane; c < A.n_chunks; c += kWave)
-#pragma unroll
-    for (int k = 0; k < B; ++k) v[k] = v[k] + A.partial[static_cast<size_t>(p0 + k) * A.pstride + c];
-  ml_wave_sum<B>(v);
-  if (lane == 0) {
+  list_sums<B>(v, A.partial + static_cast<size_t>(p0) * A.pstride, A.pstride, 0, A.n_chunks);  // (n_chunks: an int)
+  if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < B; ++k) S[p0 + k] = v[k];
   }
@@ -90,19 +85,7 @@ __global__ __launch_bounds__(kPlChunk) void k_pl_pass_gn(const PlArgs A) {
                    A.x + static_cast<size_t>(A.ent_q[e]) * D, A.x + static_cast<size_t>(A.ent_a[e]) * D, A.range_data[m],
                    A.range_data[A.n_ranges + m], s);
   }
-  ml_wave_sum<NS>(s);
-  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i) sm[w][i] = s[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    double v = sm[0][threadIdx.x];
-#pragma unroll
-    for (int j = 1; j < kPlChunk / kWave; ++j) v = v + sm[j][threadIdx.x];
-    A.partial[static_cast<size_t>(threadIdx.x) * A.pstride + blockIdx.x] = v;
-  }
+  chunk_sums<NS>(s, sm, A.partial, A.pstride, blockIdx.x);
 }
 
 template <int D>

@@ -5,7 +5,8 @@
 // ---------------------------------------------------------------------------
 // One thread per entry of a chunk, the entry's terms in registers (18 doubles at D = 3 for a chain's sums).  The terms
 // and everything the fold computes are functions of kernels.h the host mirror calls; the sums are taken in the order
-// kernels.h writes down.  No atomics on doubles; the launches are the only synchronisation between workgroups.
+// kernels.h writes down (chunk_sums and list_sums, common.inc).  No atomics on doubles; the launches are the only
+// synchronisation between workgroups.
 template <int D, int MODE>
 struct SgSums {
   static constexpr int value = MODE == 0 ? kSgLmSums(D) : (MODE == 1 ? kSgChainSums(D) : (MODE == 2 ? kSgCostSums : 1));
@@ -54,19 +55,7 @@ __global__ __launch_bounds__(kSgChunk) void k_sg_pass(const SgArgs A) {
       }
     }
   }
-  ml_wave_sum<NS>(s);
-  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i) sm[w][i] = s[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    double v = sm[0][threadIdx.x];
-#pragma unroll
-    for (int j = 1; j < kSgChunk / kWave; ++j) v = v + sm[j][threadIdx.x];
-    A.partial[static_cast<size_t>(threadIdx.x) * A.pstride + chunk] = v;
-  }
+  chunk_sums<NS>(s, sm, A.partial, A.pstride, chunk);
 }
 
 // one wavefront per list of the stage: the sums of its chunks, then lane 0 solves (sg_fold)
@@ -74,15 +63,9 @@ template <int D, int MODE>
 __global__ __launch_bounds__(kWave) void k_sg_fold(const SgArgs A) {
   constexpr int NS = SgSums<D, MODE>::value;
   const int64_t list = static_cast<int64_t>(A.list0) + blockIdx.x;
-  const int lane = threadIdx.x;
   double s[NS];
-#pragma unroll
-  for (int i = 0; i < NS; ++i) s[i] = 0.0;
-  for (int64_t c = static_cast<int64_t>(A.list_chunk0[list]) + lane; c < A.list_chunk0[list + 1]; c += kWave)
-#pragma unroll
-    for (int i = 0; i < NS; ++i) s[i] = s[i] + A.partial[static_cast<size_t>(i) * A.pstride + c];
-  ml_wave_sum<NS>(s);
-  if (lane != 0) return;
+  list_sums<NS, int64_t>(s, A.partial, A.pstride, A.list_chunk0[list], A.list_chunk0[list + 1]);
+  if (threadIdx.x != 0) return;
   double p0[D];
   const double *l0;
   (void)sg_entry<D>(A, A.chunk_begin[A.list_chunk0[list]], p0, &l0);
@@ -92,9 +75,20 @@ __global__ __launch_bounds__(kWave) void k_sg_fold(const SgArgs A) {
     atomicOr(A.flag, 1);
 }
 
-// the positions of the stage's chains under their lists' transforms; a list whose cost did not fall writes nothing
+// The rigid motion of a stage's chains (k_sg_apply), for every placement whose lists' state begins with the motion (R
+// row-major | t) and whose istate[1] is `chosen`: position i of the stage moves under the motion of its list where chosen > 0.
+// The launchers fill it from the stage their own arguments describe (chain_apply, launch.inc); a list whose cost did not fall
+// writes nothing.
+struct SgApplyArgs {
+  int d = 0;
+  int32_t apply0 = 0, n_apply = 0;
+  const int32_t *apply_pos = nullptr, *apply_list = nullptr, *pos_rot = nullptr, *pos_trn = nullptr;
+  const double *state = nullptr;
+  const int32_t *istate = nullptr;
+  double *x = nullptr;
+};
 template <int D>
-__global__ __launch_bounds__(256) void k_sg_apply(const SgArgs A) {
+__global__ __launch_bounds__(256) void k_sg_apply(const SgApplyArgs A) {
   constexpr int G = kSgG(D);
   const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (i >= A.n_apply) return;
