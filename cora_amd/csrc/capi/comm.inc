@@ -547,6 +547,18 @@ int cora_debug_spmm_window_min_slices(int min_slices) {
   return old;
 }
 
+int cora_debug_spmm_stagger_ticks(int ticks) {
+  const int old = g_spmm_stagger_ticks;
+  if (ticks >= 0) g_spmm_stagger_ticks = spmm_stagger_clamp(ticks);
+  return old;
+}
+
+int cora_debug_spmm_stagger_force(int on) {
+  const int old = g_spmm_stagger_force;
+  if (on >= 0) g_spmm_stagger_force = std::min(on, 2);
+  return old;
+}
+
 int cora_debug_local_products(cora_ctx *c, int on) {
   if (!c) return CORA_ERR_ARG;
   c->local_products = on != 0;

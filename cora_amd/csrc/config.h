@@ -42,6 +42,8 @@ namespace cora {
   X(SliceLjf, "CORA_SLICE_LJF", Flag, 1, 0, 1, Call, "pose slices first inside an XCD's range")                              \
   X(SpmmWindowMinSlices, "CORA_SPMM_WINDOW_MIN_SLICES", Int, 2048, INT32_MIN, INT32_MAX, Once,                               \
     "LDS-window form of k_spmm from this many slices")                                                                       \
+  X(SpmmStaggerTicks, "CORA_SPMM_STAGGER_TICKS", Int, 300, 0, 2000, Once,                                                    \
+    "10 ns ticks a SIMD's second pose slice of k_spmm starts late (0: off)")                                                 \
   X(FormatThreads, "CORA_FORMAT_THREADS", Int, 0, 1, INT32_MAX, Call, "format builder threads (0: by size)")                 \
   X(FormatTiming, "CORA_FORMAT_TIMING", Flag, 0, 0, 1, Call, "format builder phase times on stderr")                         \
   /* solve plan of a Cholesky factor (trisolve_build.cpp) */                                                                 \

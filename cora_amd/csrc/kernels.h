@@ -58,8 +58,33 @@ struct SpmmArgs {
   const SliceDesc *slices_pose_first = nullptr;
   int32_t n_local_poses = 0;  // poses of the shard (chain slices clamp their implied columns to them)
   int32_t win_on = 0;  // set by launch_spmm: X window + cooperative epilogue of the pose slices (n_slices >= kWinMinSlices)
+  // set by launch_spmm (spmm_stagger_ticks_for): a pose slice in an odd wave slot of its SIMD -- the second of the two the
+  // SIMD holds -- issues its first load this many ticks of the 100 MHz wall clock after it reaches the gate, so that its
+  // loads travel while the first one computes (window form only).  0: nobody waits; negative (tests): every pose slice
+  // waits that long.  Results do not depend on it.
+  int32_t stagger_ticks = 0;
 };
 extern int g_win_min_slices;  // launch_spmm: window form from this many slices on (kernels.hip)
+// The stagger of the pose slices (SpmmArgs::stagger_ticks; profiles/hvp_stagger.md).  The delay is CORA_SPMM_STAGGER_TICKS,
+// at most kStaggerMaxTicks (20 us), and applies where it was measured to win: window-form launches with an epilogue, at
+// a row stride of 5 (strides 3, 4, 6 and 8 lose or draw), with kStaggerMinPoseSlices (one per SIMD of the part: from
+// there on SIMDs hold two of them) to kStaggerMaxPoseSlices pose slices (the wavefront slots of the part: one round --
+// 2 10^5 poses and more lose at 300 ticks).  g_spmm_stagger_force (cora_debug_spmm_stagger_force) = 1 drops the
+// conditions on size, stride and epilogue, = 2 also makes every pose slice wait (small launches leave the odd wave
+// slots empty).
+extern int g_spmm_stagger_ticks, g_spmm_stagger_force;
+constexpr int kStaggerMaxTicks = 2000;
+constexpr int kStaggerMinPoseSlices = 1024, kStaggerMaxPoseSlices = 2048;
+constexpr int kStaggerMinLD = 5, kStaggerMaxLD = 5;
+inline int spmm_stagger_clamp(int64_t ticks) { return static_cast<int>(std::min<int64_t>(std::max<int64_t>(ticks, 0), kStaggerMaxTicks)); }
+inline int spmm_stagger_ticks_for(const SpmmArgs &A, int ld, int epi) {
+  if (!A.win_on || g_spmm_stagger_ticks <= 0) return 0;
+  const int pose_slices = (A.n_local_poses + kWave - 1) / kWave;
+  const bool measured = epi != EPI_NONE && ld >= kStaggerMinLD && ld <= kStaggerMaxLD && pose_slices >= kStaggerMinPoseSlices &&
+                        pose_slices <= kStaggerMaxPoseSlices;
+  if (!measured && !g_spmm_stagger_force) return 0;
+  return g_spmm_stagger_force == 2 ? -spmm_stagger_clamp(g_spmm_stagger_ticks) : spmm_stagger_clamp(g_spmm_stagger_ticks);
+}
 constexpr int kPoseFirstMaxLD = 6;
 constexpr int kWinMinSlices = 2048;  // = the wavefronts resident at once (256 CUs x 8)
 // number of blocks (= kappa partials) of a launch with these arguments

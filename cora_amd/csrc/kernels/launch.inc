@@ -25,6 +25,7 @@ static hipError_t launch_spmm_ld(const SpmmArgs &A_in, int epi, hipStream_t st) 
   SpmmArgs A = A_in;
   if (LD <= kPoseFirstMaxLD && A.slices_pose_first) A.slices = A.slices_pose_first;
   A.win_on = A.n_slices >= g_win_min_slices ? 1 : 0;
+  A.stagger_ticks = spmm_stagger_ticks_for(A, LD, epi);
   A.n_real_chunks = A.n_chunks;
   A.n_chunks = (A.n_chunks + 7) & ~7;
   A.n_slice_blocks = A.n_slices;
@@ -62,6 +63,10 @@ hipError_t launch_spmm_g5(const SpmmArgs &A, int ld, int d, int epi, hipStream_t
 // slices from which the pose slices read X through their LDS windows (kWinMinSlices; CORA_SPMM_WINDOW_MIN_SLICES or
 // cora_debug_spmm_window_min_slices: the tests run the window form of every row stride on small problems)
 int g_win_min_slices = static_cast<int>(env_int(Env::SpmmWindowMinSlices));
+// delay of the pose slices' second cohort (kernels.h, spmm_stagger_ticks_for; CORA_SPMM_STAGGER_TICKS or
+// cora_debug_spmm_stagger_ticks), and the tests' switch that applies it whatever the size and the row stride
+int g_spmm_stagger_ticks = spmm_stagger_clamp(env_int(Env::SpmmStaggerTicks));
+int g_spmm_stagger_force = 0;
 SPMM_GROUP(0)
 hipError_t launch_spmm(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st) {
   if (ld <= 5) return launch_spmm_g0(A, ld, d, epi, st);

@@ -824,12 +824,31 @@ __device__ __forceinline__ double pose_slice(const SpmmArgs &A, const SliceDesc 
   return kap + kap_t;
 }
 
+// The gate of a staggered launch (SpmmArgs::stagger_ticks): the wavefront sleeps until `ticks` of the 100 MHz wall clock
+// have passed since it got here.  It reads no memory and waits for nobody -- a clock and a trip count bound it: should
+// the clock stand still, kStaggerMaxTrips sleeps of 128 cycles (about 0.2 ms) end it.
+constexpr int kStaggerMaxTrips = 4096;
+__device__ __forceinline__ void stagger_wait(int ticks) {
+  const unsigned long long t_entry = wall_clock64();
+  for (int i = 0; i < kStaggerMaxTrips && wall_clock64() - t_entry < static_cast<unsigned long long>(ticks); ++i)
+    __builtin_amdgcn_s_sleep(2);
+}
+
 // One wavefront, one slice (lane = row, or lane = pose for the rotation rows).  Returns the lane's share of
 // <X, out> over the rows it wrote (EPI_HVP_K; 0 otherwise).
 template <int LD, int D, int EPI>
 __device__ __forceinline__ double slice_wave(const SpmmArgs &A, const SliceDesc sd, int lane) {
   if ((sd.type & kSliceTypeMask) == kSliceStiefel) {
     if (sd.nrows & kSliceRemoteTailOnly) return remote_tail_only<LD, D, EPI>(A, sd, lane);
+    // A pose slice that finds itself in an odd wave slot of its SIMD (HW_ID 3:0) -- the second of the two wavefronts
+    // the SIMD holds -- starts late, so that its loads travel while the first one computes (launch_spmm sets
+    // stagger_ticks for window-form launches only; wave-uniform; a negative value is the tests': every pose slice waits).
+    // The cohort by residency measured better than every second slice of the list (profiles/hvp_stagger.md).  The gate
+    // stands in front of the unchanged choice of the form: with the forms reordered around it the register counts of
+    // most instances of the narrow strides moved.
+    if (A.stagger_ticks != 0) {
+      if (A.stagger_ticks < 0 || (__builtin_amdgcn_s_getreg((3 << 11) | 4) & 1)) stagger_wait(abs(A.stagger_ticks));
+    }
     return A.win_on ? pose_slice<LD, D, EPI, true>(A, sd, lane) : pose_slice<LD, D, EPI, false>(A, sd, lane);
   }
   const double *__restrict__ vp = A.sval + sd.off + lane;

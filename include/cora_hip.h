@@ -1235,6 +1235,13 @@ int cora_debug_product_phases(cora_ctx *ctx, const double *dX, double *dOut, int
  * (default 2 048 = the wavefronts resident at once; below, every wavefront is resident and gathers directly).  Returns
  * the previous value; a negative argument only queries.  Results do not depend on it. */
 int cora_debug_spmm_window_min_slices(int min_slices);
+/* Test hooks (process-wide) of the staggered start of the window form: a pose slice that is the second wavefront on its
+ * SIMD issues its first load `ticks` x 10 ns late (CORA_SPMM_STAGGER_TICKS; stored clamped to 0 .. 2 000, 0 = off).
+ * The library applies the delay only to launches of the size and the row strides it was measured at; on = 1 applies
+ * it to every window-form launch, on = 2 also makes EVERY pose slice wait (a small launch leaves no SIMD with two).
+ * Each returns the previous value; a negative argument only queries.  Results do not depend on either. */
+int cora_debug_spmm_stagger_ticks(int ticks);
+int cora_debug_spmm_stagger_force(int on);
 
 /* Timing hook: with on != 0 the products of a partitioned handle skip every collective step (the operand's remote rows
  * are whatever they are, the distributed long rows stay partial sums) -- the kernel alone, for bench.py's roofline leg. */
@@ -1307,6 +1314,10 @@ int cora_debug_stpcg_graph(const cora_ctx *ctx, long out[2]);
  *   CORA_SLICE_LJF=0          no longest-first order of the slices inside an XCD's range
  *   CORA_SPMM_WINDOW_MIN_SLICES=n (2048) [once]   k_spmm's LDS-window form from n slices on
  *                             (cora_debug_spmm_window_min_slices overrides it)
+ *   CORA_SPMM_STAGGER_TICKS=n (300, 0..2000) [once]   a pose slice that is the second wavefront on its SIMD issues its first
+ *                             load n x 10 ns late (window form with an epilogue, 65 536 to 131 072 poses, row stride 5:
+ *                             where it was measured to win); 0: off (cora_debug_spmm_stagger_ticks overrides it;
+ *                             bit-identical products)
  *   CORA_FORMAT_THREADS=n, CORA_FORMAT_TIMING=1   host threads of the format builder; its phase times on stderr
  * Solve plan of a Cholesky factor (trisolve_build.cpp; every plan solves the same system, tests/test_trisolve_cpu.py):
  *   CORA_TRI_SUB=0            the explicit-stage form instead of the substitution blocks

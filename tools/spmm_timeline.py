@@ -81,7 +81,21 @@ try:
         v = v[ph[m, i] > 0]
         if len(v):
             print("pose slices, %-16s after start: mean %.2f p10 %.2f p50 %.2f p90 %.2f max %.2f us" % (nm, v.mean(), *np.percentile(v, [10, 50, 90, 100])))
-    print("pose slices, end              after start: mean %.2f" % dur[m].mean())
+    print("pose slices, end              after start: mean %.2f p10 %.2f p50 %.2f p90 %.2f max %.2f us" % (
+        dur[m].mean(), *np.percentile(dur[m], [10, 50, 90, 100])))
+    v = (t1[m] - ph[m, 0]) / 100.0
+    print("pose slices, windows landed to end       : mean %.2f p10 %.2f p50 %.2f p90 %.2f max %.2f us" % (
+        v.mean(), *np.percentile(v, [10, 50, 90, 100])))
+    # the two cohorts of a staggered launch (CORA_SPMM_STAGGER_TICKS; profiles/hvp_stagger.md): by the wave slot of the SIMD
+    slot = ph[m, 5] & 0xF
+    print("pose wavefronts by wave slot of their SIMD: %s" % np.bincount(slot).tolist())
+    for par, nm in ((0, "an even slot (start at once)"), (1, "an odd slot (start late)")):
+        s = (slot & 1) == par
+        if s.any():
+            w = (ph[m, 0][s] - base) / 100.0
+            e = end[m][s]
+            print("pose slices in %-28s: %4d, windows landed at mean %.2f p50 %.2f p90 %.2f us of the launch, end at mean %.2f p50 %.2f p90 %.2f max %.2f" % (
+                nm, s.sum(), w.mean(), np.median(w), np.percentile(w, 90), e.mean(), np.median(e), np.percentile(e, 90), e.max()))
     # where the pose wavefronts ran: HW_ID (wave 3:0, simd 5:4, pipe 7:6, cu 11:8, sh 12, se 15:13) | XCC_ID << 32
     hw = ph[m, 5]
     cu = ((hw >> 8) & 0xF) | (((hw >> 12) & 0x1) << 4) | (((hw >> 13) & 0x7) << 5) | (((hw >> 32) & 0xF) << 8)
