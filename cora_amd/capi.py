@@ -141,7 +141,14 @@ def load():
             getattr(L, name).argtypes = [C.c_void_p]
         L.cora_ctx_destroy.restype = None
         L.cora_ctx_destroy.argtypes = [C.c_void_p]
+        L.cora_debug_live_allocations.restype = C.c_int64
+        L.cora_debug_live_allocations.argtypes = []
     return _LIB
+
+
+def live_allocations():
+    """Device and pinned blocks the handles of this process hold now (cora_debug_live_allocations): 0 once all are destroyed."""
+    return int(load().cora_debug_live_allocations())
 
 
 def _d(a):

@@ -88,12 +88,57 @@ static int native_product_gather(cora_native_comm *nc, double *dX, int ld, hipSt
                                  hipEvent_t after_collective = nullptr);
 static const std::string &native_error(const cora_native_comm *nc);
 static int native_allgather_rows(cora_native_comm *nc, double *dX, int ld, int64_t row0, int64_t nrows);  // one piece of every shard, packed
-// frees the device arrays named and nulls the pointers (the device must be current): the ONE list of a table's device pointers is
-// the argument list of its release()
+// The ONE place that talks to the allocator (capi/comm.inc's transports keep their own state).  alloc_* pass the runtime's answer
+// to the caller's HIP_TRY / CREATE_TRY and write no byte; free_* free what is named and null the pointers (the device must be
+// current).  The rule of the whole handle: every resource has ONE owner -- a table struct, a DevBuf, a DevArena or a group of
+// cora_ctx's fields -- whose release(), written under the declarations, is the ONE list of its pointers; destruction names none.
+static std::atomic<int64_t> g_live_allocations{0};  // device and pinned blocks these helpers hold (cora_debug_live_allocations)
+template <class T>
+static hipError_t alloc_device(T **p, size_t bytes) {
+  const hipError_t e = hipMalloc(reinterpret_cast<void **>(p), bytes);
+  if (e == hipSuccess && *p) ++g_live_allocations;
+  return e;
+}
+template <class T>
+static hipError_t alloc_pinned(T **p, size_t bytes) {
+  const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(p), bytes);
+  if (e == hipSuccess && *p) ++g_live_allocations;
+  return e;
+}
 template <class... P>
 static void free_device(P *&...p) {
-  ((p ? (void)hipFree(p) : void(), p = nullptr), ...);
+  ((p ? ((void)hipFree(p), (void)--g_live_allocations) : void(), p = nullptr), ...);
 }
+template <class... P>
+static void free_pinned(P *&...p) {
+  ((p ? ((void)hipHostFree(p), (void)--g_live_allocations) : void(), p = nullptr), ...);
+}
+template <class... E>
+static void free_events(E &...e) {
+  ((e ? (void)hipEventDestroy(e) : void(), e = nullptr), ...);
+}
+// A grow-only device buffer: the pointer and the bytes it has.  ensure frees the old block BEFORE it allocates the larger one
+// (the peak is one block, not two), never shrinks, never zeroes, and leaves {nullptr, 0} behind where the allocation fails.
+// No destructor: a handle is destroyed with its device made current first, so release() is explicit like the tables'.
+struct DevBuf {
+  double *p = nullptr;
+  size_t bytes = 0;
+  operator double *() const { return p; }
+  hipError_t ensure(size_t need) {
+    if (bytes >= need) return hipSuccess;
+    release();
+    const hipError_t e = alloc_device(&p, need);
+    if (e == hipSuccess) bytes = need;
+    return e;
+  }
+  void release() {
+    free_device(p);
+    bytes = 0;
+  }
+  void release_above(size_t min_bytes) {
+    if (bytes > min_bytes) release();
+  }
+};
 // The measurement table of cora_set_measurements (capi/measurements.inc), rows already translated to the internal order,
 // structure-of-arrays [field][measurement] on the host and on the device (ResidualArgs, kernels.h)
 struct MeasurementTable {
@@ -106,6 +151,7 @@ struct MeasurementTable {
   int32_t *d_edge_rows = nullptr, *d_range_rows = nullptr;
   double *d_edge_data = nullptr, *d_range_data = nullptr;
   double *d_out = nullptr;  // [n_edges] rotation | [n_edges] translation | [n_ranges] range | 3 sums
+  void release() { free_device(d_edge_rows, d_range_rows, d_edge_data, d_range_data, d_out); }
 };
 // The pair table of cora_set_pose_pairs (capi/rpe.inc): the pairs as given (API pose indices) and translated to internal
 // rows, structure-of-arrays [first rotation row of i | translation row of i | first rotation row of j | translation row
@@ -117,6 +163,7 @@ struct PosePairTable {
   std::vector<int32_t> rows;  // [4][m]
   int32_t *d_rows = nullptr;
   double *d_err = nullptr;  // [m] translation | [m] rotation | 5 statistics
+  void release() { free_device(d_rows, d_err); }
 };
 // The chain tables of cora_set_odometry_chains (capi/odom.inc): one entry per chain position (a chain's head, then its
 // edges), rows already internal (OdomArgs, kernels.h); the poses in no chain and the landmarks' rows (OdomFillArgs); the
@@ -130,11 +177,7 @@ struct OdomTables {
   double *d_work = nullptr;      // totals | carry, kOdomFields(d) x tiles each
   double *d_stage = nullptr;     // starts [n_chains][d] | landmarks [nt - n][d]
   double *h_stage = nullptr;     // the same, pinned
-  void release() {
-    free_device(d_idx, d_work, d_stage);
-    if (h_stage) (void)hipHostFree(h_stage);
-    h_stage = nullptr;
-  }
+  void release() { free_device(d_idx, d_work, d_stage); free_pinned(h_stage); }
 };
 // What the initialisers below share.  Every call of theirs ends in the range-row step (range_rows_step, capi/init_common.inc),
 // which owns its device arrays on the handle (RangeRowStep below), built at first need and freed with the measurement table.
@@ -256,7 +299,6 @@ struct cora_ctx {
   SliceDesc *d_slices_int = nullptr, *d_slices_bnd = nullptr;
   int n_slices_int = 0, n_slices_bnd = 0;
   hipStream_t comm_stream = nullptr;
-  hipEvent_t ev_operand = nullptr, ev_exchanged = nullptr;
   int overlap_exchange = 1;  // cora_comm_overlap_enable: 0 never, 1 when the interior part is worth a launch of its own, 2 always
   double *d_sval = nullptr;
   double *d_head_val = nullptr;  // HostFormat::head_val
@@ -277,19 +319,28 @@ struct cora_ctx {
   // partitioned handles: distributed long rows (HostFormat::long_rows): partial-sum slots, rows, owners
   double *d_long_out = nullptr;
   int32_t *d_long_rows = nullptr, *d_long_owner = nullptr;
+  void release_format() {
+    free_device(d_slices, d_slices_pf, d_slices_int, d_slices_bnd, d_sval, d_head_val, d_scol, d_perm, d_chunks, d_chunk_order,
+                d_lval, d_lcol, d_partials, d_tickets, d_api2int, d_diag_inv, d_lam_st, d_lam_ob, d_own_sym, d_S, d_long_out,
+                d_long_rows, d_long_owner);
+  }
 
   // sparse Cholesky factors resident on the device (level-scheduled triangular solves):
   // the preconditioner's (Q + lambda I)[0:m] and, for the translation-implicit formulation,
   // the translation Laplacian Q33[0:nt-1]
   using DevStage = cora::DevStage;
   // The device sink of walk_tri_image.  A factor's arrays live in a few large device chunks handed out front to back (60
-  // arrays per factor: one hipMalloc / hipFree each cost more than the copies); a re-installed factor writes over the
+  // arrays per factor: one allocation and one free each cost more than the copies); a re-installed factor writes over the
   // chunks of the one before (rewind).  After a failed call `error` is set and put does nothing more.
   struct DevArena {
     std::vector<void *> allocs;
     std::vector<size_t> chunk_bytes;
     size_t chunk_at = 0, chunk_used = 0;
     hipError_t error = hipSuccess;
+    void release() {
+      for (void *&p : allocs) free_device(p);
+      *this = DevArena();
+    }
     void rewind() {
       chunk_at = 0;
       chunk_used = 0;
@@ -307,7 +358,7 @@ struct cora_ctx {
       if (chunk_at == allocs.size()) {
         const size_t cb = std::max<size_t>(bytes, static_cast<size_t>(64) << 20);
         void *q = nullptr;
-        if ((error = hipMalloc(&q, cb)) != hipSuccess) return nullptr;
+        if ((error = alloc_device(&q, cb)) != hipSuccess) return nullptr;
         allocs.push_back(q);
         chunk_bytes.push_back(cb);
         chunk_used = 0;
@@ -330,6 +381,9 @@ struct cora_ctx {
     unsigned long long generation = 0;  // counts installs: a captured STPCG graph carries the plan's arrays and sizes
   };
   DevFactor precond_f, implicit_f, aux_f;  // aux_f: the caller's own factor (cora_aux_set_cholesky)
+  void release_factors() {
+    for (DevFactor *f : {&precond_f, &implicit_f, &aux_f}) f->arena.release();
+  }
   bool implicit = false;  // Formulation::Implicit active
 
   bool have_point = false;
@@ -337,33 +391,52 @@ struct cora_ctx {
   // cora_tnt_trial_dev leaves Q X of its trial point here; cora_tnt_accept_dev of the same point takes it as the new
   // point's Euclidean gradient (the two buffers change places) instead of forming the product again
   double *d_G_trial = nullptr;
+  void release_rank_state() { free_device(d_Y, d_G, d_rgrad, d_G_trial); }
   const double *trial_x = nullptr;  // the trial point d_G_trial belongs to (nullptr: none)
   unsigned long long stpcg_pending_seq = 0;  // a neutral iteration of the last inner solve may still be in flight (stpcg_run)
   double f = 0.0;
   int precond = CORA_PRECOND_NONE;
 
-  double *scratch[kScratchSlots] = {nullptr};
-  size_t scratch_bytes[kScratchSlots] = {0};
-  double *d_stage = nullptr;
-  size_t stage_bytes = 0;
   std::future<void> deferred_free;  // a solve plan's host arrays being freed (install_factor)
+  unsigned long long dot_seq = 0;  // h_scalars[7] carries the sequence number of the last finished reduction
+  DevBuf scratch[kScratchSlots];
+  DevBuf d_stage;
+  DevBuf d_red;  // reduction partials
   // two pinned buffers of kPinChunk bytes and their events: big downloads are pipelined through them (DMA into one
   // while the host copies the other out) instead of hipMemcpy's own staging of pageable memory
   char *h_pin[2] = {nullptr, nullptr};
   hipEvent_t ev_pin[2] = {nullptr, nullptr};
-  double *d_red = nullptr;      // reduction partials
-  size_t red_doubles = 0;
   double *d_scalars = nullptr;  // 8 doubles
   StpcgState *d_stpcg = nullptr, *h_stpcg = nullptr;  // device-resident STPCG scalars and their pinned mirror
-  unsigned long long dot_seq = 0;  // h_scalars[7] carries the sequence number of the last finished reduction
   unsigned *d_ticket = nullptr;  // last-block ticket of the inner-product kernels (zero between launches)
+  unsigned long long *d_seq_counter = nullptr;  // the device's copy of dot_seq (kernels.h, DotArgs::seq_counter)
   double *h_scalars = nullptr;  // pinned, 8 doubles
-  double *h_gram = nullptr;     // pinned, 16 x 24 x 24 doubles: where the Gram products' reduction writes its results
+  double *h_gram = nullptr;     // pinned, 16 x 24 x 24 doubles: where the Gram products' reduction writes its results (need_gram)
   int *d_flag = nullptr;
   int *h_flag = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // measurement hook (cora_debug_profile_stpcg): event pairs around the Hessian-vector product of every
-  // device-resident STPCG iteration
+  void release_solver_buffers() {
+    for (DevBuf &b : scratch) b.release();
+    d_stage.release();
+    d_red.release();
+    free_device(d_scalars, d_stpcg, d_ticket, d_seq_counter, d_flag);
+    free_pinned(h_pin[0], h_pin[1], h_stpcg, h_scalars, h_gram, h_flag);
+    free_events(ev_pin[0], ev_pin[1], ev0, ev1);
+  }
+  // the other events: of the exchange's overlap (partitioned handles), around the assembly kernels (capi/assembly.inc), at the
+  // phase boundaries of the one-collective product in serial order (cora_debug_product_phases), and kProfMarks per profiled
+  // STPCG iteration (cora_debug_profile_stpcg: event pairs around the Hessian-vector product of every device-resident iteration)
+  hipEvent_t ev_operand = nullptr, ev_exchanged = nullptr;
+  hipEvent_t asm_ev[2] = {nullptr, nullptr};
+  std::vector<hipEvent_t> phase_events;
+  std::vector<hipEvent_t> prof_events;
+  void release_events() {
+    free_events(ev_operand, ev_exchanged, asm_ev[0], asm_ev[1]);
+    for (std::vector<hipEvent_t> *v : {&phase_events, &prof_events}) {
+      for (hipEvent_t &e : *v) free_events(e);
+      v->clear();
+    }
+  }
   // injected communication of a partitioned handle (cora_set_comm)
   cora_exchange_fn comm_exchange = nullptr;
   cora_allreduce_fn comm_allreduce = nullptr;
@@ -371,11 +444,8 @@ struct cora_ctx {
   void *comm_user = nullptr;
   bool comm_required = false;  // cora_require_comm: a collective step without communication is an error, not a no-op
   bool local_products = false;  // cora_debug_local_products: products skip every collective step (kernel timing only)
-  // cora_debug_product_phases: events at the phase boundaries of the one-collective product (serial order)
-  std::vector<hipEvent_t> phase_events;
-  bool phase_timing = false;
+  bool phase_timing = false;  // cora_debug_product_phases
   int prof_stpcg = 0;  // 0 off | 1 events around the product of every STPCG iteration | 2 around every launch of it
-  std::vector<hipEvent_t> prof_events;  // kProfMarks per iteration
   double prof_hvp_us = 0.0;
   int prof_hvp_count = 0;
   double prof_phase_us[7] = {0, 0, 0, 0, 0, 0, 0};  // mean time between marks k and k + 1 (-1: not recorded); [6]: two marks in a row
@@ -388,25 +458,25 @@ struct cora_ctx {
   // pointer and size the captured launches carry -- stays the same, i.e. normally for a whole TNT call and beyond.
   hipGraphExec_t stpcg_graph = nullptr;
   std::vector<uintptr_t> stpcg_graph_key;
-  unsigned long long *d_seq_counter = nullptr;  // the device's copy of dot_seq (kernels.h, DotArgs::seq_counter)
   long stpcg_graph_replays = 0, stpcg_graph_captures = 0;
   // in-place update of Q's values (capi/values.inc): the source map, built at the first update, its device copy
   // (sources of the five arrays at vmap_off, mirror pairs, a staging buffer for host values) and what it needs to know
   ValueMap vmap;
   int32_t *d_vmap_src = nullptr, *d_vmap_mirror = nullptr;
   double *d_vmap_vals = nullptr;
+  void release_value_map() { free_device(d_vmap_src, d_vmap_mirror, d_vmap_vals); }
   size_t vmap_off[5] = {0, 0, 0, 0, 0};
   bool dist_long = true;            // the handle was created with distributed long rows (no CORA_PART_WHOLE_LONG_ROWS)
   bool host_values_stale = false;   // cora_update_values_dev moved the device's values only: F's value arrays are old
   double values_ms[5] = {0, 0, 0, 0, 0};  // cora_update_values_times
   // assembly of Q(w) from per-measurement weights (capi/assembly.inc): the term map, its device copy, a device weight
-  // vector for the host-pointer form, events around the assembly kernels and the times of the last call
+  // vector for the host-pointer form, events around the assembly kernels (asm_ev above) and the times of the last call
   TermMap tmap;
   int32_t *d_tptr = nullptr, *d_tweight = nullptr, *d_tlong = nullptr;
   double *d_tcoef = nullptr, *d_tbase = nullptr, *d_asm_w = nullptr;
-  hipEvent_t asm_ev[2] = {nullptr, nullptr};
   double asm_ms[5] = {0, 0, 0, 0, 0};  // cora_assemble_times
   double *d_gnc = nullptr;  // cora_gnc_weights (capi/gnc.inc): thresholds | weights | residuals of the host-pointer form, 3 n_weights
+  void release_assembly() { free_device(d_tptr, d_tweight, d_tlong, d_tcoef, d_tbase, d_asm_w, d_gnc); }
   // trajectory comparison (capi/compare.inc): the pose table (internal rows: first rotation row of every pose | translation
   // row of every pose, then landmark | range rows), built at the first call, its device copy, the selection bytes, one
   // block of doubles (pose translation errors | pose rotation errors | landmark errors | 48 column sums | 6 statistics |
@@ -419,10 +489,19 @@ struct cora_ctx {
   int32_t *d_cmp_rows = nullptr;
   unsigned char *d_cmp_sel = nullptr;
   double *d_cmp = nullptr;
-  double *cmp_vec[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t cmp_vec_bytes[5] = {0, 0, 0, 0, 0};
+  DevBuf cmp_vec[5];
+  void release_compare() {
+    free_device(d_cmp_rows, d_cmp_sel, d_cmp);
+    for (DevBuf &v : cmp_vec) v.release();
+  }
   std::vector<std::pair<double *, size_t>> user_allocs;  // live vectors of cora_dev_alloc (pointer, bytes)
   std::vector<std::pair<double *, size_t>> pool;         // released ones, kept for the next request of the same size
+  void release_vectors() {
+    for (auto *v : {&user_allocs, &pool}) {
+      for (auto &p : *v) free_device(p.first);
+      v->clear();
+    }
+  }
   std::string err;
 };
 
@@ -472,7 +551,7 @@ inline void wrote(cora_ctx *c, const void *p) {
 template <typename T>
 hipError_t to_device(T **dptr, const std::vector<T> &v) {
   const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(dptr), bytes);
+  hipError_t e = alloc_device(dptr, bytes);
   if (e != hipSuccess) return e;
   if (!v.empty()) e = hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
   return e;
@@ -484,14 +563,14 @@ size_t vec_bytes(const cora_ctx *c, int ld) {
 
 int get_scratch(cora_ctx *c, int slot, int ld, double **out, int64_t extra_rows = 0) {
   const size_t need = vec_bytes(c, ld) + static_cast<size_t>(extra_rows) * ld * sizeof(double);
-  if (c->scratch_bytes[slot] < need) {
-    if (c->scratch[slot]) (void)hipFree(c->scratch[slot]);
-    c->scratch[slot] = nullptr;
-    c->scratch_bytes[slot] = 0;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->scratch[slot]), need));
-    c->scratch_bytes[slot] = need;
-  }
+  HIP_TRY(c, c->scratch[slot].ensure(need));
   *out = c->scratch[slot];
+  return CORA_OK;
+}
+
+// the pinned block the Gram products' reduction writes its results to, made at first need
+int need_gram(cora_ctx *c) {
+  if (!c->h_gram) HIP_TRY(c, alloc_pinned(&c->h_gram, 16 * kMaxLD * kMaxLD * sizeof(double)));
   return CORA_OK;
 }
 
@@ -570,13 +649,7 @@ SpmmArgs spmm_args(const cora_ctx *c, const double *X, double *out) {
 }
 
 int ensure_red(cora_ctx *c, size_t doubles) {
-  if (c->red_doubles < doubles) {
-    if (c->d_red) (void)hipFree(c->d_red);
-    c->d_red = nullptr;
-    c->red_doubles = 0;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_red), doubles * sizeof(double)));
-    c->red_doubles = doubles;
-  }
+  HIP_TRY(c, c->d_red.ensure(doubles * sizeof(double)));
   return CORA_OK;
 }
 
@@ -588,13 +661,7 @@ int upload_impl(cora_ctx *c, const double *host, int ldh, int k, double *dptr) {
   if (!host || !dptr) return fail(c, CORA_ERR_ARG, "null pointer");
   const int ld = ld_for(k);
   const size_t need = static_cast<size_t>(N) * k * sizeof(double);
-  if (c->stage_bytes < need) {
-    if (c->d_stage) (void)hipFree(c->d_stage);
-    c->d_stage = nullptr;
-    c->stage_bytes = 0;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_stage), need));
-    c->stage_bytes = need;
-  }
+  HIP_TRY(c, c->d_stage.ensure(need));
   HIP_TRY(c, hipMemcpy2DAsync(c->d_stage, N * sizeof(double), host, static_cast<size_t>(ldh) * sizeof(double),
                               N * sizeof(double), k, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemsetAsync(dptr, 0, vec_bytes(c, ld), c->stream));
@@ -609,13 +676,7 @@ int download_impl(cora_ctx *c, const double *dptr, int k, double *host, int ldh)
   if (!host || !dptr) return fail(c, CORA_ERR_ARG, "null pointer");
   const int ld = ld_for(k);
   const size_t need = static_cast<size_t>(N) * k * sizeof(double);
-  if (c->stage_bytes < need) {
-    if (c->d_stage) (void)hipFree(c->d_stage);
-    c->d_stage = nullptr;
-    c->stage_bytes = 0;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_stage), need));
-    c->stage_bytes = need;
-  }
+  HIP_TRY(c, c->d_stage.ensure(need));
   {
     const int rc = comm_allgather(c, dptr, ld);
     if (rc) return rc;
@@ -627,10 +688,10 @@ int download_impl(cora_ctx *c, const double *dptr, int k, double *host, int ldh)
     // (measured 4.4 GB/s: 0.1 s for the 430 MB Ritz block of a 10^6-pose certification); here the DMA engine fills one
     // pinned chunk while host threads copy the previous one out.
     for (int i = 0; i < 2; ++i) {
-      if (!c->h_pin[i]) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_pin[i]), kPinChunk));
+      if (!c->h_pin[i]) HIP_TRY(c, alloc_pinned(&c->h_pin[i], kPinChunk));
       if (!c->ev_pin[i]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_pin[i], hipEventDisableTiming));
     }
-    const char *src = reinterpret_cast<const char *>(c->d_stage);
+    const char *src = reinterpret_cast<const char *>(c->d_stage.p);
     char *dst = reinterpret_cast<char *>(host);
     const size_t nchunks = (need + kPinChunk - 1) / kPinChunk;
     auto bytes_of = [&](size_t ch) { return std::min(kPinChunk, need - ch * kPinChunk); };
@@ -710,13 +771,7 @@ int set_point_dev_impl(cora_ctx *c, const double *dY) {
 }
 
 void free_assembly(cora_ctx *c) {  // (the device must be current where there is one)
-  for (void *p : {static_cast<void *>(c->d_tptr), static_cast<void *>(c->d_tweight), static_cast<void *>(c->d_tlong),
-                  static_cast<void *>(c->d_tcoef), static_cast<void *>(c->d_tbase), static_cast<void *>(c->d_asm_w),
-                  static_cast<void *>(c->d_gnc)})
-    if (p) (void)hipFree(p);
-  c->d_gnc = nullptr;
-  c->d_tptr = c->d_tweight = c->d_tlong = nullptr;
-  c->d_tcoef = c->d_tbase = c->d_asm_w = nullptr;
+  c->release_assembly();
   c->tmap = TermMap();
 }
 
@@ -734,16 +789,11 @@ void free_measurements(cora_ctx *c) {  // (the device must be current)
   free_tables(c->pl);          // (and the chain placement's stages)
   free_tables(c->sg);          // (and the sighting placement's lists: their entries name its edges)
   free_tables(c->cl);          // (and the closure placement's lists: their entries name its edges)
-  MeasurementTable &M = c->meas;
-  free_device(M.d_edge_rows, M.d_range_rows, M.d_edge_data, M.d_range_data, M.d_out);
-  M = MeasurementTable();
+  free_tables(c->meas);
 }
 
 void free_rank_state(cora_ctx *c) {
-  for (double **p : {&c->d_Y, &c->d_G, &c->d_rgrad, &c->d_G_trial}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
+  c->release_rank_state();
   c->trial_x = nullptr;
   c->have_point = false;
 }

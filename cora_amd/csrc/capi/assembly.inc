@@ -9,7 +9,7 @@ int upload_term_map(cora_ctx *c) {
   HIP_TRY(c, to_device(&c->d_tcoef, M.tcoef));
   HIP_TRY(c, to_device(&c->d_tlong, M.long_entries));
   HIP_TRY(c, to_device(&c->d_tbase, M.base));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_asm_w), std::max<size_t>(static_cast<size_t>(M.n_weights), 1) * sizeof(double)));
+  HIP_TRY(c, alloc_device(&c->d_asm_w, std::max<size_t>(static_cast<size_t>(M.n_weights), 1) * sizeof(double)));
   for (hipEvent_t &e : c->asm_ev)
     if (!e) HIP_TRY(c, hipEventCreate(&e));
   return CORA_OK;

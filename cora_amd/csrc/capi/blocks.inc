@@ -99,7 +99,7 @@ int cora_gram_dev(cora_ctx *c, const double *dA, int ka, const double *dB, int k
   const int nblocks = 256, nel = ka * kb;
   int rc = ensure_red(c, static_cast<size_t>(nel) * nblocks + nel);
   if (rc) return rc;
-  if (!c->h_gram) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_gram), 16 * kMaxLD * kMaxLD * sizeof(double)));
+  if ((rc = need_gram(c))) return rc;
   // (the reduction writes the results to pinned host memory itself: no copy, one wait)
   HIP_TRY(c, launch_gram(c->F.L.base, c->F.L.local_rows, dA, ka, dB, kb, c->d_red, nblocks, c->h_gram, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -127,7 +127,7 @@ int cora_gram_batch_dev(cora_ctx *c, int n, const double *const *dA, const int *
   // and one wait, where a Rayleigh-Ritz step's twelve products were 24 launches, a copy and a wait
   int rc = ensure_red(c, need);
   if (rc) return rc;
-  if (!c->h_gram) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_gram), 16 * kMaxLD * kMaxLD * sizeof(double)));
+  if ((rc = need_gram(c))) return rc;
   HIP_TRY(c, launch_gram_batch(c->F.L.base, c->F.L.local_rows, n, dA, ka, dB, kb, c->d_red, nblocks, c->h_gram, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   const double *tmp = c->h_gram;

@@ -97,14 +97,14 @@ int cl_upload(cora_ctx *c, ClTables &T) {
   HIP_TRY(c, upload_joined(&T.d_idx, {&T.chunk_begin, &T.chunk_len, &T.chunk_list, &T.list_chunk0, &T.ent_e, &T.ent_dir, &T.apply_pos, &T.apply_list}));
   const int d = c->F.L.d;
   const size_t nlist = std::max<size_t>(T.list_item.size(), 1), nc = std::max<size_t>(T.chunk_begin.size(), 1);
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_partial), static_cast<size_t>(kClSums(d)) * nc * sizeof(double)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_state), static_cast<size_t>(kSgState(d)) * nlist * sizeof(double)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_istate), static_cast<size_t>(kSgInts) * nlist * sizeof(int32_t)));
+  HIP_TRY(c, alloc_device(&T.d_partial, static_cast<size_t>(kClSums(d)) * nc * sizeof(double)));
+  HIP_TRY(c, alloc_device(&T.d_state, static_cast<size_t>(kSgState(d)) * nlist * sizeof(double)));
+  HIP_TRY(c, alloc_device(&T.d_istate, static_cast<size_t>(kSgInts) * nlist * sizeof(int32_t)));
   // the consensus vote's scratch
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_votes), std::max<size_t>(T.ent_e.size(), 1) * sizeof(int32_t)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_cstate), static_cast<size_t>(kClCState(d)) * nlist * sizeof(double)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_cint), static_cast<size_t>(kClCInts) * nlist * sizeof(int32_t)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_inlier), std::max<size_t>(static_cast<size_t>(c->meas.n_edges), 1)));
+  HIP_TRY(c, alloc_device(&T.d_votes, std::max<size_t>(T.ent_e.size(), 1) * sizeof(int32_t)));
+  HIP_TRY(c, alloc_device(&T.d_cstate, static_cast<size_t>(kClCState(d)) * nlist * sizeof(double)));
+  HIP_TRY(c, alloc_device(&T.d_cint, static_cast<size_t>(kClCInts) * nlist * sizeof(int32_t)));
+  HIP_TRY(c, alloc_device(&T.d_inlier, std::max<size_t>(static_cast<size_t>(c->meas.n_edges), 1)));
   return CORA_OK;
 }
 

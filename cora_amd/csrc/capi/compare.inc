@@ -199,35 +199,21 @@ int compare_prepare(cora_ctx *c) {
   const Layout &L = c->F.L;
   if (const int rc = compare_pose_table(c)) return rc;
   if (!c->d_cmp_rows) HIP_TRY(c, to_device(&c->d_cmp_rows, c->cmp_rows));
-  if (!c->d_cmp_sel) HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_cmp_sel), std::max<size_t>(L.nt, 1)));
+  if (!c->d_cmp_sel) HIP_TRY(c, alloc_device(&c->d_cmp_sel, std::max<size_t>(L.nt, 1)));
   if (!c->d_cmp)
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_cmp),
-                         (static_cast<size_t>(L.n) + L.nt + 2 * kMaxLD + 6 + kMaxLD * kMaxLD) * sizeof(double)));
-  if (!c->h_gram) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_gram), 16 * kMaxLD * kMaxLD * sizeof(double)));
-  return CORA_OK;
+    HIP_TRY(c, alloc_device(&c->d_cmp, (static_cast<size_t>(L.n) + L.nt + 2 * kMaxLD + 6 + kMaxLD * kMaxLD) * sizeof(double)));
+  return need_gram(c);
 }
 
 int compare_vec(cora_ctx *c, int slot, int ld, double **out) {
-  const size_t need = vec_bytes(c, ld);
-  if (c->cmp_vec_bytes[slot] < need) {
-    if (c->cmp_vec[slot]) (void)hipFree(c->cmp_vec[slot]);
-    c->cmp_vec[slot] = nullptr;
-    c->cmp_vec_bytes[slot] = 0;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->cmp_vec[slot]), need));
-    c->cmp_vec_bytes[slot] = need;
-  }
+  HIP_TRY(c, c->cmp_vec[slot].ensure(vec_bytes(c, ld)));
   *out = c->cmp_vec[slot];
   return CORA_OK;
 }
 
 // frees the pass's vectors [from, to) that are larger than min_bytes (the stream must be idle)
 void compare_release(cora_ctx *c, int from, int to, size_t min_bytes) {
-  for (int slot = from; slot < to; ++slot) {
-    if (c->cmp_vec_bytes[slot] <= min_bytes) continue;
-    if (c->cmp_vec[slot]) (void)hipFree(c->cmp_vec[slot]);
-    c->cmp_vec[slot] = nullptr;
-    c->cmp_vec_bytes[slot] = 0;
-  }
+  for (int slot = from; slot < to; ++slot) c->cmp_vec[slot].release_above(min_bytes);
 }
 constexpr size_t kCompareKeepBytes = static_cast<size_t>(256) << 20;  // centred vectors above this are not kept between calls
 

@@ -100,7 +100,7 @@ int cora_gnc_weights(cora_ctx *c, const double *X, int ldx, int k, const double 
   NEED_DEVICE(c);
   if (!X || !barc2 || !w_out) return fail(c, CORA_ERR_ARG, "null pointer");
   const size_t nw = static_cast<size_t>(c->tmap.n_weights);
-  if (!c->d_gnc) HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_gnc), std::max<size_t>(3 * nw, 1) * sizeof(double)));
+  if (!c->d_gnc) HIP_TRY(c, alloc_device(&c->d_gnc, std::max<size_t>(3 * nw, 1) * sizeof(double)));
   double *d_barc2 = c->d_gnc, *d_w = c->d_gnc + nw, *d_r2 = c->d_gnc + 2 * nw;
   double *dX;
   if ((rc = get_scratch(c, 0, ld_for(k), &dX))) return rc;

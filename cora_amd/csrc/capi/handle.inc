@@ -111,7 +111,7 @@ int cora_ctx_create_part_opts(int device, int d, int n_poses, int n_ranges, int 
   if (!F.long_rows.empty()) {
     CREATE_TRY(to_device(&c->d_long_rows, F.long_rows));
     CREATE_TRY(to_device(&c->d_long_owner, F.long_owner));
-    CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_long_out), F.long_rows.size() * kMaxLD * sizeof(double)));
+    CREATE_TRY(alloc_device(&c->d_long_out, F.long_rows.size() * kMaxLD * sizeof(double)));
   }
   CREATE_TRY(to_device(&c->d_sval, F.sval));
   CREATE_TRY(to_device(&c->d_scol, F.scol));
@@ -130,31 +130,27 @@ int cora_ctx_create_part_opts(int device, int d, int n_poses, int n_ranges, int 
     for (size_t i = 0; i < dinv.size(); ++i) dinv[i] = 1.0 / F.diag[i];
     CREATE_TRY(to_device(&c->d_diag_inv, dinv));
   }
-  CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_partials),
-                       std::max<size_t>(c->LI.chunks.size(), 1) * kMaxLD * sizeof(double)));
-  CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_tickets),
-                       std::max<size_t>(F.n_long_rows, 1) * sizeof(unsigned)));
+  CREATE_TRY(alloc_device(&c->d_partials, std::max<size_t>(c->LI.chunks.size(), 1) * kMaxLD * sizeof(double)));
+  CREATE_TRY(alloc_device(&c->d_tickets, std::max<size_t>(F.n_long_rows, 1) * sizeof(unsigned)));
   CREATE_TRY(hipMemset(c->d_tickets, 0, std::max<size_t>(F.n_long_rows, 1) * sizeof(unsigned)));
   // (+ 2 doubles: the pose slices' cooperative epilogue reads the blocks in pairs of doubles, kernels.hip)
-  CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_lam_st),
-                       (static_cast<size_t>(F.L.nl_poses) * d * d + 2) * sizeof(double)));
+  CREATE_TRY(alloc_device(&c->d_lam_st, (static_cast<size_t>(F.L.nl_poses) * d * d + 2) * sizeof(double)));
   CREATE_TRY(hipMemset(c->d_lam_st, 0, (static_cast<size_t>(F.L.nl_poses) * d * d + 2) * sizeof(double)));
   // S starts as sym(Q_PP) (Lambda = 0, what d_lam_st holds until the first point): a product before it means what it did
   CREATE_TRY(to_device(&c->d_own_sym, F.own_sym));
   CREATE_TRY(to_device(&c->d_S, F.own_sym));
-  CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_lam_ob),
-                       std::max<size_t>(F.L.nl_ranges, 1) * sizeof(double)));
-  CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_scalars), 8 * sizeof(double)));
-  CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_ticket), 4 * sizeof(unsigned)));  // [0] inner products, [1] kappa (k_spmm)
-  CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_stpcg), sizeof(StpcgState)));
-  CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_seq_counter), sizeof(unsigned long long)));
+  CREATE_TRY(alloc_device(&c->d_lam_ob, std::max<size_t>(F.L.nl_ranges, 1) * sizeof(double)));
+  CREATE_TRY(alloc_device(&c->d_scalars, 8 * sizeof(double)));
+  CREATE_TRY(alloc_device(&c->d_ticket, 4 * sizeof(unsigned)));  // [0] inner products, [1] kappa (k_spmm)
+  CREATE_TRY(alloc_device(&c->d_stpcg, sizeof(StpcgState)));
+  CREATE_TRY(alloc_device(&c->d_seq_counter, sizeof(unsigned long long)));
   CREATE_TRY(hipMemset(c->d_seq_counter, 0, sizeof(unsigned long long)));
-  CREATE_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_stpcg), 2 * sizeof(StpcgState)));
+  CREATE_TRY(alloc_pinned(&c->h_stpcg, 2 * sizeof(StpcgState)));
   CREATE_TRY(hipMemset(c->d_ticket, 0, 4 * sizeof(unsigned)));
-  CREATE_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_scalars), 8 * sizeof(double)));
+  CREATE_TRY(alloc_pinned(&c->h_scalars, 8 * sizeof(double)));
   std::memset(c->h_scalars, 0, 8 * sizeof(double));
-  CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_flag), sizeof(int)));
-  CREATE_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_flag), sizeof(int)));
+  CREATE_TRY(alloc_device(&c->d_flag, sizeof(int)));
+  CREATE_TRY(alloc_pinned(&c->h_flag, sizeof(int)));
   CREATE_TRY(hipEventCreate(&c->ev0));
   CREATE_TRY(hipEventCreate(&c->ev1));
 #undef CREATE_TRY
@@ -176,46 +172,24 @@ void cora_ctx_destroy(cora_ctx *c) {
     c->native_comm = nullptr;
     if (c->p2p_pending) cora::p2p_destroy(c->p2p_pending);
     c->p2p_pending = nullptr;
-    free_rank_state(c);
-    free_measurements(c);
-    if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
-    if (c->ev_operand) (void)hipEventDestroy(c->ev_operand);
-    if (c->ev_exchanged) (void)hipEventDestroy(c->ev_exchanged);
-    void *ptrs[] = {c->d_slices_int, c->d_slices_bnd, c->d_slices, c->d_slices_pf, c->d_head_val, c->d_long_out, c->d_long_rows, c->d_long_owner, c->d_sval, c->d_scol, c->d_perm, c->d_chunks, c->d_chunk_order, c->d_lval, c->d_lcol,
-                    c->d_partials, c->d_tickets, c->d_api2int, c->d_diag_inv, c->d_lam_st, c->d_lam_ob, c->d_own_sym, c->d_S,
-                    c->d_stage, c->d_red, c->d_scalars, c->d_flag, c->d_ticket, c->d_stpcg, c->d_seq_counter,
-                    c->d_vmap_src, c->d_vmap_mirror, c->d_vmap_vals, c->d_cmp_rows, c->d_cmp_sel, c->d_cmp,
-                    c->cmp_vec[0], c->cmp_vec[1], c->cmp_vec[2], c->cmp_vec[3], c->cmp_vec[4], c->pairs.d_rows, c->pairs.d_err};
     if (c->stpcg_graph) (void)hipGraphExecDestroy(c->stpcg_graph);
-    for (void *p : ptrs)
-      if (p) (void)hipFree(p);
-    for (int i = 0; i < kScratchSlots; ++i)
-      if (c->scratch[i]) (void)hipFree(c->scratch[i]);
-    for (auto &p : c->user_allocs)
-      if (p.first) (void)hipFree(p.first);
-    for (auto &p : c->pool)
-      if (p.first) (void)hipFree(p.first);
-    for (auto *f : {&c->precond_f, &c->implicit_f, &c->aux_f})
-      for (void *p : f->arena.allocs)
-        if (p) (void)hipFree(p);
-    for (int i = 0; i < 2; ++i) {
-      if (c->h_pin[i]) (void)hipHostFree(c->h_pin[i]);
-      if (c->ev_pin[i]) (void)hipEventDestroy(c->ev_pin[i]);
-    }
-    if (c->h_scalars) (void)hipHostFree(c->h_scalars);
-    if (c->h_gram) (void)hipHostFree(c->h_gram);
-    if (c->h_stpcg) (void)hipHostFree(c->h_stpcg);
-    if (c->h_flag) (void)hipHostFree(c->h_flag);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    for (hipEvent_t e : c->asm_ev)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->prof_events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->phase_events) (void)hipEventDestroy(e);
+    c->release_format();
+    c->release_factors();
+    c->release_rank_state();
+    c->release_solver_buffers();
+    c->release_value_map();
+    free_measurements(c);  // (the table, the tables built from it, the assembly and GNC buffers)
+    c->release_compare();
+    c->pairs.release();
+    c->release_vectors();
+    c->release_events();
+    if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   }
   delete c;
 }
+
+int64_t cora_debug_live_allocations(void) { return g_live_allocations.load(); }
 
 int cora_set_rank(cora_ctx *c, int p) {
   if (!c) return CORA_ERR_ARG;
@@ -230,7 +204,7 @@ int cora_set_rank(cora_ctx *c, int p) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     free_rank_state(c);
     for (double **q : {&c->d_Y, &c->d_G, &c->d_rgrad}) {
-      HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(q), vec_bytes(c, c->ld)));
+      HIP_TRY(c, alloc_device(q, vec_bytes(c, c->ld)));
       HIP_TRY(c, hipMemsetAsync(*q, 0, vec_bytes(c, c->ld), c->stream));
     }
   }

@@ -33,7 +33,7 @@ int range_rows_step(cora_ctx *c, double *dX, bool exchanged, unsigned char *dege
   const size_t nr = static_cast<size_t>(M.n_ranges);
   const int nb = odom_range_blocks(M.n_ranges);
   if (const int rc = ensure_red(c, static_cast<size_t>(nb) / 2 + 4)) return rc;
-  if (!S.d_deg) HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&S.d_deg), std::max<size_t>(nr, 1)));
+  if (!S.d_deg) HIP_TRY(c, alloc_device(&S.d_deg, std::max<size_t>(nr, 1)));
   if (exchanged && !S.d_exchanged) {
     std::vector<int32_t> rows(M.range_rows);
     std::swap_ranges(rows.begin() + static_cast<std::ptrdiff_t>(nr), rows.begin() + static_cast<std::ptrdiff_t>(2 * nr), rows.begin() + static_cast<std::ptrdiff_t>(2 * nr));
@@ -44,7 +44,7 @@ int range_rows_step(cora_ctx *c, double *dX, bool exchanged, unsigned char *dege
   Fl.n_ranges = M.n_ranges;
   Fl.range_rows = exchanged ? S.d_exchanged : M.d_range_rows;
   Fl.deg = S.d_deg;
-  Fl.partial = reinterpret_cast<int *>(c->d_red);
+  Fl.partial = reinterpret_cast<int *>(c->d_red.p);
   Fl.words = Fl.partial + nb;
   Fl.flag = c->d_flag;
   Fl.out = dX;

@@ -72,7 +72,7 @@ int cora_set_measurements(cora_ctx *c, int64_t n_edges, const int32_t *edge_rows
     HIP_TRY(c, to_device(&M.d_edge_data, M.edge_data));
     HIP_TRY(c, to_device(&M.d_range_rows, M.range_rows));
     HIP_TRY(c, to_device(&M.d_range_data, M.range_data));
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&M.d_out), static_cast<size_t>(2 * n_edges + n_ranges + 3) * sizeof(double)));
+    HIP_TRY(c, alloc_device(&M.d_out, static_cast<size_t>(2 * n_edges + n_ranges + 3) * sizeof(double)));
     M.set = true;
   } else {
     c->tmap = TermMap();  // (a term map belongs to the table it was built from)

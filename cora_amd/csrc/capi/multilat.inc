@@ -61,9 +61,9 @@ int ml_upload(cora_ctx *c, MlTables &T) {
   HIP_TRY(c, to_device(&T.d_init, T.lm_init));
   const int d = c->F.L.d;
   const size_t nl = std::max<size_t>(T.lm_row.size(), 1), nc = std::max<size_t>(T.chunk_lm.size(), 1);
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_partial), static_cast<size_t>(kMlSums(d)) * nc * sizeof(double)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_state), static_cast<size_t>(kMlState(d)) * nl * sizeof(double)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_istate), static_cast<size_t>(kMlInts) * nl * sizeof(int32_t)));
+  HIP_TRY(c, alloc_device(&T.d_partial, static_cast<size_t>(kMlSums(d)) * nc * sizeof(double)));
+  HIP_TRY(c, alloc_device(&T.d_state, static_cast<size_t>(kMlState(d)) * nl * sizeof(double)));
+  HIP_TRY(c, alloc_device(&T.d_istate, static_cast<size_t>(kMlInts) * nl * sizeof(int32_t)));
   return CORA_OK;
 }
 

@@ -72,10 +72,10 @@ size_t odom_stage_doubles(const cora_ctx *c, const OdomTables &T) {
 int odom_upload(cora_ctx *c, OdomTables &T) {
   HIP_TRY(c, upload_joined(&T.d_idx, {&T.pos_edge, &T.pos_chain, &T.pos_rot, &T.pos_trn, &T.free_rot, &T.free_trn, &T.lm_row}));
   const size_t work = 2 * static_cast<size_t>(kOdomFields(c->F.L.d)) * std::max(odom_tiles(T.P), 1);
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_work), work * sizeof(double)));
+  HIP_TRY(c, alloc_device(&T.d_work, work * sizeof(double)));
   const size_t stage = std::max<size_t>(odom_stage_doubles(c, T), 1) * sizeof(double);
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_stage), stage));
-  HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&T.h_stage), stage));
+  HIP_TRY(c, alloc_device(&T.d_stage, stage));
+  HIP_TRY(c, alloc_pinned(&T.h_stage, stage));
   return CORA_OK;
 }
 
@@ -308,8 +308,7 @@ int cora_odometry_set_range_rows_dev(cora_ctx *c, int64_t m, const int32_t *rang
   wrote(c, dOut);
   if (e == hipSuccess) e = launch_move_rows(1, m, ld_for(d), d_rows, d_unit, dOut, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (d_rows) (void)hipFree(d_rows);
-  if (d_unit) (void)hipFree(d_unit);
+  free_device(d_rows, d_unit);
   HIP_TRY(c, e);
   return CORA_OK;
 }

@@ -92,9 +92,9 @@ int pl_upload(cora_ctx *c, PlTables &T) {
   HIP_TRY(c, upload_joined(&T.d_idx, {&T.chunk_begin, &T.chunk_len, &T.ent_q, &T.ent_a, &T.ent_m}));
   const int d = c->F.L.d;
   const size_t ns = std::max<size_t>(T.stage_chain.size(), 1), nc = static_cast<size_t>(std::max<int64_t>(T.max_chunks, 1));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_partial), static_cast<size_t>(kPlSums(d)) * nc * sizeof(double)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_state), static_cast<size_t>(kPlState(d)) * ns * sizeof(double)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_istate), static_cast<size_t>(kPlInts) * ns * sizeof(int32_t)));
+  HIP_TRY(c, alloc_device(&T.d_partial, static_cast<size_t>(kPlSums(d)) * nc * sizeof(double)));
+  HIP_TRY(c, alloc_device(&T.d_state, static_cast<size_t>(kPlState(d)) * ns * sizeof(double)));
+  HIP_TRY(c, alloc_device(&T.d_istate, static_cast<size_t>(kPlInts) * ns * sizeof(int32_t)));
   return CORA_OK;
 }
 

@@ -2,7 +2,7 @@
 // ------------------------------------------------------------ resident API
 
 // Resident vectors come from a small per-handle pool: TNT, the saddle escape and LOBPCG allocate and release 4-10
-// vectors per call, three to six calls per staircase level, and every hipMalloc / hipFree is a device-wide
+// vectors per call, three to six calls per staircase level, and every allocation and every free is a device-wide
 // synchronisation (a failed certification at 10^5 poses spent more time in them than in its eigensolver iterations).
 // A released vector is kept (up to kPoolMax of them) and handed to the next request of the same size, zeroed on the
 // handle's stream like a fresh one; everything returns to the driver with the handle.
@@ -17,7 +17,7 @@ int cora_dev_alloc(cora_ctx *c, int k, double **dptr) {
       c->pool.erase(c->pool.begin() + static_cast<std::ptrdiff_t>(i));
       break;
     }
-  if (!*dptr) HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(dptr), bytes));
+  if (!*dptr) HIP_TRY(c, alloc_device(dptr, bytes));
   wrote(c, *dptr);  // the allocator may return an address that was freed while a trial product of it was kept
   HIP_TRY(c, hipMemsetAsync(*dptr, 0, bytes, c->stream));
   for (auto &p : c->user_allocs)
@@ -39,7 +39,7 @@ int cora_dev_free(cora_ctx *c, double *dptr) {
         c->pool.push_back(p);  // work already enqueued on the handle's stream is ordered before any reuse
       } else {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(dptr);
+        free_device(dptr);
       }
       p = {nullptr, 0};
       return CORA_OK;
@@ -105,7 +105,7 @@ int cora_tnt_trial_dev(cora_ctx *c, const double *dS, double *dHs, double *dXpro
   c->trial_x = nullptr;
   int rc;
   if (!c->d_G_trial) {
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_G_trial), vec_bytes(c, c->ld)));
+    HIP_TRY(c, alloc_device(&c->d_G_trial, vec_bytes(c, c->ld)));
     HIP_TRY(c, hipMemsetAsync(c->d_G_trial, 0, vec_bytes(c, c->ld), c->stream));
   }
   if ((rc = apply_product(c, dS, c->ld, EPI_HVP, dHs))) return rc;

@@ -124,7 +124,7 @@ int cora_round_dev(cora_ctx *c, const double *dY, int k, double *dOut, double *o
   if (overlaps(dOut, vec_bytes(c, ldo), dY, vec_bytes(c, ldy))) return fail(c, CORA_ERR_ARG, "the rounded vector must not alias the input");
   const int gram_blocks = 256, nel = k * k, nb = round_count_blocks(L.nl_poses);
   if ((rc = ensure_red(c, std::max<size_t>(static_cast<size_t>(nel) * gram_blocks + nel, static_cast<size_t>(nb) / 2 + 4)))) return rc;
-  if (!c->h_gram) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_gram), 16 * kMaxLD * kMaxLD * sizeof(double)));
+  if ((rc = need_gram(c))) return rc;
   // step 1: G = Y^T Y (row-major k x k, straight into pinned memory), the basis on the host
   HIP_TRY(c, launch_gram(L.base, L.local_rows, dY, k, dY, k, c->d_red, gram_blocks, c->h_gram, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -162,7 +162,7 @@ int cora_round_dev(cora_ctx *c, const double *dY, int k, double *dOut, double *o
   A.ldy = ldy;
   A.Y = dY;
   A.out = dOut;
-  A.partial = reinterpret_cast<int *>(c->d_red);
+  A.partial = reinterpret_cast<int *>(c->d_red.p);
   A.words = A.partial + nb;
   A.flag = c->d_flag;
   wrote(c, dOut);

@@ -10,12 +10,6 @@ int rpe_check(cora_ctx *c, int k, int kr) {
   return CORA_OK;
 }
 
-void free_pose_pairs(cora_ctx *c) {  // (the device must be current where there is one)
-  if (c->pairs.d_rows) (void)hipFree(c->pairs.d_rows);
-  if (c->pairs.d_err) (void)hipFree(c->pairs.d_err);
-  c->pairs = PosePairTable();
-}
-
 // The d^2 + d sums of one pair for one vector as lane 0 of the pair's group holds them after the butterfly (k_rpe,
 // kernels/rpe.inc): V is a resident vector on the host (internal rows, row-major, stride ld); lane g takes the pieces
 // g, g + 8, ... of W columns (W = 2 at an even stride), one fma per term in column order; the lanes are added as
@@ -74,12 +68,12 @@ int cora_set_pose_pairs(cora_ctx *c, int64_t m, const int32_t *pairs) {
   if (c->has_device) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    free_pose_pairs(c);
+    free_tables(c->pairs);
     if (m == 0) return CORA_OK;
     c->pairs = std::move(T);
     PosePairTable &P = c->pairs;  // (set stays false until every array is up: a failed upload leaves no table)
     HIP_TRY(c, to_device(&P.d_rows, P.rows));
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&P.d_err), static_cast<size_t>(2 * m + 5) * sizeof(double)));
+    HIP_TRY(c, alloc_device(&P.d_err, static_cast<size_t>(2 * m + 5) * sizeof(double)));
     P.set = true;
   } else {
     c->pairs = std::move(T);

@@ -143,9 +143,9 @@ int sg_upload(cora_ctx *c, SgTables &T) {
                                       &T.ent_e, &T.apply_pos, &T.apply_list}));
   const int d = c->F.L.d;
   const size_t nlist = std::max<size_t>(T.list_item.size(), 1), nc = std::max<size_t>(T.chunk_begin.size(), 1);
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_partial), static_cast<size_t>(kSgMaxSums(d)) * nc * sizeof(double)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_state), static_cast<size_t>(kSgState(d)) * nlist * sizeof(double)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&T.d_istate), static_cast<size_t>(kSgInts) * nlist * sizeof(int32_t)));
+  HIP_TRY(c, alloc_device(&T.d_partial, static_cast<size_t>(kSgMaxSums(d)) * nc * sizeof(double)));
+  HIP_TRY(c, alloc_device(&T.d_state, static_cast<size_t>(kSgState(d)) * nlist * sizeof(double)));
+  HIP_TRY(c, alloc_device(&T.d_istate, static_cast<size_t>(kSgInts) * nlist * sizeof(int32_t)));
   return CORA_OK;
 }
 

@@ -20,13 +20,10 @@ int upload_value_map(cora_ctx *c) {
   for (int i = 0; i < 5; ++i) std::copy(parts[i]->begin(), parts[i]->end(), all.begin() + static_cast<std::ptrdiff_t>(c->vmap_off[i]));
   // d_lval holds the image's order of the long rows' entries (long_image.h): slot i of it is slot perm[i] of the format
   for (size_t i = 0; i < M.lval.size(); ++i) all[c->vmap_off[1] + i] = M.lval[static_cast<size_t>(c->LI.perm[i])];
-  for (void *p : {static_cast<void *>(c->d_vmap_src), static_cast<void *>(c->d_vmap_mirror), static_cast<void *>(c->d_vmap_vals)})
-    if (p) (void)hipFree(p);
-  c->d_vmap_src = c->d_vmap_mirror = nullptr;
-  c->d_vmap_vals = nullptr;
+  c->release_value_map();
   HIP_TRY(c, to_device(&c->d_vmap_src, all));
   HIP_TRY(c, to_device(&c->d_vmap_mirror, M.mirror));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void **>(&c->d_vmap_vals), std::max<size_t>(static_cast<size_t>(M.nnz), 1) * sizeof(double)));
+  HIP_TRY(c, alloc_device(&c->d_vmap_vals, std::max<size_t>(static_cast<size_t>(M.nnz), 1) * sizeof(double)));
   return CORA_OK;
 }
 

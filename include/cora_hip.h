@@ -1284,6 +1284,9 @@ int cora_debug_stpcg_path(const cora_ctx *ctx);
  * device-resident STPCG iterations captured once as a hipGraph and replayed (one GPU, fused forms).
  * out[0] = graphs captured so far, out[1] = batches replayed (both 0 unless the switch is on). */
 int cora_debug_stpcg_graph(const cora_ctx *ctx, long out[2]);
+/* Test hook: device and pinned blocks the handles of this process hold now (allocated and not yet freed), the native
+ * transports' own blocks apart.  Process-wide; 0 once every handle is destroyed. */
+int64_t cora_debug_live_allocations(void);
 /* EVERY environment variable the library reads: the table of cora_amd/csrc/config.h, the only place that reads them
  * (tests/test_config_cpu.py checks that this list names the same variables).  NONE changes what is computed beyond the
  * rounding of a different (equally valid) order of operations.  A switch ("=1") is on when the variable is set to a
