@@ -1109,6 +1109,41 @@ class Context:
         """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
         return self._ml_call(lambda *a: self.L.cora_multilaterate_dev(self.h, C.c_void_p(x_ptr), *a), gn_steps)
 
+    # ---- outlier-robust multilateration (include/cora_hip.h, cora_multilaterate_robust_dev)
+    def _mlr_call(self, fn, gn_steps, barc2, min_consensus):
+        nl, nr = self.nt - self.n, self.measurement_counts()[1]
+        out = (C.c_int64 * 6)()
+        status, chosen = np.zeros(nl + 1, dtype=np.uint8), np.zeros(nl + 1, dtype=np.int32)
+        cl, cf, deg = np.zeros(nl + 1), np.zeros(nl + 1), np.zeros(nr + 1, dtype=np.uint8)
+        el, cons, ll = (np.zeros(nl + 1, dtype=np.int32) for _ in range(3))
+        inl = np.zeros(nr + 1, dtype=np.uint8)
+        self._chk(fn(int(gn_steps), C.c_double(barc2), int(min_consensus), out, status.ctypes.data_as(C.c_void_p), _d(cl), _d(cf),
+                     chosen.ctypes.data_as(_ip), el.ctypes.data_as(_ip), cons.ctypes.data_as(_ip), ll.ctypes.data_as(_ip),
+                     inl.ctypes.data_as(C.c_void_p), deg.ctypes.data_as(C.c_void_p)))
+        return dict(solved=int(out[0]), not_solved=int(out[1]), n_degenerate=int(out[2]), steps=int(out[3]), no_consensus=int(out[4]),
+                    excluded=int(out[5]), status=status[:nl], cost_linear=cl[:nl], cost_final=cf[:nl], chosen=chosen[:nl], elected=el[:nl],
+                    consensus=cons[:nl], list_len=ll[:nl], inlier=inl[:nr], degenerate=deg[:nr].astype(bool))
+
+    def multilaterate_robust(self, X, barc2, gn_steps=5, min_consensus=None):
+        """multilaterate with a consensus vote in front of the fit: every entry of a landmark's list proposes the point its
+        sample of d + 1 ranges determines, the proposal most ranges agree with (weighted squared residual <= barc2) is elected
+        and the fit runs over the agreeing ranges only.  min_consensus None: d + 2.  Returns multilaterate's dict plus elected,
+        consensus and list_len (per landmark), inlier (per range measurement: 1 | 0 | 2 in no list that is voted on),
+        no_consensus (landmarks of status 5) and excluded (ranges with byte 0)."""
+        return self._with_host_X(self._mlr_call, self.L.cora_multilaterate_robust, X, gn_steps, barc2, self._ml_min(min_consensus))
+
+    def debug_multilaterate_robust_host(self, X, barc2, gn_steps=5, min_consensus=None):
+        """The same on the host in the device's bracket order (no GPU needed): the device's bits."""
+        return self._with_host_X(self._mlr_call, self.L.cora_debug_multilaterate_robust_host, X, gn_steps, barc2, self._ml_min(min_consensus))
+
+    def multilaterate_robust_dev(self, x_ptr, barc2, gn_steps=5, min_consensus=None):
+        """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
+        return self._mlr_call(lambda *a: self.L.cora_multilaterate_robust_dev(self.h, C.c_void_p(x_ptr), *a), gn_steps, barc2,
+                              self._ml_min(min_consensus))
+
+    def _ml_min(self, min_consensus):
+        return self.d + 2 if min_consensus is None else int(min_consensus)
+
     # ---- chain placement from inter-robot ranges (include/cora_hip.h, cora_place_chains_dev)
     def set_chain_placement(self, chain_fixed=None, min_ranges=None):
         """Orders the odometry chains into stages from the pose-pose ranges between them: chain_fixed a mask per chain or

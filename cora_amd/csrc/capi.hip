@@ -203,7 +203,12 @@ struct MlTables {
   double *d_partial = nullptr;   // [kMlSums(d)][chunks]
   double *d_state = nullptr;     // [nl][kMlState(d)]
   int32_t *d_istate = nullptr;   // [nl][kMlInts]
-  void release() { free_device(d_idx, d_init, d_partial, d_state, d_istate); }
+  // the consensus vote's (cora_multilaterate_robust_dev): scratch of a call, like d_partial
+  int32_t *d_votes = nullptr;         // [entries]
+  double *d_cstate = nullptr;         // [nl][kMlCState(d)]
+  int32_t *d_cint = nullptr;          // [nl][kMlCInts]
+  unsigned char *d_inlier = nullptr;  // [n_ranges]
+  void release() { free_device(d_idx, d_init, d_partial, d_state, d_istate, d_votes, d_cstate, d_cint, d_inlier); }
 };
 // The tables of cora_set_chain_placement (capi/placement.inc): the order of the stages, decided from structure alone; per
 // stage the chain, its positions in the chain tables, the first entry's rows and the stage's chunks; the entry lists (row

@@ -1,4 +1,4 @@
-// Part of capi.hip (one translation unit; included there, in this order).  landmark initialisation from ranges (multilateration over the range table of the measurement table): list and chunk tables, device-pointer form, host-pointer form, host mirror.  Reads the measurement table and the row maps; writes nothing the handle computes with.  What it shares with the other initialisers -- the range-row step, the host-pointer and host-mirror wrappers, installing tables, chunk cutting, the mirror's sums -- is in capi/init_common.inc.
+// Part of capi.hip (one translation unit; included there, in this order).  landmark initialisation from ranges (multilateration over the range table of the measurement table): list and chunk tables, device-pointer form, host-pointer form, host mirror; the outlier-robust forms (a consensus vote over samples of d + 1 ranges in front of the fit: MlConsensus, MlHostVote) share every one of them.  Reads the measurement table and the row maps; writes nothing the handle computes with.  What it shares with the other initialisers -- the range-row step, the host-pointer and host-mirror wrappers, installing tables, chunk cutting, the mirror's sums -- is in capi/init_common.inc.
 
 namespace {
 
@@ -64,6 +64,10 @@ int ml_upload(cora_ctx *c, MlTables &T) {
   HIP_TRY(c, alloc_device(&T.d_partial, static_cast<size_t>(kMlSums(d)) * nc * sizeof(double)));
   HIP_TRY(c, alloc_device(&T.d_state, static_cast<size_t>(kMlState(d)) * nl * sizeof(double)));
   HIP_TRY(c, alloc_device(&T.d_istate, static_cast<size_t>(kMlInts) * nl * sizeof(int32_t)));
+  HIP_TRY(c, alloc_device(&T.d_votes, std::max<size_t>(T.ent_row.size(), 1) * sizeof(int32_t)));
+  HIP_TRY(c, alloc_device(&T.d_cstate, static_cast<size_t>(kMlCState(d)) * nl * sizeof(double)));
+  HIP_TRY(c, alloc_device(&T.d_cint, static_cast<size_t>(kMlCInts) * nl * sizeof(int32_t)));
+  HIP_TRY(c, alloc_device(&T.d_inlier, std::max<size_t>(static_cast<size_t>(c->meas.n_ranges), 1)));
   return CORA_OK;
 }
 
@@ -96,11 +100,114 @@ void ml_results(const cora_ctx *c, const std::vector<double> &state, const std::
   out[3] = steps;
 }
 
+// the consensus setting and the outputs of a robust call (cora_multilaterate_robust_dev)
+struct MlConsensus {
+  double barc2;
+  int min_consensus;
+  int32_t *elected, *consensus, *list_len;
+  unsigned char *inlier;
+};
+const char *ml_not_finite(const MlConsensus *rb) {  // the refusal of a call whose flag word is set
+  return rb ? "a sum or a hypothesis of the multilateration is not finite" : "a sum of the multilateration is not finite";
+}
+int ml_consensus_check(cora_ctx *c, double barc2, int min_consensus) {
+  if (!(barc2 > 0.0) || !std::isfinite(barc2)) return fail(c, CORA_ERR_ARG, "barc2 must be finite and positive");
+  if (min_consensus < 1) return fail(c, CORA_ERR_ARG, "min_consensus must be at least 1");
+  return CORA_OK;
+}
+// the length of landmark l's list
+int32_t ml_list_len(const MlTables &T, size_t l) {
+  const size_t c0 = static_cast<size_t>(T.lm_chunk0[l]), c1 = static_cast<size_t>(T.lm_chunk0[l + 1]);
+  return c1 > c0 ? T.chunk_begin[c1 - 1] + T.chunk_len[c1 - 1] - T.chunk_begin[c0] : 0;
+}
+// what a robust call returns beyond the plain call's: cint [nl][kMlCInts] (read where lm_init == 0), inl [n_ranges] (2 where a
+// range is in no list that is voted on)
+void ml_robust_results(const cora_ctx *c, const std::vector<int32_t> &ist, const std::vector<int32_t> &cint, const std::vector<unsigned char> &inl,
+                       const MlConsensus &rb, int64_t out[6]) {
+  const MlTables &T = c->ml;
+  const size_t nl = T.lm_row.size(), nr = static_cast<size_t>(c->meas.n_ranges);
+  out[4] = out[5] = 0;
+  for (size_t l = 0; l < nl; ++l) {
+    const bool voted = T.lm_init[l] == 0;
+    if (ist[l * kMlInts] == 5) ++out[4];
+    if (rb.elected) rb.elected[l] = voted ? cint[l * kMlCInts] : -1;
+    if (rb.consensus) rb.consensus[l] = voted ? cint[l * kMlCInts + 1] : 0;
+    if (rb.list_len) rb.list_len[l] = ml_list_len(T, l);
+  }
+  for (size_t m = 0; m < nr; ++m) out[5] += inl[m] == 0 ? 1 : 0;
+  if (rb.inlier) std::copy(inl.begin(), inl.begin() + static_cast<std::ptrdiff_t>(nr), rb.inlier);
+}
+
 extern "C++" {  // (templates: this file is included inside extern "C")
+// the consensus vote of a robust call on the host: the setting and the lists' elected hypotheses, as on the device
+struct MlHostVote {
+  double barc2;
+  int min_consensus;
+  std::vector<double> cstate;      // [nl][kMlCState(d)]
+  std::vector<int32_t> cint;       // [nl][kMlCInts]
+  std::vector<unsigned char> inl;  // [n_ranges]
+};
+// the hypothesis of entry h of landmark l's list (begin, len), as k_ml_vote and k_ml_elect gather it
+template <int D>
+bool ml_host_hypothesis(const cora_ctx *c, const double *oi, size_t l, size_t begin, int32_t len, int32_t h, double *y) {
+  const MlTables &T = c->ml;
+  const MeasurementTable &M = c->meas;
+  double ts[(D + 1) * D], rs[D + 1], ws[D + 1];
+  for (int k = 0; k <= D; ++k) {
+    const size_t e = begin + static_cast<size_t>(ml_sample<D>(h, k, len)), m = static_cast<size_t>(T.ent_m[e]);
+    std::copy_n(oi + static_cast<size_t>(T.ent_row[e]) * D, D, ts + k * D);
+    rs[k] = M.range_data[m];
+    ws[k] = M.range_data[static_cast<size_t>(M.n_ranges) + m];
+  }
+  return ml_hypothesis<D>(oi + static_cast<size_t>(T.lm_origin[l]) * D, ts, rs, ws, y);
+}
+// vote and election over all lists (k_ml_vote, k_ml_elect): the votes are integers, so the order of the scoring is free
+template <int D>
+bool ml_host_vote_elect(const cora_ctx *c, const double *oi, MlHostVote &hv, std::vector<int32_t> &ist) {
+  const MlTables &T = c->ml;
+  const MeasurementTable &M = c->meas;
+  bool finite = true;
+  for (size_t l = 0; l < T.lm_row.size(); ++l) {
+    if (T.lm_init[l] != 0) continue;
+    const size_t begin = static_cast<size_t>(T.chunk_begin[static_cast<size_t>(T.lm_chunk0[l])]);
+    const int32_t len = ml_list_len(T, l);
+    const double *t0 = oi + static_cast<size_t>(T.lm_origin[l]) * D;
+    std::vector<double> ent(static_cast<size_t>(len) * (D + 2));  // u | r | omega
+    for (int32_t j = 0; j < len; ++j) {
+      const size_t e = begin + static_cast<size_t>(j), m = static_cast<size_t>(T.ent_m[e]);
+      double *f = ent.data() + static_cast<size_t>(j) * (D + 2);
+      for (int cc = 0; cc < D; ++cc) f[cc] = oi[static_cast<size_t>(T.ent_row[e]) * D + cc] - t0[cc];
+      f[D] = M.range_data[m];
+      f[D + 1] = M.range_data[static_cast<size_t>(M.n_ranges) + m];
+    }
+    int32_t bv = -1, be = len;
+    for (int32_t h = 0; h < len; ++h) {
+      double y[D];
+      int32_t vote = 0;
+      if (ml_host_hypothesis<D>(c, oi, l, begin, len, h, y)) {
+        for (int32_t j = 0; j < len; ++j) {
+          const double *f = ent.data() + static_cast<size_t>(j) * (D + 2);
+          vote += cl_agrees(ml_cost_at<D>(y, f, f[D], f[D + 1]), hv.barc2) ? 1 : 0;
+        }
+      }
+      if (cl_better(vote, h, bv, be)) {
+        bv = vote;
+        be = h;
+      }
+    }
+    double *y = hv.cstate.data() + l * kMlCState(D);
+    ml_host_hypothesis<D>(c, oi, l, begin, len, be, y);
+    hv.cint[l * kMlCInts] = be;
+    hv.cint[l * kMlCInts + 1] = bv;
+    ist[l * kMlInts] = bv < hv.min_consensus ? 5 : 0;
+    finite = odom_finite(y, D) && finite;
+  }
+  return finite;
+}
 // the whole multilateration on the host, in the kernels' order: oi a d-column resident vector; state and ist as on the device
 template <int D>
 bool ml_host_run(const cora_ctx *c, int gn_steps, double *oi, std::vector<double> &state, std::vector<int32_t> &ist, unsigned char *deg,
-                 int64_t *n_deg) {
+                 int64_t *n_deg, MlHostVote *hv = nullptr) {  // hv: over the inliers of the elected hypotheses (an entry outside adds +0.0 terms)
   const MlTables &T = c->ml;
   const MeasurementTable &M = c->meas;
   const int64_t nr = M.n_ranges;
@@ -116,16 +223,28 @@ bool ml_host_run(const cora_ctx *c, int gn_steps, double *oi, std::vector<double
         const size_t e = static_cast<size_t>(T.chunk_begin[ch]) + i, m = static_cast<size_t>(T.ent_m[e]);
         const double *t0 = oi + static_cast<size_t>(T.lm_origin[l]) * D, *ti = oi + static_cast<size_t>(T.ent_row[e]) * D;
         const double r = M.range_data[m], om = M.range_data[static_cast<size_t>(nr) + m];
+        if (hv) {
+          double u[D];
+          for (int cc = 0; cc < D; ++cc) u[cc] = ti[cc] - t0[cc];
+          const bool in = hv->cint[l * kMlCInts + 1] > 0 && cl_agrees(ml_cost_at<D>(hv->cstate.data() + l * kMlCState(D), u, r, om), hv->barc2);
+          if (stage == 0) hv->inl[m] = in ? 1 : 0;
+          if (!in) return;
+        }
         if (stage == 0) ml_linear_terms<D>(t0, ti, r, om, t);
         else ml_gn_terms<D>(state.data() + l * kMlState(D), t0, ti, r, om, t);
       };
+      if (stage == 0 && hv && ist[l * kMlInts] == 5) {  // (the bytes alone: the fold reads no sum of this list)
+        double none[kMlSums(D)];
+        for (int i = 0; i < T.chunk_len[ch]; ++i) terms(i, none);
+        continue;
+      }
       if (stage == 0) host_chunk_sums<kMlSums(D)>(T.chunk_len[ch], terms, partial.data(), nc, ch);
       else host_chunk_sums<kMlGnSums(D)>(T.chunk_len[ch], terms, partial.data(), nc, ch);
     }
     for (size_t l = 0; l < nl; ++l) {
       int32_t *li = ist.data() + l * kMlInts;
       double *st = state.data() + l * kMlState(D);
-      const int init = T.lm_init[l];
+      const int init = hv && stage == 0 && T.lm_init[l] == 0 && li[0] == 5 ? 5 : static_cast<int>(T.lm_init[l]);
       double S[kMlSums(D)] = {};
       if (stage == 0 ? init != 0 : li[0] != 0) {
         if (stage == 0) ml_fold<D>(0, 0, S, st, li, init);
@@ -142,6 +261,13 @@ bool ml_host_run(const cora_ctx *c, int gn_steps, double *oi, std::vector<double
     }
   }
   return host_range_rows<D>(M, true, oi, deg, n_deg) && finite;
+}
+// the robust multilateration on the host, in the kernels' order: vote, election, then the stages over the inliers
+template <int D>
+bool ml_host_run_robust(const cora_ctx *c, int gn_steps, double *oi, std::vector<double> &state, std::vector<int32_t> &ist, unsigned char *deg,
+                        int64_t *n_deg, MlHostVote &hv) {
+  const bool finite = ml_host_vote_elect<D>(c, oi, hv, ist);
+  return ml_host_run<D>(c, gn_steps, oi, state, ist, deg, n_deg, &hv) && finite;
 }
 }  // extern "C++"
 
@@ -163,19 +289,20 @@ int cora_multilateration_counts(const cora_ctx *c, int64_t out[4]) {
   return CORA_OK;
 }
 
-int cora_multilaterate_dev(cora_ctx *c, double *dX, int gn_steps, int64_t out[4], unsigned char *status, double *cost_linear,
-                           double *cost_final, int32_t *chosen, unsigned char *degenerate) {
-  if (!c) return CORA_ERR_ARG;
-  int rc = ml_check(c);
-  if (rc) return rc;
-  NEED_DEVICE(c);
-  if ((rc = ml_args_check(c, dX, gn_steps, out))) return rc;
+namespace {
+// the device-pointer forms: rb null, the plain multilateration (2 (gn_steps + 2) launches); else the consensus vote in front of
+// the masked passes (2 more)
+int ml_dev(cora_ctx *c, double *dX, int gn_steps, const MlConsensus *rb, int64_t *out, unsigned char *status, double *cost_linear,
+           double *cost_final, int32_t *chosen, unsigned char *degenerate) {
+  int rc;
   const Layout &L = c->F.L;
   const MeasurementTable &M = c->meas;
   MlTables &T = c->ml;
   const int d = L.d;
-  const size_t nl = T.lm_row.size(), nc = T.chunk_lm.size(), ne = T.ent_row.size();
-  MlArgs A;
+  const size_t nl = T.lm_row.size(), nc = T.chunk_lm.size(), ne = T.ent_row.size(), nr = static_cast<size_t>(M.n_ranges);
+  const bool vote = rb && nc > 0;  // (no entry: no list to vote on, the plain launches serve the call)
+  MlRobustArgs R;
+  MlArgs &A = R.A;
   A.d = d;
   A.n_lm = static_cast<int64_t>(nl);
   A.n_chunks = static_cast<int64_t>(nc);
@@ -198,19 +325,83 @@ int cora_multilaterate_dev(cora_ctx *c, double *dX, int gn_steps, int64_t out[4]
   A.flag = c->d_flag;
   wrote(c, dX);
   HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
+  if (rb) {
+    R.barc2 = rb->barc2;
+    R.min_consensus = rb->min_consensus;
+    R.votes = T.d_votes;
+    R.cstate = T.d_cstate;
+    R.cint = T.d_cint;
+    R.inlier = T.d_inlier;
+    if (nr > 0) HIP_TRY(c, hipMemsetAsync(T.d_inlier, 2, nr, c->stream));  // (a range of no list that is voted on)
+  }
+  if (vote) HIP_TRY(c, launch_multilat_vote_elect(R, c->stream));
   for (int stage = 0; stage <= gn_steps + 1; ++stage) {
     A.stage = stage;
     A.last = stage == gn_steps + 1 ? 1 : 0;
-    HIP_TRY(c, launch_multilat_stage(A, c->stream));
+    HIP_TRY(c, vote ? launch_multilat_robust_stage(R, c->stream) : launch_multilat_stage(A, c->stream));
   }
   std::vector<double> state(nl * kMlState(d));
-  std::vector<int32_t> ist(nl * kMlInts);
+  std::vector<int32_t> ist(nl * kMlInts), cint(rb ? nl * kMlCInts : 0, 0);
+  std::vector<unsigned char> inl(rb ? nr : 0);
   int64_t n_deg = 0;
-  if ((rc = range_rows_step(c, dX, true, degenerate, "a sum of the multilateration is not finite", &n_deg,  // (after the landmarks' rows)
-                            [&] { return read_back_state(c, state, T.d_state, ist, T.d_istate); })))
+  if ((rc = range_rows_step(c, dX, true, degenerate, ml_not_finite(rb), &n_deg, [&]() -> int {  // (after the landmarks' rows)
+         if (const int e = read_back_state(c, state, T.d_state, ist, T.d_istate)) return e;
+         if (vote) HIP_TRY(c, hipMemcpyAsync(cint.data(), T.d_cint, cint.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+         if (rb && nr > 0) HIP_TRY(c, hipMemcpyAsync(inl.data(), T.d_inlier, nr, hipMemcpyDeviceToHost, c->stream));
+         return CORA_OK;
+       })))
     return rc;
   ml_results(c, state, ist, n_deg, out, status, cost_linear, cost_final, chosen);
+  if (rb) ml_robust_results(c, ist, cint, inl, *rb, out);
   return CORA_OK;
+}
+// the host mirrors (with_host_x)
+int ml_mirror(cora_ctx *c, double *X, int ldx, int gn_steps, const MlConsensus *rb, int64_t *out, unsigned char *status, double *cost_linear,
+              double *cost_final, int32_t *chosen, unsigned char *degenerate) {
+  const int d = c->F.L.d;
+  const size_t nl = c->ml.lm_row.size();
+  std::vector<double> state(nl * kMlState(d), 0.0);
+  std::vector<int32_t> ist(nl * kMlInts, 0);
+  MlHostVote hv;
+  if (rb) {
+    hv.barc2 = rb->barc2;
+    hv.min_consensus = rb->min_consensus;
+    hv.cstate.assign(nl * kMlCState(d), 0.0);
+    hv.cint.assign(nl * kMlCInts, 0);
+    hv.inl.assign(static_cast<size_t>(c->meas.n_ranges), 2);
+  }
+  int64_t n_deg = 0;
+  const int rc = with_host_x(c, X, ldx, ml_not_finite(rb), [&](auto D, double *oi) {
+    return rb ? ml_host_run_robust<D()>(c, gn_steps, oi, state, ist, degenerate, &n_deg, hv)
+              : ml_host_run<D()>(c, gn_steps, oi, state, ist, degenerate, &n_deg);
+  });
+  if (rc) return rc;
+  ml_results(c, state, ist, n_deg, out, status, cost_linear, cost_final, chosen);
+  if (rb) ml_robust_results(c, ist, hv.cint, hv.inl, *rb, out);
+  return CORA_OK;
+}
+}  // namespace
+
+int cora_multilaterate_dev(cora_ctx *c, double *dX, int gn_steps, int64_t out[4], unsigned char *status, double *cost_linear,
+                           double *cost_final, int32_t *chosen, unsigned char *degenerate) {
+  if (!c) return CORA_ERR_ARG;
+  int rc = ml_check(c);
+  if (rc) return rc;
+  NEED_DEVICE(c);
+  if ((rc = ml_args_check(c, dX, gn_steps, out))) return rc;
+  return ml_dev(c, dX, gn_steps, nullptr, out, status, cost_linear, cost_final, chosen, degenerate);
+}
+
+int cora_multilaterate_robust_dev(cora_ctx *c, double *dX, int gn_steps, double barc2, int min_consensus, int64_t out[6], unsigned char *status,
+                                  double *cost_linear, double *cost_final, int32_t *chosen, int32_t *elected, int32_t *consensus,
+                                  int32_t *list_len, unsigned char *inlier, unsigned char *degenerate) {
+  if (!c) return CORA_ERR_ARG;
+  int rc = ml_check(c);
+  if (rc) return rc;
+  NEED_DEVICE(c);
+  if ((rc = ml_args_check(c, dX, gn_steps, out)) || (rc = ml_consensus_check(c, barc2, min_consensus))) return rc;
+  const MlConsensus rb{barc2, min_consensus, elected, consensus, list_len, inlier};
+  return ml_dev(c, dX, gn_steps, &rb, out, status, cost_linear, cost_final, chosen, degenerate);
 }
 
 int cora_multilaterate(cora_ctx *c, double *X, int ldx, int gn_steps, int64_t out[4], unsigned char *status, double *cost_linear,
@@ -225,20 +416,36 @@ int cora_multilaterate(cora_ctx *c, double *X, int ldx, int gn_steps, int64_t ou
   });
 }
 
-// the host mirror (with_host_x)
+int cora_multilaterate_robust(cora_ctx *c, double *X, int ldx, int gn_steps, double barc2, int min_consensus, int64_t out[6],
+                              unsigned char *status, double *cost_linear, double *cost_final, int32_t *chosen, int32_t *elected,
+                              int32_t *consensus, int32_t *list_len, unsigned char *inlier, unsigned char *degenerate) {
+  if (!c) return CORA_ERR_ARG;
+  int rc = ml_check(c);
+  if (rc) return rc;
+  NEED_DEVICE(c);
+  if ((rc = ml_args_check(c, X, gn_steps, out)) || (rc = ml_consensus_check(c, barc2, min_consensus))) return rc;
+  const MlConsensus rb{barc2, min_consensus, elected, consensus, list_len, inlier};
+  return with_uploaded_x(c, X, ldx, [&](double *dX) {
+    return ml_dev(c, dX, gn_steps, &rb, out, status, cost_linear, cost_final, chosen, degenerate);
+  });
+}
+
 int cora_debug_multilaterate_host(cora_ctx *c, double *X, int ldx, int gn_steps, int64_t out[4], unsigned char *status,
                                   double *cost_linear, double *cost_final, int32_t *chosen, unsigned char *degenerate) {
   if (!c) return CORA_ERR_ARG;
   int rc = ml_check(c);
   if (rc) return rc;
   if ((rc = ml_args_check(c, X, gn_steps, out))) return rc;
-  const size_t nl = c->ml.lm_row.size();
-  std::vector<double> state(nl * kMlState(c->F.L.d), 0.0);
-  std::vector<int32_t> ist(nl * kMlInts, 0);
-  int64_t n_deg = 0;
-  if ((rc = with_host_x(c, X, ldx, "a sum of the multilateration is not finite",
-                        [&](auto D, double *oi) { return ml_host_run<D()>(c, gn_steps, oi, state, ist, degenerate, &n_deg); })))
-    return rc;
-  ml_results(c, state, ist, n_deg, out, status, cost_linear, cost_final, chosen);
-  return CORA_OK;
+  return ml_mirror(c, X, ldx, gn_steps, nullptr, out, status, cost_linear, cost_final, chosen, degenerate);
+}
+
+int cora_debug_multilaterate_robust_host(cora_ctx *c, double *X, int ldx, int gn_steps, double barc2, int min_consensus, int64_t out[6],
+                                         unsigned char *status, double *cost_linear, double *cost_final, int32_t *chosen, int32_t *elected,
+                                         int32_t *consensus, int32_t *list_len, unsigned char *inlier, unsigned char *degenerate) {
+  if (!c) return CORA_ERR_ARG;
+  int rc = ml_check(c);
+  if (rc) return rc;
+  if ((rc = ml_args_check(c, X, gn_steps, out)) || (rc = ml_consensus_check(c, barc2, min_consensus))) return rc;
+  const MlConsensus rb{barc2, min_consensus, elected, consensus, list_len, inlier};
+  return ml_mirror(c, X, ldx, gn_steps, &rb, out, status, cost_linear, cost_final, chosen, degenerate);
 }

@@ -1171,9 +1171,11 @@ Matrix Problem::odometryInitialization(uint64_t seed) const {
   return odometryStart(seed, -1, nullptr, "Problem::odometryInitialization");
 }
 
-Matrix Problem::rangeAidedInitialization(uint64_t seed, int gn_steps, LandmarkInitInfo *info) const {
+Matrix Problem::rangeAidedInitialization(uint64_t seed, int gn_steps, LandmarkInitInfo *info, RangeConsensus consensus) const {
   if (gn_steps < 0) throw std::invalid_argument("Problem::rangeAidedInitialization: gn_steps must be in [0, 16]");
-  return odometryStart(seed, gn_steps, info, "Problem::rangeAidedInitialization");
+  if (!std::isfinite(consensus.barc2)) throw std::invalid_argument("Problem::rangeAidedInitialization: the consensus threshold must be finite");
+  return odometryStart(seed, gn_steps, info, "Problem::rangeAidedInitialization", false, 0, nullptr, false, 0, nullptr, false, 0, nullptr,
+                       ClosureConsensus(), consensus);
 }
 
 Matrix Problem::multiRobotInitialization(uint64_t seed, int gn_steps, int min_ranges, ChainPlacementInfo *chains_info, LandmarkInitInfo *info) const {
@@ -1204,7 +1206,8 @@ Matrix Problem::closureInitialization(uint64_t seed, int gn_steps, int min_range
 // edges between chains (cora_place_by_closures_dev)
 Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where, bool place, int min_ranges,
                               ChainPlacementInfo *chains_info, bool sightings, int min_sightings, SightingPlacementInfo *sight_info, bool closures,
-                              int min_closures, ClosurePlacementInfo *closure_info, ClosureConsensus consensus) const {
+                              int min_closures, ClosurePlacementInfo *closure_info, ClosureConsensus consensus,
+                              RangeConsensus range_consensus) const {
   checkUpToDate();
   if (part_world_ > 1) throw std::runtime_error(std::string(where) + ": not supported on a partitioned handle");
   ensureMeasurementTable();
@@ -1394,10 +1397,18 @@ Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *inf
     for (int l = 0; l < nl; ++l)
       if (lm_done[static_cast<size_t>(l)]) on[static_cast<size_t>(l)] = 0;  // (the sightings placed it)
     CORA_CALL(cora_set_multilateration(c, pose_ok.data(), on.data()), where);
-    int64_t out[4] = {0, 0, 0, 0};
-    std::vector<unsigned char> status(static_cast<size_t>(nl) + 1, 0), after(nr + 1, 0);
+    int64_t out[6] = {0, 0, 0, 0, 0, 0};
+    const bool robust = range_consensus.barc2 > 0;
+    std::vector<unsigned char> status(static_cast<size_t>(nl) + 1, 0), after(nr + 1, 0), inlier(robust ? nr + 1 : 0, 0);
     std::vector<double> cost_linear(static_cast<size_t>(nl) + 1, 0.0), cost_final(static_cast<size_t>(nl) + 1, 0.0);
-    CORA_CALL(cora_multilaterate_dev(c, v.x, gn_steps, out, status.data(), cost_linear.data(), cost_final.data(), nullptr, after.data()), where);
+    std::vector<int32_t> votes(robust ? static_cast<size_t>(nl) + 1 : 0, 0), lens(robust ? static_cast<size_t>(nl) + 1 : 0, 0);
+    if (robust)  // (a landmark without consensus, status 5, keeps its random draw like one that is not solved)
+      CORA_CALL(cora_multilaterate_robust_dev(c, v.x, gn_steps, range_consensus.barc2, range_consensus.min_consensus > 0 ? range_consensus.min_consensus : d + 2,
+                                              out, status.data(), cost_linear.data(), cost_final.data(), nullptr, nullptr, votes.data(), lens.data(),
+                                              inlier.data(), after.data()),
+                where);
+    else
+      CORA_CALL(cora_multilaterate_dev(c, v.x, gn_steps, out, status.data(), cost_linear.data(), cost_final.data(), nullptr, after.data()), where);
     // the rows that were degenerate before keep the direction drawn for them where they still are; a row that is
     // degenerate only now draws after everything odometryInitialization draws
     std::vector<int32_t> keep_idx;
@@ -1420,6 +1431,11 @@ Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *inf
       info->status.assign(status.begin(), status.begin() + nl);
       info->cost_linear.assign(cost_linear.begin(), cost_linear.begin() + nl);
       info->cost_final.assign(cost_final.begin(), cost_final.begin() + nl);
+      info->no_consensus = static_cast<long>(out[4]);
+      info->ranges_excluded = static_cast<long>(out[5]);
+      info->consensus.assign(votes.begin(), votes.begin() + (robust ? nl : 0));
+      info->list_len.assign(lens.begin(), lens.begin() + (robust ? nl : 0));
+      info->inlier.assign(inlier.begin(), inlier.begin() + static_cast<std::ptrdiff_t>(robust ? nr : 0));
     }
   }
   std::vector<double> lift(static_cast<size_t>(d) * p);  // the first d rows of Qm, column-major d x p

@@ -161,6 +161,21 @@ struct LandmarkInitInfo {
   long degenerate_range_rows = 0;      // range rows that got a fallback direction
   std::vector<unsigned char> status;   // per landmark (0 solved, 1 too few ranges, 2 degenerate geometry, 3 no range)
   std::vector<Scalar> cost_linear, cost_final;  // per landmark: sum omega (|x - t| - r)^2 after the linear stage, at the point written
+  // with a consensus vote (RangeConsensus; status 5: no consensus, counted in not_solved); empty / 0 without one
+  long no_consensus = 0, ranges_excluded = 0;  // status 5; ranges of the voted lists outside their inliers
+  std::vector<int32_t> consensus, list_len;    // per landmark: the vote of the elected hypothesis, the ranges of the landmark's list
+  std::vector<unsigned char> inlier;   // per range measurement: 1 inlier | 0 in a voted list, not an inlier | 2 in no voted list
+};
+
+/** The consensus vote of the multilateration (cora_multilaterate_robust_dev, include/cora_hip.h).  barc2 <= 0: off, the plain
+ * least-squares fit and its bits.  barc2 > 0: every range of a landmark's list proposes the point its sample of d + 1 ranges
+ * determines, the proposal most ranges agree with (weighted squared range residual <= barc2, the quantity the GNC weights
+ * threshold) is elected and the fit runs over the agreeing ranges only; a landmark whose elected proposal has fewer than
+ * min_consensus votes (<= 0: d + 2 -- a proposal has about d + 1 votes of its own) keeps its random draw (status 5).  One
+ * proposal per range, clean only where all d + 1 ranges of its sample are: short lists with many outliers reach no consensus. */
+struct RangeConsensus {
+  Scalar barc2 = 0;
+  int min_consensus = 0;
 };
 
 /** What Problem::multiRobotInitialization reports about the chains (cora_place_chains_dev, include/cora_hip.h). */
@@ -296,7 +311,8 @@ class Problem {
   Matrix odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where, bool place = false, int min_ranges = 0,
                        ChainPlacementInfo *chains_info = nullptr, bool sightings = false, int min_sightings = 0,
                        SightingPlacementInfo *sight_info = nullptr, bool closures = false, int min_closures = 0,
-                       ClosurePlacementInfo *closure_info = nullptr, ClosureConsensus consensus = ClosureConsensus()) const;
+                       ClosurePlacementInfo *closure_info = nullptr, ClosureConsensus consensus = ClosureConsensus(),
+                       RangeConsensus range_consensus = RangeConsensus()) const;
   void fillImplicitFormulationMatrices() const;
   [[noreturn]] void throwLast(int status, const char *where) const;
 
@@ -510,8 +526,11 @@ class Problem {
    * as the fallback of the landmarks that are not solved --, then the multilateration over the poses a chain wrote
    * (pose_ok) with gn_steps Gauss-Newton steps, the range rows recomputed; a range row that is degenerate only now draws
    * its direction after everything else, in range order.  Pose rows and the rows of unsolved landmarks have
-   * odometryInitialization's bits.  std::runtime_error on a partitioned handle. */
-  Matrix rangeAidedInitialization(uint64_t seed = 7, int gn_steps = 5, LandmarkInitInfo *info = nullptr) const;
+   * odometryInitialization's bits.  consensus: the outlier-robust multilateration (RangeConsensus; the default is off: the
+   * same bits as without the argument); std::invalid_argument for a barc2 that is not finite.  std::runtime_error on a
+   * partitioned handle. */
+  Matrix rangeAidedInitialization(uint64_t seed = 7, int gn_steps = 5, LandmarkInitInfo *info = nullptr,
+                                  RangeConsensus consensus = RangeConsensus()) const;
   /** EXTENSION beyond the reference: rangeAidedInitialization with every odometry chain after the first first moved rigidly
    * onto the chains placed before it, from the pose-pose ranges between chains (cora_place_chains_dev): exactly the draws
    * of odometryInitialization in the same order -- the random starts stay as the fallback of the chains that are not

@@ -252,6 +252,8 @@ int cora_problem_op(cora_problem *p, const char *op, int cols, const double *A, 
     else if (o == "getOdomInitialization") res = getOdomInitialization(q);
     else if (o == "odometryInitialization") res = q.odometryInitialization();
     else if (o == "rangeAidedInitialization") res = q.rangeAidedInitialization();
+    else if (o == "rangeAidedInitializationConsensus")  // (the operator form takes no arguments: barc2 = 100, min_consensus = d + 2)
+      res = q.rangeAidedInitialization(7, 5, nullptr, RangeConsensus{100.0, 0});
     else if (o == "multiRobotInitialization") res = q.multiRobotInitialization();
     else if (o == "sightingInitialization") res = q.sightingInitialization();
     else if (o == "closureInitialization") res = q.closureInitialization();
@@ -291,9 +293,27 @@ int cora_problem_odometry_chains(const cora_problem *p, int64_t counts[2], int64
 
 int cora_problem_range_aided_initialization(cora_problem *p, uint64_t seed, int gn_steps, double *out, int64_t counts[4],
                                             unsigned char *status, double *cost_linear, double *cost_final) {
+  return cora_problem_range_aided_initialization_consensus(p, seed, gn_steps, 0.0, 0, out, counts, status, cost_linear, cost_final, nullptr, nullptr,
+                                                           nullptr, nullptr);
+}
+
+int cora_problem_range_aided_initialization_consensus(cora_problem *p, uint64_t seed, int gn_steps, double consensus_barc2, int min_consensus,
+                                                      double *out, int64_t counts[4], unsigned char *status, double *cost_linear,
+                                                      double *cost_final, int64_t consensus_counts[2], int32_t *consensus, int32_t *list_len,
+                                                      unsigned char *inlier) {
   return guarded([&] {
     LandmarkInitInfo info;
-    const Matrix res = p->problem.rangeAidedInitialization(seed, gn_steps, &info);
+    RangeConsensus vote;
+    vote.barc2 = consensus_barc2;
+    vote.min_consensus = min_consensus;
+    const Matrix res = p->problem.rangeAidedInitialization(seed, gn_steps, &info, vote);
+    if (consensus_counts) {
+      consensus_counts[0] = info.no_consensus;
+      consensus_counts[1] = info.ranges_excluded;
+    }
+    if (consensus) std::copy(info.consensus.begin(), info.consensus.end(), consensus);
+    if (list_len) std::copy(info.list_len.begin(), info.list_len.end(), list_len);
+    if (inlier) std::copy(info.inlier.begin(), info.inlier.end(), inlier);
     if (res.rows() == p->problem.getExpectedVariableSize()) p->problem.checkVariablesAreValid(res);  // (throws off the manifold)
     std::memcpy(out, res.data(), sizeof(double) * static_cast<size_t>(res.size()));
     if (counts) {

@@ -1101,6 +1101,75 @@ __host__ __device__ inline bool ml_fold(int stage, int last, const double *S, do
   return true;
 }
 
+// Outlier-robust multilateration: a consensus vote over minimal hypotheses (kernels/multilat.inc; include/cora_hip.h,
+// cora_multilaterate_robust_dev).  Tables, lists, chunks, origin and masks are the plain multilateration's.  Per
+// list of a landmark with lm_init == 0, of length L >= d + 1, entries e = 0 .. L - 1 in table order, u_j = t_j - t_0:
+//   sample of entry h : entries (h + k s) mod L, k = 0 .. d, s = max(1, L / (d + 1)) (ml_sample) -- distinct as d s < L, spread
+//                       over the list, a function of (h, L, d) alone;
+//   hypothesis y_h    : the sample's ml_linear_terms added from the left in the order k = 0 .. d from +0.0, then
+//                       ml_linear_solve (ml_hypothesis); valid where the solve returns 0, else y = 0, vote 0, no flag;
+//   score             : r(h, j) = (omega_j e) e, e = |y_h - u_j| - r_j (ml_cost_at: the last term of ml_gn_terms);
+//   vote(h)           : #{j : r(h, j) <= barc2} over EVERY entry j, the sample's own included (cl_agrees: a NaN is no vote) --
+//                       a valid hypothesis has about d + 1 votes of its own, a consensus means something above d + 1 only;
+//   election          : the largest vote, among equal votes the lowest entry (cl_better); consensus = its vote; consensus <
+//                       min_consensus: status 5, the landmark keeps its row; no valid hypothesis: entry 0, consensus 0;
+//   I = {j : r(h*, j) <= barc2} (empty at consensus 0); the plain stages run over I alone: AN ENTRY OUTSIDE I ADDS +0.0 FOR
+//                       EACH OF ITS TERMS, as a lane beyond the chunk's end does, so the bracket order of a sum is the plain one's.
+// 2 + 2 (gn_steps + 2) launches: vote, elect, then the plain stages with the masked passes.  One election, one refit.
+constexpr int kMlCState(int d) { return d; }  // of the elected hypothesis: y
+constexpr int kMlCInts = 2;                   // elected entry (index in its list) | consensus
+struct MlRobustArgs {
+  MlArgs A;
+  double barc2 = 0.0;
+  int min_consensus = 0;
+  int32_t *votes = nullptr;         // [n_entries]
+  double *cstate = nullptr;         // [n_lm][kMlCState(d)]
+  int32_t *cint = nullptr;          // [n_lm][kMlCInts], written where lm_init == 0
+  unsigned char *inlier = nullptr;  // [n_ranges]: written where a range is an entry of a list with lm_init == 0, 1 in I | 0 outside
+};
+hipError_t launch_multilat_vote_elect(const MlRobustArgs &R, hipStream_t st);    // k_ml_vote and k_ml_elect over all lists
+hipError_t launch_multilat_robust_stage(const MlRobustArgs &R, hipStream_t st);  // masked pass and fold of R.A.stage
+// entry k of the sample of entry h of a list of len entries (h < len, 0 <= k <= D, len >= D + 1)
+template <int D>
+__host__ __device__ inline int32_t ml_sample(int32_t h, int k, int32_t len) {
+  const int32_t s = len / (D + 1) > 1 ? len / (D + 1) : 1;
+  const int32_t e = h + k * s;  // (< 2 len)
+  return e >= len ? e - len : e;
+}
+// The point the D + 1 ranges of a sample determine: t: the sample's anchors [D + 1][D], r, w: their ranges and precisions.
+// Returns whether the hypothesis is valid; y = 0 where it is not.
+template <int D>
+__host__ __device__ inline bool ml_hypothesis(const double *t0, const double *t, const double *r, const double *w, double *y) {
+#pragma clang fp contract(off)
+  constexpr int NS = kMlSums(D);
+  double S[NS], term[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) S[i] = 0.0;
+#pragma unroll
+  for (int k = 0; k <= D; ++k) {
+    ml_linear_terms<D>(t0, t + k * D, r[k], w[k], term);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) S[i] = S[i] + term[i];
+  }
+  if (ml_linear_solve<D>(S, y) == 0) return true;
+#pragma unroll
+  for (int c = 0; c < D; ++c) y[c] = 0.0;
+  return false;
+}
+// the weighted squared range residual of an entry (u = t_j - t_0) at the point t_0 + y, without the 1/2
+template <int D>
+__host__ __device__ inline double ml_cost_at(const double *y, const double *u, double r, double w) {
+#pragma clang fp contract(off)
+  double n2 = 0.0;
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    const double dv = y[c] - u[c];
+    n2 = fma(dv, dv, n2);
+  }
+  const double e = sqrt(n2) - r;
+  return (w * e) * e;
+}
+
 // Chain placement from inter-robot ranges (kernels/placement.inc; include/cora_hip.h, cora_place_chains_dev): the
 // multilateration with a rigid body in place of a point.  The host orders the chains into STAGES (capi/placement.inc); a
 // stage finds g = (R, t) in SE(d) that moves one chain onto the chains placed before it, from the stage's entry list (row

@@ -575,6 +575,48 @@ hipError_t launch_multilat_stage(const MlArgs &A, hipStream_t st) {
   }
   return hipGetLastError();
 }
+// the outlier-robust multilateration: the consensus vote (one workgroup per chunk of all lists, then one wavefront per list),
+// and a stage with the masked passes; the Gauss-Newton fold is the plain one
+static bool multilat_robust_args_ok(const MlRobustArgs &R) {
+  const MlArgs &A = R.A;
+  return (A.d == 2 || A.d == 3) && A.n_lm > 0 && A.n_chunks > 0 && A.n_chunks < (int64_t(1) << 31) && A.n_lm < (int64_t(1) << 31) &&
+         A.n_ranges > 0 && A.chunk_lm && A.chunk_begin && A.chunk_len && A.ent_row && A.ent_m && A.lm_chunk0 && A.lm_row && A.lm_origin &&
+         A.lm_init && A.range_data && A.partial && A.state && A.istate && A.x && A.flag && R.barc2 > 0.0 && R.min_consensus >= 1 && R.votes &&
+         R.cstate && R.cint && R.inlier;
+}
+hipError_t launch_multilat_vote_elect(const MlRobustArgs &R, hipStream_t st) {
+  if (!multilat_robust_args_ok(R)) return hipErrorInvalidValue;
+  const dim3 chunks(static_cast<unsigned>(R.A.n_chunks)), lms(static_cast<unsigned>(R.A.n_lm));
+  if (R.A.d == 2) {
+    hipLaunchKernelGGL(k_ml_vote<2>, chunks, dim3(kMlChunk), 0, st, R);
+    hipLaunchKernelGGL(k_ml_elect<2>, lms, dim3(kWave), 0, st, R);
+  } else {
+    hipLaunchKernelGGL(k_ml_vote<3>, chunks, dim3(kMlChunk), 0, st, R);
+    hipLaunchKernelGGL(k_ml_elect<3>, lms, dim3(kWave), 0, st, R);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_multilat_robust_stage(const MlRobustArgs &R, hipStream_t st) {
+  const MlArgs &A = R.A;
+  if (!multilat_robust_args_ok(R) || A.stage < 0 || A.stage > kMlMaxSteps + 1 || (A.last && A.stage == 0)) return hipErrorInvalidValue;
+  const dim3 chunks(static_cast<unsigned>(A.n_chunks)), lms(static_cast<unsigned>(A.n_lm));
+  if (A.stage == 0) {
+    if (A.d == 2) {
+      hipLaunchKernelGGL((k_ml_pass_linear<2, true>), chunks, dim3(kMlChunk), 0, st, R);
+      hipLaunchKernelGGL((k_ml_fold_linear<2, true>), lms, dim3(kWave), 0, st, A);
+    } else {
+      hipLaunchKernelGGL((k_ml_pass_linear<3, true>), chunks, dim3(kMlChunk), 0, st, R);
+      hipLaunchKernelGGL((k_ml_fold_linear<3, true>), lms, dim3(kWave), 0, st, A);
+    }
+  } else if (A.d == 2) {
+    hipLaunchKernelGGL((k_ml_pass_gn<2, true>), chunks, dim3(kMlChunk), 0, st, R);
+    hipLaunchKernelGGL(k_ml_fold_gn<2>, lms, dim3(kWave), 0, st, A);
+  } else {
+    hipLaunchKernelGGL((k_ml_pass_gn<3, true>), chunks, dim3(kMlChunk), 0, st, R);
+    hipLaunchKernelGGL(k_ml_fold_gn<3>, lms, dim3(kWave), 0, st, A);
+  }
+  return hipGetLastError();
+}
 // the chain placement (kernels/placement.inc): every launch serves the one stage A describes
 static bool place_args_ok(const PlArgs &A) {
   return (A.d == 2 || A.d == 3) && A.n_chunks > 0 && A.chunk0 >= 0 && A.pstride >= A.n_chunks && A.origin_q >= 0 && A.origin_a >= 0 &&

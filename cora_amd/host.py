@@ -200,7 +200,7 @@ class Problem:
             out = np.zeros(1)
         pa, pb, pc = ptr(A), ptr(B), ptr(C_)
         if name != "evaluateObjective":
-            full = name in ("getOdomInitialization", "odometryInitialization", "rangeAidedInitialization", "multiRobotInitialization", "sightingInitialization", "closureInitialization",
+            full = name in ("getOdomInitialization", "odometryInitialization", "rangeAidedInitialization", "rangeAidedInitializationConsensus", "multiRobotInitialization", "sightingInitialization", "closureInitialization",
                             "closureInitializationConsensus",
                             "getTranslationExplicitSolution", "alignEstimateToOrigin")
             out = np.zeros((dm["N"] if full else N, cols[0] if cols else p), order="F")
@@ -221,18 +221,30 @@ class Problem:
                                                       edges.ctypes.data_as(C.POINTER(C.c_int32))))
         return [edges[ptr[i]:ptr[i + 1]].copy() for i in range(int(cnt[0]))]
 
-    def range_aided_initialization(self, seed=7, gn_steps=5):
+    def range_aided_initialization(self, seed=7, gn_steps=5, consensus_barc2=None, min_consensus=0):
         """Problem::rangeAidedInitialization: (x0, info) with info a dict solved, not_solved, n_degenerate, steps, status,
-        cost_linear, cost_final (per landmark).  The start has passed checkVariablesAreValid."""
+        cost_linear, cost_final (per landmark).  The start has passed checkVariablesAreValid.
+        consensus_barc2: None, the plain multilateration; a threshold > 0, the multilateration with a consensus vote
+        (RangeConsensus, CORA_problem.h): the fit of a landmark runs over the ranges that agree with the elected proposal, a
+        landmark whose elected proposal has fewer than min_consensus (0: d + 2) votes has status 5, and info gains no_consensus,
+        excluded, consensus and list_len (per landmark) and inlier (per range measurement as added: 1 | 0 | 2 in no voted list)."""
         dm = self.dims()
         nl = dm["N"] - (dm["d"] + 1) * dm["n"] - dm["r"]
+        robust = consensus_barc2 is not None
+        if robust and not consensus_barc2 > 0:
+            raise HostError("consensus_barc2 must be positive (None: no consensus vote)")
+        nr = dm["r"]
         out = np.zeros((dm["N"], dm["rank"]), order="F")
-        cnt = (C.c_int64 * 4)()
+        cnt, vcnt = (C.c_int64 * 4)(), (C.c_int64 * 2)()
         status, cl, cf = np.zeros(nl + 1, dtype=np.uint8), np.zeros(nl + 1), np.zeros(nl + 1)
-        self._chk(self.L.cora_problem_range_aided_initialization(self.h, C.c_uint64(seed), int(gn_steps), out.ctypes.data_as(_dp),
-                                                                 cnt, status.ctypes.data_as(C.c_void_p), cl.ctypes.data_as(_dp),
-                                                                 cf.ctypes.data_as(_dp)))
-        return out, dict(solved=int(cnt[0]), not_solved=int(cnt[1]), n_degenerate=int(cnt[2]), steps=int(cnt[3]),
+        cons, ll, inl = np.zeros(nl + 1, dtype=np.int32), np.zeros(nl + 1, dtype=np.int32), np.zeros(nr + 1, dtype=np.uint8)
+        i32 = C.POINTER(C.c_int32)
+        self._chk(self.L.cora_problem_range_aided_initialization_consensus(
+            self.h, C.c_uint64(seed), int(gn_steps), C.c_double(consensus_barc2 if robust else 0.0), int(min_consensus),
+            out.ctypes.data_as(_dp), cnt, status.ctypes.data_as(C.c_void_p), cl.ctypes.data_as(_dp), cf.ctypes.data_as(_dp), vcnt,
+            cons.ctypes.data_as(i32), ll.ctypes.data_as(i32), inl.ctypes.data_as(C.c_void_p)))
+        extra = dict(no_consensus=int(vcnt[0]), excluded=int(vcnt[1]), consensus=cons[:nl], list_len=ll[:nl], inlier=inl[:nr]) if robust else {}
+        return out, dict(**extra, solved=int(cnt[0]), not_solved=int(cnt[1]), n_degenerate=int(cnt[2]), steps=int(cnt[3]),
                          status=status[:nl], cost_linear=cl[:nl], cost_final=cf[:nl])
 
     def multi_robot_initialization(self, seed=7, gn_steps=5, min_ranges=0):

@@ -22,13 +22,14 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding] [--device-init [--landmark-init] [--place-chains] [--sightings] [--closures [--closure-consensus barc2 [--closure-min-consensus k]]] [--gn-steps k]]" << std::endl;
+    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding] [--device-init [--landmark-init [--range-consensus barc2 [--range-min-consensus k]]] [--place-chains] [--sightings] [--closures [--closure-consensus barc2 [--closure-min-consensus k]]] [--gn-steps k]]" << std::endl;
     return 1;
   }
   int max_rank = 10, gn_steps = 5;
   std::string tum, save_dir, residuals, weights, robust, barc2, weights_out, aligned_tum, rpe_steps, rpe_dists;
   CORA::ClosureConsensus closure_consensus;
-  bool consensus_given = false;
+  CORA::RangeConsensus range_consensus;
+  bool consensus_given = false, range_consensus_given = false;
   bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false, landmark_init = false, place_chains = false, sightings = false, closures = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
@@ -62,6 +63,10 @@ int main(int argc, char **argv) {
     else if (a == "--device-init") device_init = true;
     // with --odom-init --device-init: the landmarks of the start are placed from the ranges (Problem::rangeAidedInitialization)
     else if (a == "--landmark-init") landmark_init = true;
+    // with --landmark-init: a consensus vote in front of each landmark's fit (RangeConsensus): the threshold on a range's weighted
+    // squared residual, and the votes the elected proposal needs (0: d + 2)
+    else if (a == "--range-consensus" && i + 1 < argc) range_consensus.barc2 = std::atof(argv[++i]), range_consensus_given = true;
+    else if (a == "--range-min-consensus" && i + 1 < argc) range_consensus.min_consensus = std::atoi(argv[++i]), range_consensus_given = true;
     else if (a == "--gn-steps" && i + 1 < argc) gn_steps = std::atoi(argv[++i]);
     // with --odom-init --device-init: the chains after the first are first placed from the pose-pose ranges between chains
     // (Problem::multiRobotInitialization, which then places the landmarks as --landmark-init does)
@@ -86,6 +91,8 @@ int main(int argc, char **argv) {
     if (closures && !device_init) throw std::runtime_error("--closures places the chains of the device's odometry start: it needs --odom-init --device-init");
     if (consensus_given && !closures) throw std::runtime_error("--closure-consensus and --closure-min-consensus set the vote of the closure step: they need --closures");
     if (consensus_given && !(closure_consensus.barc2 > 0)) throw std::runtime_error("--closure-consensus: expected a threshold > 0");
+    if (range_consensus_given && !landmark_init) throw std::runtime_error("--range-consensus and --range-min-consensus set the vote of the landmark step: they need --landmark-init");
+    if (range_consensus_given && !(range_consensus.barc2 > 0)) throw std::runtime_error("--range-consensus: expected a threshold > 0");
     if (landmark_init && !device_init) throw std::runtime_error("--landmark-init places the landmarks of the device's odometry start: it needs --odom-init --device-init");
     const auto t_start = clk::now();
     CORA::Problem problem = CORA::parsePyfgTextToProblem(argv[1]);
@@ -141,9 +148,17 @@ int main(int argc, char **argv) {
         return problem.measurementResiduals(implicit ? CORA::Matrix(x.block(0, 0, problem.rotAndRangeMatrixSize(), x.cols())) : x).range_sum;
       };
       const double without = range_sum(x0);
-      x0 = problem.rangeAidedInitialization(7, gn_steps, &lm);
+      x0 = problem.rangeAidedInitialization(7, gn_steps, &lm, range_consensus);
       std::printf("landmark init: %ld landmarks solved, %ld not solved (%ld Gauss-Newton steps); range residual sum at the start %.6e with it, %.6e without\n",
                   lm.solved, lm.not_solved, lm.gn_steps, range_sum(x0), without);
+      if (range_consensus_given) {
+        double least = 1.0;  // the smallest consensus / list length over the landmarks that were voted on
+        for (size_t l = 0; l < lm.list_len.size(); ++l)
+          if (lm.list_len[l] > 0 && (lm.status[l] == 0 || lm.status[l] == 2 || lm.status[l] == 5))
+            least = std::min(least, static_cast<double>(lm.consensus[l]) / lm.list_len[l]);
+        std::printf("range consensus: %ld landmarks without consensus, %ld ranges excluded; smallest consensus / list length %.4f\n",
+                    lm.no_consensus, lm.ranges_excluded, least);
+      }
     }
     if (place_chains) {  // (an extension beyond the reference: Problem::multiRobotInitialization)
       CORA::ChainPlacementInfo ci;

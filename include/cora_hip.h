@@ -853,6 +853,57 @@ int cora_multilaterate(cora_ctx *ctx, double *X, int ldx, int gn_steps, int64_t 
 int cora_debug_multilaterate_host(cora_ctx *ctx, double *X, int ldx, int gn_steps, int64_t out[4], unsigned char *status,
                                   double *cost_linear, double *cost_final, int32_t *chosen, unsigned char *degenerate);
 
+/* Outlier-robust multilateration: a consensus vote over minimal samples of d + 1 ranges in front of the fit.  A
+ * range that is grossly long (NLOS, multipath) drags the linear stage, which works in SQUARED ranges, far off, and the
+ * Gauss-Newton steps then descend the contaminated cost.  Tables, lists, chunks, origin, masks, the range-row step and the
+ * meaning of gn_steps are exactly those above: there is no new set call.  Per list of a landmark that is to be solved (L >= d
+ * + 1 entries e = 0 .. L - 1 in table order; origin t_0 the first anchor, whether or not it turns out an inlier; u_j = t_j - t_0):
+ *   sample of h      the entries (h + k s) mod L, k = 0 .. d, s = max(1, L / (d + 1)) (integer division): d + 1 distinct
+ *                    entries (d s < L) spread over the list instead of d + 1 consecutive, nearly collinear poses; a function
+ *                    of (h, L, d) alone: no random number, the same bits on every call and in the mirror.
+ *   hypothesis       y_h: the linear stage's terms of the sample's entries (their own omega, relative to t_0) added from the
+ *                    left in the order k = 0 .. d starting from +0.0, then the linear stage's solve.  VALID where that solve
+ *                    has status 0 (pivots > 1e-8, a finite result: the plain fit's rule filters a near-degenerate sample); an
+ *                    invalid hypothesis has vote 0 and y = 0 and sets no flag.
+ *   score            r(h, j) = (omega_j e) e, e = |y_h - u_j| - r_j: the difference, fma from +0.0, one square root -- the
+ *                    operations and order of the Gauss-Newton cost term: the weighted squared range residual that
+ *                    cora_gnc_weights thresholds, no 1/2.
+ *   vote             vote(h) = #{ j : r(h, j) <= barc2 } over EVERY entry of the list, the sample's own included; a NaN is no
+ *                    vote.  A valid hypothesis therefore starts with about d + 1 votes of its own: A CONSENSUS MEANS SOMETHING
+ *                    ONLY ABOVE d + 1.  barc2: one finite scalar > 0.
+ *   election         h* = the entry of largest vote, among equal votes the lowest entry; consensus = vote(h*).  A list without
+ *                    a valid hypothesis elects entry 0 with consensus 0.  consensus < min_consensus (min_consensus >= 1):
+ *                    status 5, "no consensus": the landmark keeps the row the caller wrote and counts as not solved.  (4 is
+ *                    not used by the multilateration.)
+ *   inliers          I = { j : r(h*, j) <= barc2 }, the same function and bits as the vote; empty at consensus 0.
+ *   refit            the plain fit over I only: one linear stage (status 2 is still possible), gn_steps Gauss-Newton stages, the
+ *                    last evaluation, the visited point of least cost, the earliest on ties.  AN ENTRY OUTSIDE I ADDS +0.0 FOR
+ *                    EACH OF ITS TERMS (it is not skipped: the bracket order of every sum is the plain call's, a lane beyond a
+ *                    chunk's end adds the same +0.0).  cost_linear and cost_final are sums over I.  One election, one refit.
+ *   cost             L^2 scores per list of L entries, by design: every entry is a hypothesis.
+ *   limit            one hypothesis per entry, and a hypothesis is clean only where all d + 1 entries of its sample are
+ *                    inliers: a fraction (1 - eps)^(d + 1) of the L hypotheses at an outlier fraction eps.  Short lists with
+ *                    many outliers do not reach a consensus (status 5) or elect a contaminated hypothesis.
+ * out = the plain call's four fields, then {landmarks without consensus (status 5; they are among out[1]), ranges excluded: the
+ * inlier bytes equal to 0}.  status, cost_linear, cost_final, chosen, degenerate: as the plain call's.  elected [nl]: h*, -1
+ * where the landmark's list is not voted on (status 1 or 3);  consensus [nl]: 0 there;  list_len [nl]: the entries of the
+ * landmark's list;  inlier [n_ranges]: 1 in I | 0 in a list that is voted on, outside I (every entry of a list with consensus 0)
+ * | 2 in no such list (pose-pose, landmark-landmark, masked, a list that is too short).  Every array may be NULL.
+ * 2 + 2 (gn_steps + 2) launches (vote, elect, then the stages with masked passes), then the range rows.
+ * cora_multilaterate_robust: the host-pointer form.  cora_debug_multilaterate_robust_host: the mirror, the same functions in the
+ * same bracket order: the device's bits; works on a plan-only handle.
+ * ERRORS.  The plain call's; CORA_ERR_ARG also for barc2 not finite or <= 0 and for min_consensus < 1; CORA_ERR_NAN also for an
+ * elected hypothesis that is not finite.  STATE.  Nothing the handle computes with changes, nor its tables. */
+int cora_multilaterate_robust_dev(cora_ctx *ctx, double *dX, int gn_steps, double barc2, int min_consensus, int64_t out[6],
+                                  unsigned char *status, double *cost_linear, double *cost_final, int32_t *chosen, int32_t *elected,
+                                  int32_t *consensus, int32_t *list_len, unsigned char *inlier, unsigned char *degenerate);
+int cora_multilaterate_robust(cora_ctx *ctx, double *X, int ldx, int gn_steps, double barc2, int min_consensus, int64_t out[6],
+                              unsigned char *status, double *cost_linear, double *cost_final, int32_t *chosen, int32_t *elected,
+                              int32_t *consensus, int32_t *list_len, unsigned char *inlier, unsigned char *degenerate);
+int cora_debug_multilaterate_robust_host(cora_ctx *ctx, double *X, int ldx, int gn_steps, double barc2, int min_consensus, int64_t out[6],
+                                         unsigned char *status, double *cost_linear, double *cost_final, int32_t *chosen, int32_t *elected,
+                                         int32_t *consensus, int32_t *list_len, unsigned char *inlier, unsigned char *degenerate);
+
 /* ---- CHAIN PLACEMENT FROM INTER-ROBOT RANGES, on the device ---------------------------------------------------------------
  * Moves whole odometry chains of a resident vector of d columns (the output of cora_odometry_init_dev: every chain
  * composed in its own frame) rigidly into the frame of the chains that are fixed, from the pose-pose ranges between

@@ -94,6 +94,7 @@ int cora_problem_variable_size(cora_problem *p, int64_t *rows);
  *                                                        seed 7: getOdomInitialization's start up to rounding)
  *  "rangeAidedInitialization" (none)             -> out   odometryInitialization with the landmarks placed from the ranges
  *                                                        (Problem::rangeAidedInitialization, seed 7, 5 Gauss-Newton steps)
+ *  "rangeAidedInitializationConsensus" (none)    -> out   the same with the multilateration's consensus vote (RangeConsensus{100, 0})
  *  "multiRobotInitialization" (none)             -> out   rangeAidedInitialization with the chains first placed from the ranges
  *                                                        between them (Problem::multiRobotInitialization, seed 7, 5 steps, default min_ranges)
  *  "sightingInitialization"   (none)             -> out   multiRobotInitialization with landmarks and chains first placed from the
@@ -117,6 +118,17 @@ int cora_problem_odometry_chains(const cora_problem *p, int64_t counts[2], int64
  * formulation the result is passed through checkVariablesAreValid (an error off the manifold). */
 int cora_problem_range_aided_initialization(cora_problem *p, uint64_t seed, int gn_steps, double *out, int64_t counts[4],
                                             unsigned char *status, double *cost_linear, double *cost_final);
+/* The same with the multilateration's consensus vote (RangeConsensus, CORA_problem.h; cora_multilaterate_robust_dev,
+ * include/cora_hip.h): consensus_barc2 <= 0 is off and has cora_problem_range_aided_initialization's bits; > 0: every range of a
+ * landmark's list proposes the point its sample of d + 1 ranges determines, the fit runs over the ranges that agree with the
+ * elected proposal, and a landmark whose elected proposal has fewer than min_consensus (<= 0: d + 2) votes has status 5 and keeps
+ * its random draw (it is among "not solved").  consensus_counts = { landmarks without consensus, ranges excluded };  consensus,
+ * list_len: one entry per landmark;  inlier: one byte per range measurement as added (1 inlier | 0 in a voted list, not an
+ * inlier | 2 in no voted list).  With the vote off the three arrays are not written.  Every array but out may be NULL. */
+int cora_problem_range_aided_initialization_consensus(cora_problem *p, uint64_t seed, int gn_steps, double consensus_barc2, int min_consensus,
+                                                      double *out, int64_t counts[4], unsigned char *status, double *cost_linear,
+                                                      double *cost_final, int64_t consensus_counts[2], int32_t *consensus, int32_t *list_len,
+                                                      unsigned char *inlier);
 /* Problem::multiRobotInitialization (an extension beyond the reference; include/cora_hip.h, "chain placement from
  * inter-robot ranges").  min_ranges <= 0: the default.  out: data-matrix-size x rank.  counts = { chains placed, not placed,
  * Gauss-Newton steps taken, stages }; status, cost_start, cost_linear, cost_final: one entry per chain of
