@@ -61,6 +61,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "../../include/cora_hip.h"
 #include "config.h"
 #include "cora_internal.h"
+#include "dispatch.h"
 #include "kernels.h"
 #include "long_image.h"
 #include "p2p.h"

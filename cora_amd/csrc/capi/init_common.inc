@@ -119,7 +119,7 @@ int with_host_x(cora_ctx *c, double *X, int ldx, const char *not_finite, HostRun
   std::vector<double> oi(static_cast<size_t>(L.rows) * d, 0.0);
   for (int cc = 0; cc < d; ++cc)
     for (int64_t i = 0; i < L.N; ++i) oi[static_cast<size_t>(F.api2int[i]) * d + cc] = X[static_cast<size_t>(cc) * ldx + i];
-  const bool finite = d == 2 ? host_run(std::integral_constant<int, 2>(), oi.data()) : host_run(std::integral_constant<int, 3>(), oi.data());
+  const bool finite = for_d(d, [&](auto D) { return host_run(D, oi.data()); });
   if (!finite) return fail(c, CORA_ERR_NAN, not_finite);
   for (int cc = 0; cc < d; ++cc)
     for (int64_t i = 0; i < L.N; ++i) X[static_cast<size_t>(cc) * ldx + i] = oi[static_cast<size_t>(F.api2int[i]) * d + cc];

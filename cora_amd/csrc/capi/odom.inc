@@ -297,7 +297,7 @@ int cora_odometry_set_range_rows_dev(cora_ctx *c, int64_t m, const int32_t *rang
     const double *dir = dirs + static_cast<size_t>(i) * d;
     double *u = unit.data() + static_cast<size_t>(i) * d;
     if (!all_finite(dir, static_cast<size_t>(d))) return fail(c, CORA_ERR_ARG, "direction " + std::to_string(i) + " is not finite");
-    const bool degenerate = d == 2 ? odom_range_row<2>(zero, dir, u) : odom_range_row<3>(zero, dir, u);
+    const bool degenerate = for_d(d, [&](auto D) { return odom_range_row<D()>(zero, dir, u); });
     if (degenerate || !all_finite(u, static_cast<size_t>(d))) return fail(c, CORA_ERR_ARG, "direction " + std::to_string(i) + " has no usable length");
   }
   // the rare path: the scatter of the exchange (k_move_rows) moves the rows; its two arrays live for this call only
@@ -329,8 +329,7 @@ int cora_debug_odometry_init_host(cora_ctx *c, const double *starts, const doubl
   const int d = L.d;
   std::vector<double> oi(static_cast<size_t>(L.rows) * d, 0.0);
   int64_t n_deg = 0;
-  const bool finite = d == 2 ? odom_host_run<2>(c, starts, landmarks, oi.data(), degenerate, &n_deg)
-                             : odom_host_run<3>(c, starts, landmarks, oi.data(), degenerate, &n_deg);
+  const bool finite = for_d(d, [&](auto D) { return odom_host_run<D()>(c, starts, landmarks, oi.data(), degenerate, &n_deg); });
   if (!finite) return fail(c, CORA_ERR_NAN, "a product of the odometry initialisation is not finite");
   for (int cc = 0; cc < d; ++cc)
     for (int64_t i = 0; i < L.N; ++i) Out[static_cast<size_t>(cc) * ldo + i] = oi[static_cast<size_t>(F.api2int[i]) * d + cc];

@@ -241,8 +241,7 @@ int cora_debug_round_host(cora_ctx *c, const double *Y, int ldy, int k, const do
   std::copy(basis ? basis : own, (basis ? basis : own) + k * d, vd);
   for (int i = 0; i < k * d; ++i) vd_dir[i] = std::ldexp(vd[i], e);
   int count = 0, flip = 0;
-  const bool finite = d == 2 ? round_host_units<2>(L, xi.data(), ldi, k, vd, vd_dir, oi.data(), &count, &flip)
-                             : round_host_units<3>(L, xi.data(), ldi, k, vd, vd_dir, oi.data(), &count, &flip);
+  const bool finite = for_d(d, [&](auto D) { return round_host_units<D()>(L, xi.data(), ldi, k, vd, vd_dir, oi.data(), &count, &flip); });
   if (!finite) return fail(c, CORA_ERR_NAN, "a product of the rounding is not finite");
   for (int cc = 0; cc < d; ++cc)
     for (int64_t i = 0; i < N; ++i) Out[static_cast<size_t>(cc) * ldo + i] = oi[static_cast<size_t>(F.api2int[i]) * d + cc];

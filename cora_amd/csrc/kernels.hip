@@ -14,6 +14,7 @@
 
 #include "config.h"
 #include "cora_internal.h"
+#include "dispatch.h"
 #include "kernels.h"
 
 // The file is compiled several times in parallel (cora_amd/build.py): CORA_TU selects the kernel families of a
@@ -44,7 +45,7 @@
 //   kernels/update_values.inc  in-place update of Q's values: check of the new values, gather passes                CORA_TU & 2
 //   kernels/assemble.inc  Q(w) from per-measurement weights through the term map: check, short and long entries     CORA_TU & 2
 //   kernels/tri.inc      the staged Cholesky solve: k_rowop, k_blockop, k_subblock                                 CORA_TU & 4
-//   kernels/launch.inc   host-side launch wrappers (kernels.h), per translation unit and row-stride group
+//   kernels/launch.inc   host-side launch wrappers (kernels.h), per translation unit and row-stride group; every choice of an instantiation goes through dispatch.h
 namespace cora {
 #include "kernels/common.inc"
 #include "kernels/spmm.inc"

@@ -1,10 +1,8 @@
 // Part of kernels.hip (included there, in this order, inside namespace cora).  host-side launch wrappers (kernels.h), per translation unit and row-stride group.
+// Which instantiation a runtime d, row stride, piece width, switch or mode selects is decided by the helpers of dispatch.h.
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-#define CORA_LD_CASES(M) \
-  M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15) M(16) M(17) M(18) M(19) M(20) M(21) M(22) M(23) M(24)
-
 static inline int grid_for(int64_t n, int per_block = 256, int cap = 2048) {
   int64_t g = (n + per_block - 1) / per_block;
   if (g < 1) g = 1;
@@ -12,12 +10,14 @@ static inline int grid_for(int64_t n, int per_block = 256, int cap = 2048) {
   return static_cast<int>(g);
 }
 
-#define CORA_LD_CASES_G0(M) M(2) M(3) M(4) M(5)
-#define CORA_LD_CASES_G1(M) M(6) M(7) M(8) M(9)
-#define CORA_LD_CASES_G2(M) M(10) M(11) M(12)
-#define CORA_LD_CASES_G3(M) M(13) M(14) M(15) M(16)
-#define CORA_LD_CASES_G4(M) M(17) M(18) M(19) M(20)
-#define CORA_LD_CASES_G5(M) M(21) M(22) M(23) M(24)
+// e = run(LD) for a stride of the row-stride group G (kLdGroups, dispatch.h) of a family (SpMM, staged solves); refused outside.
+// Each group's launcher is defined in the translation unit that instantiates the group's kernels (CORA_LDG bit G).
+template <int G, class Run>
+static hipError_t in_ld_group(int ld, Run run) {
+  hipError_t e = hipErrorInvalidValue;
+  for_ld<kLdGroups[G].first, kLdGroups[G].last>(ld, [&](auto LD) { e = run(LD); });
+  return e;
+}
 
 #if CORA_TU & 1
 template <int LD, int D>
@@ -45,20 +45,12 @@ static hipError_t launch_spmm_ld(const SpmmArgs &A_in, int epi, hipStream_t st) 
 }
 
 // one launcher per row-stride group, each in the translation unit that instantiates the group's kernels
-#define CASE(L)                                                      \
-  if (ld == L)                                                       \
-    return d == 2 ? launch_spmm_ld<L, 2>(A, epi, st) : launch_spmm_ld<L, 3>(A, epi, st);
-#define SPMM_GROUP(G)                                                                       \
-  hipError_t launch_spmm_g##G(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st) { \
-    CORA_LD_CASES_G##G(CASE)                                                                \
-    return hipErrorInvalidValue;                                                            \
-  }
-hipError_t launch_spmm_g0(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st);
-hipError_t launch_spmm_g1(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st);
-hipError_t launch_spmm_g2(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st);
-hipError_t launch_spmm_g3(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st);
-hipError_t launch_spmm_g4(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st);
-hipError_t launch_spmm_g5(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st);
+template <int G>
+static hipError_t spmm_group(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st) {
+  return in_ld_group<G>(ld, [&](auto LD) { return for_d(d, [&](auto D) { return launch_spmm_ld<LD(), D()>(A, epi, st); }); });
+}
+using SpmmGroupFn = hipError_t(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st);
+SpmmGroupFn launch_spmm_g0, launch_spmm_g1, launch_spmm_g2, launch_spmm_g3, launch_spmm_g4, launch_spmm_g5;
 #if CORA_LDG & 1
 // slices from which the pose slices read X through their LDS windows (kWinMinSlices; CORA_SPMM_WINDOW_MIN_SLICES or
 // cora_debug_spmm_window_min_slices: the tests run the window form of every row stride on small problems)
@@ -67,95 +59,77 @@ int g_win_min_slices = static_cast<int>(env_int(Env::SpmmWindowMinSlices));
 // cora_debug_spmm_stagger_ticks), and the tests' switch that applies it whatever the size and the row stride
 int g_spmm_stagger_ticks = spmm_stagger_clamp(env_int(Env::SpmmStaggerTicks));
 int g_spmm_stagger_force = 0;
-SPMM_GROUP(0)
+hipError_t launch_spmm_g0(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st) { return spmm_group<0>(A, ld, d, epi, st); }
 hipError_t launch_spmm(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st) {
-  if (ld <= 5) return launch_spmm_g0(A, ld, d, epi, st);
-  if (ld <= 9) return launch_spmm_g1(A, ld, d, epi, st);
-  if (ld <= 12) return launch_spmm_g2(A, ld, d, epi, st);
-  if (ld <= 16) return launch_spmm_g3(A, ld, d, epi, st);
-  if (ld <= 20) return launch_spmm_g4(A, ld, d, epi, st);
-  return launch_spmm_g5(A, ld, d, epi, st);
+  SpmmGroupFn *const group[kNumLdGroups] = {launch_spmm_g0, launch_spmm_g1, launch_spmm_g2, launch_spmm_g3, launch_spmm_g4, launch_spmm_g5};
+  const int g = ld_group_of(ld);
+  return g < kNumLdGroups ? group[g](A, ld, d, epi, st) : hipErrorInvalidValue;
 }
 #endif
 #if CORA_LDG & 2
-SPMM_GROUP(1)
+hipError_t launch_spmm_g1(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st) { return spmm_group<1>(A, ld, d, epi, st); }
 #endif
 #if CORA_LDG & 4
-SPMM_GROUP(2)
+hipError_t launch_spmm_g2(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st) { return spmm_group<2>(A, ld, d, epi, st); }
 #endif
 #if CORA_LDG & 8
-SPMM_GROUP(3)
+hipError_t launch_spmm_g3(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st) { return spmm_group<3>(A, ld, d, epi, st); }
 #endif
 #if CORA_LDG & 16
-SPMM_GROUP(4)
+hipError_t launch_spmm_g4(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st) { return spmm_group<4>(A, ld, d, epi, st); }
 #endif
 #if CORA_LDG & 32
-SPMM_GROUP(5)
+hipError_t launch_spmm_g5(const SpmmArgs &A, int ld, int d, int epi, hipStream_t st) { return spmm_group<5>(A, ld, d, epi, st); }
 #endif
-#undef SPMM_GROUP
-#undef CASE
 #endif  // CORA_TU & 1
 
 #if CORA_TU & 2
 
+// the grid of a row-unit kernel: 256 units (poses, range rows, translation rows) per block
+static inline int row_unit_blocks(const RowArgs &R) {
+  const int64_t units = static_cast<int64_t>(R.nl_poses) + R.nl_ranges + R.nl_trans;
+  return static_cast<int>((units + 255) / 256);
+}
+// launch(LD, D) of a row-unit kernel instantiated for the strides LO..HI; a stride outside is refused
+template <int LO, int HI, class Launch>
+static hipError_t launch_row_units(const RowArgs &R, int ld, Launch launch) {
+  const bool known = for_ld<LO, HI>(ld, [&](auto LD) { for_d(R.d, [&](auto D) { launch(LD, D); }); });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+
 hipError_t launch_point_finish(const RowArgs &R, int ld, const double *Y, const double *G,
                                double *rgrad, double *lam_st, double *lam_ob, const double *own_sym, double *S,
                                double *partial, int *nblocks, hipStream_t st) {
-  const int64_t units = static_cast<int64_t>(R.nl_poses) + R.nl_ranges + R.nl_trans;
-  const int grid = static_cast<int>((units + 255) / 256);
+  const int grid = row_unit_blocks(R);
   *nblocks = grid;
   if (grid == 0) return hipSuccess;
-#define CASE(L)                                                                               \
-  if (ld == L) {                                                                              \
-    if (R.d == 2) hipLaunchKernelGGL((k_point_finish<L, 2>), dim3(grid), dim3(256), 0, st, R, \
-                                     Y, G, rgrad, lam_st, lam_ob, own_sym, S, partial);       \
-    else hipLaunchKernelGGL((k_point_finish<L, 3>), dim3(grid), dim3(256), 0, st, R, Y, G,    \
-                            rgrad, lam_st, lam_ob, own_sym, S, partial);                      \
-    return hipGetLastError();                                                                 \
-  }
-  CORA_LD_CASES(CASE)
-#undef CASE
-  return hipErrorInvalidValue;
+  return launch_row_units<2, kMaxLD>(R, ld, [&](auto LD, auto D) {
+    hipLaunchKernelGGL((k_point_finish<LD(), D()>), dim3(grid), dim3(256), 0, st, R, Y, G, rgrad, lam_st, lam_ob, own_sym, S, partial);
+  });
 }
 
 hipError_t launch_tangent_project(const RowArgs &R, int ld, const double *Y, const double *V,
                                   const double *scale, double *out, hipStream_t st) {
-  const int64_t units = static_cast<int64_t>(R.nl_poses) + R.nl_ranges + R.nl_trans;
-  const int grid = static_cast<int>((units + 255) / 256);
+  const int grid = row_unit_blocks(R);
   if (grid == 0) return hipSuccess;
-#define CASE(L)                                                                                  \
-  if (ld == L) {                                                                                 \
-    if (R.d == 2) hipLaunchKernelGGL((k_tangent_project<L, 2>), dim3(grid), dim3(256), 0, st, R, \
-                                     Y, V, scale, out);                                          \
-    else hipLaunchKernelGGL((k_tangent_project<L, 3>), dim3(grid), dim3(256), 0, st, R, Y, V,    \
-                            scale, out);                                                         \
-    return hipGetLastError();                                                                    \
-  }
-  CORA_LD_CASES(CASE)
-#undef CASE
-  return hipErrorInvalidValue;
+  return launch_row_units<2, kMaxLD>(R, ld, [&](auto LD, auto D) {
+    hipLaunchKernelGGL((k_tangent_project<LD(), D()>), dim3(grid), dim3(256), 0, st, R, Y, V, scale, out);
+  });
 }
 
 hipError_t launch_project_manifold(const RowArgs &R, int ld, const double *A, const double *V,
                                    double alpha, double *out, hipStream_t st) {
-  const int64_t units = static_cast<int64_t>(R.nl_poses) + R.nl_ranges + R.nl_trans;
-  const int grid = static_cast<int>((units + 255) / 256);
+  const int grid = row_unit_blocks(R);
   if (grid == 0) return hipSuccess;
-#define CASE(L)                                                                                   \
-  if (ld == L) {                                                                                  \
-    if (R.d == 2) hipLaunchKernelGGL((k_project_manifold<L, 2>), dim3(grid), dim3(256), 0, st, R, \
-                                     A, V, alpha, out);                                           \
-    else hipLaunchKernelGGL((k_project_manifold<L, 3>), dim3(grid), dim3(256), 0, st, R, A, V,    \
-                            alpha, out);                                                          \
-    return hipGetLastError();                                                                     \
-  }
-  CORA_LD_CASES(CASE)
-#undef CASE
-  return hipErrorInvalidValue;
+  return launch_row_units<2, kMaxLD>(R, ld, [&](auto LD, auto D) {
+    hipLaunchKernelGGL((k_project_manifold<LD(), D()>), dim3(grid), dim3(256), 0, st, R, A, V, alpha, out);
+  });
 }
 
-static inline bool vec2_ok(int64_t n, const void *a, const void *b) {
-  return (n % 2 == 0) && (reinterpret_cast<uintptr_t>(a) % 16 == 0) && (reinterpret_cast<uintptr_t>(b) % 16 == 0);
+// n doubles as n / 2 double2: an even count and every pointer 16-byte aligned
+template <class... P>
+static inline bool vec2_ok(int64_t n, const P *...p) {
+  return n % 2 == 0 && ((reinterpret_cast<uintptr_t>(p) % 16 == 0) && ...);
 }
 
 hipError_t launch_axpby(int64_t n, double a, const double *x, double b, double *y, hipStream_t st) {
@@ -191,7 +165,7 @@ hipError_t launch_stpcg_direction(int64_t n, const StpcgState *S, const double *
 // D: mode / st / st_host / partial / ticket / seq fields set by the caller; n doubles, even, 16-byte aligned
 hipError_t launch_kappa_residual(const DotArgs &D_in, const double *kpartial, int nk, int64_t n, const double *Hp, double *r,
                                  hipStream_t st) {
-  if (n <= 0 || n % 2 || reinterpret_cast<uintptr_t>(Hp) % 16 || reinterpret_cast<uintptr_t>(r) % 16) return hipErrorInvalidValue;
+  if (n <= 0 || !vec2_ok(n, Hp, r)) return hipErrorInvalidValue;
   DotArgs D = D_in;
   D.count = 1;
   D.n2 = n / 2;
@@ -204,14 +178,14 @@ int kappa_residual_slots_blocks(int64_t n) { return grid_for(n / 2, 256, 256); }
 // rr_slot: kappa_residual_slots_blocks(n) doubles, one per block of the launch (added by an RvTail block)
 hipError_t launch_kappa_residual_slots(const StpcgState *S, const double *kpartial, int nk, int64_t n, const double *Hp, double *r,
                                        double *rr_slot, hipStream_t st) {
-  if (n <= 0 || n % 2 || reinterpret_cast<uintptr_t>(Hp) % 16 || reinterpret_cast<uintptr_t>(r) % 16) return hipErrorInvalidValue;
+  if (n <= 0 || !vec2_ok(n, Hp, r)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_kappa_residual_slots, dim3(kappa_residual_slots_blocks(n)), dim3(256), 0, st, S, kpartial, nk, n / 2,
                      reinterpret_cast<const double2 *>(Hp), reinterpret_cast<double2 *>(r), rr_slot);
   return hipGetLastError();
 }
 // D: mode / st / st_host / partial / ticket / seq fields set by the caller; n doubles, even, 16-byte aligned
 hipError_t launch_stpcg_residual(const DotArgs &D_in, int64_t n, const double *Hp, double *r, hipStream_t st) {
-  if (n <= 0 || n % 2 || reinterpret_cast<uintptr_t>(Hp) % 16 || reinterpret_cast<uintptr_t>(r) % 16) return hipErrorInvalidValue;
+  if (n <= 0 || !vec2_ok(n, Hp, r)) return hipErrorInvalidValue;
   DotArgs D = D_in;
   D.count = 1;
   D.n2 = n / 2;
@@ -232,9 +206,7 @@ hipError_t launch_stpcg_init(int64_t n, const double *g, const double *Pg, doubl
 }
 hipError_t launch_stpcg_step_direction(int64_t n, const StpcgState *S, const double *v, double *p, double *s,
                                        hipStream_t st) {
-  if (n <= 0 || n % 2 || reinterpret_cast<uintptr_t>(v) % 16 || reinterpret_cast<uintptr_t>(p) % 16 ||
-      reinterpret_cast<uintptr_t>(s) % 16)
-    return hipErrorInvalidValue;
+  if (n <= 0 || !vec2_ok(n, v, p, s)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_stpcg_step_direction, dim3(grid_for(n / 2)), dim3(256), 0, st, n / 2, S,
                      reinterpret_cast<const double2 *>(v), reinterpret_cast<double2 *>(p), reinterpret_cast<double2 *>(s));
   return hipGetLastError();
@@ -242,41 +214,23 @@ hipError_t launch_stpcg_step_direction(int64_t n, const StpcgState *S, const dou
 
 hipError_t launch_tangent_project_update(const RowArgs &R, const StpcgState *S, int ld, const double *Y, const double *X,
                                          double *p, double *s, hipStream_t st) {
-  const int64_t units = static_cast<int64_t>(R.nl_poses) + R.nl_ranges + R.nl_trans;
-  const int grid = static_cast<int>((units + 255) / 256);
+  const int grid = row_unit_blocks(R);
   if (grid == 0) return hipErrorInvalidValue;
-#define CASE(L)                                                                                            \
-  if (ld == L) {                                                                                           \
-    if (R.d == 2) hipLaunchKernelGGL((k_tangent_project_update<L, 2>), dim3(grid), dim3(256), 0, st, R, S, \
-                                     Y, X, p, s);                                                          \
-    else hipLaunchKernelGGL((k_tangent_project_update<L, 3>), dim3(grid), dim3(256), 0, st, R, S, Y, X,    \
-                            p, s);                                                                         \
-    return hipGetLastError();                                                                              \
-  }
-  CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12)
-#undef CASE
-  return hipErrorInvalidValue;
+  return launch_row_units<2, 12>(R, ld, [&](auto LD, auto D) {  // (the fused iteration's strides)
+    hipLaunchKernelGGL((k_tangent_project_update<LD(), D()>), dim3(grid), dim3(256), 0, st, R, S, Y, X, p, s);
+  });
 }
 
 // out = Proj_Y(V) and <r, out>; the partial array of D needs one slot per 256 row units
 hipError_t launch_tangent_project_dot(const RowArgs &R, const DotArgs &D_in, int ld, const double *Y, const double *V,
                                       const double *scale, const double *r, double *out, hipStream_t st) {
-  const int64_t units = static_cast<int64_t>(R.nl_poses) + R.nl_ranges + R.nl_trans;
-  const int grid = static_cast<int>((units + 255) / 256);
+  const int grid = row_unit_blocks(R);
   if (grid == 0) return hipErrorInvalidValue;
-  DotArgs D = D_in;
-  D.count = 1;
-#define CASE(L)                                                                                          \
-  if (ld == L) {                                                                                         \
-    if (R.d == 2) hipLaunchKernelGGL((k_tangent_project_dot<L, 2>), dim3(grid), dim3(256), 0, st, R, D,  \
-                                     Y, V, scale, r, out);                                               \
-    else hipLaunchKernelGGL((k_tangent_project_dot<L, 3>), dim3(grid), dim3(256), 0, st, R, D, Y, V,     \
-                            scale, r, out);                                                              \
-    return hipGetLastError();                                                                            \
-  }
-  CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12)
-#undef CASE
-  return hipErrorInvalidValue;
+  DotArgs Dot = D_in;
+  Dot.count = 1;
+  return launch_row_units<2, 12>(R, ld, [&](auto LD, auto D) {  // (the fused iteration's strides)
+    hipLaunchKernelGGL((k_tangent_project_dot<LD(), D()>), dim3(grid), dim3(256), 0, st, R, Dot, Y, V, scale, r, out);
+  });
 }
 
 hipError_t launch_scale_rows(int64_t rows, int ld, const double *scale, const double *x, double *y,
@@ -367,14 +321,7 @@ hipError_t launch_edge_residuals(const ResidualArgs &A, hipStream_t st) {
   if (A.n <= 0) return hipSuccess;
   if ((A.d != 2 && A.d != 3) || A.k < 1 || A.k > A.ld) return hipErrorInvalidValue;
   const dim3 grid(residual_blocks(A.n)), block(256);
-  const bool wide = A.ld % 2 == 0;
-  if (A.d == 2) {
-    if (wide) hipLaunchKernelGGL((k_edge_residuals<2, 2>), grid, block, 0, st, A);
-    else hipLaunchKernelGGL((k_edge_residuals<2, 1>), grid, block, 0, st, A);
-  } else {
-    if (wide) hipLaunchKernelGGL((k_edge_residuals<3, 2>), grid, block, 0, st, A);
-    else hipLaunchKernelGGL((k_edge_residuals<3, 1>), grid, block, 0, st, A);
-  }
+  for_d(A.d, [&](auto D) { for_width(A.ld, [&](auto W) { hipLaunchKernelGGL((k_edge_residuals<D(), W()>), grid, block, 0, st, A); }); });
   return hipGetLastError();
 }
 
@@ -382,8 +329,7 @@ hipError_t launch_range_residuals(const ResidualArgs &A, hipStream_t st) {
   if (A.n <= 0) return hipSuccess;
   if (A.k < 1 || A.k > A.ld) return hipErrorInvalidValue;
   const dim3 grid(residual_blocks(A.n)), block(256);
-  if (A.ld % 2 == 0) hipLaunchKernelGGL((k_range_residuals<2>), grid, block, 0, st, A);
-  else hipLaunchKernelGGL((k_range_residuals<1>), grid, block, 0, st, A);
+  for_width(A.ld, [&](auto W) { hipLaunchKernelGGL((k_range_residuals<W()>), grid, block, 0, st, A); });
   return hipGetLastError();
 }
 
@@ -393,14 +339,7 @@ hipError_t launch_gnc_edges(const GncArgs &A, hipStream_t st) {
   if (R.n <= 0) return hipSuccess;
   if ((R.d != 2 && R.d != 3) || R.k < 1 || R.k > R.ld) return hipErrorInvalidValue;
   const dim3 grid(residual_blocks(R.n)), block(256);
-  const bool wide = R.ld % 2 == 0;
-  if (R.d == 2) {
-    if (wide) hipLaunchKernelGGL((k_gnc_edges<2, 2>), grid, block, 0, st, A);
-    else hipLaunchKernelGGL((k_gnc_edges<2, 1>), grid, block, 0, st, A);
-  } else {
-    if (wide) hipLaunchKernelGGL((k_gnc_edges<3, 2>), grid, block, 0, st, A);
-    else hipLaunchKernelGGL((k_gnc_edges<3, 1>), grid, block, 0, st, A);
-  }
+  for_d(R.d, [&](auto D) { for_width(R.ld, [&](auto W) { hipLaunchKernelGGL((k_gnc_edges<D(), W()>), grid, block, 0, st, A); }); });
   return hipGetLastError();
 }
 
@@ -409,8 +348,7 @@ hipError_t launch_gnc_ranges(const GncArgs &A, hipStream_t st) {
   if (R.n <= 0) return hipSuccess;
   if (R.k < 1 || R.k > R.ld) return hipErrorInvalidValue;
   const dim3 grid(residual_blocks(R.n)), block(256);
-  if (R.ld % 2 == 0) hipLaunchKernelGGL((k_gnc_ranges<2>), grid, block, 0, st, A);
-  else hipLaunchKernelGGL((k_gnc_ranges<1>), grid, block, 0, st, A);
+  for_width(R.ld, [&](auto W) { hipLaunchKernelGGL((k_gnc_ranges<W()>), grid, block, 0, st, A); });
   return hipGetLastError();
 }
 
@@ -424,55 +362,37 @@ static bool compare_args_ok(const CompareArgs &A) {
   return (A.d == 2 || A.d == 3) && A.k >= 1 && A.k <= A.ldx && A.kr >= 1 && A.kr <= A.ldr && A.k <= kMaxLD && A.kr <= A.k &&
          A.n >= 0 && A.nt >= A.n && A.nr >= 0;
 }
-#define COMPARE_BY_WIDTH(kernel, grid)                                                         \
-  do {                                                                                          \
-    const bool wx = A.ldx % 2 == 0, wr = A.ldr % 2 == 0;                                        \
-    if (wx && wr) hipLaunchKernelGGL((kernel<2, 2>), dim3(grid), dim3(256), 0, st, A);          \
-    else if (wx) hipLaunchKernelGGL((kernel<2, 1>), dim3(grid), dim3(256), 0, st, A);           \
-    else if (wr) hipLaunchKernelGGL((kernel<1, 2>), dim3(grid), dim3(256), 0, st, A);           \
-    else hipLaunchKernelGGL((kernel<1, 1>), dim3(grid), dim3(256), 0, st, A);                   \
-  } while (0)
+// f(WX, WR): the piece widths of the strides of X and of the reference
+template <class Args, class F>
+static void for_widths(const Args &A, F f) {
+  for_width(A.ldx, [&](auto WX) { for_width(A.ldr, [&](auto WR) { f(WX, WR); }); });
+}
 hipError_t launch_compare_sums(const CompareArgs &A, hipStream_t st) {
   if (!compare_args_ok(A) || A.n < 1) return hipErrorInvalidValue;
-  COMPARE_BY_WIDTH(k_compare_sums, compare_blocks(A.n));
+  const dim3 grid(compare_blocks(A.n)), block(256);
+  for_widths(A, [&](auto WX, auto WR) { hipLaunchKernelGGL((k_compare_sums<WX(), WR()>), grid, block, 0, st, A); });
   return hipGetLastError();
 }
 hipError_t launch_compare_centre(const CompareArgs &A, hipStream_t st) {
   if (!compare_args_ok(A) || A.n < 1) return hipErrorInvalidValue;
-  COMPARE_BY_WIDTH(k_compare_centre, compare_blocks(A.n));
+  const dim3 grid(compare_blocks(A.n)), block(256);
+  for_widths(A, [&](auto WX, auto WR) { hipLaunchKernelGGL((k_compare_centre<WX(), WR()>), grid, block, 0, st, A); });
   return hipGetLastError();
 }
-#undef COMPARE_BY_WIDTH
 hipError_t launch_compare_errors(const CompareArgs &A, hipStream_t st) {
   if (!compare_args_ok(A) || A.nt < 1) return hipErrorInvalidValue;
   const dim3 grid(compare_blocks(static_cast<int64_t>(A.nt) + (A.aligned ? A.nr : 0))), block(256);
-  const bool wide = A.ldr % 2 == 0;
-  if (A.d == 2) {
-    if (wide) hipLaunchKernelGGL((k_compare_errors<2, 2>), grid, block, 0, st, A);
-    else hipLaunchKernelGGL((k_compare_errors<2, 1>), grid, block, 0, st, A);
-  } else {
-    if (wide) hipLaunchKernelGGL((k_compare_errors<3, 2>), grid, block, 0, st, A);
-    else hipLaunchKernelGGL((k_compare_errors<3, 1>), grid, block, 0, st, A);
-  }
+  for_d(A.d, [&](auto D) { for_width(A.ldr, [&](auto WR) { hipLaunchKernelGGL((k_compare_errors<D(), WR()>), grid, block, 0, st, A); }); });
   return hipGetLastError();
 }
 
 // the relative pose error (kernels/rpe.inc): grid sized by the count, piece widths by the parity of the two strides
-template <int D>
-static void launch_rpe_d(const RpeArgs &A, hipStream_t st) {
-  const dim3 grid(rpe_blocks(A.m)), block(256);
-  const bool wx = A.ldx % 2 == 0, wr = A.ldr % 2 == 0;
-  if (wx && wr) hipLaunchKernelGGL((k_rpe<D, 2, 2>), grid, block, 0, st, A);
-  else if (wx) hipLaunchKernelGGL((k_rpe<D, 2, 1>), grid, block, 0, st, A);
-  else if (wr) hipLaunchKernelGGL((k_rpe<D, 1, 2>), grid, block, 0, st, A);
-  else hipLaunchKernelGGL((k_rpe<D, 1, 1>), grid, block, 0, st, A);
-}
 hipError_t launch_rpe(const RpeArgs &A, hipStream_t st) {
   if ((A.d != 2 && A.d != 3) || A.k < 1 || A.k > A.ldx || A.kr < 1 || A.kr > A.ldr || A.ldx > kMaxLD || A.ldr > kMaxLD || A.m < 1 ||
       A.m > kRpeMaxPairs)
     return hipErrorInvalidValue;
-  if (A.d == 2) launch_rpe_d<2>(A, st);
-  else launch_rpe_d<3>(A, st);
+  const dim3 grid(rpe_blocks(A.m)), block(256);
+  for_d(A.d, [&](auto D) { for_widths(A, [&](auto WX, auto WR) { hipLaunchKernelGGL((k_rpe<D(), WX(), WR()>), grid, block, 0, st, A); }); });
   return hipGetLastError();
 }
 hipError_t launch_rpe_finish(const double *partial, int nblocks, int64_t m, double *stats, hipStream_t st) {
@@ -493,20 +413,16 @@ static bool round_args_ok(const RoundArgs &A) {
 hipError_t launch_round_count(const RoundArgs &A, hipStream_t st) {
   if (!round_args_ok(A)) return hipErrorInvalidValue;
   const int nb = round_count_blocks(A.R.nl_poses);
-  if (nb > 0) {
-    if (A.R.d == 2) hipLaunchKernelGGL(k_round_count<2>, dim3(nb), dim3(kRoundCountBlock), 0, st, A);
-    else hipLaunchKernelGGL(k_round_count<3>, dim3(nb), dim3(kRoundCountBlock), 0, st, A);
-  }
+  if (nb > 0)
+    for_d(A.R.d, [&](auto D) { hipLaunchKernelGGL(k_round_count<D()>, dim3(nb), dim3(kRoundCountBlock), 0, st, A); });
   hipLaunchKernelGGL(k_round_finish, dim3(1), dim3(64), 0, st, A.partial, nb, A.R.nl_poses, A.words);
   return hipGetLastError();
 }
 hipError_t launch_round_apply(const RoundArgs &A, hipStream_t st) {
   if (!round_args_ok(A)) return hipErrorInvalidValue;
-  const int64_t units = static_cast<int64_t>(A.R.nl_poses) + A.R.nl_ranges + A.R.nl_trans;
-  const int grid = static_cast<int>((units + 255) / 256);
+  const int grid = row_unit_blocks(A.R);
   if (grid == 0) return hipSuccess;
-  if (A.R.d == 2) hipLaunchKernelGGL(k_round_apply<2>, dim3(grid), dim3(256), 0, st, A);
-  else hipLaunchKernelGGL(k_round_apply<3>, dim3(grid), dim3(256), 0, st, A);
+  for_d(A.R.d, [&](auto D) { hipLaunchKernelGGL(k_round_apply<D()>, dim3(grid), dim3(256), 0, st, A); });
   return hipGetLastError();
 }
 // the odometry initialisation (kernels/odom.inc): the scan's three launches; the fill; the range rows with the sum of their counts
@@ -516,15 +432,11 @@ hipError_t launch_odom_scan(const OdomArgs &A, hipStream_t st) {
       !A.totals || !A.carry || !A.out || !A.flag || (A.n_edges > 0 && !A.edge_data))
     return hipErrorInvalidValue;
   const dim3 grid(A.ntiles), block(kOdomTile);
-  if (A.d == 2) {
-    hipLaunchKernelGGL(k_odom_totals<2>, grid, block, 0, st, A);
-    hipLaunchKernelGGL(k_odom_middle<2>, dim3(1), dim3(kOdomSweep), 0, st, A);
-    hipLaunchKernelGGL(k_odom_scan<2>, grid, block, 0, st, A);
-  } else {
-    hipLaunchKernelGGL(k_odom_totals<3>, grid, block, 0, st, A);
-    hipLaunchKernelGGL(k_odom_middle<3>, dim3(1), dim3(kOdomSweep), 0, st, A);
-    hipLaunchKernelGGL(k_odom_scan<3>, grid, block, 0, st, A);
-  }
+  for_d(A.d, [&](auto D) {
+    hipLaunchKernelGGL(k_odom_totals<D()>, grid, block, 0, st, A);
+    hipLaunchKernelGGL(k_odom_middle<D()>, dim3(1), dim3(kOdomSweep), 0, st, A);
+    hipLaunchKernelGGL(k_odom_scan<D()>, grid, block, 0, st, A);
+  });
   return hipGetLastError();
 }
 hipError_t launch_odom_fill(const OdomFillArgs &A, hipStream_t st) {
@@ -534,8 +446,7 @@ hipError_t launch_odom_fill(const OdomFillArgs &A, hipStream_t st) {
     return hipErrorInvalidValue;
   const int64_t grid = (units + 255) / 256;
   if (grid >= (int64_t(1) << 31)) return hipErrorInvalidValue;
-  if (A.d == 2) hipLaunchKernelGGL(k_odom_fill<2>, dim3(grid), dim3(256), 0, st, A);
-  else hipLaunchKernelGGL(k_odom_fill<3>, dim3(grid), dim3(256), 0, st, A);
+  for_d(A.d, [&](auto D) { hipLaunchKernelGGL(k_odom_fill<D()>, dim3(grid), dim3(256), 0, st, A); });
   return hipGetLastError();
 }
 hipError_t launch_odom_ranges(const OdomFillArgs &A, hipStream_t st) {
@@ -543,13 +454,30 @@ hipError_t launch_odom_ranges(const OdomFillArgs &A, hipStream_t st) {
   const int nb = odom_range_blocks(A.n_ranges);
   if (nb > 0) {
     if (!A.out || !A.range_rows || !A.deg || !A.flag) return hipErrorInvalidValue;
-    if (A.d == 2) hipLaunchKernelGGL(k_odom_ranges<2>, dim3(nb), dim3(kWave), 0, st, A);
-    else hipLaunchKernelGGL(k_odom_ranges<3>, dim3(nb), dim3(kWave), 0, st, A);
+    for_d(A.d, [&](auto D) { hipLaunchKernelGGL(k_odom_ranges<D()>, dim3(nb), dim3(kWave), 0, st, A); });
   }
   hipLaunchKernelGGL(k_round_finish, dim3(1), dim3(64), 0, st, A.partial, nb, 0, A.words);  // words[0] = the sum
   return hipGetLastError();
 }
-// the multilateration (kernels/multilat.inc): the pass over the chunks and the fold per landmark of one stage
+// the multilateration (kernels/multilat.inc): the pass over the chunks and the fold per landmark of one stage, plain or with
+// the masked passes of the robust form (whose Gauss-Newton fold is the plain one).  (The stage stands outside d: the linear
+// kernels of both d are instantiated before the Gauss-Newton ones, and keep their places in the code object.)
+template <bool ROBUST>
+static hipError_t multilat_pass_fold(const MlKernelArgs<ROBUST> &K, hipStream_t st) {
+  const MlArgs &A = ml_plain(K);
+  const dim3 chunks(static_cast<unsigned>(A.n_chunks)), lms(static_cast<unsigned>(A.n_lm));
+  if (A.stage == 0)
+    for_d(A.d, [&](auto D) {
+      if (A.n_chunks > 0) hipLaunchKernelGGL((k_ml_pass_linear<D(), ROBUST>), chunks, dim3(kMlChunk), 0, st, K);
+      hipLaunchKernelGGL((k_ml_fold_linear<D(), ROBUST>), lms, dim3(kWave), 0, st, A);
+    });
+  else
+    for_d(A.d, [&](auto D) {
+      if (A.n_chunks > 0) hipLaunchKernelGGL((k_ml_pass_gn<D(), ROBUST>), chunks, dim3(kMlChunk), 0, st, K);
+      hipLaunchKernelGGL(k_ml_fold_gn<D()>, lms, dim3(kWave), 0, st, A);
+    });
+  return hipGetLastError();
+}
 hipError_t launch_multilat_stage(const MlArgs &A, hipStream_t st) {
   if (A.n_lm <= 0) return hipSuccess;
   if ((A.d != 2 && A.d != 3) || A.stage < 0 || A.stage > kMlMaxSteps + 1 || (A.last && A.stage == 0) || A.n_chunks < 0 ||
@@ -557,26 +485,10 @@ hipError_t launch_multilat_stage(const MlArgs &A, hipStream_t st) {
       !A.state || !A.istate || !A.x || !A.flag ||
       (A.n_chunks > 0 && (!A.chunk_lm || !A.chunk_begin || !A.chunk_len || !A.ent_row || !A.ent_m || !A.range_data || !A.partial)))
     return hipErrorInvalidValue;
-  const dim3 chunks(static_cast<unsigned>(A.n_chunks)), lms(static_cast<unsigned>(A.n_lm));
-  if (A.stage == 0) {
-    if (A.d == 2) {
-      if (A.n_chunks > 0) hipLaunchKernelGGL(k_ml_pass_linear<2>, chunks, dim3(kMlChunk), 0, st, A);
-      hipLaunchKernelGGL(k_ml_fold_linear<2>, lms, dim3(kWave), 0, st, A);
-    } else {
-      if (A.n_chunks > 0) hipLaunchKernelGGL(k_ml_pass_linear<3>, chunks, dim3(kMlChunk), 0, st, A);
-      hipLaunchKernelGGL(k_ml_fold_linear<3>, lms, dim3(kWave), 0, st, A);
-    }
-  } else if (A.d == 2) {
-    if (A.n_chunks > 0) hipLaunchKernelGGL(k_ml_pass_gn<2>, chunks, dim3(kMlChunk), 0, st, A);
-    hipLaunchKernelGGL(k_ml_fold_gn<2>, lms, dim3(kWave), 0, st, A);
-  } else {
-    if (A.n_chunks > 0) hipLaunchKernelGGL(k_ml_pass_gn<3>, chunks, dim3(kMlChunk), 0, st, A);
-    hipLaunchKernelGGL(k_ml_fold_gn<3>, lms, dim3(kWave), 0, st, A);
-  }
-  return hipGetLastError();
+  return multilat_pass_fold<false>(A, st);
 }
 // the outlier-robust multilateration: the consensus vote (one workgroup per chunk of all lists, then one wavefront per list),
-// and a stage with the masked passes; the Gauss-Newton fold is the plain one
+// and a stage with the masked passes (every list has chunks: multilat_robust_args_ok)
 static bool multilat_robust_args_ok(const MlRobustArgs &R) {
   const MlArgs &A = R.A;
   return (A.d == 2 || A.d == 3) && A.n_lm > 0 && A.n_chunks > 0 && A.n_chunks < (int64_t(1) << 31) && A.n_lm < (int64_t(1) << 31) &&
@@ -587,35 +499,16 @@ static bool multilat_robust_args_ok(const MlRobustArgs &R) {
 hipError_t launch_multilat_vote_elect(const MlRobustArgs &R, hipStream_t st) {
   if (!multilat_robust_args_ok(R)) return hipErrorInvalidValue;
   const dim3 chunks(static_cast<unsigned>(R.A.n_chunks)), lms(static_cast<unsigned>(R.A.n_lm));
-  if (R.A.d == 2) {
-    hipLaunchKernelGGL(k_ml_vote<2>, chunks, dim3(kMlChunk), 0, st, R);
-    hipLaunchKernelGGL(k_ml_elect<2>, lms, dim3(kWave), 0, st, R);
-  } else {
-    hipLaunchKernelGGL(k_ml_vote<3>, chunks, dim3(kMlChunk), 0, st, R);
-    hipLaunchKernelGGL(k_ml_elect<3>, lms, dim3(kWave), 0, st, R);
-  }
+  for_d(R.A.d, [&](auto D) {
+    hipLaunchKernelGGL(k_ml_vote<D()>, chunks, dim3(kMlChunk), 0, st, R);
+    hipLaunchKernelGGL(k_ml_elect<D()>, lms, dim3(kWave), 0, st, R);
+  });
   return hipGetLastError();
 }
 hipError_t launch_multilat_robust_stage(const MlRobustArgs &R, hipStream_t st) {
   const MlArgs &A = R.A;
   if (!multilat_robust_args_ok(R) || A.stage < 0 || A.stage > kMlMaxSteps + 1 || (A.last && A.stage == 0)) return hipErrorInvalidValue;
-  const dim3 chunks(static_cast<unsigned>(A.n_chunks)), lms(static_cast<unsigned>(A.n_lm));
-  if (A.stage == 0) {
-    if (A.d == 2) {
-      hipLaunchKernelGGL((k_ml_pass_linear<2, true>), chunks, dim3(kMlChunk), 0, st, R);
-      hipLaunchKernelGGL((k_ml_fold_linear<2, true>), lms, dim3(kWave), 0, st, A);
-    } else {
-      hipLaunchKernelGGL((k_ml_pass_linear<3, true>), chunks, dim3(kMlChunk), 0, st, R);
-      hipLaunchKernelGGL((k_ml_fold_linear<3, true>), lms, dim3(kWave), 0, st, A);
-    }
-  } else if (A.d == 2) {
-    hipLaunchKernelGGL((k_ml_pass_gn<2, true>), chunks, dim3(kMlChunk), 0, st, R);
-    hipLaunchKernelGGL(k_ml_fold_gn<2>, lms, dim3(kWave), 0, st, A);
-  } else {
-    hipLaunchKernelGGL((k_ml_pass_gn<3, true>), chunks, dim3(kMlChunk), 0, st, R);
-    hipLaunchKernelGGL(k_ml_fold_gn<3>, lms, dim3(kWave), 0, st, A);
-  }
-  return hipGetLastError();
+  return multilat_pass_fold<true>(R, st);
 }
 // the chain placement (kernels/placement.inc): every launch serves the one stage A describes
 static bool place_args_ok(const PlArgs &A) {
@@ -626,48 +519,26 @@ static bool place_args_ok(const PlArgs &A) {
 hipError_t launch_place_linear(const PlArgs &A, hipStream_t st) {
   if (!place_args_ok(A)) return hipErrorInvalidValue;
   const dim3 chunks(static_cast<unsigned>(A.n_chunks));
-  if (A.d == 2) {
-    hipLaunchKernelGGL(k_pl_pass_linear<2>, chunks, dim3(kPlChunk), 0, st, A);
-    hipLaunchKernelGGL(k_pl_fold_linear<2>, dim3(1), dim3(kWave), 0, st, A);
-  } else {
-    hipLaunchKernelGGL(k_pl_pass_linear<3>, chunks, dim3(kPlChunk), 0, st, A);
-    hipLaunchKernelGGL(k_pl_fold_linear<3>, dim3(1), dim3(kWave), 0, st, A);
-  }
+  for_d(A.d, [&](auto D) {
+    hipLaunchKernelGGL(k_pl_pass_linear<D()>, chunks, dim3(kPlChunk), 0, st, A);
+    hipLaunchKernelGGL(k_pl_fold_linear<D()>, dim3(1), dim3(kWave), 0, st, A);
+  });
   return hipGetLastError();
 }
 hipError_t launch_place_gn(const PlArgs &A, hipStream_t st) {
   if (!place_args_ok(A) || A.step < 0 || A.step > kPlMaxSteps + 1) return hipErrorInvalidValue;
   const dim3 chunks(static_cast<unsigned>(A.n_chunks));
-  if (A.d == 2) {
-    hipLaunchKernelGGL(k_pl_pass_gn<2>, chunks, dim3(kPlChunk), 0, st, A);
-    hipLaunchKernelGGL(k_pl_fold_gn<2>, dim3(1), dim3(kWave), 0, st, A);
-  } else {
-    hipLaunchKernelGGL(k_pl_pass_gn<3>, chunks, dim3(kPlChunk), 0, st, A);
-    hipLaunchKernelGGL(k_pl_fold_gn<3>, dim3(1), dim3(kWave), 0, st, A);
-  }
+  for_d(A.d, [&](auto D) {
+    hipLaunchKernelGGL(k_pl_pass_gn<D()>, chunks, dim3(kPlChunk), 0, st, A);
+    hipLaunchKernelGGL(k_pl_fold_gn<D()>, dim3(1), dim3(kWave), 0, st, A);
+  });
   return hipGetLastError();
 }
 hipError_t launch_place_apply(const PlArgs &A, hipStream_t st) {
   if (!place_args_ok(A)) return hipErrorInvalidValue;
   const dim3 grid(static_cast<unsigned>((A.n_pos + 255) / 256));
-  if (A.d == 2) hipLaunchKernelGGL(k_pl_apply<2>, grid, dim3(256), 0, st, A);
-  else hipLaunchKernelGGL(k_pl_apply<3>, grid, dim3(256), 0, st, A);
+  for_d(A.d, [&](auto D) { hipLaunchKernelGGL(k_pl_apply<D()>, grid, dim3(256), 0, st, A); });
   return hipGetLastError();
-}
-// f(integral_constant D, integral_constant MODE) for the d (2 | 3) and the mode (0 .. MODES - 1, MODES 2 | 4; both checked by the
-// caller) of a call
-template <int MODES, class F>
-static void for_d_and_mode(int d, int mode, F f) {
-  auto with_d = [&](auto D) {
-    if (mode == 0) f(D, std::integral_constant<int, 0>());
-    else if (mode == 1) f(D, std::integral_constant<int, 1>());
-    else if constexpr (MODES == 4) {
-      if (mode == 2) f(D, std::integral_constant<int, 2>());
-      else f(D, std::integral_constant<int, 3>());
-    }
-  };
-  if (d == 2) with_d(std::integral_constant<int, 2>());
-  else with_d(std::integral_constant<int, 3>());
 }
 // the placement from sightings (kernels/sighting.inc): every launch serves all lists of the one stage A describes
 static bool sighting_args_ok(const SgArgs &A) {
@@ -677,9 +548,11 @@ static bool sighting_args_ok(const SgArgs &A) {
 }
 hipError_t launch_sighting_pass_fold(const SgArgs &A, hipStream_t st) {
   if (!sighting_args_ok(A) || A.mode < 0 || A.mode > 3) return hipErrorInvalidValue;
-  for_d_and_mode<4>(A.d, A.mode, [&](auto D, auto MODE) {
-    hipLaunchKernelGGL((k_sg_pass<D(), MODE()>), dim3(static_cast<unsigned>(A.n_chunks)), dim3(kSgChunk), 0, st, A);
-    hipLaunchKernelGGL((k_sg_fold<D(), MODE()>), dim3(static_cast<unsigned>(A.n_lists)), dim3(kWave), 0, st, A);
+  for_d(A.d, [&](auto D) {
+    for_mode<4>(A.mode, [&](auto MODE) {
+      hipLaunchKernelGGL((k_sg_pass<D(), MODE()>), dim3(static_cast<unsigned>(A.n_chunks)), dim3(kSgChunk), 0, st, A);
+      hipLaunchKernelGGL((k_sg_fold<D(), MODE()>), dim3(static_cast<unsigned>(A.n_lists)), dim3(kWave), 0, st, A);
+    });
   });
   return hipGetLastError();
 }
@@ -690,8 +563,7 @@ static hipError_t chain_apply(const Args &A, hipStream_t st) {
   if (A.n_apply <= 0 || A.apply0 < 0 || !A.apply_pos || !A.apply_list || !A.pos_rot || !A.pos_trn) return hipErrorInvalidValue;
   const SgApplyArgs G{A.d, A.apply0, A.n_apply, A.apply_pos, A.apply_list, A.pos_rot, A.pos_trn, A.state, A.istate, A.x};
   const dim3 grid(static_cast<unsigned>((A.n_apply + 255) / 256));
-  if (A.d == 2) hipLaunchKernelGGL(k_sg_apply<2>, grid, dim3(256), 0, st, G);
-  else hipLaunchKernelGGL(k_sg_apply<3>, grid, dim3(256), 0, st, G);
+  for_d(A.d, [&](auto D) { hipLaunchKernelGGL(k_sg_apply<D()>, grid, dim3(256), 0, st, G); });
   return hipGetLastError();
 }
 hipError_t launch_sighting_apply(const SgArgs &A, hipStream_t st) { return sighting_args_ok(A) ? chain_apply(A, st) : hipErrorInvalidValue; }
@@ -708,9 +580,11 @@ template <bool ROBUST>
 static hipError_t closure_pass_fold(const ClKernelArgs<ROBUST> &K, hipStream_t st) {
   const ClArgs &A = cl_plain(K);
   if (!closure_args_ok(K) || A.mode < 0 || A.mode > 1) return hipErrorInvalidValue;
-  for_d_and_mode<2>(A.d, A.mode, [&](auto D, auto MODE) {
-    hipLaunchKernelGGL((k_cl_pass<D(), MODE(), ROBUST>), dim3(static_cast<unsigned>(A.n_chunks)), dim3(kClChunk), 0, st, K);
-    hipLaunchKernelGGL((k_cl_fold<D(), MODE(), ROBUST>), dim3(static_cast<unsigned>(A.n_lists)), dim3(kWave), 0, st, K);
+  for_d(A.d, [&](auto D) {
+    for_mode<2>(A.mode, [&](auto MODE) {
+      hipLaunchKernelGGL((k_cl_pass<D(), MODE(), ROBUST>), dim3(static_cast<unsigned>(A.n_chunks)), dim3(kClChunk), 0, st, K);
+      hipLaunchKernelGGL((k_cl_fold<D(), MODE(), ROBUST>), dim3(static_cast<unsigned>(A.n_lists)), dim3(kWave), 0, st, K);
+    });
   });
   return hipGetLastError();
 }
@@ -721,13 +595,10 @@ hipError_t launch_closure_apply(const ClArgs &A, hipStream_t st) { return closur
 hipError_t launch_closure_vote_elect(const ClRobustArgs &R, hipStream_t st) {
   if (!closure_args_ok(R)) return hipErrorInvalidValue;
   const dim3 chunks(static_cast<unsigned>(R.A.n_chunks)), lists(static_cast<unsigned>(R.A.n_lists));
-  if (R.A.d == 2) {
-    hipLaunchKernelGGL(k_cl_vote<2>, chunks, dim3(kClChunk), 0, st, R);
-    hipLaunchKernelGGL(k_cl_elect<2>, lists, dim3(kWave), 0, st, R);
-  } else {
-    hipLaunchKernelGGL(k_cl_vote<3>, chunks, dim3(kClChunk), 0, st, R);
-    hipLaunchKernelGGL(k_cl_elect<3>, lists, dim3(kWave), 0, st, R);
-  }
+  for_d(R.A.d, [&](auto D) {
+    hipLaunchKernelGGL(k_cl_vote<D()>, chunks, dim3(kClChunk), 0, st, R);
+    hipLaunchKernelGGL(k_cl_elect<D()>, lists, dim3(kWave), 0, st, R);
+  });
   return hipGetLastError();
 }
 hipError_t launch_round_amax(int64_t n, const double *y, double *partial, int nblocks, int *flag, hipStream_t st) {
@@ -753,8 +624,7 @@ hipError_t launch_values_gather(int64_t n, const int32_t *src, const double *val
                                 hipStream_t st) {
   if (n <= 0) return hipSuccess;
   const dim3 grid(grid_for((n + 1) / 2)), block(256);
-  if (reciprocal) hipLaunchKernelGGL((k_values_gather<true>), grid, block, 0, st, n, src, vals, dst);
-  else hipLaunchKernelGGL((k_values_gather<false>), grid, block, 0, st, n, src, vals, dst);
+  for_bool(reciprocal, [&](auto RECIPROCAL) { hipLaunchKernelGGL((k_values_gather<RECIPROCAL()>), grid, block, 0, st, n, src, vals, dst); });
   return hipGetLastError();
 }
 
@@ -804,8 +674,7 @@ template <int LD>
 static hipError_t blockop_ld(const BlockOpDev &B, bool backward, const double *src, double *dst, hipStream_t st) {
   const int grid = (B.nblocks + 3) >> 2;
   if (grid <= 0) return hipSuccess;
-  if (backward) hipLaunchKernelGGL((k_blockop<LD, true>), dim3(grid), dim3(256), 0, st, B, src, dst);
-  else hipLaunchKernelGGL((k_blockop<LD, false>), dim3(grid), dim3(256), 0, st, B, src, dst);
+  for_bool(backward, [&](auto BACKWARD) { hipLaunchKernelGGL((k_blockop<LD, BACKWARD()>), dim3(grid), dim3(256), 0, st, B, src, dst); });
   return hipGetLastError();
 }
 
@@ -824,29 +693,28 @@ static hipError_t subblock_ld(const SubOpDev &S, bool backward, const double *sr
   if (F) {
     // the fused sweeps exist where cora_stpcg_dev dispatches them (row stride x d <= 24: above, the fused backward sweep
     // spills -- 172 to 380 bytes of scratch per lane at row strides 10-12 with d = 3 -- and was never launched)
+    // the sweep's third template argument: 1 forward, d backward
     if (!backward) {
       if constexpr (LD <= 12) hipLaunchKernelGGL((k_subblock<LD, false, 1>), g, t, lds, st, S, src, work, dst, *F);
       else return hipErrorInvalidValue;
-    } else if (F->d == 2) {
-      if constexpr (LD <= 12) hipLaunchKernelGGL((k_subblock<LD, true, 2>), g, t, lds, st, S, src, work, dst, *F);
-      else return hipErrorInvalidValue;
-    } else if (F->d == 3) {
-      if constexpr (LD <= 8) hipLaunchKernelGGL((k_subblock<LD, true, 3>), g, t, lds, st, S, src, work, dst, *F);
-      else return hipErrorInvalidValue;
-    } else {
-      return hipErrorInvalidValue;
+      return hipGetLastError();
     }
-    return hipGetLastError();
+    if (F->d != 2 && F->d != 3) return hipErrorInvalidValue;
+    return for_d(F->d, [&](auto D) {
+      if constexpr (LD * D() <= 24) {
+        hipLaunchKernelGGL((k_subblock<LD, true, D()>), g, t, lds, st, S, src, work, dst, *F);
+        return hipGetLastError();
+      } else {
+        return hipErrorInvalidValue;
+      }
+    });
   }
   const SubFuse none{};
-  if (backward) {
-    if (const hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_subblock<LD, true, 0>)); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_subblock<LD, true, 0>), g, t, lds, st, S, src, work, dst, none);
-  } else {
-    if (const hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_subblock<LD, false, 0>)); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_subblock<LD, false, 0>), g, t, lds, st, S, src, work, dst, none);
-  }
-  return hipGetLastError();
+  return for_bool(backward, [&](auto BACKWARD) {
+    if (const hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_subblock<LD, BACKWARD(), 0>)); e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_subblock<LD, BACKWARD(), 0>), g, t, lds, st, S, src, work, dst, none);
+    return hipGetLastError();
+  });
 }
 
 // one set of launchers per row-stride group, each in the translation unit that instantiates the group's kernels
@@ -862,48 +730,38 @@ struct TriCall {  // what a staged-solve launch needs, whichever kernel it is
   double *work, *dst;
   const RvTail *tail = nullptr;
 };
-#define CASE(L)                                                                                       \
-  if (c.ld == L) {                                                                                    \
-    if (c.kind == 0) return blockop_ld<L>(*c.B, c.backward, c.a, c.dst, st);                          \
-    if (c.kind == 1) return rowop_ld<L>(*c.R, c.a, c.b, c.dst, st, c.tail);                           \
-    if (c.kind == 2) return subblock_ld<L>(*c.S, c.backward, c.a, c.work, c.dst, st);                 \
-    return subblock_ld<L>(*c.S, c.backward, c.a, c.work, c.dst, st, c.F);                             \
-  }
-#define TRI_GROUP(G)                                             \
-  hipError_t launch_tri_g##G(const TriCall &c, hipStream_t st) { \
-    CORA_LD_CASES_G##G(CASE)                                     \
-    return hipErrorInvalidValue;                                 \
-  }
-hipError_t launch_tri_g0(const TriCall &c, hipStream_t st);
-hipError_t launch_tri_g1(const TriCall &c, hipStream_t st);
-hipError_t launch_tri_g2(const TriCall &c, hipStream_t st);
-hipError_t launch_tri_g3(const TriCall &c, hipStream_t st);
-hipError_t launch_tri_g4(const TriCall &c, hipStream_t st);
-hipError_t launch_tri_g5(const TriCall &c, hipStream_t st);
+template <int G>
+static hipError_t tri_group(const TriCall &c, hipStream_t st) {
+  return in_ld_group<G>(c.ld, [&](auto LD) {
+    if (c.kind == 0) return blockop_ld<LD()>(*c.B, c.backward, c.a, c.dst, st);
+    if (c.kind == 1) return rowop_ld<LD()>(*c.R, c.a, c.b, c.dst, st, c.tail);
+    if (c.kind == 2) return subblock_ld<LD()>(*c.S, c.backward, c.a, c.work, c.dst, st);
+    return subblock_ld<LD()>(*c.S, c.backward, c.a, c.work, c.dst, st, c.F);
+  });
+}
+using TriGroupFn = hipError_t(const TriCall &c, hipStream_t st);
+TriGroupFn launch_tri_g0, launch_tri_g1, launch_tri_g2, launch_tri_g3, launch_tri_g4, launch_tri_g5;
 #if CORA_LDG & 2
-TRI_GROUP(1)
+hipError_t launch_tri_g1(const TriCall &c, hipStream_t st) { return tri_group<1>(c, st); }
 #endif
 #if CORA_LDG & 4
-TRI_GROUP(2)
+hipError_t launch_tri_g2(const TriCall &c, hipStream_t st) { return tri_group<2>(c, st); }
 #endif
 #if CORA_LDG & 8
-TRI_GROUP(3)
+hipError_t launch_tri_g3(const TriCall &c, hipStream_t st) { return tri_group<3>(c, st); }
 #endif
 #if CORA_LDG & 16
-TRI_GROUP(4)
+hipError_t launch_tri_g4(const TriCall &c, hipStream_t st) { return tri_group<4>(c, st); }
 #endif
 #if CORA_LDG & 32
-TRI_GROUP(5)
+hipError_t launch_tri_g5(const TriCall &c, hipStream_t st) { return tri_group<5>(c, st); }
 #endif
 #if CORA_LDG & 1
-TRI_GROUP(0)
+hipError_t launch_tri_g0(const TriCall &c, hipStream_t st) { return tri_group<0>(c, st); }
 static hipError_t launch_tri(const TriCall &c, hipStream_t st) {
-  if (c.ld <= 5) return launch_tri_g0(c, st);
-  if (c.ld <= 9) return launch_tri_g1(c, st);
-  if (c.ld <= 12) return launch_tri_g2(c, st);
-  if (c.ld <= 16) return launch_tri_g3(c, st);
-  if (c.ld <= 20) return launch_tri_g4(c, st);
-  return launch_tri_g5(c, st);
+  TriGroupFn *const group[kNumLdGroups] = {launch_tri_g0, launch_tri_g1, launch_tri_g2, launch_tri_g3, launch_tri_g4, launch_tri_g5};
+  const int g = ld_group_of(c.ld);
+  return g < kNumLdGroups ? group[g](c, st) : hipErrorInvalidValue;
 }
 hipError_t launch_blockop(const BlockOpDev &B, int ld, bool backward, const double *src, double *dst, hipStream_t st) {
   return launch_tri(TriCall{0, ld, backward, &B, nullptr, nullptr, nullptr, src, nullptr, nullptr, dst}, st);
@@ -930,8 +788,6 @@ hipError_t launch_zero_row(double *x, size_t row, int ld, hipStream_t st) {
   return hipGetLastError();
 }
 #endif  // CORA_LDG & 1
-#undef TRI_GROUP
-#undef CASE
 
 #endif  // CORA_TU & 4
 #if CORA_TU & 2

@@ -61,6 +61,21 @@ def test_device_against_the_reference_and_the_host_mirror(d, n):
         against_host_mirror(dev, ctx.debug_rpe_host(X, Ref), len(pairs), what)
 
 
+def test_even_stride_against_an_odd_reference_stride_in_the_plane():
+    """d = 2 with 16-byte pieces of X and 8-byte pieces of the reference: k = 4 against kr = 3, the one pair of piece widths
+    that rpe_ref.RANKS(2) does not hold (its reference strides 2 and 24 are even, and 5 goes with k = 5)."""
+    d, n = 2, 30
+    ctx, dims, truth, chains = built(d, n)
+    rng = np.random.default_rng(43)
+    pairs = np.concatenate([rp.pairs_by_step(chains, 1)[0], rp.pairs_by_step(chains, 7)[0], [[0, 0], [n - 1, 0]]]).astype(np.int32)
+    ctx.set_pose_pairs(pairs)
+    Ref = rp.reference_of_rank(truth, 3, rng)
+    X = estimate(Ref, truth, dims, 4, rng)
+    dev = ctx.rpe(X, Ref)
+    rp.check(dev, X, Ref, *dims, pairs, what="d=2 k=4 kr=3")
+    against_host_mirror(dev, ctx.debug_rpe_host(X, Ref), len(pairs), "d=2 k=4 kr=3")
+
+
 @pytest.mark.parametrize("d", [2, 3])
 def test_launch_edges_resident_vectors_and_table_replacement(d):
     """m = 1, 31, 32, 33 (one block, its last group, a second block of one pair), 2 945 pairs (93 blocks of partials: more
