@@ -94,7 +94,26 @@ const char *cora_last_error(const cora_ctx *ctx);
 int cora_set_rank(cora_ctx *ctx, int p);
 int cora_get_rank(const cora_ctx *ctx);
 
-/* Use an externally created hipStream_t (e.g. torch's current stream). */
+/* Use an externally created hipStream_t (e.g. torch's current stream) for everything the handle enqueues from now on.
+ * The contract, pinned on the GPU by tests/test_gpu_streams.py:
+ *   - the call first waits on the host for the handle's old stream, so work pending there has finished when it returns and
+ *     a later call on the new stream may read its results; the handle's own stream (the one it was created with) is
+ *     destroyed then, a caller's stream never is -- not by a later cora_set_stream, not by cora_ctx_destroy, which waits
+ *     for the handle's pending work and leaves the stream usable.  The caller keeps the stream alive while the handle
+ *     uses it.  On a handle without a device: CORA_ERR_HIP.
+ *   - hip_stream = NULL, the legacy default stream 0, is allowed (it is what torch's default current stream is).
+ *   - ordering: whatever a call enqueues is ordered AFTER the work already on that stream when the call is made (the
+ *     caller's own kernels and copies included: operands may still be in the making, with no host wait) and BEFORE the work
+ *     the caller enqueues after the call returns.  That covers the handle's state: the current point, a kept trial product,
+ *     scratch, and vectors of cora_dev_alloc (zeroed on the stream, also when recycled) -- all survive a move.
+ *   - which calls wait on the host: those that return values to the host -- cora_dots_dev, cora_dot_dev, cora_gram_dev,
+ *     cora_gram_batch_dev, cora_objective_dev, cora_tnt_trial_dev, cora_tnt_accept_dev, cora_stpcg_dev and its warm form,
+ *     cora_set_point_dev (the cost), cora_gnc_weights_dev, the evaluation calls and the initialisers, cora_upload,
+ *     cora_download, cora_timer_stop_ms, cora_sync -- return when the stream has reached them, so they also wait for the
+ *     caller's earlier work on it.  Calls that only write device vectors (products, row operations, the projected
+ *     preconditioner, cora_copy_dev, cora_fill_random_dev) return as soon as their work is enqueued.
+ *   - not supported: the opt-in graph replay of the inner solve (CORA_STPCG_GRAPH) on stream 0 -- a stream capture on the
+ *     legacy default stream is not legal HIP.  Use a created stream with it. */
 int cora_set_stream(cora_ctx *ctx, void *hip_stream);
 
 /* Layout queries for the `_dev` API. */

@@ -133,3 +133,15 @@ def test_error_paths():
     assert e.value.code == 4
     with pytest.raises(capi.CoraError):
         ctx.debug_measurement_residuals_host(np.zeros((dm.N, 25)))
+
+
+def test_set_stream_needs_a_device():
+    """cora_set_stream on a plan-only handle: CORA_ERR_HIP, for a stream and for stream 0, and the handle stays usable."""
+    g = make_graph(d=2, n=12, n_landmarks=2, n_ranges=6, n_loops=1)
+    ctx, dm = _ctx(g)
+    for stream in (0, 0x1000):
+        with pytest.raises(capi.CoraError) as e:
+            ctx.set_stream(stream)
+        assert e.value.code == 4
+    ctx.set_measurements(*rr.table(g))
+    assert ctx.measurement_counts() == (len(rr.edges(g)), len(g.ranges))
