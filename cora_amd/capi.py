@@ -1245,6 +1245,49 @@ class Context:
         """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
         return self._sg_call(lambda *a: self.L.cora_place_by_sightings_dev(self.h, C.c_void_p(x_ptr), *a))
 
+    # ---- outlier-robust placement from sightings (include/cora_hip.h, cora_place_by_sightings_robust_dev)
+    def _sgr_call(self, fn, barc2, min_chain_consensus, min_landmark_consensus):
+        nch, (ne, nr), g, nl = self.odometry_chains_count()[0], self.measurement_counts()[:2], self.d * self.d + self.d, self.nt - self.n
+        if min_chain_consensus is None or min_chain_consensus <= 0:
+            min_chain_consensus = self.d + 1
+        out = (C.c_int64 * 10)()
+        status, chosen = np.zeros(nch + 1, dtype=np.uint8), np.zeros(nch + 1, dtype=np.int32)
+        cs, cf, tr = np.zeros(nch + 1), np.zeros(nch + 1), np.zeros((nch + 1) * g)
+        ls, lc = np.zeros(nl + 1, dtype=np.uint8), np.zeros(nl + 1)
+        deg = np.zeros(nr + 1, dtype=np.uint8)
+        cc, cl = np.zeros(nch + 1, dtype=np.int32), np.zeros(nch + 1, dtype=np.int32)
+        lcn, ll = np.zeros(nl + 1, dtype=np.int32), np.zeros(nl + 1, dtype=np.int32)
+        ic, il = np.zeros(ne + 1, dtype=np.uint8), np.zeros(ne + 1, dtype=np.uint8)
+        self._chk(fn(C.c_double(barc2), int(min_chain_consensus), int(min_landmark_consensus), out, status.ctypes.data_as(C.c_void_p), _d(cs),
+                     _d(cf), chosen.ctypes.data_as(_ip), _d(tr), ls.ctypes.data_as(C.c_void_p), _d(lc), deg.ctypes.data_as(C.c_void_p),
+                     cc.ctypes.data_as(_ip), cl.ctypes.data_as(_ip), lcn.ctypes.data_as(_ip), ll.ctypes.data_as(_ip),
+                     ic.ctypes.data_as(C.c_void_p), il.ctypes.data_as(C.c_void_p)))
+        return dict(placed=int(out[0]), not_placed=int(out[1]), landmarks_placed=int(out[2]), landmarks_not_placed=int(out[3]),
+                    n_degenerate=int(out[4]), stages=int(out[5]), chains_no_consensus=int(out[6]), landmarks_no_consensus=int(out[7]),
+                    chain_excluded=int(out[8]), landmark_excluded=int(out[9]), status=status[:nch], cost_start=cs[:nch], cost_final=cf[:nch],
+                    chosen=chosen[:nch], transforms=tr[:nch * g].reshape(nch, g), landmark_status=ls[:nl], landmark_cost=lc[:nl],
+                    degenerate=deg[:nr].astype(bool), chain_consensus=cc[:nch], chain_list_len=cl[:nch], landmark_consensus=lcn[:nl],
+                    landmark_list_len=ll[:nl], inlier_chain=ic[:ne], inlier_landmark=il[:ne])
+
+    def place_by_sightings_robust(self, X, barc2, min_chain_consensus=0, min_landmark_consensus=1):
+        """place_by_sightings with a consensus vote in front of every fit: every sighting of a list proposes (a landmark at
+        its own prediction; a chain motion from a sample of d sightings), the proposal most sightings agree with (tau |.|^2 <=
+        barc2) is elected and the fit runs over the agreeing sightings only.  min_chain_consensus <= 0: d + 1.  Returns
+        place_by_sightings' dict plus chain_consensus, chain_list_len (per chain), landmark_consensus, landmark_list_len (per
+        landmark, the REFIT's), inlier_chain, inlier_landmark (per edge of the measurement table: 1 | 0 | 2 in no list),
+        chains_no_consensus, landmarks_no_consensus (status 5) and chain_excluded, landmark_excluded (entries outside the inliers)."""
+        return self._with_host_X(self._sgr_call, self.L.cora_place_by_sightings_robust, X, barc2, min_chain_consensus, min_landmark_consensus)
+
+    def debug_place_by_sightings_robust_host(self, X, barc2, min_chain_consensus=0, min_landmark_consensus=1):
+        """The same on the host in the device's bracket order (no GPU needed): the device's bits."""
+        return self._with_host_X(self._sgr_call, self.L.cora_debug_place_by_sightings_robust_host, X, barc2, min_chain_consensus,
+                                 min_landmark_consensus)
+
+    def place_by_sightings_robust_dev(self, x_ptr, barc2, min_chain_consensus=0, min_landmark_consensus=1):
+        """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
+        return self._sgr_call(lambda *a: self.L.cora_place_by_sightings_robust_dev(self.h, C.c_void_p(x_ptr), *a), barc2, min_chain_consensus,
+                              min_landmark_consensus)
+
     # ---- placement from inter-chain relative-pose edges (include/cora_hip.h, cora_place_by_closures_dev)
     def set_closure_placement(self, chain_fixed=None, min_closures=1):
         """Orders the odometry chains into stages from the relative-pose edges between chains: chain_fixed a mask per chain

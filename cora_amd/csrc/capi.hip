@@ -250,7 +250,13 @@ struct SgTables {
   double *d_partial = nullptr;   // [kSgMaxSums(d)][chunks]
   double *d_state = nullptr;     // [lists][kSgState(d)]
   int32_t *d_istate = nullptr;   // [lists][kSgInts]
-  void release() { free_device(d_idx, d_partial, d_state, d_istate); }
+  // the consensus vote's (cora_place_by_sightings_robust_dev): scratch of a call, like d_partial
+  int32_t *d_votes = nullptr;         // [entries]
+  double *d_hyp = nullptr;            // [kSgCState(d)][entries]
+  double *d_cstate = nullptr;         // [lists][kSgCState(d)]
+  int32_t *d_cint = nullptr;          // [lists][kSgCInts]
+  unsigned char *d_inlier = nullptr;  // [2][n_edges]: chain lists | landmark lists
+  void release() { free_device(d_idx, d_partial, d_state, d_istate, d_votes, d_hyp, d_cstate, d_cint, d_inlier); }
 };
 // The tables of cora_set_closure_placement (capi/closure.inc): the order of the stages, decided from structure alone; per
 // stage its lists; per list the chain and its chunks; the entries (edge, direction) in table order, cut into chunks of

@@ -1183,21 +1183,33 @@ Matrix Problem::multiRobotInitialization(uint64_t seed, int gn_steps, int min_ra
   return odometryStart(seed, gn_steps, info, "Problem::multiRobotInitialization", true, min_ranges, chains_info);
 }
 
+namespace {
+// the minima of an active vote: the chains' <= 0 is the default (d + 1), the landmarks' is at least 1
+void checkSightingConsensus(const SightingConsensus &consensus, const char *where) {
+  if (!std::isfinite(consensus.barc2)) throw std::invalid_argument(std::string(where) + ": the sighting consensus threshold must be finite");
+  if (consensus.barc2 > 0 && consensus.min_landmark_consensus < 1)
+    throw std::invalid_argument(std::string(where) + ": min_landmark_consensus must be at least 1");
+}
+}  // namespace
+
 Matrix Problem::sightingInitialization(uint64_t seed, int gn_steps, int min_ranges, int min_sightings, SightingPlacementInfo *sight_info,
-                                       ChainPlacementInfo *chains_info, LandmarkInitInfo *info) const {
+                                       ChainPlacementInfo *chains_info, LandmarkInitInfo *info, SightingConsensus consensus) const {
   if (gn_steps < 0) throw std::invalid_argument("Problem::sightingInitialization: gn_steps must be in [0, 16]");
-  return odometryStart(seed, gn_steps, info, "Problem::sightingInitialization", true, min_ranges, chains_info, true, min_sightings, sight_info);
+  checkSightingConsensus(consensus, "Problem::sightingInitialization");
+  return odometryStart(seed, gn_steps, info, "Problem::sightingInitialization", true, min_ranges, chains_info, true, min_sightings, sight_info, false,
+                       0, nullptr, ClosureConsensus(), RangeConsensus(), consensus);
 }
 
 Matrix Problem::closureInitialization(uint64_t seed, int gn_steps, int min_ranges, int min_sightings, int min_closures,
                                       ClosurePlacementInfo *closure_info, SightingPlacementInfo *sight_info, ChainPlacementInfo *chains_info,
-                                      LandmarkInitInfo *info, ClosureConsensus consensus) const {
+                                      LandmarkInitInfo *info, ClosureConsensus consensus, SightingConsensus sighting_consensus) const {
   if (gn_steps < 0) throw std::invalid_argument("Problem::closureInitialization: gn_steps must be in [0, 16]");
+  checkSightingConsensus(sighting_consensus, "Problem::closureInitialization");
   if (!std::isfinite(consensus.barc2)) throw std::invalid_argument("Problem::closureInitialization: the consensus threshold must be finite");
   if (consensus.barc2 > 0 && consensus.min_consensus < 1)
     throw std::invalid_argument("Problem::closureInitialization: min_consensus must be at least 1");
   return odometryStart(seed, gn_steps, info, "Problem::closureInitialization", true, min_ranges, chains_info, true, min_sightings, sight_info, true,
-                       min_closures, closure_info, consensus);
+                       min_closures, closure_info, consensus, RangeConsensus(), sighting_consensus);
 }
 
 // the odometry start; with gn_steps >= 0 the landmarks are then placed from the ranges (cora_multilaterate_dev), with
@@ -1207,7 +1219,7 @@ Matrix Problem::closureInitialization(uint64_t seed, int gn_steps, int min_range
 Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where, bool place, int min_ranges,
                               ChainPlacementInfo *chains_info, bool sightings, int min_sightings, SightingPlacementInfo *sight_info, bool closures,
                               int min_closures, ClosurePlacementInfo *closure_info, ClosureConsensus consensus,
-                              RangeConsensus range_consensus) const {
+                              RangeConsensus range_consensus, SightingConsensus sighting_consensus) const {
   checkUpToDate();
   if (part_world_ > 1) throw std::runtime_error(std::string(where) + ": not supported on a partitioned handle");
   ensureMeasurementTable();
@@ -1320,12 +1332,25 @@ Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *inf
     const size_t nch = chains.size(), G = static_cast<size_t>(d) * d + d;
     CORA_CALL(cora_set_sighting_placement(c, closure_done.empty() ? nullptr : closure_done.data(), nullptr, min_sightings > 0 ? min_sightings : 4 * d),
               where);
-    int64_t out[6] = {0, 0, 0, 0, 0, 0};
+    int64_t out[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, mc[2] = {0, 0};
+    const bool robust = sighting_consensus.barc2 > 0;
     std::vector<unsigned char> status(nch + 1, 0), ls(static_cast<size_t>(nl) + 1, 0);
     std::vector<int32_t> chosen(nch + 1, 0);
     std::vector<double> cs(nch + 1, 0.0), cf(nch + 1, 0.0), tr(nch * G + 1, 0.0), lc(static_cast<size_t>(nl) + 1, 0.0);
-    CORA_CALL(cora_place_by_sightings_dev(c, v.x, out, status.data(), cs.data(), cf.data(), chosen.data(), tr.data(), ls.data(), lc.data(), nullptr),
-              where);
+    CORA_CALL(cora_measurement_counts(c, mc), where);
+    const size_t ne = robust ? static_cast<size_t>(mc[0]) : 0, vch = robust ? nch : 0, vl = robust ? static_cast<size_t>(nl) : 0;
+    std::vector<int32_t> cvotes(vch + 1, 0), clens(vch + 1, 0), lvotes(vl + 1, 0), llens(vl + 1, 0);
+    std::vector<unsigned char> inl_c(ne + 1, 0), inl_l(ne + 1, 0);
+    if (robust)  // (a chain without consensus, status 5, is left to the range placement; a landmark, to the multilateration)
+      CORA_CALL(cora_place_by_sightings_robust_dev(c, v.x, sighting_consensus.barc2,
+                                                   sighting_consensus.min_chain_consensus > 0 ? sighting_consensus.min_chain_consensus : d + 1,
+                                                   sighting_consensus.min_landmark_consensus, out, status.data(), cs.data(), cf.data(), chosen.data(),
+                                                   tr.data(), ls.data(), lc.data(), nullptr, cvotes.data(), clens.data(), lvotes.data(), llens.data(),
+                                                   inl_c.data(), inl_l.data()),
+                where);
+    else
+      CORA_CALL(cora_place_by_sightings_dev(c, v.x, out, status.data(), cs.data(), cf.data(), chosen.data(), tr.data(), ls.data(), lc.data(), nullptr),
+                where);
     chain_done.assign(nch + 1, 0);
     long fixed = 0;
     for (size_t ch = 0; ch < nch; ++ch) {
@@ -1347,6 +1372,16 @@ Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *inf
       sight_info->transforms.assign(tr.begin(), tr.begin() + static_cast<std::ptrdiff_t>(nch * G));
       sight_info->landmark_status.assign(ls.begin(), ls.begin() + nl);
       sight_info->landmark_cost.assign(lc.begin(), lc.begin() + nl);
+      sight_info->chains_no_consensus = static_cast<long>(out[6]);
+      sight_info->landmarks_no_consensus = static_cast<long>(out[7]);
+      sight_info->chain_entries_excluded = static_cast<long>(out[8]);
+      sight_info->landmark_entries_excluded = static_cast<long>(out[9]);
+      sight_info->chain_consensus.assign(cvotes.begin(), cvotes.begin() + static_cast<std::ptrdiff_t>(vch));
+      sight_info->chain_list_len.assign(clens.begin(), clens.begin() + static_cast<std::ptrdiff_t>(vch));
+      sight_info->landmark_consensus.assign(lvotes.begin(), lvotes.begin() + static_cast<std::ptrdiff_t>(vl));
+      sight_info->landmark_list_len.assign(llens.begin(), llens.begin() + static_cast<std::ptrdiff_t>(vl));
+      sight_info->inlier_chain.assign(inl_c.begin(), inl_c.begin() + static_cast<std::ptrdiff_t>(ne));
+      sight_info->inlier_landmark.assign(inl_l.begin(), inl_l.begin() + static_cast<std::ptrdiff_t>(ne));
     }
   }
   bool chains_left = true;  // (the sighting step may have left no chain to the ranges)

@@ -199,6 +199,25 @@ struct SightingPlacementInfo {
   std::vector<Scalar> transforms;      // per chain d * d + d: R row-major, then t, as applied
   std::vector<unsigned char> landmark_status;  // per landmark (0 placed, 1 no sighting from a placed chain, 2 sum tau <= 0, 3 fixed)
   std::vector<Scalar> landmark_cost;   // per landmark: the sighting cost of its REFIT list at the row written
+  // with a consensus vote (SightingConsensus; status 5: no consensus, chain or landmark); empty / 0 without one
+  long chains_no_consensus = 0, landmarks_no_consensus = 0;  // status 5 (the landmarks: in the REFIT)
+  long chain_entries_excluded = 0, landmark_entries_excluded = 0;  // entries of the C-stage lists / the REFIT lists outside their inliers
+  std::vector<int32_t> chain_consensus, chain_list_len;        // per chain: the vote of the elected hypothesis, the sightings of its list
+  std::vector<int32_t> landmark_consensus, landmark_list_len;  // per landmark, the REFIT's
+  std::vector<unsigned char> inlier_chain, inlier_landmark;    // per edge of the measurement table: 1 inlier | 0 in a list, not an inlier | 2 in no list
+};
+
+/** The consensus vote of the sighting step (cora_place_by_sightings_robust_dev, include/cora_hip.h).  barc2 <= 0: off, the plain
+ * step and its bits.  barc2 > 0: the threshold on tau |.|^2 of a sighting (the quantity the GNC weights threshold).  Every
+ * sighting of a landmark's list proposes the landmark at its own prediction, every sighting of a chain's list the alignment of
+ * a sample of d sightings; the proposal most sightings agree with is elected and the fit runs over the agreeing sightings only.
+ * A chain whose elected proposal has fewer than min_chain_consensus votes (<= 0: d + 1) keeps its rows (status 5) and is left to
+ * the range placement like a refused one; a landmark below min_landmark_consensus keeps its row (status 5) and is left to the
+ * multilateration.  One proposal per sighting, clean only where all d sightings of its sample are. */
+struct SightingConsensus {
+  Scalar barc2 = 0;
+  int min_chain_consensus = 0;
+  int min_landmark_consensus = 1;
 };
 
 /** What Problem::closureInitialization reports about the closure step (cora_place_by_closures_dev, include/cora_hip.h). */
@@ -312,7 +331,8 @@ class Problem {
                        ChainPlacementInfo *chains_info = nullptr, bool sightings = false, int min_sightings = 0,
                        SightingPlacementInfo *sight_info = nullptr, bool closures = false, int min_closures = 0,
                        ClosurePlacementInfo *closure_info = nullptr, ClosureConsensus consensus = ClosureConsensus(),
-                       RangeConsensus range_consensus = RangeConsensus()) const;
+                       RangeConsensus range_consensus = RangeConsensus(),
+                       SightingConsensus sighting_consensus = SightingConsensus()) const;
   void fillImplicitFormulationMatrices() const;
   [[noreturn]] void throwLast(int status, const char *where) const;
 
@@ -546,10 +566,12 @@ class Problem {
    * the sightings left (its fixed chains: every chain the sighting step fixed or placed; skipped when none is left), then
    * the multilateration for the landmarks the sightings did not place, the range rows and the lift.  On a problem without
    * sightings the result has multiRobotInitialization's bits.  A landmark that only a range-placed chain sights is not
-   * revisited.  min_sightings <= 0: 4 d.  std::runtime_error on a partitioned handle. */
+   * revisited.  min_sightings <= 0: 4 d.  consensus: the outlier-robust sighting step (SightingConsensus; the default is off:
+   * the same bits as without the argument); std::invalid_argument for a barc2 that is not finite or a minimum below 1.
+   * std::runtime_error on a partitioned handle. */
   Matrix sightingInitialization(uint64_t seed = 7, int gn_steps = 5, int min_ranges = 0, int min_sightings = 0,
                                 SightingPlacementInfo *sight_info = nullptr, ChainPlacementInfo *chains_info = nullptr,
-                                LandmarkInitInfo *info = nullptr) const;
+                                LandmarkInitInfo *info = nullptr, SightingConsensus consensus = SightingConsensus()) const;
   /** EXTENSION beyond the reference: sightingInitialization with the chains first placed from the relative-pose edges
    * BETWEEN chains (cora_place_by_closures_dev), chain 0 fixed: exactly the draws of odometryInitialization in the same
    * order (the new step draws nothing), then the closure placement, then the sighting placement with every chain of
@@ -557,11 +579,13 @@ class Problem {
    * range rows and the lift: one pipeline (odometryStart) with one more step.  On a problem without inter-chain closures
    * the result has sightingInitialization's bits.  min_closures <= 0: 1.  consensus: the outlier-robust closure step
    * (ClosureConsensus; the default is off: the same bits as without the argument); std::invalid_argument for a barc2 that is
-   * not finite or a min_consensus below 1.  std::runtime_error on a partitioned handle. */
+   * not finite or a min_consensus below 1.  sighting_consensus: the vote of the sighting step that follows (SightingConsensus,
+   * as in sightingInitialization).  std::runtime_error on a partitioned handle. */
   Matrix closureInitialization(uint64_t seed = 7, int gn_steps = 5, int min_ranges = 0, int min_sightings = 0, int min_closures = 0,
                                ClosurePlacementInfo *closure_info = nullptr, SightingPlacementInfo *sight_info = nullptr,
                                ChainPlacementInfo *chains_info = nullptr, LandmarkInitInfo *info = nullptr,
-                               ClosureConsensus consensus = ClosureConsensus()) const;
+                               ClosureConsensus consensus = ClosureConsensus(),
+                               SightingConsensus sighting_consensus = SightingConsensus()) const;
 
   /********** Certification **************/
   using LambdaBlocks = std::pair<Matrix, Vector>;

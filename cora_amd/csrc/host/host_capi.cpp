@@ -256,6 +256,8 @@ int cora_problem_op(cora_problem *p, const char *op, int cols, const double *A, 
       res = q.rangeAidedInitialization(7, 5, nullptr, RangeConsensus{100.0, 0});
     else if (o == "multiRobotInitialization") res = q.multiRobotInitialization();
     else if (o == "sightingInitialization") res = q.sightingInitialization();
+    else if (o == "sightingInitializationConsensus")  // (the operator form takes no arguments: barc2 = 1, the default minima)
+      res = q.sightingInitialization(7, 5, 0, 0, nullptr, nullptr, nullptr, SightingConsensus{1.0, 0, 1});
     else if (o == "closureInitialization") res = q.closureInitialization();
     else if (o == "closureInitializationConsensus")  // (the operator form takes no arguments: barc2 = 200, min_consensus = 2)
       res = q.closureInitialization(7, 5, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, ClosureConsensus{200.0, 2});
@@ -362,11 +364,41 @@ int cora_problem_sighting_initialization(cora_problem *p, uint64_t seed, int gn_
                                          int64_t counts[6], unsigned char *status, double *cost_start, double *cost_final, int32_t *chosen,
                                          double *transforms, unsigned char *landmark_status, double *landmark_cost, int64_t chain_counts[4],
                                          unsigned char *chain_status, int64_t landmark_counts[4], unsigned char *range_landmark_status) {
+  return cora_problem_sighting_initialization_consensus(p, seed, gn_steps, min_ranges, min_sightings, 0.0, 0, 1, out, counts, status, cost_start,
+                                                        cost_final, chosen, transforms, landmark_status, landmark_cost, nullptr, nullptr, nullptr,
+                                                        nullptr, nullptr, nullptr, nullptr, chain_counts, chain_status, landmark_counts,
+                                                        range_landmark_status);
+}
+
+int cora_problem_sighting_initialization_consensus(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, int min_sightings,
+                                                   double consensus_barc2, int min_chain_consensus, int min_landmark_consensus, double *out,
+                                                   int64_t counts[6], unsigned char *status, double *cost_start, double *cost_final,
+                                                   int32_t *chosen, double *transforms, unsigned char *landmark_status, double *landmark_cost,
+                                                   int64_t consensus_counts[4], int32_t *chain_consensus, int32_t *chain_list_len,
+                                                   int32_t *landmark_consensus, int32_t *landmark_list_len, unsigned char *inlier_chain,
+                                                   unsigned char *inlier_landmark, int64_t chain_counts[4], unsigned char *chain_status,
+                                                   int64_t landmark_counts[4], unsigned char *range_landmark_status) {
   return guarded([&] {
     SightingPlacementInfo si;
     ChainPlacementInfo ci;
     LandmarkInitInfo info;
-    const Matrix res = p->problem.sightingInitialization(seed, gn_steps, min_ranges, min_sightings, &si, &ci, &info);
+    SightingConsensus vote;
+    vote.barc2 = consensus_barc2;
+    vote.min_chain_consensus = min_chain_consensus;
+    vote.min_landmark_consensus = min_landmark_consensus;
+    const Matrix res = p->problem.sightingInitialization(seed, gn_steps, min_ranges, min_sightings, &si, &ci, &info, vote);
+    if (consensus_counts) {
+      consensus_counts[0] = si.chains_no_consensus;
+      consensus_counts[1] = si.landmarks_no_consensus;
+      consensus_counts[2] = si.chain_entries_excluded;
+      consensus_counts[3] = si.landmark_entries_excluded;
+    }
+    if (chain_consensus) std::copy(si.chain_consensus.begin(), si.chain_consensus.end(), chain_consensus);
+    if (chain_list_len) std::copy(si.chain_list_len.begin(), si.chain_list_len.end(), chain_list_len);
+    if (landmark_consensus) std::copy(si.landmark_consensus.begin(), si.landmark_consensus.end(), landmark_consensus);
+    if (landmark_list_len) std::copy(si.landmark_list_len.begin(), si.landmark_list_len.end(), landmark_list_len);
+    if (inlier_chain) std::copy(si.inlier_chain.begin(), si.inlier_chain.end(), inlier_chain);
+    if (inlier_landmark) std::copy(si.inlier_landmark.begin(), si.inlier_landmark.end(), inlier_landmark);
     if (res.rows() == p->problem.getExpectedVariableSize()) p->problem.checkVariablesAreValid(res);  // (throws off the manifold)
     std::memcpy(out, res.data(), sizeof(double) * static_cast<size_t>(res.size()));
     if (counts) {

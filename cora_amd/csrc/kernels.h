@@ -1743,25 +1743,35 @@ __host__ __device__ inline int sg_chain_solve(const double *S, const double *p0,
   }
   return 0;
 }
-// the two costs of one entry: at the identity, tau |x_t(l) - p|^2 as the table has it; at g, tau |R p' + t' - l'|^2
+// the cost of one entry at g from its relative coordinates p' = p - p_0, l' = l - l_0: tau |R p' + t' - l'|^2
 template <int D>
-__host__ __device__ inline void sg_cost_terms(const double *g, const double *p0, const double *l0, const double *p, const double *l, double tau,
-                                              double *s) {
+__host__ __device__ inline double sg_cost_rel(const double *g, const double *pp, const double *ll, double tau) {
 #pragma clang fp contract(off)
   constexpr int G = kSgG(D);
-  s[0] = sg_lm_cost<D>(p, l, tau);
-  double pp[D], q = 0.0;
-#pragma unroll
-  for (int c = 0; c < D; ++c) pp[c] = p[c] - p0[c];
+  double q = 0.0;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
     double v = g[G + a];
 #pragma unroll
     for (int k = 0; k < D; ++k) v = fma(g[a * D + k], pp[k], v);
-    const double r = v - (l[a] - l0[a]);
+    const double r = v - ll[a];
     q = fma(r, r, q);
   }
-  s[1] = tau * q;
+  return tau * q;
+}
+// the two costs of one entry: at the identity, tau |x_t(l) - p|^2 as the table has it; at g, sg_cost_rel at p' and l'
+template <int D>
+__host__ __device__ inline void sg_cost_terms(const double *g, const double *p0, const double *l0, const double *p, const double *l, double tau,
+                                              double *s) {
+#pragma clang fp contract(off)
+  s[0] = sg_lm_cost<D>(p, l, tau);
+  double pp[D], ll[D];
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    pp[c] = p[c] - p0[c];
+    ll[c] = l[c] - l0[c];
+  }
+  s[1] = sg_cost_rel<D>(g, pp, ll, tau);
 }
 // what lane 0 of a list's fold does with the list's sums S in mode MODE; row: the landmark's row of x (modes 0 and 3);
 // p0, l0: the first entry's prediction and landmark.  False where a sum is not finite.
@@ -2094,6 +2104,94 @@ __host__ __device__ inline bool cl_fold_robust(const double *S, double *st, int3
     ist[1] = 0;
     st[G + D] = S[0];
     st[G + D + 1] = S[0];
+  }
+  return finite;
+}
+
+// Outlier-robust placement from sightings: a consensus vote in front of every closed-form fit (kernels/sighting.inc;
+// include/cora_hip.h, cora_place_by_sightings_robust_dev).  Tables, stages, lists, chunks and the origin (the list's
+// first entry, inlier or not) are the plain placement's.
+//   landmark list: entry h proposes y_h = p'_h; r(h, j) = sg_lm_cost(p'_j, y_h, tau_j) = tau_j |y_h - p'_j|^2.
+//   chain list of L entries: entry h proposes the plain chain solve of its SAMPLE, the d entries (h + k s) mod L, k = 0 .. d - 1,
+//     s = max(1, L / d) (sg_sample_entry; distinct, since L >= d), their sg_chain_terms added from the left to +0.0
+//     (sg_hypothesis); VALID where the solve is not refused and g is finite; r(h, j) = sg_cost_rel(g_h, p'_j, l'_j, tau_j).
+// vote(h) = #{j : r(h, j) <= barc2} (cl_agrees: a NaN is no vote; an invalid h has vote 0 and sets no flag).  Elected: the
+// largest vote, among equal votes the lowest entry (cl_better); consensus = its vote; a list without a valid hypothesis elects
+// entry 0 with consensus 0.  consensus below the minimum of the list's kind: status 5, the rows are not touched.  I = {j :
+// r(h*, j) <= barc2}; the plain sums and costs run over I alone: AN ENTRY OUTSIDE I ADDS +0.0 FOR EACH OF ITS TERMS, exactly as
+// a lane beyond the chunk's end does, so the bracket order of a sum is the plain placement's and a list without an outlier has
+// the plain call's bits.  Launches per stage:
+//   L-stage 4: vote, elect, masked pass and fold (mode 0);  REFIT 6: these and the masked pass and fold of the cost (mode 3);
+//   C-stage 8: hypotheses, vote, elect, masked pass and fold of the sums (mode 1) and of the two costs (mode 2), apply.
+// The chain hypotheses are computed in a launch of their own into a workspace (hyp) the vote reads: the one-sided Jacobi of
+// the solve does not share registers with the vote's inner loop.
+constexpr int kSgCState(int d) { return kSgG(d) + d; }  // of the elected hypothesis: chain R | t | t'; landmark y (the first d)
+constexpr int kSgCInts = 2;                             // elected entry (index in its list) | consensus
+struct SgRobustArgs {
+  SgArgs A;
+  double barc2 = 0.0;
+  int min_chain_consensus = 0, min_landmark_consensus = 0;
+  int32_t *votes = nullptr;         // [entries]; between k_sg_hyp and k_sg_vote of a C-stage: 0 valid | -1 invalid
+  double *hyp = nullptr;            // [kSgCState(d)][hstride]: the chain hypothesis of every entry
+  int64_t hstride = 0;              // the entries of all lists
+  double *cstate = nullptr;         // [lists][kSgCState(d)]
+  int32_t *cint = nullptr;          // [lists][kSgCInts]
+  unsigned char *inlier_chain = nullptr;     // [n_edges]: written where an edge is an entry of a C-stage list, 1 in I | 0 outside
+  unsigned char *inlier_landmark = nullptr;  // [n_edges]: the same for the landmark lists (the REFIT's pass writes last)
+};
+hipError_t launch_sighting_vote_elect(const SgRobustArgs &R, int kind, hipStream_t st);  // kind 0 landmark lists | 1 chain lists (with k_sg_hyp)
+hipError_t launch_sighting_robust_pass_fold(const SgRobustArgs &R, hipStream_t st);       // masked pass and fold of R.A.mode
+// entry k of the sample of entry h in a list of len entries
+__host__ __device__ inline int32_t sg_sample_entry(int32_t h, int32_t len, int d, int k) {
+  const int64_t s = len / d > 1 ? len / d : 1;
+  return static_cast<int32_t>((static_cast<int64_t>(h) + k * s) % len);
+}
+// The motion entry h of a list of len entries proposes.  entry(j, p, &l) gives prediction, landmark row and tau of entry j of
+// the list; p0, l0: the first entry's.  g: R | t | t'.  True where the hypothesis is valid.
+template <int D, class Entry>
+__host__ __device__ inline bool sg_hypothesis(int32_t h, int32_t len, const double *p0, const double *l0, Entry entry, double *g) {
+#pragma clang fp contract(off)
+  constexpr int NS = kSgChainSums(D);
+  double S[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) S[i] = 0.0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    double p[D], t[NS];
+    const double *l;
+    const double tau = entry(sg_sample_entry(h, len, D, k), p, &l);
+    sg_chain_terms<D>(p0, l0, p, l, tau, t);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) S[i] = S[i] + t[i];
+  }
+  return sg_chain_solve<D>(S, p0, l0, g) == 0 && odom_finite(g, kSgCState(D));
+}
+// sg_fold with status 5 passed through: a list without consensus writes no row, has the identity and is never chosen
+template <int D, int MODE>
+__host__ __device__ inline bool sg_fold_robust(const double *S, double *st, int32_t *ist, const double *p0, const double *l0, double *row) {
+  constexpr int G = kSgG(D);
+  constexpr int ns = MODE == 0 ? kSgLmSums(D) : (MODE == 1 ? kSgChainSums(D) : (MODE == 2 ? kSgCostSums : 1));
+  if (ist[0] != 5) return sg_fold<D, MODE>(S, st, ist, p0, l0, row);
+  const bool finite = odom_finite(S, ns);
+  ist[1] = 0;
+  if constexpr (MODE == 0) {
+#pragma unroll
+    for (int c = 0; c < D; ++c) st[c] = row[c];
+    st[D] = S[0];
+    st[D + 1] = 0.0;
+  } else if constexpr (MODE == 1) {
+#pragma unroll
+    for (int i = 0; i < D * D; ++i) st[i] = i / D == i % D ? 1.0 : 0.0;
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+      st[D * D + c] = 0.0;
+      st[G + c] = p0[c] - l0[c];
+    }
+  } else if constexpr (MODE == 2) {
+    st[G + D] = S[0];
+    st[G + D + 1] = S[0];
+  } else {
+    st[D + 1] = S[0];
   }
   return finite;
 }

@@ -40,7 +40,7 @@
 //   kernels/odom.inc     odometry initialisation: segmented scan of SE(d) over the chain positions, fill of the other rows  CORA_TU & 2
 //   kernels/multilat.inc  landmark initialisation from ranges: pass over the chunks of the range lists, fold and solve per landmark  CORA_TU & 2
 //   kernels/placement.inc  chain placement from inter-robot ranges: linear and Gauss-Newton pass and fold per stage, the rigid motion of a chain  CORA_TU & 2
-//   kernels/sighting.inc  placement from pose-landmark sightings: pass and fold over all lists of a stage, the rigid motion of a stage's chains  CORA_TU & 2
+//   kernels/sighting.inc  placement from pose-landmark sightings: pass and fold over all lists of a stage, the rigid motion of a stage's chains; the hypotheses, consensus vote, election and masked passes of the robust form  CORA_TU & 2
 //   kernels/closure.inc  placement from inter-chain relative-pose edges: pass and fold over all lists of a stage (sums and solve, costs); the consensus vote, election and masked passes of the robust form  CORA_TU & 2
 //   kernels/update_values.inc  in-place update of Q's values: check of the new values, gather passes                CORA_TU & 2
 //   kernels/assemble.inc  Q(w) from per-measurement weights through the term map: check, short and long entries     CORA_TU & 2

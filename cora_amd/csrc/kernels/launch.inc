@@ -546,12 +546,34 @@ static bool sighting_args_ok(const SgArgs &A) {
          A.pstride >= static_cast<int64_t>(A.chunk0) + A.n_chunks && A.chunk_begin && A.chunk_len && A.chunk_list && A.list_chunk0 && A.list_row &&
          A.ent_rot && A.ent_trn && A.ent_lm && A.ent_e && A.edge_data && A.partial && A.state && A.istate && A.x && A.flag;
 }
-hipError_t launch_sighting_pass_fold(const SgArgs &A, hipStream_t st) {
-  if (!sighting_args_ok(A) || A.mode < 0 || A.mode > 3) return hipErrorInvalidValue;
+static bool sighting_args_ok(const SgRobustArgs &R) {
+  return sighting_args_ok(R.A) && R.barc2 > 0.0 && R.min_chain_consensus >= 1 && R.min_landmark_consensus >= 1 && R.votes && R.hyp &&
+         R.hstride > 0 && R.cstate && R.cint && R.inlier_chain && R.inlier_landmark;
+}
+template <bool ROBUST>
+static hipError_t sighting_pass_fold(const SgKernelArgs<ROBUST> &K, hipStream_t st) {
+  const SgArgs &A = sg_plain(K);
+  if (!sighting_args_ok(K) || A.mode < 0 || A.mode > 3) return hipErrorInvalidValue;
   for_d(A.d, [&](auto D) {
     for_mode<4>(A.mode, [&](auto MODE) {
-      hipLaunchKernelGGL((k_sg_pass<D(), MODE()>), dim3(static_cast<unsigned>(A.n_chunks)), dim3(kSgChunk), 0, st, A);
-      hipLaunchKernelGGL((k_sg_fold<D(), MODE()>), dim3(static_cast<unsigned>(A.n_lists)), dim3(kWave), 0, st, A);
+      hipLaunchKernelGGL((k_sg_pass<D(), MODE(), ROBUST>), dim3(static_cast<unsigned>(A.n_chunks)), dim3(kSgChunk), 0, st, K);
+      hipLaunchKernelGGL((k_sg_fold<D(), MODE(), ROBUST>), dim3(static_cast<unsigned>(A.n_lists)), dim3(kWave), 0, st, K);
+    });
+  });
+  return hipGetLastError();
+}
+hipError_t launch_sighting_pass_fold(const SgArgs &A, hipStream_t st) { return sighting_pass_fold<false>(A, st); }
+hipError_t launch_sighting_robust_pass_fold(const SgRobustArgs &R, hipStream_t st) { return sighting_pass_fold<true>(R, st); }
+// the consensus vote of the robust placement: (chain lists: one thread per entry for the hypotheses,) one workgroup per chunk,
+// then one wavefront per list
+hipError_t launch_sighting_vote_elect(const SgRobustArgs &R, int kind, hipStream_t st) {
+  if (!sighting_args_ok(R) || kind < 0 || kind > 1) return hipErrorInvalidValue;
+  const dim3 chunks(static_cast<unsigned>(R.A.n_chunks)), lists(static_cast<unsigned>(R.A.n_lists));
+  for_d(R.A.d, [&](auto D) {
+    for_mode<2>(kind, [&](auto KIND) {
+      if constexpr (KIND() == 1) hipLaunchKernelGGL(k_sg_hyp<D()>, chunks, dim3(kSgChunk), 0, st, R);
+      hipLaunchKernelGGL((k_sg_vote<D(), KIND()>), chunks, dim3(kSgChunk), 0, st, R);
+      hipLaunchKernelGGL((k_sg_elect<D(), KIND()>), lists, dim3(kWave), 0, st, R);
     });
   });
   return hipGetLastError();

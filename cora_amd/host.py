@@ -200,7 +200,7 @@ class Problem:
             out = np.zeros(1)
         pa, pb, pc = ptr(A), ptr(B), ptr(C_)
         if name != "evaluateObjective":
-            full = name in ("getOdomInitialization", "odometryInitialization", "rangeAidedInitialization", "rangeAidedInitializationConsensus", "multiRobotInitialization", "sightingInitialization", "closureInitialization",
+            full = name in ("getOdomInitialization", "odometryInitialization", "rangeAidedInitialization", "rangeAidedInitializationConsensus", "multiRobotInitialization", "sightingInitialization", "sightingInitializationConsensus", "closureInitialization",
                             "closureInitializationConsensus",
                             "getTranslationExplicitSolution", "alignEstimateToOrigin")
             out = np.zeros((dm["N"] if full else N, cols[0] if cols else p), order="F")
@@ -268,27 +268,48 @@ class Problem:
                          landmarks=dict(solved=int(lcnt[0]), not_solved=int(lcnt[1]), n_degenerate=int(lcnt[2]), steps=int(lcnt[3]),
                                         status=lstatus[:nl]))
 
-    def sighting_initialization(self, seed=7, gn_steps=5, min_ranges=0, min_sightings=0):
+    def sighting_initialization(self, seed=7, gn_steps=5, min_ranges=0, min_sightings=0, consensus_barc2=None, min_chain_consensus=0,
+                                min_landmark_consensus=1):
         """Problem::sightingInitialization: (x0, info) with info a dict fixed, placed, not_placed, landmarks_placed,
         landmarks_not_placed, stages, status, cost_start, cost_final, chosen, transforms (per chain of odometry_chains()),
         landmark_status, landmark_cost (per landmark) of the sighting step; chains (placed, not_placed, steps, stages, status
         of the range placement that followed) and landmarks (the dict of range_aided_initialization without the costs).
-        0: the defaults.  The start has passed checkVariablesAreValid."""
+        0: the defaults.  The start has passed checkVariablesAreValid.
+        consensus_barc2: None, the plain sighting step; a threshold > 0, the sighting step with a consensus vote
+        (SightingConsensus, CORA_problem.h): every fit runs over the sightings that agree with the elected proposal, a chain
+        below min_chain_consensus (0: d + 1) or a landmark below min_landmark_consensus has status 5, and info gains
+        chains_no_consensus, landmarks_no_consensus, chain_excluded, landmark_excluded, chain_consensus, chain_list_len (per chain),
+        landmark_consensus, landmark_list_len (per landmark), inlier_chain and inlier_landmark (per edge of the measurement table,
+        relative poses first: 1 | 0 | 2 in no list)."""
         dm = self.dims()
         d = dm["d"]
         nl = dm["N"] - (d + 1) * dm["n"] - dm["r"]
         nch = len(self.odometry_chains())
+        robust = consensus_barc2 is not None
+        if robust and not consensus_barc2 > 0:
+            raise HostError("consensus_barc2 must be positive (None: no consensus vote)")
+        mcnt, vcnt = (C.c_int64 * 5)(), (C.c_int64 * 4)()
+        self._chk(self.L.cora_problem_measurement_counts(self.h, mcnt))
+        ne = int(sum(mcnt[:4]))
+        i32 = C.POINTER(C.c_int32)
+        cc, cl, lcn, ll = (np.zeros(k + 1, dtype=np.int32) for k in (nch, nch, nl, nl))
+        ic, il = np.zeros(ne + 1, dtype=np.uint8), np.zeros(ne + 1, dtype=np.uint8)
         out = np.zeros((dm["N"], dm["rank"]), order="F")
         cnt, ccnt, lcnt = (C.c_int64 * 6)(), (C.c_int64 * 4)(), (C.c_int64 * 4)()
         status, cstatus, chosen = np.zeros(nch + 1, dtype=np.uint8), np.zeros(nch + 1, dtype=np.uint8), np.zeros(nch + 1, dtype=np.int32)
         ls, rls, lc = np.zeros(nl + 1, dtype=np.uint8), np.zeros(nl + 1, dtype=np.uint8), np.zeros(nl + 1)
         cs, cf, tr = np.zeros(nch + 1), np.zeros(nch + 1), np.zeros(nch * (d * d + d) + 1)
-        self._chk(self.L.cora_problem_sighting_initialization(
-            self.h, C.c_uint64(seed), int(gn_steps), int(min_ranges), int(min_sightings), out.ctypes.data_as(_dp), cnt,
-            status.ctypes.data_as(C.c_void_p), cs.ctypes.data_as(_dp), cf.ctypes.data_as(_dp), chosen.ctypes.data_as(C.POINTER(C.c_int32)),
-            tr.ctypes.data_as(_dp), ls.ctypes.data_as(C.c_void_p), lc.ctypes.data_as(_dp), ccnt, cstatus.ctypes.data_as(C.c_void_p), lcnt,
-            rls.ctypes.data_as(C.c_void_p)))
-        return out, dict(fixed=int(cnt[0]), placed=int(cnt[1]), not_placed=int(cnt[2]), landmarks_placed=int(cnt[3]),
+        self._chk(self.L.cora_problem_sighting_initialization_consensus(
+            self.h, C.c_uint64(seed), int(gn_steps), int(min_ranges), int(min_sightings), C.c_double(consensus_barc2 if robust else 0.0),
+            int(min_chain_consensus), int(min_landmark_consensus), out.ctypes.data_as(_dp), cnt,
+            status.ctypes.data_as(C.c_void_p), cs.ctypes.data_as(_dp), cf.ctypes.data_as(_dp), chosen.ctypes.data_as(i32),
+            tr.ctypes.data_as(_dp), ls.ctypes.data_as(C.c_void_p), lc.ctypes.data_as(_dp), vcnt, cc.ctypes.data_as(i32), cl.ctypes.data_as(i32),
+            lcn.ctypes.data_as(i32), ll.ctypes.data_as(i32), ic.ctypes.data_as(C.c_void_p), il.ctypes.data_as(C.c_void_p), ccnt,
+            cstatus.ctypes.data_as(C.c_void_p), lcnt, rls.ctypes.data_as(C.c_void_p)))
+        extra = dict(chains_no_consensus=int(vcnt[0]), landmarks_no_consensus=int(vcnt[1]), chain_excluded=int(vcnt[2]),
+                     landmark_excluded=int(vcnt[3]), chain_consensus=cc[:nch], chain_list_len=cl[:nch], landmark_consensus=lcn[:nl],
+                     landmark_list_len=ll[:nl], inlier_chain=ic[:ne], inlier_landmark=il[:ne]) if robust else {}
+        return out, dict(**extra, fixed=int(cnt[0]), placed=int(cnt[1]), not_placed=int(cnt[2]), landmarks_placed=int(cnt[3]),
                          landmarks_not_placed=int(cnt[4]), stages=int(cnt[5]), status=status[:nch], cost_start=cs[:nch], cost_final=cf[:nch],
                          chosen=chosen[:nch], transforms=tr[:-1].reshape(nch, d * d + d), landmark_status=ls[:nl], landmark_cost=lc[:nl],
                          chains=dict(placed=int(ccnt[0]), not_placed=int(ccnt[1]), steps=int(ccnt[2]), stages=int(ccnt[3]), status=cstatus[:nch]),

@@ -22,14 +22,15 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding] [--device-init [--landmark-init [--range-consensus barc2 [--range-min-consensus k]]] [--place-chains] [--sightings] [--closures [--closure-consensus barc2 [--closure-min-consensus k]]] [--gn-steps k]]" << std::endl;
+    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding] [--device-init [--landmark-init [--range-consensus barc2 [--range-min-consensus k]]] [--place-chains] [--sightings [--sighting-consensus barc2 [--sighting-min-consensus k] [--sighting-min-landmark-consensus k]]] [--closures [--closure-consensus barc2 [--closure-min-consensus k]]] [--gn-steps k]]" << std::endl;
     return 1;
   }
   int max_rank = 10, gn_steps = 5;
   std::string tum, save_dir, residuals, weights, robust, barc2, weights_out, aligned_tum, rpe_steps, rpe_dists;
   CORA::ClosureConsensus closure_consensus;
   CORA::RangeConsensus range_consensus;
-  bool consensus_given = false, range_consensus_given = false;
+  CORA::SightingConsensus sighting_consensus;
+  bool consensus_given = false, range_consensus_given = false, sighting_consensus_given = false;
   bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false, landmark_init = false, place_chains = false, sightings = false, closures = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
@@ -74,6 +75,11 @@ int main(int argc, char **argv) {
     // with --odom-init --device-init: landmarks and chains are first placed from the pose-landmark sightings, then the chains
     // that are left from the ranges and the landmarks that are left by multilateration (Problem::sightingInitialization)
     else if (a == "--sightings") sightings = true;
+    // with --sightings: a consensus vote in front of every fit of the sighting step (SightingConsensus): the threshold on a
+    // sighting's tau |.|^2, and the votes the elected proposal of a chain (0: d + 1) and of a landmark needs
+    else if (a == "--sighting-consensus" && i + 1 < argc) sighting_consensus.barc2 = std::atof(argv[++i]), sighting_consensus_given = true;
+    else if (a == "--sighting-min-consensus" && i + 1 < argc) sighting_consensus.min_chain_consensus = std::atoi(argv[++i]), sighting_consensus_given = true;
+    else if (a == "--sighting-min-landmark-consensus" && i + 1 < argc) sighting_consensus.min_landmark_consensus = std::atoi(argv[++i]), sighting_consensus_given = true;
     // with --odom-init --device-init: the chains are first placed from the relative-pose edges between chains, then everything
     // --sightings does (Problem::closureInitialization)
     else if (a == "--closures") closures = true;
@@ -91,6 +97,8 @@ int main(int argc, char **argv) {
     if (closures && !device_init) throw std::runtime_error("--closures places the chains of the device's odometry start: it needs --odom-init --device-init");
     if (consensus_given && !closures) throw std::runtime_error("--closure-consensus and --closure-min-consensus set the vote of the closure step: they need --closures");
     if (consensus_given && !(closure_consensus.barc2 > 0)) throw std::runtime_error("--closure-consensus: expected a threshold > 0");
+    if (sighting_consensus_given && !sightings) throw std::runtime_error("--sighting-consensus, --sighting-min-consensus and --sighting-min-landmark-consensus set the vote of the sighting step: they need --sightings");
+    if (sighting_consensus_given && !(sighting_consensus.barc2 > 0)) throw std::runtime_error("--sighting-consensus: expected a threshold > 0");
     if (range_consensus_given && !landmark_init) throw std::runtime_error("--range-consensus and --range-min-consensus set the vote of the landmark step: they need --landmark-init");
     if (range_consensus_given && !(range_consensus.barc2 > 0)) throw std::runtime_error("--range-consensus: expected a threshold > 0");
     if (landmark_init && !device_init) throw std::runtime_error("--landmark-init places the landmarks of the device's odometry start: it needs --odom-init --device-init");
@@ -180,10 +188,19 @@ int main(int argc, char **argv) {
         return sum;
       };
       const double without = sighting_sum(x0);  // (the start as it stands)
-      x0 = problem.sightingInitialization(7, gn_steps, 0, 0, &si);
+      x0 = problem.sightingInitialization(7, gn_steps, 0, 0, &si, nullptr, nullptr, sighting_consensus);
       std::printf("sighting placement: %ld chains fixed or placed, %ld not placed; %ld landmarks placed, %ld not placed (%ld stages); sighting cost at the start %.6e with it, %.6e without\n",
                   si.chains_fixed + si.chains_placed, si.chains_not_placed, si.landmarks_placed, si.landmarks_not_placed, si.stages,
                   sighting_sum(x0), without);
+      if (sighting_consensus_given) {
+        double least = 1.0;  // the smallest consensus / list length over the chains' lists and the REFIT's lists
+        for (size_t ch = 0; ch < si.chain_list_len.size(); ++ch)
+          if (si.chain_list_len[ch] > 0) least = std::min(least, static_cast<double>(si.chain_consensus[ch]) / si.chain_list_len[ch]);
+        for (size_t l = 0; l < si.landmark_list_len.size(); ++l)
+          if (si.landmark_list_len[l] > 0) least = std::min(least, static_cast<double>(si.landmark_consensus[l]) / si.landmark_list_len[l]);
+        std::printf("sighting consensus: %ld chains without consensus, %ld landmarks without consensus, %ld chain sightings excluded, %ld landmark sightings excluded; smallest consensus / list length %.4f\n",
+                    si.chains_no_consensus, si.landmarks_no_consensus, si.chain_entries_excluded, si.landmark_entries_excluded, least);
+      }
     }
     if (closures) {  // (an extension beyond the reference: Problem::closureInitialization)
       CORA::ClosurePlacementInfo li;

@@ -1081,6 +1081,80 @@ int cora_debug_place_by_sightings_host(cora_ctx *ctx, double *X, int ldx, int64_
                                        double *cost_final, int32_t *chosen, double *transforms, unsigned char *landmark_status,
                                        double *landmark_cost, unsigned char *degenerate);
 
+/* ---- OUTLIER-ROBUST PLACEMENT FROM SIGHTINGS: a consensus vote in front of every fit ---------------------------------------
+ * cora_place_by_sightings_dev with a vote that keeps a sighting credited to the wrong landmark (the data-association
+ * outlier) out of the landmark means and out of the chains' rigid alignments.  Tables, stages (L / C / REFIT), lists,
+ * 256-entry chunks, the origin (the list's first entry, inlier or not), the refusal rule, "cost must fall", the apply and
+ * the range-row step are exactly those of cora_set_sighting_placement: there is no new set call, and the order still
+ * depends on structure alone.  One finite barc2 > 0 is given: the threshold on tau |.|^2, the quantity cora_gnc_weights
+ * thresholds for a sighting (no 1/2).
+ * LANDMARK LISTS (L-stages and the REFIT).
+ *   hypothesis       entry h proposes the landmark at its own prediction, y_h = p'_h = p_h - p_0.  Every entry is valid.
+ *   score            r(h, j) = tau_j |y_h - p'_j|^2, the operations and order of the sighting cost of one entry.
+ *   vote             vote(h) = #{ j : r(h, j) <= barc2 }.  A NaN is no vote.
+ *   election         h* is the entry of largest vote, the lowest entry among equal votes.  consensus = vote(h*).
+ *   no consensus     consensus < min_landmark_consensus (>= 1): landmark status 5.  The row is not touched.  By the
+ *                    structural order the landmark STILL COUNTS AS PLACED for later C-stages, as a refused chain does: its
+ *                    sightings then enter those lists as gross outliers, and the chains' vote is what excludes them.
+ *   refit            inliers I = { j : r(h*, j) <= barc2 }, the vote's function and bits.  The plain mean is taken over I:
+ *                    an entry outside I adds +0.0 for each of its terms, so the bracket order is the plain call's.
+ *                    landmark_cost is summed over I.
+ * CHAIN LISTS (C-stages), a list of L entries.
+ *   sample           the sample of h is the entries (h + k s) mod L, k = 0 .. d-1, s = max(1, L / d): d distinct entries,
+ *                    because L >= min_sightings >= d; a function of (h, L, d) alone.
+ *   hypothesis       g_h = (R_h, t'_h): the sample's terms of the alignment's sums (their own tau, relative to the list's
+ *                    origin) are added from the left in the order k = 0 .. d-1, starting from +0.0; then the plain chain
+ *                    solve runs, refusal rule included.  VALID where that solve is not refused and the result is finite.
+ *                    Two sample entries that sight one landmark, or at d = 3 three landmarks on a line, are filtered by the
+ *                    plain rule.  An invalid hypothesis has vote 0 and sets no flag.
+ *   score            r(h, j) = tau_j |R_h p'_j + t'_h - l'_j|^2, the function and bits of the plain call's cost at g.
+ *   vote, election, inliers   as above.  A list without a valid hypothesis elects entry 0 with consensus 0.
+ *   no consensus     consensus < min_chain_consensus (>= 1): chain status 5, "taken, no consensus".  The chain keeps its
+ *                    rows (chosen 0, the identity).  It counts as placed for later stages, as status 2 does.
+ *   refit            the plain sums, solve (status 2 still possible) and the two costs over I only, with the same +0.0 rule.
+ *                    The chain moves only where the cost over I falls.  One election, one refit.
+ * LIMIT.  There is one hypothesis per entry.  It is clean only where all d entries of its sample are, a share (1 - eps)^d
+ * of the hypotheses at an outlier fraction eps: the vote finds the consensus as long as ONE clean sample exists, but with
+ * L (1 - eps)^d below about 1 no hypothesis may be clean and the list ends without consensus (status 5) or, worse, elects a
+ * hypothesis a group of consistent outliers supports.  Landmark lists have d = 1 in this count.
+ * cora_place_by_sightings_robust_dev   the arguments of cora_place_by_sightings_dev plus barc2, min_chain_consensus and
+ *            min_landmark_consensus.  out (host, 10 fields) = the plain call's six, then {chains without consensus (status 5;
+ *            not among "not placed"), landmarks without consensus in the REFIT, C-list entries outside I, REFIT entries
+ *            outside I}.  New arrays, each NULL-allowed:  chain_consensus, chain_list_len [chains] (0 without a list);
+ *            landmark_consensus, landmark_list_len [landmarks], the REFIT's;  inlier_chain [n_edges]: 1 in I of its C list,
+ *            0 in a C list outside I, 2 in no C list;  inlier_landmark [n_edges]: the same for the REFIT lists (the L-stages'
+ *            flags are superseded by the REFIT's: an L-stage's list is a part of the REFIT's list of the same landmark).  A
+ *            list of status 5 reports the inliers of its elected hypothesis all the same.
+ *            Launches per stage: L-stage 4 (vote, elect, masked pass and fold), REFIT 4 + 2 for the landmarks' cost, C-stage 8
+ *            (hypotheses, vote, elect, masked pass and fold of the sums and of the costs, apply); then the range rows.  The
+ *            chain hypotheses are a launch of their own into a workspace the vote reads.  The votes, the hypotheses, the
+ *            elected hypotheses and the inlier bytes are scratch of the tables, allocated with them.  Everything on the
+ *            handle's stream; synchronises once, at the end.
+ * cora_place_by_sightings_robust       the host-pointer form.
+ * cora_debug_place_by_sightings_robust_host   the mirror: the device's bits, on a plan-only handle too.
+ * ARITHMETIC.  The plain section's: + - x / and sqrt only, never contracted; the votes are integers; no atomics on doubles;
+ * the launches are the only synchronisation between workgroups.  A list in which every entry is an inlier has the plain
+ * call's bits.
+ * ERRORS.  The plain call's, plus CORA_ERR_ARG: barc2 not finite or <= 0, a minimum < 1;  CORA_ERR_NAN: an elected hypothesis
+ * that is not finite.
+ * STATE.  Nothing the handle computes with changes, nor its tables. */
+int cora_place_by_sightings_robust_dev(cora_ctx *ctx, double *dX, double barc2, int min_chain_consensus, int min_landmark_consensus,
+                                       int64_t out[10], unsigned char *status, double *cost_start, double *cost_final, int32_t *chosen,
+                                       double *transforms, unsigned char *landmark_status, double *landmark_cost, unsigned char *degenerate,
+                                       int32_t *chain_consensus, int32_t *chain_list_len, int32_t *landmark_consensus,
+                                       int32_t *landmark_list_len, unsigned char *inlier_chain, unsigned char *inlier_landmark);
+int cora_place_by_sightings_robust(cora_ctx *ctx, double *X, int ldx, double barc2, int min_chain_consensus, int min_landmark_consensus,
+                                   int64_t out[10], unsigned char *status, double *cost_start, double *cost_final, int32_t *chosen,
+                                   double *transforms, unsigned char *landmark_status, double *landmark_cost, unsigned char *degenerate,
+                                   int32_t *chain_consensus, int32_t *chain_list_len, int32_t *landmark_consensus,
+                                   int32_t *landmark_list_len, unsigned char *inlier_chain, unsigned char *inlier_landmark);
+int cora_debug_place_by_sightings_robust_host(cora_ctx *ctx, double *X, int ldx, double barc2, int min_chain_consensus,
+                                              int min_landmark_consensus, int64_t out[10], unsigned char *status, double *cost_start,
+                                              double *cost_final, int32_t *chosen, double *transforms, unsigned char *landmark_status,
+                                              double *landmark_cost, unsigned char *degenerate, int32_t *chain_consensus,
+                                              int32_t *chain_list_len, int32_t *landmark_consensus, int32_t *landmark_list_len,
+                                              unsigned char *inlier_chain, unsigned char *inlier_landmark);
+
 /* ---- PLACEMENT FROM INTER-CHAIN RELATIVE-POSE EDGES (closures), on the device ------------------------------------------------
  * Moves whole odometry chains by one rigid motion each so that the relative-pose edges BETWEEN chains (inter-robot loop
  * closures, rendezvous, closures across a gap in one robot's odometry) are met, in place; the solve is closed-form and

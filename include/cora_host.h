@@ -99,6 +99,7 @@ int cora_problem_variable_size(cora_problem *p, int64_t *rows);
  *                                                        between them (Problem::multiRobotInitialization, seed 7, 5 steps, default min_ranges)
  *  "sightingInitialization"   (none)             -> out   multiRobotInitialization with landmarks and chains first placed from the
  *                                                        pose-landmark sightings (Problem::sightingInitialization, seed 7, defaults)
+ *  "sightingInitializationConsensus" (none)      -> out   the same with the sighting step's consensus vote (SightingConsensus{1, 0, 1})
  *  "closureInitialization"    (none)             -> out   sightingInitialization with the chains first placed from the relative-pose
  *                                                        edges between chains (Problem::closureInitialization, seed 7, defaults)
  *  "getTranslationExplicitSolution" A=Y (implicit) -> out (d+1)n + r + l rows (src/CORA_problem.cpp:1168)
@@ -149,6 +150,22 @@ int cora_problem_sighting_initialization(cora_problem *p, uint64_t seed, int gn_
                                          int64_t counts[6], unsigned char *status, double *cost_start, double *cost_final, int32_t *chosen,
                                          double *transforms, unsigned char *landmark_status, double *landmark_cost, int64_t chain_counts[4],
                                          unsigned char *chain_status, int64_t landmark_counts[4], unsigned char *range_landmark_status);
+/* The same with the sighting step's consensus vote (SightingConsensus, CORA_problem.h; cora_place_by_sightings_robust_dev,
+ * include/cora_hip.h): consensus_barc2 <= 0 is off and has cora_problem_sighting_initialization's bits; > 0: every sighting of
+ * a list proposes, the proposal most sightings agree with (tau |.|^2 <= consensus_barc2) is elected and the fit runs over the
+ * agreeing sightings; a chain below min_chain_consensus (<= 0: d + 1) or a landmark below min_landmark_consensus (>= 1) has
+ * status 5 and is left to the steps that follow.  consensus_counts = { chains without consensus, landmarks without consensus,
+ * C-list entries outside their inliers, REFIT entries outside their inliers };  chain_consensus, chain_list_len: per chain;
+ * landmark_consensus, landmark_list_len: per landmark;  inlier_chain, inlier_landmark: one byte per edge of the measurement
+ * table (relative poses first, as added), 1 | 0 | 2 in no list -- all empty / 0 without a vote.  Every array but out may be NULL. */
+int cora_problem_sighting_initialization_consensus(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, int min_sightings,
+                                                   double consensus_barc2, int min_chain_consensus, int min_landmark_consensus, double *out,
+                                                   int64_t counts[6], unsigned char *status, double *cost_start, double *cost_final,
+                                                   int32_t *chosen, double *transforms, unsigned char *landmark_status, double *landmark_cost,
+                                                   int64_t consensus_counts[4], int32_t *chain_consensus, int32_t *chain_list_len,
+                                                   int32_t *landmark_consensus, int32_t *landmark_list_len, unsigned char *inlier_chain,
+                                                   unsigned char *inlier_landmark, int64_t chain_counts[4], unsigned char *chain_status,
+                                                   int64_t landmark_counts[4], unsigned char *range_landmark_status);
 /* Problem::closureInitialization (an extension beyond the reference; include/cora_hip.h, "placement from inter-chain
  * relative-pose edges").  min_ranges, min_sightings, min_closures <= 0: the defaults.  out: data-matrix-size x rank.
  * counts = { chains fixed, placed, not placed, refused, stages, closures used, skipped + unused edges } of the closure step;
