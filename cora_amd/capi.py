@@ -17,6 +17,7 @@ _LIB = None
 STATUS = {0: "CORA_OK", 1: "CORA_ERR_SHAPE", 2: "CORA_ERR_NOT_READY", 3: "CORA_ERR_NAN",
           4: "CORA_ERR_HIP", 5: "CORA_ERR_ARG", 6: "CORA_ERR_NOMEM"}
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_CHOLESKY, PRECOND_REGULARIZED_CHOLESKY = 0, 1, 2, 3
+PL_ORDER_GREEDY, PL_ORDER_LEVELS = 0, 1   # cora_set_chain_placement_order
 
 
 # callback types of cora_set_comm (user pointer, device / host pointer as an integer, count)
@@ -1153,6 +1154,15 @@ class Context:
         keep, ptr = self._mask(chain_fixed, self.odometry_chains_count()[0], "chain_fixed")
         self._chk(self.L.cora_set_chain_placement(self.h, ptr, int(min_ranges)))
 
+    def set_chain_placement_order(self, chain_fixed=None, min_ranges=None, order=PL_ORDER_LEVELS):
+        """set_chain_placement with the order of the stages chosen: PL_ORDER_GREEDY (its tables exactly) or PL_ORDER_LEVELS
+        (level k: every chain not yet placed with min_ranges entries against the chains of levels < k, its list those
+        entries only)."""
+        if min_ranges is None:
+            min_ranges = 4 * (7 if self.d == 2 else 16)
+        keep, ptr = self._mask(chain_fixed, self.odometry_chains_count()[0], "chain_fixed")
+        self._chk(self.L.cora_set_chain_placement_order(self.h, ptr, int(min_ranges), int(order)))
+
     def chain_placement_counts(self):
         """(stages, entries, chunks, skipped ranges) of the installed tables."""
         out = (C.c_int64 * 4)()
@@ -1165,17 +1175,26 @@ class Context:
         self._chk(self.L.cora_chain_placement_order(self.h, order.ctypes.data_as(_ip)))
         return order[:-1]
 
-    def _pl_call(self, fn, gn_steps):
+    def chain_placement_levels(self):
+        """The level (>= 1; level 0 holds the fixed chains) of every stage, in the order of the stages."""
+        level = np.zeros(self.chain_placement_counts()[0] + 1, dtype=np.int32)
+        self._chk(self.L.cora_chain_placement_levels(self.h, level.ctypes.data_as(_ip)))
+        return level[:-1]
+
+    def _pl_call(self, fn, gn_steps, batched=False):
         nch, nr, g = self.odometry_chains_count()[0], self.measurement_counts()[1], self.d * self.d + self.d
-        out = (C.c_int64 * 5)()
+        out = (C.c_int64 * 6)()
         status, chosen = np.zeros(nch + 1, dtype=np.uint8), np.zeros(nch + 1, dtype=np.int32)
         cs, cl, cf, tr = np.zeros(nch + 1), np.zeros(nch + 1), np.zeros(nch + 1), np.zeros((nch + 1) * g)
         deg = np.zeros(nr + 1, dtype=np.uint8)
         self._chk(fn(int(gn_steps), out, status.ctypes.data_as(C.c_void_p), _d(cs), _d(cl), _d(cf), chosen.ctypes.data_as(_ip), _d(tr),
                      deg.ctypes.data_as(C.c_void_p)))
-        return dict(placed=int(out[0]), not_placed=int(out[1]), steps=int(out[2]), n_degenerate=int(out[3]), stages=int(out[4]),
-                    status=status[:nch], cost_start=cs[:nch], cost_linear=cl[:nch], cost_final=cf[:nch], chosen=chosen[:nch],
-                    transforms=tr[:nch * g].reshape(nch, g), degenerate=deg[:nr].astype(bool))
+        res = dict(placed=int(out[0]), not_placed=int(out[1]), steps=int(out[2]), n_degenerate=int(out[3]), stages=int(out[4]),
+                   status=status[:nch], cost_start=cs[:nch], cost_linear=cl[:nch], cost_final=cf[:nch], chosen=chosen[:nch],
+                   transforms=tr[:nch * g].reshape(nch, g), degenerate=deg[:nr].astype(bool))
+        if batched:
+            res["levels"] = int(out[5])
+        return res
 
     def place_chains(self, X, gn_steps=5):
         """The chains of the host matrix X (N x d) moved rigidly onto the fixed chains from the ranges between chains, on
@@ -1191,6 +1210,15 @@ class Context:
     def place_chains_dev(self, x_ptr, gn_steps=5):
         """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
         return self._pl_call(lambda *a: self.L.cora_place_chains_dev(self.h, C.c_void_p(x_ptr), *a), gn_steps)
+
+    def place_chains_batched(self, X, gn_steps=5):
+        """place_chains with every launch serving all stages of one level of the installed tables (the same bits); the dict
+        also holds levels."""
+        return self._with_host_X(lambda fn, g: self._pl_call(fn, g, batched=True), self.L.cora_place_chains_batched, X, gn_steps)
+
+    def place_chains_batched_dev(self, x_ptr, gn_steps=5):
+        """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
+        return self._pl_call(lambda *a: self.L.cora_place_chains_batched_dev(self.h, C.c_void_p(x_ptr), *a), gn_steps, batched=True)
 
     # ---- placement from pose-landmark sightings (include/cora_hip.h, cora_place_by_sightings_dev)
     def set_sighting_placement(self, chain_fixed=None, landmark_fixed=None, min_sightings=None):

@@ -224,8 +224,15 @@ struct PlTables {
   std::vector<int32_t> chunk_begin, chunk_len;                // [chunks]
   std::vector<int32_t> ent_q, ent_a, ent_m;                   // [entries]
   std::vector<unsigned char> chain_init;                      // [chains]: 0 a stage | 1 too few entries | 3 no entry | 4 fixed
-  int32_t *d_idx = nullptr;      // chunk_begin | chunk_len | ent_q | ent_a | ent_m
-  double *d_partial = nullptr;   // [kPlSums(d)][max_chunks]
+  // the levels (cora_place_chains_batched_dev): stages whose lists name only chains of earlier levels, so independent of
+  // each other; the greedy order stores every stage as a level of its own
+  int order = 0;                                              // CORA_PL_ORDER_GREEDY | CORA_PL_ORDER_LEVELS
+  int64_t max_level_chunks = 0;
+  std::vector<int32_t> level_stage0, level_tile0;             // [levels + 1]: into the stages, into the apply tiles
+  std::vector<int32_t> chunk_stage;                           // [chunks]
+  std::vector<int32_t> tile_stage, tile_off;                  // [tiles]: 256 positions of one chain, from tile_off within it
+  int32_t *d_idx = nullptr;      // chunk_begin | chunk_len | ent_q | ent_a | ent_m | chunk_stage | stage_chunk0 | stage_origin_q | stage_origin_a | stage_pos0 | stage_npos | tile_stage | tile_off
+  double *d_partial = nullptr;   // [kPlSums(d)][max_level_chunks] (>= max_chunks)
   double *d_state = nullptr;     // [stages][kPlState(d)]
   int32_t *d_istate = nullptr;   // [stages][kPlInts]
   void release() { free_device(d_idx, d_partial, d_state, d_istate); }

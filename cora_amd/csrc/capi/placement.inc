@@ -9,8 +9,13 @@ int pl_check(cora_ctx *c) {
   return CORA_OK;
 }
 
-// the order of the stages and their entry lists, from structure alone (host part of T only)
-int pl_build(cora_ctx *c, const unsigned char *chain_fixed, int min_ranges, PlTables &T) {
+// the order of the stages and their entry lists, from structure alone (host part of T only).  order CORA_PL_ORDER_GREEDY:
+// one chain at a time, the one with the most entries against the chains placed so far; a stage is a level of its own.
+// CORA_PL_ORDER_LEVELS: level k holds, in ascending chain index, every chain not yet placed with at least min_ranges
+// entries against the chains of levels < k, and a stage's list only those entries -- a range to a chain of the same level
+// is left out, which is what makes the stages of a level independent.
+int pl_build(cora_ctx *c, const unsigned char *chain_fixed, int min_ranges, int order, PlTables &T) {
+  if (order != CORA_PL_ORDER_GREEDY && order != CORA_PL_ORDER_LEVELS) return fail(c, CORA_ERR_ARG, "order must be CORA_PL_ORDER_GREEDY or CORA_PL_ORDER_LEVELS");
   const Layout &L = c->F.L;
   const MeasurementTable &M = c->meas;
   const OdomTables &O = c->odom;
@@ -46,14 +51,11 @@ int pl_build(cora_ctx *c, const unsigned char *chain_fixed, int min_ranges, PlTa
   for (int64_t ch = 0; ch < nch; ++ch)
     for (int64_t o = 0; o < nch; ++o)
       if (placed[static_cast<size_t>(o)]) against[static_cast<size_t>(ch)] += cnt[static_cast<size_t>(ch * nch + o)];
-  for (;;) {
-    int64_t take = -1, most = -1;
-    for (int64_t ch = 0; ch < nch; ++ch)
-      if (!placed[static_cast<size_t>(ch)] && against[static_cast<size_t>(ch)] > most) {  // (ties: the lowest index)
-        most = against[static_cast<size_t>(ch)];
-        take = ch;
-      }
-    if (take < 0 || most < min_ranges) break;
+  T.order = order;
+  T.level_stage0.assign(1, 0);
+  T.level_tile0.assign(1, 0);
+  // the stage of chain `take`: its entries against the chains placed at this moment, in table order
+  auto add_stage = [&](int64_t take) {
     const size_t begin = T.ent_m.size();
     for (size_t u = 0; u < use_m.size(); ++u) {
       const int32_t m = use_m[u];
@@ -65,16 +67,49 @@ int pl_build(cora_ctx *c, const unsigned char *chain_fixed, int min_ranges, PlTa
       T.ent_m.push_back(m);
     }
     const int64_t len = static_cast<int64_t>(T.ent_m.size() - begin);
-    cut_chunks(static_cast<int64_t>(begin), len, T.chunk_begin, T.chunk_len, nullptr, 0);
+    const int32_t stage = static_cast<int32_t>(T.stage_chain.size()), npos = static_cast<int32_t>(maps.chain_pos[static_cast<size_t>(take)].size());
+    cut_chunks(static_cast<int64_t>(begin), len, T.chunk_begin, T.chunk_len, &T.chunk_stage, stage);
     T.stage_chain.push_back(static_cast<int32_t>(take));
     T.stage_origin_q.push_back(T.ent_q[begin]);
     T.stage_origin_a.push_back(T.ent_a[begin]);
     T.stage_pos0.push_back(maps.chain_pos[static_cast<size_t>(take)].front());
-    T.stage_npos.push_back(static_cast<int32_t>(maps.chain_pos[static_cast<size_t>(take)].size()));
+    T.stage_npos.push_back(npos);
     T.stage_chunk0.push_back(static_cast<int32_t>(T.chunk_begin.size()));
     T.max_chunks = std::max<int64_t>(T.max_chunks, (len + kPlChunk - 1) / kPlChunk);
+    for (int32_t off = 0; off < npos; off += 256) {
+      T.tile_stage.push_back(stage);
+      T.tile_off.push_back(off);
+    }
+  };
+  auto now_placed = [&](int64_t take) {
     placed[static_cast<size_t>(take)] = 1;
     for (int64_t ch = 0; ch < nch; ++ch) against[static_cast<size_t>(ch)] += cnt[static_cast<size_t>(ch * nch + take)];
+  };
+  auto end_level = [&] {
+    T.max_level_chunks = std::max<int64_t>(T.max_level_chunks, static_cast<int64_t>(T.chunk_begin.size()) - T.stage_chunk0[static_cast<size_t>(T.level_stage0.back())]);
+    T.level_stage0.push_back(static_cast<int32_t>(T.stage_chain.size()));
+    T.level_tile0.push_back(static_cast<int32_t>(T.tile_stage.size()));
+  };
+  while (order == CORA_PL_ORDER_GREEDY) {
+    int64_t take = -1, most = -1;
+    for (int64_t ch = 0; ch < nch; ++ch)
+      if (!placed[static_cast<size_t>(ch)] && against[static_cast<size_t>(ch)] > most) {  // (ties: the lowest index)
+        most = against[static_cast<size_t>(ch)];
+        take = ch;
+      }
+    if (take < 0 || most < min_ranges) break;
+    add_stage(take);
+    now_placed(take);
+    end_level();
+  }
+  while (order == CORA_PL_ORDER_LEVELS) {
+    std::vector<int64_t> level;
+    for (int64_t ch = 0; ch < nch; ++ch)
+      if (!placed[static_cast<size_t>(ch)] && against[static_cast<size_t>(ch)] >= min_ranges) level.push_back(ch);
+    if (level.empty()) break;
+    for (const int64_t take : level) add_stage(take);  // (all against the chains of the levels before)
+    for (const int64_t take : level) now_placed(take);
+    end_level();
   }
   for (int64_t ch = 0; ch < nch; ++ch) {
     if (placed[static_cast<size_t>(ch)]) continue;
@@ -89,9 +124,10 @@ int pl_build(cora_ctx *c, const unsigned char *chain_fixed, int min_ranges, PlTa
 
 // the device side of freshly built tables (T's device pointers are null); on failure T owns what was allocated
 int pl_upload(cora_ctx *c, PlTables &T) {
-  HIP_TRY(c, upload_joined(&T.d_idx, {&T.chunk_begin, &T.chunk_len, &T.ent_q, &T.ent_a, &T.ent_m}));
+  HIP_TRY(c, upload_joined(&T.d_idx, {&T.chunk_begin, &T.chunk_len, &T.ent_q, &T.ent_a, &T.ent_m, &T.chunk_stage, &T.stage_chunk0, &T.stage_origin_q,
+                                      &T.stage_origin_a, &T.stage_pos0, &T.stage_npos, &T.tile_stage, &T.tile_off}));
   const int d = c->F.L.d;
-  const size_t ns = std::max<size_t>(T.stage_chain.size(), 1), nc = static_cast<size_t>(std::max<int64_t>(T.max_chunks, 1));
+  const size_t ns = std::max<size_t>(T.stage_chain.size(), 1), nc = static_cast<size_t>(std::max<int64_t>(T.max_level_chunks, 1));  // (>= max_chunks)
   HIP_TRY(c, alloc_device(&T.d_partial, static_cast<size_t>(kPlSums(d)) * nc * sizeof(double)));
   HIP_TRY(c, alloc_device(&T.d_state, static_cast<size_t>(kPlState(d)) * ns * sizeof(double)));
   HIP_TRY(c, alloc_device(&T.d_istate, static_cast<size_t>(kPlInts) * ns * sizeof(int32_t)));
@@ -103,6 +139,29 @@ int pl_args_check(cora_ctx *c, const double *X, int gn_steps, const int64_t *out
   if (gn_steps < 0 || gn_steps > kPlMaxSteps) return fail(c, CORA_ERR_ARG, "gn_steps must be in [0, 16]");
   if (!X || !out) return fail(c, CORA_ERR_ARG, "null pointer");
   return CORA_OK;
+}
+
+// the fields of the kernels' arguments that hold for every stage of a call on dX (pstride, and the stage's or level's own
+// fields, are the caller's)
+PlArgs pl_table_args(const cora_ctx *c, double *dX) {
+  const PlTables &T = c->pl;
+  const OdomTables &O = c->odom;
+  const size_t nc = T.chunk_begin.size(), ne = T.ent_m.size();
+  PlArgs A;
+  A.d = c->F.L.d;
+  A.n_ranges = c->meas.n_ranges;
+  A.chunk_begin = T.d_idx;
+  A.chunk_len = A.chunk_begin + nc;
+  A.ent_q = A.chunk_len + nc;
+  A.ent_a = A.ent_q + ne;
+  A.ent_m = A.ent_a + ne;
+  A.pos_rot = O.d_idx + 2 * O.P;
+  A.pos_trn = O.d_idx + 3 * O.P;
+  A.range_data = c->meas.d_range_data;
+  A.partial = T.d_partial;
+  A.x = dX;
+  A.flag = c->d_flag;
+  return A;
 }
 
 // what a call returns, from the stages' state ([stages][kPlState(d)], [stages][kPlInts])
@@ -203,7 +262,14 @@ int cora_set_chain_placement(cora_ctx *c, const unsigned char *chain_fixed, int 
   if (!c) return CORA_ERR_ARG;
   int rc = pl_check(c);
   if (rc) return rc;
-  return install_tables(c, c->pl, [&](PlTables &T) { return pl_build(c, chain_fixed, min_ranges, T); }, [&](PlTables &T) { return pl_upload(c, T); });
+  return install_tables(c, c->pl, [&](PlTables &T) { return pl_build(c, chain_fixed, min_ranges, CORA_PL_ORDER_GREEDY, T); }, [&](PlTables &T) { return pl_upload(c, T); });
+}
+
+int cora_set_chain_placement_order(cora_ctx *c, const unsigned char *chain_fixed, int min_ranges, int order) {
+  if (!c) return CORA_ERR_ARG;
+  int rc = pl_check(c);
+  if (rc) return rc;
+  return install_tables(c, c->pl, [&](PlTables &T) { return pl_build(c, chain_fixed, min_ranges, order, T); }, [&](PlTables &T) { return pl_upload(c, T); });
 }
 
 int cora_chain_placement_counts(const cora_ctx *c, int64_t out[4]) {
@@ -221,54 +287,71 @@ int cora_chain_placement_order(const cora_ctx *c, int32_t *stage_chain) {
   return CORA_OK;
 }
 
-int cora_place_chains_dev(cora_ctx *c, double *dX, int gn_steps, int64_t out[5], unsigned char *status, double *cost_start,
-                          double *cost_linear, double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate) {
-  if (!c) return CORA_ERR_ARG;
+namespace {
+// both device-pointer forms: stage after stage (17 launches per stage at 5 steps), or level after level with every launch
+// serving all stages of the level (the same number per level); then the range rows and the results
+int pl_place_dev(cora_ctx *c, double *dX, int gn_steps, bool batched, int64_t *out, unsigned char *status, double *cost_start,
+                 double *cost_linear, double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate) {
   int rc = pl_check(c);
   if (rc) return rc;
   NEED_DEVICE(c);
   if ((rc = pl_args_check(c, dX, gn_steps, out))) return rc;
-  const Layout &L = c->F.L;
-  const MeasurementTable &M = c->meas;
   PlTables &T = c->pl;
-  const OdomTables &O = c->odom;
-  const int d = L.d;
-  const size_t ns = T.stage_chain.size(), nc = T.chunk_begin.size(), ne = T.ent_m.size();
-  PlArgs A;
-  A.d = d;
-  A.n_ranges = M.n_ranges;
-  A.pstride = std::max<int64_t>(T.max_chunks, 1);
-  A.chunk_begin = T.d_idx;
-  A.chunk_len = A.chunk_begin + nc;
-  A.ent_q = A.chunk_len + nc;
-  A.ent_a = A.ent_q + ne;
-  A.ent_m = A.ent_a + ne;
-  A.pos_rot = O.d_idx + 2 * O.P;
-  A.pos_trn = O.d_idx + 3 * O.P;
-  A.range_data = M.d_range_data;
-  A.partial = T.d_partial;
-  A.x = dX;
-  A.flag = c->d_flag;
+  const int d = c->F.L.d;
+  const size_t ns = T.stage_chain.size(), nl = T.level_stage0.size() - 1;
+  PlArgs A = pl_table_args(c, dX);
   wrote(c, dX);
   HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
-  for (size_t s = 0; s < ns; ++s) {  // dependent: a stage reads the rows the stages before it wrote
-    A.chunk0 = T.stage_chunk0[s];
-    A.n_chunks = T.stage_chunk0[s + 1] - T.stage_chunk0[s];
-    A.origin_q = T.stage_origin_q[s];
-    A.origin_a = T.stage_origin_a[s];
-    A.pos0 = T.stage_pos0[s];
-    A.n_pos = T.stage_npos[s];
-    A.state = T.d_state + s * kPlState(d);
-    A.istate = T.d_istate + s * kPlInts;
-    A.step = 0;
-    A.last = 0;
-    HIP_TRY(c, launch_place_linear(A, c->stream));
+  // linear stage, evaluations 0 .. gn_steps + 1, apply: of one stage (PlArgs) or of one level (PlBatchArgs)
+  auto launches = [&](auto &K, PlArgs &S) -> int {
+    S.step = 0;
+    S.last = 0;
+    HIP_TRY(c, launch_place_linear(K, c->stream));
     for (int step = 0; step <= gn_steps + 1; ++step) {
-      A.step = step;
-      A.last = step == gn_steps + 1 ? 1 : 0;
-      HIP_TRY(c, launch_place_gn(A, c->stream));
+      S.step = step;
+      S.last = step == gn_steps + 1 ? 1 : 0;
+      HIP_TRY(c, launch_place_gn(K, c->stream));
     }
-    HIP_TRY(c, launch_place_apply(A, c->stream));
+    HIP_TRY(c, launch_place_apply(K, c->stream));
+    return static_cast<int>(CORA_OK);
+  };
+  if (!batched) {
+    A.pstride = std::max<int64_t>(T.max_chunks, 1);
+    for (size_t s = 0; s < ns; ++s) {  // dependent: a stage reads the rows the stages before it wrote
+      A.chunk0 = T.stage_chunk0[s];
+      A.n_chunks = T.stage_chunk0[s + 1] - T.stage_chunk0[s];
+      A.origin_q = T.stage_origin_q[s];
+      A.origin_a = T.stage_origin_a[s];
+      A.pos0 = T.stage_pos0[s];
+      A.n_pos = T.stage_npos[s];
+      A.state = T.d_state + s * kPlState(d);
+      A.istate = T.d_istate + s * kPlInts;
+      if ((rc = launches(A, A))) return rc;
+    }
+  } else {
+    PlBatchArgs B;
+    A.pstride = std::max<int64_t>(T.max_level_chunks, 1);
+    A.state = T.d_state;
+    A.istate = T.d_istate;
+    B.A = A;
+    B.chunk_stage = A.ent_m + T.ent_m.size();
+    B.stage_chunk0 = B.chunk_stage + T.chunk_begin.size();
+    B.stage_origin_q = B.stage_chunk0 + ns + 1;
+    B.stage_origin_a = B.stage_origin_q + ns;
+    B.stage_pos0 = B.stage_origin_a + ns;
+    B.stage_npos = B.stage_pos0 + ns;
+    B.tile_stage = B.stage_npos + ns;
+    B.tile_off = B.tile_stage + T.tile_stage.size();
+    for (size_t l = 0; l < nl; ++l) {  // dependent: a level reads the rows the levels before it wrote
+      const size_t s0 = static_cast<size_t>(T.level_stage0[l]), s1 = static_cast<size_t>(T.level_stage0[l + 1]);
+      B.stage0 = static_cast<int32_t>(s0);
+      B.n_stages = static_cast<int32_t>(s1 - s0);
+      B.A.chunk0 = T.stage_chunk0[s0];
+      B.A.n_chunks = T.stage_chunk0[s1] - T.stage_chunk0[s0];
+      B.tile0 = T.level_tile0[l];
+      B.n_tiles = T.level_tile0[l + 1] - T.level_tile0[l];
+      if ((rc = launches(B, B.A))) return rc;
+    }
   }
   std::vector<double> state(ns * kPlState(d));
   std::vector<int32_t> ist(ns * kPlInts);
@@ -277,7 +360,40 @@ int cora_place_chains_dev(cora_ctx *c, double *dX, int gn_steps, int64_t out[5],
                             [&] { return read_back_state(c, state, T.d_state, ist, T.d_istate); })))
     return rc;
   pl_results(c, state, ist, n_deg, out, status, cost_start, cost_linear, cost_final, chosen, transforms);
+  if (batched) out[5] = static_cast<int64_t>(nl);
   return CORA_OK;
+}
+}  // namespace
+
+int cora_chain_placement_levels(const cora_ctx *c, int32_t *stage_level) {
+  if (!c || !stage_level) return CORA_ERR_ARG;
+  const std::vector<int32_t> &l0 = c->pl.level_stage0;
+  for (size_t l = 0; l + 1 < l0.size(); ++l) std::fill(stage_level + l0[l], stage_level + l0[l + 1], static_cast<int32_t>(l + 1));  // (level 0: the fixed chains)
+  return CORA_OK;
+}
+
+int cora_place_chains_dev(cora_ctx *c, double *dX, int gn_steps, int64_t out[5], unsigned char *status, double *cost_start,
+                          double *cost_linear, double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate) {
+  if (!c) return CORA_ERR_ARG;
+  return pl_place_dev(c, dX, gn_steps, false, out, status, cost_start, cost_linear, cost_final, chosen, transforms, degenerate);
+}
+
+int cora_place_chains_batched_dev(cora_ctx *c, double *dX, int gn_steps, int64_t out[6], unsigned char *status, double *cost_start,
+                                  double *cost_linear, double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate) {
+  if (!c) return CORA_ERR_ARG;
+  return pl_place_dev(c, dX, gn_steps, true, out, status, cost_start, cost_linear, cost_final, chosen, transforms, degenerate);
+}
+
+int cora_place_chains_batched(cora_ctx *c, double *X, int ldx, int gn_steps, int64_t out[6], unsigned char *status, double *cost_start,
+                              double *cost_linear, double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate) {
+  if (!c) return CORA_ERR_ARG;
+  int rc = pl_check(c);
+  if (rc) return rc;
+  NEED_DEVICE(c);
+  if ((rc = pl_args_check(c, X, gn_steps, out))) return rc;
+  return with_uploaded_x(c, X, ldx, [&](double *dX) {
+    return cora_place_chains_batched_dev(c, dX, gn_steps, out, status, cost_start, cost_linear, cost_final, chosen, transforms, degenerate);
+  });
 }
 
 int cora_place_chains(cora_ctx *c, double *X, int ldx, int gn_steps, int64_t out[5], unsigned char *status, double *cost_start,

@@ -1178,9 +1178,12 @@ Matrix Problem::rangeAidedInitialization(uint64_t seed, int gn_steps, LandmarkIn
                        ClosureConsensus(), consensus);
 }
 
-Matrix Problem::multiRobotInitialization(uint64_t seed, int gn_steps, int min_ranges, ChainPlacementInfo *chains_info, LandmarkInitInfo *info) const {
+Matrix Problem::multiRobotInitialization(uint64_t seed, int gn_steps, int min_ranges, ChainPlacementInfo *chains_info, LandmarkInitInfo *info,
+                                         ChainOrder order) const {
   if (gn_steps < 0) throw std::invalid_argument("Problem::multiRobotInitialization: gn_steps must be in [0, 16]");
-  return odometryStart(seed, gn_steps, info, "Problem::multiRobotInitialization", true, min_ranges, chains_info);
+  if (order != ChainOrder::Greedy && order != ChainOrder::Levels) throw std::invalid_argument("Problem::multiRobotInitialization: unknown ChainOrder");
+  return odometryStart(seed, gn_steps, info, "Problem::multiRobotInitialization", true, min_ranges, chains_info, false, 0, nullptr, false, 0, nullptr,
+                       ClosureConsensus(), RangeConsensus(), SightingConsensus(), order);
 }
 
 namespace {
@@ -1219,7 +1222,7 @@ Matrix Problem::closureInitialization(uint64_t seed, int gn_steps, int min_range
 Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where, bool place, int min_ranges,
                               ChainPlacementInfo *chains_info, bool sightings, int min_sightings, SightingPlacementInfo *sight_info, bool closures,
                               int min_closures, ClosurePlacementInfo *closure_info, ClosureConsensus consensus,
-                              RangeConsensus range_consensus, SightingConsensus sighting_consensus) const {
+                              RangeConsensus range_consensus, SightingConsensus sighting_consensus, ChainOrder chain_order) const {
   checkUpToDate();
   if (part_world_ > 1) throw std::runtime_error(std::string(where) + ": not supported on a partitioned handle");
   ensureMeasurementTable();
@@ -1403,16 +1406,25 @@ Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *inf
     // (after every draw of odometryInitialization: the placement draws nothing.  Its range rows are recomputed by the
     // multilateration below, which also decides the fallback directions.)
     const size_t nch = chains.size(), G = static_cast<size_t>(d) * d + d;
-    CORA_CALL(cora_set_chain_placement(c, chain_done.empty() ? nullptr : chain_done.data(), min_ranges > 0 ? min_ranges : 4 * (d == 2 ? 7 : 16)), where);
-    int64_t out[5] = {0, 0, 0, 0, 0};
+    const unsigned char *fixed = chain_done.empty() ? nullptr : chain_done.data();
+    const int least = min_ranges > 0 ? min_ranges : 4 * (d == 2 ? 7 : 16);
+    int64_t out[6] = {0, 0, 0, 0, 0, 0};
     std::vector<unsigned char> status(nch + 1, 0);
     std::vector<double> cs(nch + 1, 0.0), cl(nch + 1, 0.0), cf(nch + 1, 0.0), tr(nch * G + 1, 0.0);
-    CORA_CALL(cora_place_chains_dev(c, v.x, gn_steps, out, status.data(), cs.data(), cl.data(), cf.data(), nullptr, tr.data(), nullptr), where);
+    if (chain_order == ChainOrder::Levels) {  // a level's chains together
+      CORA_CALL(cora_set_chain_placement_order(c, fixed, least, CORA_PL_ORDER_LEVELS), where);
+      CORA_CALL(cora_place_chains_batched_dev(c, v.x, gn_steps, out, status.data(), cs.data(), cl.data(), cf.data(), nullptr, tr.data(), nullptr), where);
+    } else {
+      CORA_CALL(cora_set_chain_placement(c, fixed, least), where);
+      CORA_CALL(cora_place_chains_dev(c, v.x, gn_steps, out, status.data(), cs.data(), cl.data(), cf.data(), nullptr, tr.data(), nullptr), where);
+      out[5] = out[4];
+    }
     if (chains_info) {
       chains_info->placed = static_cast<long>(out[0]);
       chains_info->not_placed = static_cast<long>(out[1]);
       chains_info->gn_steps = static_cast<long>(out[2]);
       chains_info->stages = static_cast<long>(out[4]);
+      chains_info->levels = static_cast<long>(out[5]);
       chains_info->status.assign(status.begin(), status.begin() + static_cast<std::ptrdiff_t>(nch));
       chains_info->cost_start.assign(cs.begin(), cs.begin() + static_cast<std::ptrdiff_t>(nch));
       chains_info->cost_linear.assign(cl.begin(), cl.begin() + static_cast<std::ptrdiff_t>(nch));

@@ -178,11 +178,17 @@ struct RangeConsensus {
   int min_consensus = 0;
 };
 
+/** The order of the stages of Problem::multiRobotInitialization (cora_set_chain_placement_order, include/cora_hip.h): Greedy,
+ * one chain after the other; Levels, every chain that can be placed independently in one level, a level's chains placed
+ * together (cora_place_chains_batched_dev) -- from fewer ranges where chains of one level range against each other. */
+enum class ChainOrder { Greedy = 0, Levels = 1 };
+
 /** What Problem::multiRobotInitialization reports about the chains (cora_place_chains_dev, include/cora_hip.h). */
 struct ChainPlacementInfo {
   long placed = 0, not_placed = 0;     // chains moved onto the fixed ones | left at their random start
   long gn_steps = 0;                   // Gauss-Newton steps taken, summed over the stages
   long stages = 0;
+  long levels = 0;                     // ChainOrder::Levels: the levels the stages stand in; Greedy: = stages
   std::vector<unsigned char> status;   // per chain (0 placed, 1 too few ranges, 2 placed without the linear stage, 3 no range, 4 fixed)
   std::vector<Scalar> cost_start, cost_linear, cost_final;  // per chain: sum omega (|R q + t - a| - r)^2 over the stage's entries
   std::vector<Scalar> transforms;      // per chain d * d + d: R row-major, then t, as written
@@ -332,7 +338,7 @@ class Problem {
                        SightingPlacementInfo *sight_info = nullptr, bool closures = false, int min_closures = 0,
                        ClosurePlacementInfo *closure_info = nullptr, ClosureConsensus consensus = ClosureConsensus(),
                        RangeConsensus range_consensus = RangeConsensus(),
-                       SightingConsensus sighting_consensus = SightingConsensus()) const;
+                       SightingConsensus sighting_consensus = SightingConsensus(), ChainOrder chain_order = ChainOrder::Greedy) const;
   void fillImplicitFormulationMatrices() const;
   [[noreturn]] void throwLast(int status, const char *where) const;
 
@@ -557,9 +563,13 @@ class Problem {
    * placed --, then the placement, the multilateration over the poses a chain wrote, the range rows and the lift.  Rows of
    * chains that are not placed and of landmarks that are not solved have rangeAidedInitialization's bits.  min_ranges <= 0:
    * 4 x the unknowns of the linear stage (28 at d = 2, 64 at d = 3), a judgement (profiles/chain_placement.md).  A stage
-   * never raises the range cost over its own entries; nothing else is promised.  std::runtime_error on a partitioned handle. */
+   * never raises the range cost over its own entries; nothing else is promised.  std::runtime_error on a partitioned handle.
+   * order: ChainOrder::Greedy (the default: the bits of the call without the argument) or ChainOrder::Levels, the level
+   * order with a level's chains placed in the same launches (cora_place_chains_batched_dev): 17 launches per level at 5 steps
+   * where the greedy order spends 17 per chain, at the price of ignoring the ranges between chains of one level
+   * (profiles/chain_placement_levels.md). */
   Matrix multiRobotInitialization(uint64_t seed = 7, int gn_steps = 5, int min_ranges = 0, ChainPlacementInfo *chains_info = nullptr,
-                                  LandmarkInitInfo *info = nullptr) const;
+                                  LandmarkInitInfo *info = nullptr, ChainOrder order = ChainOrder::Greedy) const;
   /** EXTENSION beyond the reference: multiRobotInitialization with landmarks and chains first placed from the
    * pose-landmark sightings (cora_place_by_sightings_dev), chain 0 fixed: exactly the draws of odometryInitialization in
    * the same order (the new step draws nothing), then the sighting placement, then cora_place_chains_dev for the chains

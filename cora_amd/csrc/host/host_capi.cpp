@@ -333,10 +333,22 @@ int cora_problem_range_aided_initialization_consensus(cora_problem *p, uint64_t 
 int cora_problem_multi_robot_initialization(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, double *out, int64_t counts[4],
                                             unsigned char *status, double *cost_start, double *cost_linear, double *cost_final,
                                             double *transforms, int64_t landmark_counts[4], unsigned char *landmark_status) {
+  int64_t five[5] = {0, 0, 0, 0, 0};
+  const int rc = cora_problem_multi_robot_initialization_order(p, seed, gn_steps, min_ranges, 0, out, counts ? five : nullptr, status, cost_start,
+                                                               cost_linear, cost_final, transforms, landmark_counts, landmark_status);
+  if (counts) std::copy(five, five + 4, counts);
+  return rc;
+}
+
+int cora_problem_multi_robot_initialization_order(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, int order, double *out,
+                                                  int64_t counts[5], unsigned char *status, double *cost_start, double *cost_linear,
+                                                  double *cost_final, double *transforms, int64_t landmark_counts[4],
+                                                  unsigned char *landmark_status) {
   return guarded([&] {
     ChainPlacementInfo ci;
     LandmarkInitInfo info;
-    const Matrix res = p->problem.multiRobotInitialization(seed, gn_steps, min_ranges, &ci, &info);
+    if (order != 0 && order != 1) throw std::invalid_argument("cora_problem_multi_robot_initialization_order: order must be 0 or 1");
+    const Matrix res = p->problem.multiRobotInitialization(seed, gn_steps, min_ranges, &ci, &info, order == 1 ? ChainOrder::Levels : ChainOrder::Greedy);
     if (res.rows() == p->problem.getExpectedVariableSize()) p->problem.checkVariablesAreValid(res);  // (throws off the manifold)
     std::memcpy(out, res.data(), sizeof(double) * static_cast<size_t>(res.size()));
     if (counts) {
@@ -344,6 +356,7 @@ int cora_problem_multi_robot_initialization(cora_problem *p, uint64_t seed, int 
       counts[1] = ci.not_placed;
       counts[2] = ci.gn_steps;
       counts[3] = ci.stages;
+      counts[4] = ci.levels;
     }
     if (status) std::copy(ci.status.begin(), ci.status.end(), status);
     if (cost_start) std::copy(ci.cost_start.begin(), ci.cost_start.end(), cost_start);

@@ -1222,6 +1222,27 @@ struct PlArgs {
 hipError_t launch_place_linear(const PlArgs &A, hipStream_t st);  // pass and fold of the linear stage
 hipError_t launch_place_gn(const PlArgs &A, hipStream_t st);      // pass and fold of evaluation A.step
 hipError_t launch_place_apply(const PlArgs &A, hipStream_t st);
+// The batched form (cora_place_chains_batched_dev): the host groups the stages into LEVELS (capi/placement.inc; a level's
+// stages read only rows that earlier levels wrote, so they are independent) and every launch serves ALL stages of one level:
+// the passes one workgroup per chunk of the level, the folds one wavefront per stage, the apply one workgroup per tile of
+// 256 positions of one chain -- 2 (s + 3) + 1 launches per level.  The kernels are the plain ones' bodies (template axis
+// BATCHED, kernels/placement.inc); terms, chunk sums and the fold's bracket order over a stage's own chunks are the plain
+// call's, so the bits are.  In A: chunk0 / n_chunks the LEVEL's chunks, partial [kPlSums(d)][pstride] indexed by the chunk's
+// place in its level (pstride >= the most chunks of a level), state / istate the arrays of ALL stages; origin_q, origin_a,
+// pos0, n_pos unused.
+struct PlBatchArgs {
+  PlArgs A;
+  int32_t stage0 = 0, n_stages = 0;                    // the level's stages
+  int32_t tile0 = 0, n_tiles = 0;                      // the level's apply tiles
+  const int32_t *chunk_stage = nullptr;                // [chunks of all stages]
+  const int32_t *stage_chunk0 = nullptr;               // [stages + 1]
+  const int32_t *stage_origin_q = nullptr, *stage_origin_a = nullptr;  // [stages]: INTERNAL rows of the first entry
+  const int32_t *stage_pos0 = nullptr, *stage_npos = nullptr;          // [stages]: the chain's positions in the chain tables
+  const int32_t *tile_stage = nullptr, *tile_off = nullptr;            // [tiles]: stage, first position of the tile within the chain
+};
+hipError_t launch_place_linear(const PlBatchArgs &B, hipStream_t st);
+hipError_t launch_place_gn(const PlBatchArgs &B, hipStream_t st);  // evaluation B.A.step
+hipError_t launch_place_apply(const PlBatchArgs &B, hipStream_t st);
 // pair p of the upper triangle in row-major order: (0,0), (0,1), .., (0,nt-1), (1,1), ..
 __host__ __device__ inline void pl_pair(int nt, int p, int *i, int *j) {
   int r = 0;

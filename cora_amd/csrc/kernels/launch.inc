@@ -874,3 +874,39 @@ hipError_t launch_combine(int64_t row0, int64_t rows, int nblocks, const double 
 }
 
 #endif  // CORA_TU & 2
+// the chain placement's batched form (kernels/placement.inc, BATCHED): every launch serves all stages of the one level B
+// describes.  A translation unit of its own: the plain and the batched kernels call the same functions of kernels.h, and the
+// compiler inlines and unrolls a function with one caller in a unit differently from one with two -- side by side the
+// plain kernels would no longer be the ones profiles/chain_placement.md measured.
+#if CORA_TU & 8
+static bool place_args_ok(const PlBatchArgs &B) {
+  const PlArgs &A = B.A;
+  return (A.d == 2 || A.d == 3) && A.n_chunks > 0 && A.chunk0 >= 0 && A.pstride >= A.n_chunks && B.n_stages > 0 && B.stage0 >= 0 &&
+         B.n_stages <= A.n_chunks && B.n_tiles >= B.n_stages && B.tile0 >= 0 && A.n_ranges > 0 && A.chunk_begin && A.chunk_len && A.ent_q &&
+         A.ent_a && A.ent_m && A.pos_rot && A.pos_trn && A.range_data && A.partial && A.state && A.istate && A.x && A.flag && B.chunk_stage &&
+         B.stage_chunk0 && B.stage_origin_q && B.stage_origin_a && B.stage_pos0 && B.stage_npos && B.tile_stage && B.tile_off;
+}
+hipError_t launch_place_linear(const PlBatchArgs &B, hipStream_t st) {
+  if (!place_args_ok(B)) return hipErrorInvalidValue;
+  const dim3 chunks(static_cast<unsigned>(B.A.n_chunks)), stages(static_cast<unsigned>(B.n_stages));
+  for_d(B.A.d, [&](auto D) {
+    hipLaunchKernelGGL((k_pl_pass_linear<D(), true>), chunks, dim3(kPlChunk), 0, st, B);
+    hipLaunchKernelGGL((k_pl_fold_linear<D(), true>), stages, dim3(kWave), 0, st, B);
+  });
+  return hipGetLastError();
+}
+hipError_t launch_place_gn(const PlBatchArgs &B, hipStream_t st) {
+  if (!place_args_ok(B) || B.A.step < 0 || B.A.step > kPlMaxSteps + 1) return hipErrorInvalidValue;
+  const dim3 chunks(static_cast<unsigned>(B.A.n_chunks)), stages(static_cast<unsigned>(B.n_stages));
+  for_d(B.A.d, [&](auto D) {
+    hipLaunchKernelGGL((k_pl_pass_gn<D(), true>), chunks, dim3(kPlChunk), 0, st, B);
+    hipLaunchKernelGGL((k_pl_fold_gn<D(), true>), stages, dim3(kWave), 0, st, B);
+  });
+  return hipGetLastError();
+}
+hipError_t launch_place_apply(const PlBatchArgs &B, hipStream_t st) {
+  if (!place_args_ok(B)) return hipErrorInvalidValue;
+  for_d(B.A.d, [&](auto D) { hipLaunchKernelGGL((k_pl_apply<D(), true>), dim3(static_cast<unsigned>(B.n_tiles)), dim3(256), 0, st, B); });
+  return hipGetLastError();
+}
+#endif  // CORA_TU & 8

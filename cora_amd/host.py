@@ -247,23 +247,31 @@ class Problem:
         return out, dict(**extra, solved=int(cnt[0]), not_solved=int(cnt[1]), n_degenerate=int(cnt[2]), steps=int(cnt[3]),
                          status=status[:nl], cost_linear=cl[:nl], cost_final=cf[:nl])
 
-    def multi_robot_initialization(self, seed=7, gn_steps=5, min_ranges=0):
+    def multi_robot_initialization(self, seed=7, gn_steps=5, min_ranges=0, order=None):
         """Problem::multiRobotInitialization: (x0, info) with info a dict placed, not_placed, steps, stages, status, cost_start,
         cost_linear, cost_final, transforms (per chain of odometry_chains()), landmarks (the dict of
-        range_aided_initialization without the costs).  min_ranges 0: the default.  The start has passed checkVariablesAreValid."""
+        range_aided_initialization without the costs).  min_ranges 0: the default.  The start has passed checkVariablesAreValid.
+        order: None, the call without the argument (ChainOrder::Greedy); "greedy" | "levels", the ChainOrder given, and info
+        gains levels."""
+        if order not in (None, "greedy", "levels"):
+            raise ValueError("order must be None, 'greedy' or 'levels'")
         dm = self.dims()
         d = dm["d"]
         nl = dm["N"] - (d + 1) * dm["n"] - dm["r"]
         nch = len(self.odometry_chains())
         out = np.zeros((dm["N"], dm["rank"]), order="F")
-        cnt, lcnt = (C.c_int64 * 4)(), (C.c_int64 * 4)()
+        cnt, lcnt = (C.c_int64 * 5)(), (C.c_int64 * 4)()
         status, lstatus = np.zeros(nch + 1, dtype=np.uint8), np.zeros(nl + 1, dtype=np.uint8)
         cs, cl, cf, tr = np.zeros(nch + 1), np.zeros(nch + 1), np.zeros(nch + 1), np.zeros(nch * (d * d + d) + 1)
-        self._chk(self.L.cora_problem_multi_robot_initialization(
-            self.h, C.c_uint64(seed), int(gn_steps), int(min_ranges), out.ctypes.data_as(_dp), cnt, status.ctypes.data_as(C.c_void_p),
-            cs.ctypes.data_as(_dp), cl.ctypes.data_as(_dp), cf.ctypes.data_as(_dp), tr.ctypes.data_as(_dp), lcnt,
-            lstatus.ctypes.data_as(C.c_void_p)))
-        return out, dict(placed=int(cnt[0]), not_placed=int(cnt[1]), steps=int(cnt[2]), stages=int(cnt[3]), status=status[:nch],
+        tail = (out.ctypes.data_as(_dp), cnt, status.ctypes.data_as(C.c_void_p), cs.ctypes.data_as(_dp), cl.ctypes.data_as(_dp),
+                cf.ctypes.data_as(_dp), tr.ctypes.data_as(_dp), lcnt, lstatus.ctypes.data_as(C.c_void_p))
+        if order is None:
+            self._chk(self.L.cora_problem_multi_robot_initialization(self.h, C.c_uint64(seed), int(gn_steps), int(min_ranges), *tail))
+        else:
+            self._chk(self.L.cora_problem_multi_robot_initialization_order(self.h, C.c_uint64(seed), int(gn_steps), int(min_ranges),
+                                                                           1 if order == "levels" else 0, *tail))
+        extra = {} if order is None else dict(levels=int(cnt[4]))
+        return out, dict(**extra, placed=int(cnt[0]), not_placed=int(cnt[1]), steps=int(cnt[2]), stages=int(cnt[3]), status=status[:nch],
                          cost_start=cs[:nch], cost_linear=cl[:nch], cost_final=cf[:nch], transforms=tr[:-1].reshape(nch, d * d + d),
                          landmarks=dict(solved=int(lcnt[0]), not_solved=int(lcnt[1]), n_degenerate=int(lcnt[2]), steps=int(lcnt[3]),
                                         status=lstatus[:nl]))

@@ -31,7 +31,7 @@ int main(int argc, char **argv) {
   CORA::RangeConsensus range_consensus;
   CORA::SightingConsensus sighting_consensus;
   bool consensus_given = false, range_consensus_given = false, sighting_consensus_given = false;
-  bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false, landmark_init = false, place_chains = false, sightings = false, closures = false;
+  bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false, landmark_init = false, place_chains = false, chain_levels = false, sightings = false, closures = false;
   for (int i = 2; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--jacobi") jacobi = true;
@@ -72,6 +72,8 @@ int main(int argc, char **argv) {
     // with --odom-init --device-init: the chains after the first are first placed from the pose-pose ranges between chains
     // (Problem::multiRobotInitialization, which then places the landmarks as --landmark-init does)
     else if (a == "--place-chains") place_chains = true;
+    // with --place-chains: the level order, a level's chains placed together (ChainOrder::Levels)
+    else if (a == "--chain-levels") chain_levels = true;
     // with --odom-init --device-init: landmarks and chains are first placed from the pose-landmark sightings, then the chains
     // that are left from the ranges and the landmarks that are left by multilateration (Problem::sightingInitialization)
     else if (a == "--sightings") sightings = true;
@@ -93,6 +95,7 @@ int main(int argc, char **argv) {
   try {
     if (device_init && !odom) throw std::runtime_error("--device-init composes the odometry start on the device: it needs --odom-init");
     if (place_chains && !device_init) throw std::runtime_error("--place-chains places the chains of the device's odometry start: it needs --odom-init --device-init");
+    if (chain_levels && !place_chains) throw std::runtime_error("--chain-levels chooses the order of --place-chains: it needs --place-chains");
     if (sightings && !device_init) throw std::runtime_error("--sightings places landmarks and chains of the device's odometry start: it needs --odom-init --device-init");
     if (closures && !device_init) throw std::runtime_error("--closures places the chains of the device's odometry start: it needs --odom-init --device-init");
     if (consensus_given && !closures) throw std::runtime_error("--closure-consensus and --closure-min-consensus set the vote of the closure step: they need --closures");
@@ -174,9 +177,10 @@ int main(int argc, char **argv) {
         return problem.measurementResiduals(implicit ? CORA::Matrix(x.block(0, 0, problem.rotAndRangeMatrixSize(), x.cols())) : x).range_sum;
       };
       const double without = range_sum(x0);  // (the start as it stands: with the landmarks placed under --landmark-init)
-      x0 = problem.multiRobotInitialization(7, gn_steps, 0, &ci);
+      x0 = problem.multiRobotInitialization(7, gn_steps, 0, &ci, nullptr, chain_levels ? CORA::ChainOrder::Levels : CORA::ChainOrder::Greedy);
       std::printf("chain placement: %ld chains placed, %ld not placed (%ld Gauss-Newton steps); range residual sum at the start %.6e with it, %.6e without\n",
                   ci.placed, ci.not_placed, ci.gn_steps, range_sum(x0), without);
+      if (chain_levels) std::printf("chain placement: level order, %ld stages in %ld levels\n", ci.stages, ci.levels);
     }
     if (sightings) {  // (an extension beyond the reference: Problem::sightingInitialization)
       CORA::SightingPlacementInfo si;

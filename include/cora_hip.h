@@ -994,6 +994,44 @@ int cora_debug_place_chains_host(cora_ctx *ctx, double *X, int ldx, int gn_steps
                                  double *cost_start, double *cost_linear, double *cost_final, int32_t *chosen, double *transforms,
                                  unsigned char *degenerate);
 
+/* ---- CHAIN PLACEMENT FROM INTER-ROBOT RANGES: LEVELS, and a level's chains placed together ----------------------------------
+ * A second, opt-in order of the stages of the chain placement above and the batched launches it makes possible.  The greedy
+ * order, cora_set_chain_placement, cora_place_chains_dev and their bits are unchanged.
+ * DEFINITIONS.
+ *   level order      level 0 = the chains of chain_fixed (NULL: chain 0).  Level k >= 1 = every chain not yet placed whose
+ *                    entries against chains of levels < k number at least min_ranges; its stages stand in ascending chain
+ *                    index.  A stage's list: the chain's entries against chains of levels < k ONLY, in table order -- an
+ *                    entry against a chain of the same level is NOT in the list, which is what makes the stages of a level
+ *                    independent of each other.  The order ends where a level would be empty; the chains left over have
+ *                    status 1 or 3 by the rule above.  From structure alone, like the greedy order.
+ *   THE LIMIT        a chain is placed from FEWER ranges than under the greedy order wherever chains of its own level range
+ *                    against it: those ranges are ignored (under the greedy order the later of the two chains uses them).
+ *                    Where every chain ranges only against earlier levels (a star, a relay) the lists and the bits coincide.
+ *                    Measured on the shipped data sets: profiles/chain_placement_levels.md.  The promise is the one above: a
+ *                    stage never raises the range cost over its own entries.
+ *   greedy as levels the greedy order stores every stage as a level of its own, so every call below serves both orders.
+ * cora_set_chain_placement_order   cora_set_chain_placement with the order chosen: CORA_PL_ORDER_GREEDY gives its tables
+ *            exactly, CORA_PL_ORDER_LEVELS the level order.  Counts, the order of the stages, the plain device forms and the
+ *            host mirror run on either tables, one stage after the other in table order -- a legal dependent order, so they
+ *            are the reference and the mirror of the batched call.
+ * cora_chain_placement_levels   stage_level[stages] = the level k >= 1 of every stage, in the order of the stages
+ *            (ascending; level 0, the fixed chains, has no stage).  The number of levels is the last entry.
+ * cora_place_chains_batched_dev   cora_place_chains_dev with every launch serving ALL stages of one level: the passes one
+ *            workgroup per chunk of the level, the folds one wavefront per stage, the apply one workgroup per 256 positions
+ *            of one chain.  2 (gn_steps + 3) + 1 launches per LEVEL, then the range rows.  out (host) = the five fields of
+ *            cora_place_chains_dev, then the number of levels.  Every other argument, every error and the state are
+ *            cora_place_chains_dev's; X, the per-chain outputs, the degenerate bytes and out[0..4] have its bits on the same
+ *            tables (the terms, the chunk sums and the fold's bracket order over a stage's own chunks are the same).
+ * cora_place_chains_batched       the host-pointer form. */
+enum { CORA_PL_ORDER_GREEDY = 0, CORA_PL_ORDER_LEVELS = 1 };
+int cora_set_chain_placement_order(cora_ctx *ctx, const unsigned char *chain_fixed /* [chains] or NULL */, int min_ranges, int order);
+int cora_chain_placement_levels(const cora_ctx *ctx, int32_t *stage_level);
+int cora_place_chains_batched_dev(cora_ctx *ctx, double *dX, int gn_steps, int64_t out[6], unsigned char *status, double *cost_start,
+                                  double *cost_linear, double *cost_final, int32_t *chosen, double *transforms,
+                                  unsigned char *degenerate);
+int cora_place_chains_batched(cora_ctx *ctx, double *X, int ldx, int gn_steps, int64_t out[6], unsigned char *status, double *cost_start,
+                              double *cost_linear, double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate);
+
 /* ---- PLACEMENT FROM POSE-LANDMARK SIGHTINGS, on the device ----------------------------------------------------------------
  * Places landmarks and whole odometry chains of a resident vector of d columns (the output of cora_odometry_init_dev)
  * from the pose-landmark sightings of the measurement table, in place; both solves are closed-form.  Needs a measurement

@@ -138,6 +138,12 @@ int cora_problem_range_aided_initialization_consensus(cora_problem *p, uint64_t 
 int cora_problem_multi_robot_initialization(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, double *out, int64_t counts[4],
                                             unsigned char *status, double *cost_start, double *cost_linear, double *cost_final,
                                             double *transforms, int64_t landmark_counts[4], unsigned char *landmark_status);
+/* The same with the order of the stages (ChainOrder, CORA_problem.h): 0 greedy -- the call above --, 1 levels, a level's
+ * chains placed together (include/cora_hip.h, cora_place_chains_batched_dev).  counts has a fifth entry, the levels. */
+int cora_problem_multi_robot_initialization_order(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, int order, double *out,
+                                                  int64_t counts[5], unsigned char *status, double *cost_start, double *cost_linear,
+                                                  double *cost_final, double *transforms, int64_t landmark_counts[4],
+                                                  unsigned char *landmark_status);
 /* Problem::sightingInitialization (an extension beyond the reference; include/cora_hip.h, "placement from pose-landmark
  * sightings").  min_ranges, min_sightings <= 0: the defaults.  out: data-matrix-size x rank.  counts = { chains fixed, placed,
  * not placed, landmarks placed, not placed, stages } of the sighting step; status, cost_start, cost_final, chosen: one entry
