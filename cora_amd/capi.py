@@ -1220,6 +1220,43 @@ class Context:
         """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
         return self._pl_call(lambda *a: self.L.cora_place_chains_batched_dev(self.h, C.c_void_p(x_ptr), *a), gn_steps, batched=True)
 
+    # ---- outlier-robust chain placement (include/cora_hip.h, cora_place_chains_robust_dev)
+    def _plr_call(self, fn, gn_steps, barc2, min_consensus):
+        nch, nr, g = self.odometry_chains_count()[0], self.measurement_counts()[1], self.d * self.d + self.d
+        out = (C.c_int64 * 8)()
+        status, chosen = np.zeros(nch + 1, dtype=np.uint8), np.zeros(nch + 1, dtype=np.int32)
+        cs, cl, cf, tr = np.zeros(nch + 1), np.zeros(nch + 1), np.zeros(nch + 1), np.zeros((nch + 1) * g)
+        el, cons, ll = (np.zeros(nch + 1, dtype=np.int32) for _ in range(3))
+        inl, deg = np.zeros(nr + 1, dtype=np.uint8), np.zeros(nr + 1, dtype=np.uint8)
+        self._chk(fn(int(gn_steps), C.c_double(barc2), int(min_consensus), out, status.ctypes.data_as(C.c_void_p), _d(cs), _d(cl), _d(cf),
+                     chosen.ctypes.data_as(_ip), _d(tr), el.ctypes.data_as(_ip), cons.ctypes.data_as(_ip), ll.ctypes.data_as(_ip),
+                     inl.ctypes.data_as(C.c_void_p), deg.ctypes.data_as(C.c_void_p)))
+        return dict(placed=int(out[0]), not_placed=int(out[1]), steps=int(out[2]), n_degenerate=int(out[3]), stages=int(out[4]),
+                    levels=int(out[5]), no_consensus=int(out[6]), excluded=int(out[7]), status=status[:nch], cost_start=cs[:nch],
+                    cost_linear=cl[:nch], cost_final=cf[:nch], chosen=chosen[:nch], transforms=tr[:nch * g].reshape(nch, g),
+                    elected=el[:nch], consensus=cons[:nch], list_len=ll[:nch], inlier=inl[:nr], degenerate=deg[:nr].astype(bool))
+
+    def place_chains_robust(self, X, barc2, gn_steps=5, min_consensus=None):
+        """place_chains_batched with a consensus vote in front of the fit: every entry of a stage's list proposes the motion its
+        sample of m ranges determines (m = 8 at d = 2, 17 at d = 3: the linear stage, then 3 Gauss-Newton steps on the sample),
+        the proposal most ranges agree with (weighted squared residual <= barc2) is elected and the fit runs over the agreeing
+        ranges only.  min_consensus None: 2 m.  Returns place_chains_batched's dict plus elected, consensus and list_len (per
+        chain), inlier (per range measurement: 1 | 0 | 2 in no stage list), no_consensus (stages of status 5) and excluded
+        (ranges with byte 0)."""
+        return self._with_host_X(self._plr_call, self.L.cora_place_chains_robust, X, gn_steps, barc2, self._pl_min(min_consensus))
+
+    def debug_place_chains_robust_host(self, X, barc2, gn_steps=5, min_consensus=None):
+        """The same on the host in the device's bracket order (no GPU needed): the device's bits."""
+        return self._with_host_X(self._plr_call, self.L.cora_debug_place_chains_robust_host, X, gn_steps, barc2, self._pl_min(min_consensus))
+
+    def place_chains_robust_dev(self, x_ptr, barc2, gn_steps=5, min_consensus=None):
+        """The same in place in a resident vector of d columns (a raw pointer as an int); the dict without X."""
+        return self._plr_call(lambda *a: self.L.cora_place_chains_robust_dev(self.h, C.c_void_p(x_ptr), *a), gn_steps, barc2,
+                              self._pl_min(min_consensus))
+
+    def _pl_min(self, min_consensus):
+        return 2 * (8 if self.d == 2 else 17) if min_consensus is None else int(min_consensus)
+
     # ---- placement from pose-landmark sightings (include/cora_hip.h, cora_place_by_sightings_dev)
     def set_sighting_placement(self, chain_fixed=None, landmark_fixed=None, min_sightings=None):
         """Orders landmarks and odometry chains into stages from the pose-landmark sightings: chain_fixed a mask per chain

@@ -235,7 +235,13 @@ struct PlTables {
   double *d_partial = nullptr;   // [kPlSums(d)][max_level_chunks] (>= max_chunks)
   double *d_state = nullptr;     // [stages][kPlState(d)]
   int32_t *d_istate = nullptr;   // [stages][kPlInts]
-  void release() { free_device(d_idx, d_partial, d_state, d_istate); }
+  // the consensus vote's (cora_place_chains_robust_dev): scratch of a call, like d_partial; made at the first robust call
+  int32_t *d_votes = nullptr;         // [entries]
+  double *d_hyp = nullptr;            // [kPlG(d)][entries]
+  double *d_cstate = nullptr;         // [stages][kPlCState(d)]
+  int32_t *d_cint = nullptr;          // [stages][kPlCInts]
+  unsigned char *d_inlier = nullptr;  // [n_ranges]
+  void release() { free_device(d_idx, d_partial, d_state, d_istate, d_votes, d_hyp, d_cstate, d_cint, d_inlier); }
 };
 // The tables of cora_set_sighting_placement (capi/sighting.inc): the order of the stages, decided from structure alone; per
 // stage its kind and its lists; per list the landmark or chain and its chunks; the entries (first rotation row and

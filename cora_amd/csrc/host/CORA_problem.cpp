@@ -1179,11 +1179,12 @@ Matrix Problem::rangeAidedInitialization(uint64_t seed, int gn_steps, LandmarkIn
 }
 
 Matrix Problem::multiRobotInitialization(uint64_t seed, int gn_steps, int min_ranges, ChainPlacementInfo *chains_info, LandmarkInitInfo *info,
-                                         ChainOrder order) const {
+                                         ChainOrder order, ChainRangeConsensus consensus) const {
   if (gn_steps < 0) throw std::invalid_argument("Problem::multiRobotInitialization: gn_steps must be in [0, 16]");
   if (order != ChainOrder::Greedy && order != ChainOrder::Levels) throw std::invalid_argument("Problem::multiRobotInitialization: unknown ChainOrder");
+  if (!std::isfinite(consensus.barc2)) throw std::invalid_argument("Problem::multiRobotInitialization: the consensus threshold must be finite");
   return odometryStart(seed, gn_steps, info, "Problem::multiRobotInitialization", true, min_ranges, chains_info, false, 0, nullptr, false, 0, nullptr,
-                       ClosureConsensus(), RangeConsensus(), SightingConsensus(), order);
+                       ClosureConsensus(), RangeConsensus(), SightingConsensus(), order, consensus);
 }
 
 namespace {
@@ -1222,7 +1223,8 @@ Matrix Problem::closureInitialization(uint64_t seed, int gn_steps, int min_range
 Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *info, const char *where, bool place, int min_ranges,
                               ChainPlacementInfo *chains_info, bool sightings, int min_sightings, SightingPlacementInfo *sight_info, bool closures,
                               int min_closures, ClosurePlacementInfo *closure_info, ClosureConsensus consensus,
-                              RangeConsensus range_consensus, SightingConsensus sighting_consensus, ChainOrder chain_order) const {
+                              RangeConsensus range_consensus, SightingConsensus sighting_consensus, ChainOrder chain_order,
+                              ChainRangeConsensus chain_consensus) const {
   checkUpToDate();
   if (part_world_ > 1) throw std::runtime_error(std::string(where) + ": not supported on a partitioned handle");
   ensureMeasurementTable();
@@ -1408,10 +1410,19 @@ Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *inf
     const size_t nch = chains.size(), G = static_cast<size_t>(d) * d + d;
     const unsigned char *fixed = chain_done.empty() ? nullptr : chain_done.data();
     const int least = min_ranges > 0 ? min_ranges : 4 * (d == 2 ? 7 : 16);
-    int64_t out[6] = {0, 0, 0, 0, 0, 0};
+    int64_t out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<unsigned char> status(nch + 1, 0);
     std::vector<double> cs(nch + 1, 0.0), cl(nch + 1, 0.0), cf(nch + 1, 0.0), tr(nch * G + 1, 0.0);
-    if (chain_order == ChainOrder::Levels) {  // a level's chains together
+    const bool vote = chain_consensus.barc2 > 0;
+    std::vector<int32_t> votes(vote ? nch + 1 : 0, 0), lens(vote ? nch + 1 : 0, 0);
+    std::vector<unsigned char> inl(vote ? nr + 1 : 0, 0);
+    if (vote) {  // the consensus vote in front of the fit, under either order (the greedy order stores a stage as a level of its own)
+      CORA_CALL(cora_set_chain_placement_order(c, fixed, least, chain_order == ChainOrder::Levels ? CORA_PL_ORDER_LEVELS : CORA_PL_ORDER_GREEDY), where);
+      CORA_CALL(cora_place_chains_robust_dev(c, v.x, gn_steps, chain_consensus.barc2,
+                                             chain_consensus.min_consensus > 0 ? chain_consensus.min_consensus : 2 * (d == 2 ? 8 : 17), out, status.data(),
+                                             cs.data(), cl.data(), cf.data(), nullptr, tr.data(), nullptr, votes.data(), lens.data(), inl.data(), nullptr),
+                where);
+    } else if (chain_order == ChainOrder::Levels) {  // a level's chains together
       CORA_CALL(cora_set_chain_placement_order(c, fixed, least, CORA_PL_ORDER_LEVELS), where);
       CORA_CALL(cora_place_chains_batched_dev(c, v.x, gn_steps, out, status.data(), cs.data(), cl.data(), cf.data(), nullptr, tr.data(), nullptr), where);
     } else {
@@ -1430,6 +1441,17 @@ Matrix Problem::odometryStart(uint64_t seed, int gn_steps, LandmarkInitInfo *inf
       chains_info->cost_linear.assign(cl.begin(), cl.begin() + static_cast<std::ptrdiff_t>(nch));
       chains_info->cost_final.assign(cf.begin(), cf.begin() + static_cast<std::ptrdiff_t>(nch));
       chains_info->transforms.assign(tr.begin(), tr.begin() + static_cast<std::ptrdiff_t>(nch * G));
+      chains_info->no_consensus = chains_info->ranges_excluded = 0;
+      chains_info->consensus.clear();
+      chains_info->list_len.clear();
+      chains_info->inlier.clear();
+      if (vote) {
+        chains_info->no_consensus = static_cast<long>(out[6]);
+        chains_info->ranges_excluded = static_cast<long>(out[7]);
+        chains_info->consensus.assign(votes.begin(), votes.begin() + static_cast<std::ptrdiff_t>(nch));
+        chains_info->list_len.assign(lens.begin(), lens.begin() + static_cast<std::ptrdiff_t>(nch));
+        chains_info->inlier.assign(inl.begin(), inl.begin() + static_cast<std::ptrdiff_t>(nr));
+      }
     }
   }
   if (gn_steps >= 0) {

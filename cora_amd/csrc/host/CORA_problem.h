@@ -192,6 +192,22 @@ struct ChainPlacementInfo {
   std::vector<unsigned char> status;   // per chain (0 placed, 1 too few ranges, 2 placed without the linear stage, 3 no range, 4 fixed)
   std::vector<Scalar> cost_start, cost_linear, cost_final;  // per chain: sum omega (|R q + t - a| - r)^2 over the stage's entries
   std::vector<Scalar> transforms;      // per chain d * d + d: R row-major, then t, as written
+  // with a consensus vote (ChainRangeConsensus; status 5: no consensus, counted in not_placed); empty / 0 without one
+  long no_consensus = 0, ranges_excluded = 0;  // status 5; ranges of the stage lists outside their inliers
+  std::vector<int32_t> consensus, list_len;    // per chain: the vote of the elected hypothesis, the ranges of the chain's stage list
+  std::vector<unsigned char> inlier;   // per range measurement: 1 inlier | 0 in a stage list, not an inlier | 2 in no stage list
+};
+
+/** The consensus vote of the chain placement from ranges (cora_place_chains_robust_dev, include/cora_hip.h).  barc2 <= 0: off,
+ * the plain fit and its bits.  barc2 > 0: every range of a chain's stage list proposes the motion its sample of m ranges
+ * determines (m = 8 at d = 2, 17 at d = 3: the linear stage, then 3 Gauss-Newton steps on the sample), the proposal most ranges
+ * agree with (weighted squared range residual <= barc2, the quantity the GNC weights threshold) is elected and the fit runs over
+ * the agreeing ranges only; a chain whose elected proposal has fewer than min_consensus votes (<= 0: 2 m -- a proposal has about m
+ * votes of its own) keeps its random start (status 5).  One proposal per range, clean only where all m ranges of its sample
+ * are: short lists with many outliers reach no consensus. */
+struct ChainRangeConsensus {
+  Scalar barc2 = 0;
+  int min_consensus = 0;
 };
 
 /** What Problem::sightingInitialization reports about the sighting step (cora_place_by_sightings_dev, include/cora_hip.h). */
@@ -338,7 +354,8 @@ class Problem {
                        SightingPlacementInfo *sight_info = nullptr, bool closures = false, int min_closures = 0,
                        ClosurePlacementInfo *closure_info = nullptr, ClosureConsensus consensus = ClosureConsensus(),
                        RangeConsensus range_consensus = RangeConsensus(),
-                       SightingConsensus sighting_consensus = SightingConsensus(), ChainOrder chain_order = ChainOrder::Greedy) const;
+                       SightingConsensus sighting_consensus = SightingConsensus(), ChainOrder chain_order = ChainOrder::Greedy,
+                       ChainRangeConsensus chain_consensus = ChainRangeConsensus()) const;
   void fillImplicitFormulationMatrices() const;
   [[noreturn]] void throwLast(int status, const char *where) const;
 
@@ -567,9 +584,13 @@ class Problem {
    * order: ChainOrder::Greedy (the default: the bits of the call without the argument) or ChainOrder::Levels, the level
    * order with a level's chains placed in the same launches (cora_place_chains_batched_dev): 17 launches per level at 5 steps
    * where the greedy order spends 17 per chain, at the price of ignoring the ranges between chains of one level
-   * (profiles/chain_placement_levels.md). */
+   * (profiles/chain_placement_levels.md).
+   * consensus: the outlier-robust placement (ChainRangeConsensus; the default is off: the bits of the call without the argument),
+   * under either order (cora_place_chains_robust_dev; profiles/chain_consensus.md).  std::invalid_argument for a threshold that
+   * is not finite. */
   Matrix multiRobotInitialization(uint64_t seed = 7, int gn_steps = 5, int min_ranges = 0, ChainPlacementInfo *chains_info = nullptr,
-                                  LandmarkInitInfo *info = nullptr, ChainOrder order = ChainOrder::Greedy) const;
+                                  LandmarkInitInfo *info = nullptr, ChainOrder order = ChainOrder::Greedy,
+                                  ChainRangeConsensus consensus = ChainRangeConsensus()) const;
   /** EXTENSION beyond the reference: multiRobotInitialization with landmarks and chains first placed from the
    * pose-landmark sightings (cora_place_by_sightings_dev), chain 0 fixed: exactly the draws of odometryInitialization in
    * the same order (the new step draws nothing), then the sighting placement, then cora_place_chains_dev for the chains

@@ -344,11 +344,30 @@ int cora_problem_multi_robot_initialization_order(cora_problem *p, uint64_t seed
                                                   int64_t counts[5], unsigned char *status, double *cost_start, double *cost_linear,
                                                   double *cost_final, double *transforms, int64_t landmark_counts[4],
                                                   unsigned char *landmark_status) {
+  return cora_problem_multi_robot_initialization_consensus(p, seed, gn_steps, min_ranges, order, 0.0, 0, out, counts, status, cost_start, cost_linear,
+                                                           cost_final, transforms, landmark_counts, landmark_status, nullptr, nullptr, nullptr, nullptr);
+}
+
+int cora_problem_multi_robot_initialization_consensus(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, int order, double consensus_barc2,
+                                                      int min_consensus, double *out, int64_t counts[5], unsigned char *status, double *cost_start,
+                                                      double *cost_linear, double *cost_final, double *transforms, int64_t landmark_counts[4],
+                                                      unsigned char *landmark_status, int64_t consensus_counts[2], int32_t *consensus,
+                                                      int32_t *list_len, unsigned char *inlier) {
   return guarded([&] {
     ChainPlacementInfo ci;
     LandmarkInitInfo info;
     if (order != 0 && order != 1) throw std::invalid_argument("cora_problem_multi_robot_initialization_order: order must be 0 or 1");
-    const Matrix res = p->problem.multiRobotInitialization(seed, gn_steps, min_ranges, &ci, &info, order == 1 ? ChainOrder::Levels : ChainOrder::Greedy);
+    ChainRangeConsensus vote;
+    vote.barc2 = consensus_barc2;
+    vote.min_consensus = min_consensus;
+    const Matrix res = p->problem.multiRobotInitialization(seed, gn_steps, min_ranges, &ci, &info, order == 1 ? ChainOrder::Levels : ChainOrder::Greedy, vote);
+    if (consensus_counts) {
+      consensus_counts[0] = ci.no_consensus;
+      consensus_counts[1] = ci.ranges_excluded;
+    }
+    if (consensus) std::copy(ci.consensus.begin(), ci.consensus.end(), consensus);
+    if (list_len) std::copy(ci.list_len.begin(), ci.list_len.end(), list_len);
+    if (inlier) std::copy(ci.inlier.begin(), ci.inlier.end(), inlier);
     if (res.rows() == p->problem.getExpectedVariableSize()) p->problem.checkVariablesAreValid(res);  // (throws off the manifold)
     std::memcpy(out, res.data(), sizeof(double) * static_cast<size_t>(res.size()));
     if (counts) {

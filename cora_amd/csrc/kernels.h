@@ -1240,6 +1240,14 @@ struct PlBatchArgs {
   const int32_t *stage_pos0 = nullptr, *stage_npos = nullptr;          // [stages]: the chain's positions in the chain tables
   const int32_t *tile_stage = nullptr, *tile_off = nullptr;            // [tiles]: stage, first position of the tile within the chain
 };
+// what every batched launch asks of its arguments (the robust form's too: PlRobustArgs below)
+inline bool pl_batch_args_ok(const PlBatchArgs &B) {
+  const PlArgs &A = B.A;
+  return (A.d == 2 || A.d == 3) && A.n_chunks > 0 && A.chunk0 >= 0 && A.pstride >= A.n_chunks && B.n_stages > 0 && B.stage0 >= 0 &&
+         B.n_stages <= A.n_chunks && B.n_tiles >= B.n_stages && B.tile0 >= 0 && A.n_ranges > 0 && A.chunk_begin && A.chunk_len && A.ent_q &&
+         A.ent_a && A.ent_m && A.pos_rot && A.pos_trn && A.range_data && A.partial && A.state && A.istate && A.x && A.flag && B.chunk_stage &&
+         B.stage_chunk0 && B.stage_origin_q && B.stage_origin_a && B.stage_pos0 && B.stage_npos && B.tile_stage && B.tile_off;
+}
 hipError_t launch_place_linear(const PlBatchArgs &B, hipStream_t st);
 hipError_t launch_place_gn(const PlBatchArgs &B, hipStream_t st);  // evaluation B.A.step
 hipError_t launch_place_apply(const PlBatchArgs &B, hipStream_t st);
@@ -1583,6 +1591,131 @@ __host__ __device__ inline void pl_apply(const double *g, double *rot, double *t
   for (int i = 0; i < D * D; ++i) rot[i] = nr[i];
 #pragma unroll
   for (int c = 0; c < D; ++c) trn[c] = nt[c];
+}
+
+// Outlier-robust chain placement: a consensus vote over hypotheses from samples of m = kPlTerms(d) ranges in front of the
+// batched fit (kernels/placement.inc, MASK; include/cora_hip.h, cora_place_chains_robust_dev).  Tables, order,
+// lists, chunks and origin are the batched call's; every launch serves ALL stages of one level.  Per stage list of length
+// L >= m (the least min_ranges), entries e = 0 .. L - 1 in table order, q' = q - q_0, a' = a - a_0:
+//   sample of entry h : entries (h + k s) mod L, k = 0 .. m - 1, s = max(1, L / m) (pl_sample) -- distinct as (m - 1) s < L, a
+//                       function of (h, L, d) alone;
+//   hypothesis g_h    : the sample's pl_linear_terms and weights, the pair products added from the left in the order k (pl_pair_sum
+//                       over the m staged entries), pl_linear_solve -- valid where it returns 0, else g = the identity (pl_identity),
+//                       vote 0, no flag; then kPlHypSteps Gauss-Newton steps ON THE SAMPLE'S OWN m ENTRIES (pl_hyp_polish: pl_gn_terms
+//                       added from the left in the order k from +0.0, pl_gn_step with the sample's L and sum w); a refused step keeps
+//                       the point and ends the stepping, the hypothesis stays valid;
+//   score             : r(h, j) = (w_j e) e, e = |R_h q'_j + t'_h - a'_j| - r_j (pl_cost_at: the last term of pl_gn_terms);
+//   vote(h)           : #{j : r(h, j) <= barc2} over EVERY entry j, the sample's own included (cl_agrees: a NaN is no vote) -- a
+//                       consensus means something above m only;
+//   election          : the largest vote, among equal votes the lowest entry (cl_better); consensus = its vote; consensus <
+//                       min_consensus: status 5, the chain keeps its rows; no valid hypothesis: entry 0, consensus 0;
+//   I = {j : r(h*, j) <= barc2} (empty at consensus 0); the batched stages run over I alone: AN ENTRY OUTSIDE I ADDS +0.0 FOR
+//                       EACH OF ITS TERMS (pl_pair_sum_masked; a Gauss-Newton lane that holds +0.0), so the bracket order of a
+//                       sum is the plain one's and a list without outliers has the batched call's bits.
+// Per level 3 + 2 (gn_steps + 3) + 1 launches: hypotheses, vote, election, then the batched call's.  One election, one refit.
+constexpr int kPlHypSteps = 3;
+constexpr int kPlCState(int d) { return kPlG(d); }  // of the elected hypothesis: (R, t')
+constexpr int kPlCInts = 2;                         // elected entry (index in its list) | consensus
+struct PlRobustArgs {
+  PlBatchArgs B;
+  double barc2 = 0.0;
+  int min_consensus = 0;
+  int32_t ent0 = 0, n_ent = 0;      // the level's entries (those of its chunks, consecutive)
+  int64_t hstride = 0;
+  double *hyp = nullptr;            // [kPlG(d)][hstride], by entry
+  int32_t *votes = nullptr;         // [entries]
+  double *cstate = nullptr;         // [stages][kPlCState(d)]
+  int32_t *cint = nullptr;          // [stages][kPlCInts]
+  unsigned char *inlier = nullptr;  // [n_ranges]: written where a range is an entry of a stage list, 1 in I | 0 outside
+};
+hipError_t launch_place_vote_elect(const PlRobustArgs &R, hipStream_t st);  // k_pl_hyp, k_pl_vote, k_pl_elect of the level
+hipError_t launch_place_linear(const PlRobustArgs &R, hipStream_t st);      // the masked forms of the batched launches
+hipError_t launch_place_gn(const PlRobustArgs &R, hipStream_t st);
+hipError_t launch_place_apply(const PlRobustArgs &R, hipStream_t st);
+// entry k of the sample of entry h of a list of len entries (h < len, 0 <= k < kPlTerms(D), len >= kPlTerms(D))
+template <int D>
+__host__ __device__ inline int32_t pl_sample(int32_t h, int k, int32_t len) {
+  const int32_t s = len / kPlTerms(D) > 1 ? len / kPlTerms(D) : 1;
+  const int32_t e = h + k * s;  // (< 2 len)
+  return e >= len ? e - len : e;
+}
+// pl_pair_sum over the entries with in[e] != 0: an entry outside adds +0.0
+__host__ __device__ inline double pl_pair_sum_masked(const double *term, const double *wt, const unsigned char *in, int len, int nt, int i, int j) {
+#pragma clang fp contract(off)
+  double v = 0.0;
+  for (int e = 0; e < len; ++e) v = v + (in[e] ? (wt[e] * term[e * nt + i]) * term[e * nt + j] : 0.0);
+  return v;
+}
+// the weighted squared range residual of an entry (qq = q', aa = a') at g = (R, t'), without the 1/2: the last term of pl_gn_terms
+template <int D>
+__host__ __device__ inline double pl_cost_at(const double *g, const double *qq, const double *aa, double r, double w) {
+#pragma clang fp contract(off)
+  double n2 = 0.0;
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) v = fma(g[i * D + k], qq[k], v);
+    const double p = (v + g[D * D + i]) - aa[i];
+    n2 = fma(p, p, n2);
+  }
+  const double e = sqrt(n2) - r;
+  return (w * e) * e;
+}
+// The polish of a valid hypothesis: kPlHypSteps Gauss-Newton steps from g on the sample's own entries.  entry(k, &q, &a, &r,
+// &w) gives entry k of the sample: the rows of its position and anchor, its range and precision.
+template <int D, class Entry>
+__host__ __device__ inline void pl_hyp_polish(double sw, double L, const double *q0, const double *a0, Entry entry, double *g) {
+#pragma clang fp contract(off)
+  constexpr int NS = kPlGnSums(D);
+  for (int step = 0; step < kPlHypSteps; ++step) {
+    double S[NS], t[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) S[i] = 0.0;
+    for (int k = 0; k < kPlTerms(D); ++k) {
+      const double *q, *a;
+      double r, w;
+      entry(k, &q, &a, &r, &w);
+      pl_gn_terms<D>(g, L, q0, a0, q, a, r, w, t);
+#pragma unroll
+      for (int i = 0; i < NS; ++i) S[i] = S[i] + t[i];
+    }
+    if (!pl_gn_step<D>(S, sw, L, g)) return;
+  }
+}
+// The hypothesis from the pair sums S of its sample (kPlSums(D)): the linear solve, then the polish.  Returns whether it is
+// valid; g = the identity where it is not.  work: kPlUnknowns(D) (kPlUnknowns(D) + 1) doubles.
+template <int D, class Entry>
+__host__ __device__ inline bool pl_hypothesis(const double *S, double *work, const double *q0, const double *a0, Entry entry, double *g) {
+  double L, sw;
+  if (pl_linear_solve<D>(S, work, g, &L, &sw) != 0) {
+    pl_identity<D>(q0, a0, g);
+    return false;
+  }
+  pl_hyp_polish<D>(sw, L, q0, a0, entry, g);
+  return true;
+}
+// What the folds of a masked stage do: a stage the election left at status 5 keeps the identity, takes no step and writes the
+// identity; every other stage is the plain fold's.
+template <int D>
+__host__ __device__ inline bool pl_fold_linear_robust(const double *S, double *work, double *st, int32_t *ist, const double *q0, const double *a0) {
+  if (ist[0] != 5) return pl_fold_linear<D>(S, work, st, ist, q0, a0);
+  constexpr int G = kPlG(D);
+  for (int i = 0; i < kPlState(D); ++i) st[i] = 0.0;
+  pl_identity<D>(q0, a0, st);
+  pl_identity<D>(q0, a0, st + G);
+  st[3 * G + 4] = 1.0;
+  ist[1] = -1;
+  ist[2] = 0;
+  ist[3] = 0;
+  return true;
+}
+template <int D>
+__host__ __device__ inline bool pl_fold_gn_robust(int step, int last, const double *S, double *st, int32_t *ist, const double *q0, const double *a0) {
+  if (ist[0] != 5) return pl_fold_gn<D>(step, last, S, st, ist, q0, a0);
+  if (last)
+    for (int i = 0; i < kPlG(D); ++i) st[2 * kPlG(D) + i] = i < D * D && i / D == i % D ? 1.0 : 0.0;
+  return true;
 }
 
 // Placement from pose-landmark sightings (kernels/sighting.inc; include/cora_hip.h, cora_place_by_sightings_dev).  A

@@ -18,10 +18,10 @@
 #include "kernels.h"
 
 // The file is compiled several times in parallel (cora_amd/build.py): CORA_TU selects the kernel families of a
-// translation unit (1 SpMM, 2 row-unit / vector / block kernels, 4 staged triangular solves, 8 the chain placement's batched kernels), CORA_LDG the row strides
+// translation unit (1 SpMM, 2 row-unit / vector / block kernels, 4 staged triangular solves, 8 the chain placement's batched kernels, 16 its outlier-robust kernels), CORA_LDG the row strides
 // it instantiates of the two big families (1: LD 2-5, 2: 6-9, 4: 10-12, 8: 13-16, 16: 17-20, 32: 21-24).  Default: all.
 #ifndef CORA_TU
-#define CORA_TU 15
+#define CORA_TU 31
 #endif
 #ifndef CORA_LDG
 #define CORA_LDG 63
@@ -39,7 +39,7 @@
 //   kernels/round.inc    rounding of a resident vector to SE(d): count, finish, per-unit pass                       CORA_TU & 2
 //   kernels/odom.inc     odometry initialisation: segmented scan of SE(d) over the chain positions, fill of the other rows  CORA_TU & 2
 //   kernels/multilat.inc  landmark initialisation from ranges: pass over the chunks of the range lists, fold and solve per landmark  CORA_TU & 2
-//   kernels/placement.inc  chain placement from inter-robot ranges: linear and Gauss-Newton pass and fold per stage, the rigid motion of a chain  CORA_TU & 2; the same for all stages of a level  CORA_TU & 8
+//   kernels/placement.inc  chain placement from inter-robot ranges: linear and Gauss-Newton pass and fold per stage, the rigid motion of a chain  CORA_TU & 2; the same for all stages of a level  CORA_TU & 8; the hypotheses, consensus vote, election and masked passes of the robust form  CORA_TU & 16
 //   kernels/sighting.inc  placement from pose-landmark sightings: pass and fold over all lists of a stage, the rigid motion of a stage's chains; the hypotheses, consensus vote, election and masked passes of the robust form  CORA_TU & 2
 //   kernels/closure.inc  placement from inter-chain relative-pose edges: pass and fold over all lists of a stage (sums and solve, costs); the consensus vote, election and masked passes of the robust form  CORA_TU & 2
 //   kernels/update_values.inc  in-place update of Q's values: check of the new values, gather passes                CORA_TU & 2

@@ -879,13 +879,7 @@ hipError_t launch_combine(int64_t row0, int64_t rows, int nblocks, const double 
 // compiler inlines and unrolls a function with one caller in a unit differently from one with two -- side by side the
 // plain kernels would no longer be the ones profiles/chain_placement.md measured.
 #if CORA_TU & 8
-static bool place_args_ok(const PlBatchArgs &B) {
-  const PlArgs &A = B.A;
-  return (A.d == 2 || A.d == 3) && A.n_chunks > 0 && A.chunk0 >= 0 && A.pstride >= A.n_chunks && B.n_stages > 0 && B.stage0 >= 0 &&
-         B.n_stages <= A.n_chunks && B.n_tiles >= B.n_stages && B.tile0 >= 0 && A.n_ranges > 0 && A.chunk_begin && A.chunk_len && A.ent_q &&
-         A.ent_a && A.ent_m && A.pos_rot && A.pos_trn && A.range_data && A.partial && A.state && A.istate && A.x && A.flag && B.chunk_stage &&
-         B.stage_chunk0 && B.stage_origin_q && B.stage_origin_a && B.stage_pos0 && B.stage_npos && B.tile_stage && B.tile_off;
-}
+static bool place_args_ok(const PlBatchArgs &B) { return pl_batch_args_ok(B); }
 hipError_t launch_place_linear(const PlBatchArgs &B, hipStream_t st) {
   if (!place_args_ok(B)) return hipErrorInvalidValue;
   const dim3 chunks(static_cast<unsigned>(B.A.n_chunks)), stages(static_cast<unsigned>(B.n_stages));
@@ -910,3 +904,47 @@ hipError_t launch_place_apply(const PlBatchArgs &B, hipStream_t st) {
   return hipGetLastError();
 }
 #endif  // CORA_TU & 8
+// the chain placement's outlier-robust form (kernels/placement.inc, MASK): the consensus vote of the one level R describes, and
+// the batched launches over the inliers.  A translation unit of its own, for the reason above: the plain and the batched
+// kernels stay the code objects they were.
+#if CORA_TU & 16
+static bool place_args_ok(const PlRobustArgs &R) {
+  const PlArgs &A = R.B.A;
+  return pl_batch_args_ok(R.B) && R.barc2 > 0.0 && R.min_consensus >= 1 && R.ent0 >= 0 && R.n_ent >= A.n_chunks && R.hstride >= static_cast<int64_t>(R.ent0) + R.n_ent &&
+         R.hyp && R.votes && R.cstate && R.cint && R.inlier;
+}
+hipError_t launch_place_vote_elect(const PlRobustArgs &R, hipStream_t st) {
+  if (!place_args_ok(R)) return hipErrorInvalidValue;
+  const dim3 hyps(static_cast<unsigned>((R.n_ent + 256 / kWave - 1) / (256 / kWave))), chunks(static_cast<unsigned>(R.B.A.n_chunks)),
+      stages(static_cast<unsigned>(R.B.n_stages));
+  for_d(R.B.A.d, [&](auto D) {
+    hipLaunchKernelGGL(k_pl_hyp<D()>, hyps, dim3(256), 0, st, R);
+    hipLaunchKernelGGL(k_pl_vote<D()>, chunks, dim3(kPlChunk), 0, st, R);
+    hipLaunchKernelGGL(k_pl_elect<D()>, stages, dim3(kWave), 0, st, R);
+  });
+  return hipGetLastError();
+}
+hipError_t launch_place_linear(const PlRobustArgs &R, hipStream_t st) {
+  if (!place_args_ok(R)) return hipErrorInvalidValue;
+  const dim3 chunks(static_cast<unsigned>(R.B.A.n_chunks)), stages(static_cast<unsigned>(R.B.n_stages));
+  for_d(R.B.A.d, [&](auto D) {
+    hipLaunchKernelGGL((k_pl_pass_linear<D(), true, true>), chunks, dim3(kPlChunk), 0, st, R);
+    hipLaunchKernelGGL((k_pl_fold_linear<D(), true, true>), stages, dim3(kWave), 0, st, R);
+  });
+  return hipGetLastError();
+}
+hipError_t launch_place_gn(const PlRobustArgs &R, hipStream_t st) {
+  if (!place_args_ok(R) || R.B.A.step < 0 || R.B.A.step > kPlMaxSteps + 1) return hipErrorInvalidValue;
+  const dim3 chunks(static_cast<unsigned>(R.B.A.n_chunks)), stages(static_cast<unsigned>(R.B.n_stages));
+  for_d(R.B.A.d, [&](auto D) {
+    hipLaunchKernelGGL((k_pl_pass_gn<D(), true, true>), chunks, dim3(kPlChunk), 0, st, R);
+    hipLaunchKernelGGL((k_pl_fold_gn<D(), true, true>), stages, dim3(kWave), 0, st, R);
+  });
+  return hipGetLastError();
+}
+hipError_t launch_place_apply(const PlRobustArgs &R, hipStream_t st) {
+  if (!place_args_ok(R)) return hipErrorInvalidValue;
+  for_d(R.B.A.d, [&](auto D) { hipLaunchKernelGGL((k_pl_apply<D(), true, true>), dim3(static_cast<unsigned>(R.B.n_tiles)), dim3(256), 0, st, R); });
+  return hipGetLastError();
+}
+#endif  // CORA_TU & 16

@@ -247,14 +247,22 @@ class Problem:
         return out, dict(**extra, solved=int(cnt[0]), not_solved=int(cnt[1]), n_degenerate=int(cnt[2]), steps=int(cnt[3]),
                          status=status[:nl], cost_linear=cl[:nl], cost_final=cf[:nl])
 
-    def multi_robot_initialization(self, seed=7, gn_steps=5, min_ranges=0, order=None):
+    def multi_robot_initialization(self, seed=7, gn_steps=5, min_ranges=0, order=None, consensus_barc2=None, min_consensus=0):
         """Problem::multiRobotInitialization: (x0, info) with info a dict placed, not_placed, steps, stages, status, cost_start,
         cost_linear, cost_final, transforms (per chain of odometry_chains()), landmarks (the dict of
         range_aided_initialization without the costs).  min_ranges 0: the default.  The start has passed checkVariablesAreValid.
         order: None, the call without the argument (ChainOrder::Greedy); "greedy" | "levels", the ChainOrder given, and info
-        gains levels."""
+        gains levels.
+        consensus_barc2: None, the plain placement; a threshold > 0, the placement with a consensus vote (ChainRangeConsensus,
+        CORA_problem.h) under the order given (None: greedy): the fit of a chain runs over the ranges that agree with the elected
+        proposal, a chain whose elected proposal has fewer than min_consensus (0: 2 m, m = 8 / 17) votes has status 5, and info
+        gains levels, no_consensus, excluded, consensus and list_len (per chain) and inlier (per range measurement as added:
+        1 | 0 | 2 in no stage list)."""
         if order not in (None, "greedy", "levels"):
             raise ValueError("order must be None, 'greedy' or 'levels'")
+        robust = consensus_barc2 is not None
+        if robust and not consensus_barc2 > 0:
+            raise HostError("consensus_barc2 must be positive (None: no consensus vote)")
         dm = self.dims()
         d = dm["d"]
         nl = dm["N"] - (d + 1) * dm["n"] - dm["r"]
@@ -265,12 +273,22 @@ class Problem:
         cs, cl, cf, tr = np.zeros(nch + 1), np.zeros(nch + 1), np.zeros(nch + 1), np.zeros(nch * (d * d + d) + 1)
         tail = (out.ctypes.data_as(_dp), cnt, status.ctypes.data_as(C.c_void_p), cs.ctypes.data_as(_dp), cl.ctypes.data_as(_dp),
                 cf.ctypes.data_as(_dp), tr.ctypes.data_as(_dp), lcnt, lstatus.ctypes.data_as(C.c_void_p))
-        if order is None:
+        if robust:
+            nr, i32 = dm["r"], C.POINTER(C.c_int32)
+            vcnt = (C.c_int64 * 2)()
+            cons, ll, inl = np.zeros(nch + 1, dtype=np.int32), np.zeros(nch + 1, dtype=np.int32), np.zeros(nr + 1, dtype=np.uint8)
+            self._chk(self.L.cora_problem_multi_robot_initialization_consensus(
+                self.h, C.c_uint64(seed), int(gn_steps), int(min_ranges), 1 if order == "levels" else 0, C.c_double(consensus_barc2),
+                int(min_consensus), *tail, vcnt, cons.ctypes.data_as(i32), ll.ctypes.data_as(i32), inl.ctypes.data_as(C.c_void_p)))
+            order = order or "greedy"
+        elif order is None:
             self._chk(self.L.cora_problem_multi_robot_initialization(self.h, C.c_uint64(seed), int(gn_steps), int(min_ranges), *tail))
         else:
             self._chk(self.L.cora_problem_multi_robot_initialization_order(self.h, C.c_uint64(seed), int(gn_steps), int(min_ranges),
                                                                            1 if order == "levels" else 0, *tail))
         extra = {} if order is None else dict(levels=int(cnt[4]))
+        if robust:
+            extra.update(no_consensus=int(vcnt[0]), excluded=int(vcnt[1]), consensus=cons[:nch], list_len=ll[:nch], inlier=inl[:nr])
         return out, dict(**extra, placed=int(cnt[0]), not_placed=int(cnt[1]), steps=int(cnt[2]), stages=int(cnt[3]), status=status[:nch],
                          cost_start=cs[:nch], cost_linear=cl[:nch], cost_final=cf[:nch], transforms=tr[:-1].reshape(nch, d * d + d),
                          landmarks=dict(solved=int(lcnt[0]), not_solved=int(lcnt[1]), n_degenerate=int(lcnt[2]), steps=int(lcnt[3]),

@@ -22,7 +22,7 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding] [--device-init [--landmark-init [--range-consensus barc2 [--range-min-consensus k]]] [--place-chains] [--sightings [--sighting-consensus barc2 [--sighting-min-consensus k] [--sighting-min-landmark-consensus k]]] [--closures [--closure-consensus barc2 [--closure-min-consensus k]]] [--gn-steps k]]" << std::endl;
+    std::cout << "Usage: " << argv[0] << " [input .pyfg file] [--jacobi] [--implicit] [--odom-init] [--tum out.tum] [--save-dir dir] [--max-rank r] [--residuals out.csv] [--weights in.csv] [--robust tls|gm --barc2 kind=value[,kind=value...] [--weights-out out.csv]] [--evaluate] [--aligned-tum out.tum] [--rpe step[,step...]] [--rpe-dist L[,L...]] [--device-rounding] [--device-init [--landmark-init [--range-consensus barc2 [--range-min-consensus k]]] [--place-chains [--chain-levels] [--chain-consensus barc2[,min]]] [--sightings [--sighting-consensus barc2 [--sighting-min-consensus k] [--sighting-min-landmark-consensus k]]] [--closures [--closure-consensus barc2 [--closure-min-consensus k]]] [--gn-steps k]]" << std::endl;
     return 1;
   }
   int max_rank = 10, gn_steps = 5;
@@ -30,6 +30,8 @@ int main(int argc, char **argv) {
   CORA::ClosureConsensus closure_consensus;
   CORA::RangeConsensus range_consensus;
   CORA::SightingConsensus sighting_consensus;
+  CORA::ChainRangeConsensus chain_consensus;
+  bool chain_consensus_given = false;
   bool consensus_given = false, range_consensus_given = false, sighting_consensus_given = false;
   bool jacobi = false, implicit = false, odom = false, evaluate = false, device_rounding = false, device_init = false, landmark_init = false, place_chains = false, chain_levels = false, sightings = false, closures = false;
   for (int i = 2; i < argc; ++i) {
@@ -74,6 +76,15 @@ int main(int argc, char **argv) {
     else if (a == "--place-chains") place_chains = true;
     // with --place-chains: the level order, a level's chains placed together (ChainOrder::Levels)
     else if (a == "--chain-levels") chain_levels = true;
+    // with --place-chains: a consensus vote in front of each chain's fit (ChainRangeConsensus): barc2[,min], the threshold on a
+    // range's weighted squared residual and the least consensus (default 2 m, m = 8 / 17)
+    else if (a == "--chain-consensus" && i + 1 < argc) {
+      const std::string v = argv[++i];
+      const size_t comma = v.find(',');
+      chain_consensus.barc2 = std::atof(v.substr(0, comma).c_str());
+      if (comma != std::string::npos) chain_consensus.min_consensus = std::atoi(v.substr(comma + 1).c_str());
+      chain_consensus_given = true;
+    }
     // with --odom-init --device-init: landmarks and chains are first placed from the pose-landmark sightings, then the chains
     // that are left from the ranges and the landmarks that are left by multilateration (Problem::sightingInitialization)
     else if (a == "--sightings") sightings = true;
@@ -96,6 +107,8 @@ int main(int argc, char **argv) {
     if (device_init && !odom) throw std::runtime_error("--device-init composes the odometry start on the device: it needs --odom-init");
     if (place_chains && !device_init) throw std::runtime_error("--place-chains places the chains of the device's odometry start: it needs --odom-init --device-init");
     if (chain_levels && !place_chains) throw std::runtime_error("--chain-levels chooses the order of --place-chains: it needs --place-chains");
+    if (chain_consensus_given && !place_chains) throw std::runtime_error("--chain-consensus sets the vote of --place-chains: it needs --place-chains");
+    if (chain_consensus_given && !(chain_consensus.barc2 > 0)) throw std::runtime_error("--chain-consensus: expected a threshold > 0");
     if (sightings && !device_init) throw std::runtime_error("--sightings places landmarks and chains of the device's odometry start: it needs --odom-init --device-init");
     if (closures && !device_init) throw std::runtime_error("--closures places the chains of the device's odometry start: it needs --odom-init --device-init");
     if (consensus_given && !closures) throw std::runtime_error("--closure-consensus and --closure-min-consensus set the vote of the closure step: they need --closures");
@@ -177,10 +190,18 @@ int main(int argc, char **argv) {
         return problem.measurementResiduals(implicit ? CORA::Matrix(x.block(0, 0, problem.rotAndRangeMatrixSize(), x.cols())) : x).range_sum;
       };
       const double without = range_sum(x0);  // (the start as it stands: with the landmarks placed under --landmark-init)
-      x0 = problem.multiRobotInitialization(7, gn_steps, 0, &ci, nullptr, chain_levels ? CORA::ChainOrder::Levels : CORA::ChainOrder::Greedy);
+      x0 = problem.multiRobotInitialization(7, gn_steps, 0, &ci, nullptr, chain_levels ? CORA::ChainOrder::Levels : CORA::ChainOrder::Greedy,
+                                            chain_consensus);
       std::printf("chain placement: %ld chains placed, %ld not placed (%ld Gauss-Newton steps); range residual sum at the start %.6e with it, %.6e without\n",
                   ci.placed, ci.not_placed, ci.gn_steps, range_sum(x0), without);
       if (chain_levels) std::printf("chain placement: level order, %ld stages in %ld levels\n", ci.stages, ci.levels);
+      if (chain_consensus_given) {
+        double least = 1.0;  // the smallest consensus / list length over the stages
+        for (size_t ch = 0; ch < ci.list_len.size(); ++ch)
+          if (ci.list_len[ch] > 0) least = std::min(least, static_cast<double>(ci.consensus[ch]) / ci.list_len[ch]);
+        std::printf("chain consensus: %ld chains without consensus, %ld ranges excluded; smallest consensus / list length %.4f\n", ci.no_consensus,
+                    ci.ranges_excluded, least);
+      }
     }
     if (sightings) {  // (an extension beyond the reference: Problem::sightingInitialization)
       CORA::SightingPlacementInfo si;

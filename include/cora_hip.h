@@ -1032,6 +1032,71 @@ int cora_place_chains_batched_dev(cora_ctx *ctx, double *dX, int gn_steps, int64
 int cora_place_chains_batched(cora_ctx *ctx, double *X, int ldx, int gn_steps, int64_t out[6], unsigned char *status, double *cost_start,
                               double *cost_linear, double *cost_final, int32_t *chosen, double *transforms, unsigned char *degenerate);
 
+/* Outlier-robust chain placement: a consensus vote over samples of m ranges in front of the batched fit.  The first
+ * visited point of a stage is a linear stage in the SQUARED ranges with 7 (d = 2) or 16 (d = 3) unknowns: one NLOS or multipath
+ * range lengthened by 10 m enters with its square and drags all of them, the Gauss-Newton steps then descend the contaminated
+ * cost, and every later stage and the landmark multilateration inherit the misplaced chain.  Tables, order (greedy or levels),
+ * lists, chunks, origin, the range-row step and the meaning of gn_steps are those of cora_set_chain_placement_order: there is no
+ * new set call.  Per stage list of L entries e = 0 .. L - 1 in table order (origin q_0, a_0 of the first entry, whether or not
+ * it turns out an inlier; q' = q - q_0, a' = a - a_0; the stage carries g = (R, t')), with m = unknowns + 1 = 8 at d = 2 and
+ * 17 at d = 3, the least min_ranges the set call accepts, so L >= m:
+ *   sample of h      the entries (h + k s) mod L, k = 0 .. m - 1, s = max(1, L / m) (integer division): m distinct entries
+ *                    spread over the list, a function of (h, L, d) alone: no random number, the same bits on every call and
+ *                    in the mirror.
+ *   hypothesis       g_h: the linear stage's terms and weights of the sample's entries, every pair product added from the left
+ *                    in the order k = 0 .. m - 1 starting from +0.0, then the linear stage's solve.  VALID only where that
+ *                    solve has status 0.  A valid hypothesis then takes 3 Gauss-Newton steps ON THE SAMPLE'S OWN m ENTRIES
+ *                    (the Gauss-Newton terms added from the left in the order k from +0.0; the step with the sample's length
+ *                    scale and sum omega); a refused step keeps the point and ends the stepping, the hypothesis stays valid.
+ *                    The linear stage from 17 noisy ranges is badly conditioned at d = 3; the 17 ranges over-determine the 6
+ *                    degrees of freedom well once it has found the basin.  An invalid hypothesis has g = the identity and
+ *                    vote 0 and sets no flag.
+ *   score            r(h, j) = (omega_j e) e, e = |R_h q'_j + t'_h - a'_j| - r_j: the operations and order of the Gauss-Newton
+ *                    cost term: the weighted squared range residual that cora_gnc_weights thresholds, no 1/2.
+ *   vote             vote(h) = #{ j : r(h, j) <= barc2 } over EVERY entry of the list, the sample's own included; a NaN is no
+ *                    vote.  A CONSENSUS MEANS SOMETHING ONLY ABOVE m.  barc2: one finite scalar > 0.
+ *   election         h* = the entry of largest vote, among equal votes the lowest entry; consensus = vote(h*).  A list without
+ *                    a valid hypothesis elects entry 0 with consensus 0.  consensus < min_consensus (min_consensus >= 1):
+ *                    status 5, "no consensus": the chain's rows are not touched and the chain counts as not placed; later
+ *                    stages still read its rows, as they do after a stage where point 0 won.
+ *   inliers          I = { j : r(h*, j) <= barc2 }, the same function and bits as the vote; empty at consensus 0.
+ *   refit            the plain stages over I only: the identity's cost, the linear stage (status 2 is still possible), the
+ *                    gn_steps Gauss-Newton steps, the last evaluation; the visited point of least cost is written, the
+ *                    earliest on ties.  AN ENTRY OUTSIDE I ADDS +0.0 FOR EACH OF ITS TERMS, in the pair products of the linear
+ *                    pass and in the sums of the Gauss-Newton pass (it is not skipped: the bracket order of every sum is the
+ *                    plain call's).  A list without outliers therefore has cora_place_chains_batched_dev's bits.  cost_start,
+ *                    cost_linear and cost_final are sums over I.  One election, one refit.
+ *   cost             L^2 scores per list of L entries, by design: every entry is a hypothesis.
+ *   limit            a hypothesis is clean only where all m entries of its sample are inliers: a share (1 - eps)^m of the
+ *                    hypotheses at an outlier share eps -- 0.43 / 0.17 at eps = 0.1 for d = 2 / 3, 0.17 / 0.02 at eps = 0.2.
+ *                    Strided samples overlap (sample h and sample h + s share m - 1 entries), so clean samples come in runs.
+ *                    Short lists with many outliers end in status 5 or elect a contaminated hypothesis.
+ * out = the six fields of cora_place_chains_batched_dev (a stage without consensus is among out[1], not placed, and not among
+ * out[0], placed; out[4] counts it as a stage), then {stages without
+ * consensus, ranges excluded: the inlier bytes equal to 0}.  status, cost_start, cost_linear, cost_final, chosen, transforms,
+ * degenerate: as the batched call's (costs 0, chosen -1, the identity at status 5).  elected [chains]: h*, -1 where the chain is
+ * no stage;  consensus [chains]: 0 there;  list_len [chains]: the entries of the chain's stage list, 0 there;  inlier [n_ranges]:
+ * 1 in I | 0 in a stage list, outside I (every entry of a list with consensus 0) | 2 in no stage list.  Every array may be NULL.
+ * Per LEVEL 3 launches (hypotheses, vote, election), then the 2 (gn_steps + 3) + 1 of the batched call with masked passes; then
+ * the range rows.  Everything on the handle's stream; synchronises once, at the end.  The vote's workspaces are made at the
+ * first robust call on the tables and freed with them.
+ * cora_place_chains_robust: the host-pointer form.  cora_debug_place_chains_robust_host: the mirror, the same functions in the
+ * same bracket order: the device's bits; works on a plan-only handle.
+ * ERRORS.  The plain call's; CORA_ERR_ARG also for barc2 not finite or <= 0 and for min_consensus < 1; CORA_ERR_NAN also for an
+ * elected hypothesis that is not finite.  STATE.  Nothing the handle computes with changes, nor its tables. */
+int cora_place_chains_robust_dev(cora_ctx *ctx, double *dX, int gn_steps, double barc2, int min_consensus, int64_t out[8],
+                                 unsigned char *status, double *cost_start, double *cost_linear, double *cost_final, int32_t *chosen,
+                                 double *transforms, int32_t *elected, int32_t *consensus, int32_t *list_len, unsigned char *inlier,
+                                 unsigned char *degenerate);
+int cora_place_chains_robust(cora_ctx *ctx, double *X, int ldx, int gn_steps, double barc2, int min_consensus, int64_t out[8],
+                             unsigned char *status, double *cost_start, double *cost_linear, double *cost_final, int32_t *chosen,
+                             double *transforms, int32_t *elected, int32_t *consensus, int32_t *list_len, unsigned char *inlier,
+                             unsigned char *degenerate);
+int cora_debug_place_chains_robust_host(cora_ctx *ctx, double *X, int ldx, int gn_steps, double barc2, int min_consensus, int64_t out[8],
+                                        unsigned char *status, double *cost_start, double *cost_linear, double *cost_final,
+                                        int32_t *chosen, double *transforms, int32_t *elected, int32_t *consensus, int32_t *list_len,
+                                        unsigned char *inlier, unsigned char *degenerate);
+
 /* ---- PLACEMENT FROM POSE-LANDMARK SIGHTINGS, on the device ----------------------------------------------------------------
  * Places landmarks and whole odometry chains of a resident vector of d columns (the output of cora_odometry_init_dev)
  * from the pose-landmark sightings of the measurement table, in place; both solves are closed-form.  Needs a measurement

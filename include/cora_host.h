@@ -144,6 +144,18 @@ int cora_problem_multi_robot_initialization_order(cora_problem *p, uint64_t seed
                                                   int64_t counts[5], unsigned char *status, double *cost_start, double *cost_linear,
                                                   double *cost_final, double *transforms, int64_t landmark_counts[4],
                                                   unsigned char *landmark_status);
+/* The same with the chain placement's consensus vote (ChainRangeConsensus, CORA_problem.h; cora_place_chains_robust_dev,
+ * include/cora_hip.h), under either order: consensus_barc2 <= 0 is off and has the call above's bits; > 0: every range of a
+ * chain's stage list proposes the motion its sample of m = 8 / 17 ranges determines, the fit runs over the ranges that agree
+ * with the elected proposal, and a chain whose elected proposal has fewer than min_consensus (<= 0: 2 m) votes has status 5 and
+ * keeps its random start (it is among "not placed").  consensus_counts = { chains without consensus, ranges excluded };
+ * consensus, list_len: one entry per chain;  inlier: one byte per range measurement as added (1 inlier | 0 in a stage list, not
+ * an inlier | 2 in no stage list).  With the vote off the three arrays are not written.  Every array but out may be NULL. */
+int cora_problem_multi_robot_initialization_consensus(cora_problem *p, uint64_t seed, int gn_steps, int min_ranges, int order, double consensus_barc2,
+                                                      int min_consensus, double *out, int64_t counts[5], unsigned char *status, double *cost_start,
+                                                      double *cost_linear, double *cost_final, double *transforms, int64_t landmark_counts[4],
+                                                      unsigned char *landmark_status, int64_t consensus_counts[2], int32_t *consensus,
+                                                      int32_t *list_len, unsigned char *inlier);
 /* Problem::sightingInitialization (an extension beyond the reference; include/cora_hip.h, "placement from pose-landmark
  * sightings").  min_ranges, min_sightings <= 0: the defaults.  out: data-matrix-size x rank.  counts = { chains fixed, placed,
  * not placed, landmarks placed, not placed, stages } of the sighting step; status, cost_start, cost_final, chosen: one entry
